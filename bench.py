@@ -14,6 +14,9 @@
     ... --projection-only                  # SURVEY 8d micro-benchmark: Xb ~ N(0,1)^L through the projection kernels alone
     ... --sharding allreduce               # force the general sharded path: RCCL all-reduce of [A X | sums | A(S-C)] (2m+2
                                            # doubles) before every replicated host y-solve, instead of owned constraints
+    ... --full                             # also the supplementary measurements: steady state, checkpointed rate, PCIe-inclusive
+                                           # rate, per-class breakdown, y-solve, allreduce_path (N > 1), time to tolerance, CPU baseline
+    ... --dump-outputs DIR                 # X, y, S after the last timed step as DIR/<name>.npy (float64; see dump_outputs)
 
 Workload c2 (default): synthetic strictly-feasible SDP with 10 000 PSD blocks of 32x32 PER GPU (5 constraints/block, 8 nnz
 each, dense C; cuadmm_amd.synthetic.config_c2), fp64, ADMM-only iterations (switch_admm=0), stop_tol=0 so exactly K
@@ -22,7 +25,8 @@ blocks sharded by block index (weak scaling); value = N * iterations / time.  Th
 constraint touches one block), so by default each rank keeps its own constraints and the ranks exchange only the four
 scalars of the stopping test, folded into one small all-reduce per iteration; `--sharding allreduce`
 measures the general path the north star names (A*svec(X) all-reduce + replicated solve) on the same problem.
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the K steps, writes its outputs when asked and prints the
+line (`value`, `ms_per_step`, the roofline of the timed projection); every measurement that takes runs of its own is behind --full.
 """
 import argparse
 import ctypes
@@ -41,6 +45,19 @@ BLOCK_N = 32
 HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec peak
 FP64_PEAK_TFLOPS = 78.6        # MI355X FP64 vector = matrix peak (256 CU x 128 FLOP/clk x 2.4 GHz)
 SUSTAINED_FP64_MFMA_TFLOPS = 67.9   # measured: every SIMD issuing independent v_mfma_f64_16x16x4_f64 only (tools/ubench/mfma_sustained.hip)
+DUMP_MAX_ELEMS = 1 << 21       # --dump-outputs: at most 16 MB of float64 per array (three arrays: well below 64 MB in all)
+
+
+def dump_outputs(directory, arrays):
+    """--dump-outputs: every array as <directory>/<name>.npy in float64.  An array longer than DUMP_MAX_ELEMS is stored as the
+    fixed sample of DUMP_MAX_ELEMS of its elements at sorted indices drawn with numpy's PCG64(0): the same indices for every
+    array of that length, so that two builds can be compared output for output."""
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, np.float64).ravel()
+        if a.size > DUMP_MAX_ELEMS:
+            a = a[np.sort(np.random.default_rng(0).choice(a.size, DUMP_MAX_ELEMS, replace=False))]
+        np.save(os.path.join(directory, name + ".npy"), a)
 
 
 def cpu_baseline(prob, threads, budget_s=20.0):
@@ -235,6 +252,8 @@ def projection_only(args, lib):
     check(lib.cuadmm_dev_sync())
     dt = (time.perf_counter() - t0) / args.steps
     steps_blk = steps_dev.get()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"Xproj": dout.get()})
     nominal = (32.0 / 3.0) * float(np.sum(blk.astype(np.float64) ** 3))
     issued = issued_mfma_flops(blk, steps_blk)
     print(json.dumps({
@@ -305,7 +324,11 @@ def main():
     ap.add_argument("--config", choices=["c1", "c2", "c3", "c4", "c5"], default="c2")
     ap.add_argument("--c-sparse", action="store_true", help="c2 / c4 with the sparse C of SURVEY 8d (C = A^T y0 + svec(I))")
     ap.add_argument("--projection-only", action="store_true", help="time the PSD projection of Xb ~ N(0,1)^L alone (cuadmm_op_psd_project)")
-    ap.add_argument("--time-to-tol", type=float, default=None, help="also run a fresh solve to this tolerance (untimed region) and report it")
+    ap.add_argument("--full", action="store_true", help="also run the supplementary measurements (steady state, checkpointed and PCIe-inclusive "
+                    "rates, per-class breakdown, allreduce_path, time to tolerance, CPU baseline); a plain run times the headline figure only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write X, y, S after the last timed step as DIR/<name>.npy "
+                    "(float64, rank 0's shard; arrays above %d elements as a fixed seeded sample)" % DUMP_MAX_ELEMS)
+    ap.add_argument("--time-to-tol", type=float, default=None, help="--full: also run a fresh solve to this tolerance (untimed region) and report it")
     ap.add_argument("--convergence-cap", type=int, default=None, help="c5: iteration cap of the convergence run with the reference log's parameters "
                     "(default 100 000, the reference's own; 1 000 000 for profiles/r06_pendulum_convergence.json)")
     ap.add_argument("--blocks-per-gpu", type=int, default=None)
@@ -328,6 +351,10 @@ def main():
         args.scaling = "weak" if args.config == "c2" else "strong"
     if args.blocks_per_gpu is None:
         args.blocks_per_gpu = {"c1": 122, "c2": BLOCKS_PER_GPU, "c3": 1, "c4": 100000, "c5": 239}[args.config]
+    if not args.full:
+        # a plain run: the headline figure alone, none of the measurements that take runs of their own
+        args.no_cpu_baseline = args.no_breakdown = args.no_allreduce_path = True
+        args.time_to_tol = 0.0
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -472,19 +499,23 @@ def main():
     prof = solver.profile()
     st = solver.state()
     steps_blk = solver.psd_steps()
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed solve receives, read before any supplementary run continues the solver
+        dump_outputs(args.dump_outputs, {"X": solver.X, "y": solver.y, "S": solver.S})
     # Supplementary, NOT `value`: the same solver continued for a longer stretch.  The chip ramps its clocks over the first ~30 ms
     # of dense work (tools/probe_rampup.py), so a 20-step timed region right after init sits below the rate a
     # solve of thousands of iterations sees; both numbers are in the line.
     ss_steps = {"c1": 300, "c2": 400, "c3": 40, "c4": 150, "c5": 400}[args.config]
-    sync()
-    t0 = time.perf_counter()
-    solver.solve(ss_steps, 0.0, 0, 50, 100, switch, 1.05, if_first=False)
-    sync()
-    dt_ss = time.perf_counter() - t0
-    if dist is not None:
-        t = torch.tensor([dt_ss], dtype=torch.float64, device="cpu" if dist.get_backend() == "gloo" else "cuda")
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        dt_ss = float(t.item())
+    if args.full:
+        sync()
+        t0 = time.perf_counter()
+        solver.solve(ss_steps, 0.0, 0, 50, 100, switch, 1.05, if_first=False)
+        sync()
+        dt_ss = time.perf_counter() - t0
+        if dist is not None:
+            t = torch.tensor([dt_ss], dtype=torch.float64, device="cpu" if dist.get_backend() == "gloo" else "cuda")
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            dt_ss = float(t.item())
     # Supplementary, NOT `value`: the timed region runs with stop_tol = 0 (exactly K iterations), so the engine takes no checkpoint
     # before a launch of several iterations; a solve WITH a tolerance checkpoints X, S, y, [A X | A (S - C)] at the start of every
     # batch (one copy kernel).  The same solver continued with a tolerance that is never met: the rate production solves see.
@@ -503,12 +534,13 @@ def main():
         ck = (ck_steps, dt_ck, solver.info_iter_num)
     # Supplementary, NOT `value`: the boundary takes host arrays in init and hands X, y, S back to host arrays -- the PCIe-inclusive
     # rate of the whole job (init with its uploads + the timed iterations + the read-back of the results), DESIGN.md section 6
-    sync()
-    t0 = time.perf_counter()
-    _x, _y, _s = solver.X, solver.y, solver.S
-    sync()
-    t_readback = time.perf_counter() - t0
-    del _x, _y, _s
+    if args.full:
+        sync()
+        t0 = time.perf_counter()
+        _x, _y, _s = solver.X, solver.y, solver.S
+        sync()
+        t_readback = time.perf_counter() - t0
+        del _x, _y, _s
     _, _, kb, ke = solver.shard()
     blk_local = np.asarray(prob.blk)[kb:ke]
 
@@ -719,12 +751,13 @@ def main():
                          "blocks_per_s": blk_local.size / per_s if per_s > 0 else 0.0},
             "final_state": {k: st[k] for k in ("errRp", "errRd", "relgap", "sig")},
         }
-        out["steady_state"] = {"value": (world if (args.scaling == "weak" or replicas) else 1) * ss_steps / dt_ss, "steps": ss_steps,
-                               "ms_per_step": dt_ss / ss_steps * 1e3,
-                               "note": "supplementary: the same solver continued for this many more iterations after the timed region (clock ramp over)"}
-        out["pcie_inclusive"] = {"value": (world if (args.scaling == "weak" or replicas) else 1) * args.steps / (t_init + dt + t_readback),
-                                 "init_s": t_init, "readback_s": t_readback,
-                                 "note": "supplementary: init (host arrays uploaded, A A^T factored) + the timed iterations + X, y, S read back to host arrays"}
+        if args.full:
+            out["steady_state"] = {"value": (world if (args.scaling == "weak" or replicas) else 1) * ss_steps / dt_ss, "steps": ss_steps,
+                                   "ms_per_step": dt_ss / ss_steps * 1e3,
+                                   "note": "supplementary: the same solver continued for this many more iterations after the timed region (clock ramp over)"}
+            out["pcie_inclusive"] = {"value": (world if (args.scaling == "weak" or replicas) else 1) * args.steps / (t_init + dt + t_readback),
+                                     "init_s": t_init, "readback_s": t_readback,
+                                     "note": "supplementary: init (host arrays uploaded, A A^T factored) + the timed iterations + X, y, S read back to host arrays"}
         if ck is not None:
             out["with_checkpoint"] = {"value": (world if (args.scaling == "weak" or replicas) else 1) * ck[0] / ck[1], "steps": ck[0], "ms_per_step": ck[1] / ck[0] * 1e3,
                                       "note": "supplementary: continued with stop_tol = 1e-300 (never met): every launch of several iterations starts from a "

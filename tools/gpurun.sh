@@ -13,7 +13,7 @@
 #   trace <tag> <bench args>   kernel stats of one bench configuration
 #   real [fixture switch cap [k=v ...]]   the reference's largest shipped inputs to 1e-3 (tools/run_large.py); no args: all of them
 #   moment "<keys>" "<k=v,..;k=v,..>"   oracle-trajectory deviations under option variants (tools/probe_moment.py)
-#   convergence [cap]          BASELINE configs[4] with the reference log's parameters (bench.py --config c5 --convergence-cap)
+#   convergence [cap]          BASELINE configs[4] with the reference log's parameters (bench.py --full --config c5 --convergence-cap)
 #   ubench <name> [args]       build tools/ubench/<name>.hip for gfx950 and run it
 set -u
 : "${GRAFT_REPO_ROOT:=$(cd "$(dirname "$0")/.." && pwd)}"
@@ -67,7 +67,7 @@ case "$recipe" in
     python bench.py --steps 20 --warmup 5 | tee "$G/r${ROUND}_bench_driver.json" | cut -c1-400 ;;
   bench)
     for c in ${*:-c2_20 c2 c3 c4 c1 c5}; do
-      python bench.py $(bench_args $c) > "$G/r${ROUND}_bench_$c.json" 2> "$G/r${ROUND}_bench_$c.err"
+      python bench.py $(bench_args $c) --full > "$G/r${ROUND}_bench_$c.json" 2> "$G/r${ROUND}_bench_$c.err"
       python - "$G/r${ROUND}_bench_$c.json" $c <<'P'
 import json, sys
 d = json.load(open(sys.argv[1]))
@@ -78,7 +78,7 @@ P
   ab)
     key=$1; vals=$2; shift 2
     for v in ${vals//,/ }; do for c in ${*:-c1 c5}; do
-      python bench.py $(bench_args $c) --no-cpu-baseline --time-to-tol 0 --option $key=$v > "$G/r${ROUND}_ab_${key}_${v}_$c.json" 2> "$G/r${ROUND}_ab_${key}_${v}_$c.err"
+      python bench.py $(bench_args $c) --full --no-cpu-baseline --time-to-tol 0 --option $key=$v > "$G/r${ROUND}_ab_${key}_${v}_$c.json" 2> "$G/r${ROUND}_ab_${key}_${v}_$c.err"
       python - "$G/r${ROUND}_ab_${key}_${v}_$c.json" "$key=$v" $c <<'P'
 import json, sys
 d = json.load(open(sys.argv[1]))
@@ -92,7 +92,7 @@ P
     for set_ in "${SETS[@]}"; do for c in ${*:-c1 c5}; do
       tag=$(echo "$set_" | tr ' =' '__'); opts=""
       for kv in $set_; do opts="$opts --option $kv"; done
-      python bench.py $(bench_args $c) --no-cpu-baseline --time-to-tol 0 $opts > "$G/r${ROUND}_ab_${tag}_$c.json" 2> "$G/r${ROUND}_ab_${tag}_$c.err"
+      python bench.py $(bench_args $c) --full --no-cpu-baseline --time-to-tol 0 $opts > "$G/r${ROUND}_ab_${tag}_$c.json" 2> "$G/r${ROUND}_ab_${tag}_$c.err"
       python - "$G/r${ROUND}_ab_${tag}_$c.json" "$set_" $c <<'P'
 import json, sys
 d = json.load(open(sys.argv[1]))
@@ -102,12 +102,12 @@ P
   prof)
     for c in ${*:-c2 c2_20 c4 c1 c5 c3}; do
       case $c in
-        c2)    prof c2 python3 "$R/bench.py" --steps 200 --warmup 20 --no-cpu-baseline --no-breakdown ;;
-        c2_20) prof c2_20 python3 "$R/bench.py" --steps 20 --warmup 5 --no-cpu-baseline --no-breakdown ;;
-        c3)    prof c3 python3 "$R/bench.py" --config c3 --steps 10 --warmup 2 --no-cpu-baseline --no-breakdown ;;
-        c4)    prof c4 python3 "$R/bench.py" --config c4 --steps 40 --warmup 5 --no-cpu-baseline --no-breakdown ;;
-        c1)    prof c1 python3 "$R/bench.py" --config c1 --steps 60 --warmup 5 --no-cpu-baseline --no-breakdown --time-to-tol 0 ;;
-        c5)    prof c5 python3 "$R/bench.py" --config c5 --steps 100 --warmup 5 --no-cpu-baseline --no-breakdown --time-to-tol 0 ;;
+        c2)    prof c2 python3 "$R/bench.py" --steps 200 --warmup 20 --full --no-cpu-baseline --no-breakdown ;;
+        c2_20) prof c2_20 python3 "$R/bench.py" --steps 20 --warmup 5 --full --no-cpu-baseline --no-breakdown ;;
+        c3)    prof c3 python3 "$R/bench.py" --config c3 --steps 10 --warmup 2 --full --no-cpu-baseline --no-breakdown ;;
+        c4)    prof c4 python3 "$R/bench.py" --config c4 --steps 40 --warmup 5 --full --no-cpu-baseline --no-breakdown ;;
+        c1)    prof c1 python3 "$R/bench.py" --config c1 --steps 60 --warmup 5 --full --no-cpu-baseline --no-breakdown --time-to-tol 0 ;;
+        c5)    prof c5 python3 "$R/bench.py" --config c5 --steps 100 --warmup 5 --full --no-cpu-baseline --no-breakdown --time-to-tol 0 ;;
       esac
     done
     # the summaries were written under profiles/ of the box's copy: only gpurun_out/ travels back
@@ -116,7 +116,7 @@ P
   trace)
     tag=$1; shift
     ( cd /tmp && export TMPDIR=/tmp
-      timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$G/prof_$tag" -- python3 "$R/bench.py" "$@" --no-cpu-baseline --no-breakdown > "$G/${tag}_trace.log" 2>&1 )
+      timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$G/prof_$tag" -- python3 "$R/bench.py" "$@" --full --no-cpu-baseline --no-breakdown > "$G/${tag}_trace.log" 2>&1 )
     cp "$(find "$G/prof_$tag" -name '*kernel_stats.csv' | head -1)" "$G/r${ROUND}_${tag}_kernel_stats.csv"; rm -rf "$G/prof_$tag"
     head -24 "$G/r${ROUND}_${tag}_kernel_stats.csv" | cut -c1-200 ;;
   real)
@@ -132,7 +132,7 @@ P
   moment)
     python tools/probe_moment.py "$1" "${2:-}" 2>&1 | tee -a "$G/r${ROUND}_moment_probe.log" | grep -v absdiff ;;
   convergence)
-    python bench.py --config c5 --no-cpu-baseline --convergence-cap "${1:-1000000}" > "$G/r${ROUND}_pendulum_convergence.json" 2> "$G/r${ROUND}_pendulum_convergence.err"
+    python bench.py --config c5 --full --no-cpu-baseline --convergence-cap "${1:-1000000}" > "$G/r${ROUND}_pendulum_convergence.json" 2> "$G/r${ROUND}_pendulum_convergence.err"
     python -c "import json; print(json.dumps(json.load(open('$G/r${ROUND}_pendulum_convergence.json'))['time_to_tol'], indent=1))" ;;
   ubench)
     n=$1; shift
