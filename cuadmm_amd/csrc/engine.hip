@@ -952,7 +952,6 @@ static int init_plan(Solver* s, const InitIn& in, InitCtx& c) {
     s->plan.d_steps = s->steps_d.p;
     s->plan.sign.d_steps = s->steps_d.p;
   }
-  s->plan.sign.allow_graph = true;   // same buffers every iteration: replay the sign-path launch sequence from a hipGraph
   if (rc) return rc;
 
   return rc;

@@ -11,12 +11,13 @@ namespace cuadmm {
 struct ClusterMulti;
 
 struct SignPsd {
-  // pred: steps the previous projection needed.  merged: the group runs its whole sign iteration in ONE launch shared with the other
-  // merged groups (lg_sign_cluster_kernel over several padded sizes), so it has a workspace of its own (ws_off: elements into X0 / S /
-  // Y / T; mem_off: members into d_state / d_done / d_bar; part_off: into each half of d_part; slot: which [2] of d_group and which table
-  // of d_xcc); the others run on the caller's stream one after the other in the shared region (all offsets 0)
+  // pred: steps the previous projection needed.  mem_off: the group's own range of members in d_state / d_done / d_bar / scale (every
+  // group one, in group order).  merged: the group runs its whole sign iteration in ONE launch shared with the other merged groups
+  // (lg_sign_cluster_kernel over several padded sizes), so it has a workspace of its own too (ws_off: elements into X0 / S / Y / T;
+  // part_off: into each half of d_part; slot: which [2] of d_group and which table of d_xcc); the others run on the caller's stream one
+  // after the other and share the workspace at offset 0
   struct Group { int N = 0, begin = 0, count = 0, pred = 0, mem_off = 0, slot = 0; bool merged = false; size_t ws_off = 0, part_off = 0, cs_off = 0;
-                 mutable int bar_par = 0; };      // cs_off: into colsum_f; bar_par: which of the two barrier-counter sets the next fused projection uses
+                 mutable int bar_par = 0; };      // cs_off: into colsum_f; bar_par: which of the group's two barrier-counter sets the next fused projection uses
   PsdOptions opt;                            // the owner's switches (PsdPlan::build copies its own)
   std::vector<Group> groups;                 // same padded size N, bounded workspace
   int* d_ids = nullptr;                      // block ids, group after group
@@ -26,19 +27,17 @@ struct SignPsd {
                                              // 66 ... 120: projection 1.03 -> 0.98 ms, taha1a 1.08 -> 1.02), one n = 2 000 block loses a step (C3 17 -> 18).
                                              // A property of the group, not of the path: launches and one-launch kernel stay bit-identical
   double *X0 = nullptr, *S = nullptr, *Y = nullptr, *T = nullptr, *colsum = nullptr, *scale = nullptr;
-  double* Mw = nullptr;                      // fifth matrix per member: M = R - R Y of a clean mega-lift (allocated when a group padded to <= clean_max_n exists)
   double* colsum_f = nullptr;                // fused one-launch prologue: [group][member][LG_CS_ROWS][N] column-sum chunks (every group its own: merged groups run together)
-  int* d_cont = nullptr;                     // [parity][member]: the next step is a clean mega-lift's second slot
-  int clean_max_n = 480;                     // (below 512: a single block padded to 512 runs the super-block tile order, which has no second slot) like hint_max_n: a property of the group, so launches and one-launch kernel stay bit-identical and C3 pays nothing
-  void* d_state = nullptr;                   // 2 x SignDevState per member of the largest group (adaptive schedule, sign_sched.h)
+  void* d_state = nullptr;                   // 2 x SignDevState per member (adaptive schedule, sign_sched.h)
   void* d_done = nullptr;                    // SignDone per member
   double* d_part = nullptr;                  // per-tile partial sums of the schedule statistics (p1 | p2)
   size_t part_half = 0;
   int* d_group = nullptr;                    // [members not finished, largest step count] of the group in flight
   int* h_group = nullptr;                    // pinned host copy (polled between chunks of steps)
-  unsigned* d_bar = nullptr;                 // per member, two sets (members_cap apart): barrier counter of the one-launch variant; a fused projection zeroes the other set
-  mutable int shared_bar_par = 0;            // the counter set the next fused projection of a NON-merged group uses (they share the region at offset 0)
-  size_t bar_stride = 0;                     // members_cap: distance between the two counter sets
+  unsigned* d_bar = nullptr;                 // per member, two sets (members_cap apart): barrier counter of the one-launch variant.  A fused group
+                                             // alternates between its two sets and zeroes the other one for its next projection; a run that is
+                                             // not fused counts in set 0 and zeroes it at its start
+  size_t bar_stride = 0;                     // members_cap (all groups' counts): distance between the two counter sets
   int* d_xcc = nullptr;                      // [member][tile]: XCD of every workgroup of the one-launch variant (run-time check)
   int build(const int* blk, const std::vector<int>& members);
   int launch_group(Group& g, const double* in, double* out, const long long* boff, const int* bn, int* d_fail, hipStream_t st, bool poll);
@@ -46,10 +45,6 @@ struct SignPsd {
   int cluster_run(ClusterMulti& cm, bool prologue, const double* in, double* out, const long long* boff, const int* bn, int* d_fail, hipStream_t st);
   void release();
   int project(const double* in, double* out, const long long* boff, const int* bn, int* d_fail, hipStream_t st);
-  int project_launch(const double* in, double* out, const long long* boff, const int* bn, int* d_fail, hipStream_t st);
-  bool allow_graph = false;                  // set by long-lived owners (the engine); one-shot plans launch directly
-  hipGraphExec_t graph_exec = nullptr;       // captured launch sequence of project_launch for (g_in, g_out, ...)
-  const double* g_in = nullptr; double* g_out = nullptr; const long long* g_boff = nullptr; const int* g_bn = nullptr; int* g_fail = nullptr;
   bool empty() const { return groups.empty(); }
   ~SignPsd() { release(); }
 };

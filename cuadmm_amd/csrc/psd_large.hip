@@ -79,24 +79,18 @@ struct SignArgs {
   const int* ids;           // member -> block id
   int count, step;
   unsigned* bar;            // per member: barrier counter of the one-launch variant (lg_sign_cluster_kernel); may be null
-  int* cont;                // [parity][member]: version k says whether step k is the SECOND slot of a clean mega-lift (sign_sched.h); null: never
-  int clean;                // this group's schedule takes clean mega-lifts (padded size <= 512: the fifth matrix per member exists)
-  int cap;                  // the step limit of this projection (a mega-lift's two slots never straddle it)
 };
 // fresh schedule state of a member (version 0)
 __device__ __forceinline__ void lg_fresh_state(const SignArgs& sa, int m, int id, int n, bool reset_bar = true) {
   SignDevState st;
   st.sched = SignSched();
   if (sa.hint && sa.hint[id] > 0) st.sched.lift0 = sa.hint[id];
-  st.sched.clean = sa.clean != 0 && sa.cont != nullptr;
-  if (sa.cap > 0 && sa.cap < SignSched::kCap) st.sched.cap = sa.cap;
   st.mu = 1.0;
   st.n = n;
   sa.st[m] = st;
   sa.done[m].done_at = 0x7fffffff;
   sa.done[m].steps = 0;
   if (sa.bar && reset_bar) sa.bar[m] = 0u;
-  if (sa.cont) { sa.cont[m] = 0; sa.cont[sa.count + m] = 0; }
 }
 
 // Sums the statistics' slots in a fixed order (all 256 threads), runs the schedule's decision for step sa.step on thread 0
@@ -135,11 +129,8 @@ __device__ __forceinline__ double lg_reduce_decide(const SignArgs& sa, int membe
     v.mu = v.sched.decide<true>(v.n, a, b, 0.0, last);
     red[12] = v.mu;
     red[13] = v.sched.cm;                 // > 0: a mega-lift (sign_sched.h), coefficients -cm, 1 + cm
-    red[14] = (double)v.sched.half;       // clean mega-lift: 1 = this step's output is R = S - S Y, 2 = this step applies S + cmc (M - Y M)
-    red[15] = v.sched.cmc;
     if (writer) {
       sa.st[(size_t)(par ^ 1) * sa.count + member] = v;
-      if (sa.cont) __hip_atomic_store(sa.cont + (size_t)(par ^ 1) * sa.count + member, v.sched.cont ? 1 : 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       if (last) {
         sa.done[member].steps = v.sched.steps;
         sa.done[member].done_at = sa.step + 1;
@@ -171,19 +162,13 @@ __global__ __launch_bounds__(256) void lg_decide_kernel(SignArgs sa, int ntiles)
 //         no mirror image, no lg_pack_kernel behind it; a non-finite entry raises *fail like that kernel does.
 // ROLE 3: the final product: B = the buffer that holds the last iterate (Bb after an even number of steps, B2b after
 //         an odd one).
-// CLEAN MEGA-LIFT (sign_sched.h; B2b = the member's fifth matrix M in roles 1, 2, 4).  Its first slot is an ordinary step whose coefficients
-// (-1, 1) leave R = S - S Y where the next iterate would be; the launches of the SECOND slot find that out from the device state and change
-// operands: ROLE 1 forms M = R - R Y instead of Y = S S -- as a FULL product, the tile and its transpose one after the other, no mirroring
-// (R (I - Y) is symmetric only up to the noise the step removes) -- and ROLE 2 / 4 forms S + cmc (M - Y M), mirrored, in place over the old
-// iterate (which the step before left in the output buffer; an element is read and written by the same thread).
 template <bool MIRROR, int TM, int BK>
 struct LgGemmCfg {
   static constexpr int LDS = TM + 16;      // row stride (doubles): the 4 k-rows of a fragment read fall on disjoint banks
   static constexpr int SMEM = MIRROR ? (TM * (TM + 1) > 2 * BK * LDS ? TM * (TM + 1) : 2 * BK * LDS) : 2 * BK * LDS;
 };
 // The body of one output tile: workgroup (tile_x of grid_x, member).  smem: LgGemmCfg::SMEM doubles, red: 16 doubles.
-// CLEAN: the instantiation knows the second slot of a clean mega-lift (groups that never take one -- C3's single large block -- run the other: not a register more)
-template <bool MIRROR, int TM, int BK, int ROLE, bool CLEAN = false, bool LATE = true>
+template <bool MIRROR, int TM, int BK, int ROLE, bool LATE = true>
 __device__ __forceinline__ void lg_gemm_sym_body(int N, const double* __restrict__ Ab, const double* __restrict__ Bb,
                                                  double alpha, double beta, const double* __restrict__ Eb,
                                                  double* __restrict__ Cb, int sb, const SignArgs& sg, const double* __restrict__ B2b,
@@ -192,14 +177,8 @@ __device__ __forceinline__ void lg_gemm_sym_body(int N, const double* __restrict
   constexpr int LDS = TM + 16;      // row stride (doubles): the 4 k-rows of a fragment read fall on disjoint banks
   constexpr int WT = TM / 2;        // rows / cols per wave
   constexpr int NTW = WT / 16;      // 16x16 MFMA tiles per wave per direction
-  bool slot2 = false;               // ROLE 1: this step is the second slot of a clean mega-lift
-  if (ROLE == 1 || ROLE == 2 || ROLE == 4) {
-    int sl = 0;
-    if (CLEAN && ROLE == 1 && sg.cont)               // (issued with the load of done_at: one trip to the L2, not two)
-      sl = __hip_atomic_load(sg.cont + (size_t)(sg.step & 1) * sg.count + member, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (!known_live && sg.done[member].done_at <= sg.step) return;   // uniform over the workgroup: before any barrier (the one-launch kernel has just looked)
-    slot2 = sl != 0;
-  }
+  if ((ROLE == 1 || ROLE == 2 || ROLE == 4) && !known_live && sg.done[member].done_at <= sg.step)
+    return;                         // uniform over the workgroup: before any barrier (the one-launch kernel has just looked)
   if (ROLE == 3) {
     const int steps = sg.done[member].done_at <= sg.step ? sg.done[member].steps : sg.step;   // sg.step = steps enqueued
     if (steps & 1) Bb = B2b;
@@ -235,46 +214,28 @@ __device__ __forceinline__ void lg_gemm_sym_body(int N, const double* __restrict
   }
   const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wy = wave >> 1, wx = wave & 1;
-  int row0 = by * TM, col0 = bx * TM;
+  const int row0 = by * TM, col0 = bx * TM;
   const int r16 = lane & 15, kk = lane >> 4;
   const int nbt = N / TM, ntiles = nbt * (nbt + 1) / 2;
-  bool full = false;                // ROLE 1, second slot of a clean mega-lift: the full product M = R - R Y
-  double gamma = 0.0;               // ROLE 2 / 4, second slot: C = E + gamma (M - A B)
-  const double* Madd = nullptr;
   auto decide = [&]() {
-    double mu, cm, cmc;
-    int half;
+    double mu, cm;
     if (ROLE == 2) {
       mu = lg_reduce_decide(sg, member, ntiles, bx == 0 && by == 0, red);
-      cm = red[13]; half = (int)red[14]; cmc = red[15];
+      cm = red[13];
     } else {
       const SignDevState& v = sg.st[(size_t)((sg.step & 1) ^ 1) * sg.count + member];
-      mu = v.mu; cm = v.sched.cm; half = v.sched.half; cmc = v.sched.cmc;
+      mu = v.mu; cm = v.sched.cm;
     }
     alpha = cm > 0.0 ? -cm : -0.5 * mu * mu * mu;
     beta = cm > 0.0 ? 1.0 + cm : 1.5 * mu;
-    if (CLEAN && half == 1) { alpha = -1.0; beta = 1.0; }
-    if (CLEAN && half == 2) {       // A = Y, B = M, E = C = the old iterate (in the output buffer), + cmc M
-      A = Bb + mat; B = B2b + mat; E = Cb + mat; Madd = B2b + mat;
-      alpha = -cmc; beta = 1.0; gamma = cmc;
-    }
   };
-  // The decision only sets the epilogue's coefficients -- unless a clean mega-lift may change the operands.  Without one (ROLE 2) it runs
-  // BEHIND the first operand loads: the slots' and the state's trips to the L2 overlap the operands' instead of preceding them.
+  // The decision only sets the epilogue's coefficients: in ROLE 2 it runs BEHIND the first operand loads, so the slots' and the state's
+  // trips to the L2 overlap the operands' instead of preceding them.
   // (LATE = false: the one-launch kernel -- the operands live across the state machine cost 46 registers, and three of its workgroups must fit a CU)
-  constexpr bool kLateDecision = ROLE == 2 && !CLEAN && LATE;
+  constexpr bool kLateDecision = ROLE == 2 && LATE;
   if ((ROLE == 2 || ROLE == 4) && !kLateDecision) decide();
-  if (CLEAN && ROLE == 1 && slot2) {      // A = R (the step before left it where the iterate would be), B = Y, C = M
-    full = true;
-    B = Cb + mat; E = Ab + mat; C = const_cast<double*>(B2b) + mat;
-    alpha = -1.0; beta = 1.0;
-  }
 
   double p0 = 0.0, p1 = 0.0;     // ROLE 1: tr Y, ||Y||_F^2; ROLE 2 / 4: ||S - S Y||_F^2 (this tile's share)
-  // (a full product runs the tile and then its transpose: the same workgroup, operands swapped by symmetry of the ROLES, not of the result)
-  const int npass = (CLEAN && full && by != bx) ? 2 : 1;
-  for (int pass = 0; pass < npass; ++pass) {
-  if (pass == 1) { const int t_ = by; by = bx; bx = t_; row0 = by * TM; col0 = bx * TM; }
   lg_v4f64 acc[NTW][NTW];
 #pragma unroll
   for (int i = 0; i < NTW; ++i)
@@ -358,7 +319,6 @@ __device__ __forceinline__ void lg_gemm_sym_body(int N, const double* __restrict
           c += beta * ev;
           if (ROLE == 2 || ROLE == 4) { const double d = ev - acc[i][j][r]; p0 += d * d; }
         }
-        if (CLEAN && (ROLE == 2 || ROLE == 4) && Madd) c += gamma * Madd[idx];
         if (ROLE == 1) {
           p1 += acc[i][j][r] * acc[i][j][r];
           if (row == col) p0 += acc[i][j][r];
@@ -369,20 +329,19 @@ __device__ __forceinline__ void lg_gemm_sym_body(int N, const double* __restrict
             C[(size_t)col * (col + 1) / 2 + row] = row == col ? c : c * kSqrt2;
           }
         } else {
-        if (!MIRROR || full || col >= row) C[idx] = c;        // diagonal tiles: the upper triangle decides (a full product: every entry is its own)
-        if (MIRROR && !full) Ct[lcol * (TM + 1) + lrow] = c;
+          if (!MIRROR || col >= row) C[idx] = c;        // diagonal tiles: the upper triangle decides
+          if (MIRROR) Ct[lcol * (TM + 1) + lrow] = c;
         }
       }
-  if (MIRROR && !full && ROLE != 5) {
+  if (MIRROR && ROLE != 5) {
     __syncthreads();
     const int q = tid % TM;                           // original row   -> column of the mirrored tile
 #pragma unroll 4
     for (int p = tid / TM; p < TM; p += 256 / TM)     // original column -> row of the mirrored tile
       if (by != bx || q < p) C[(size_t)(col0 + p) * N + row0 + q] = Ct[p * (TM + 1) + q];
   }
-  }    // pass
-  if ((ROLE == 1 && !full) || ROLE == 2 || ROLE == 4) {
-    // this tile's partial sums -> its fixed slot (read by the next launch; the full product of a second slot leaves none: nothing reads them)
+  if (ROLE == 1 || ROLE == 2 || ROLE == 4) {
+    // this tile's partial sums -> its fixed slot (read by the next launch)
     const double w = (by == bx) ? 1.0 : 2.0;                 // an off-diagonal tile stands for its mirror image too
     p0 = wave_sum(p0);
     p1 = wave_sum(p1);
@@ -404,13 +363,13 @@ __device__ __forceinline__ void lg_gemm_sym_body(int N, const double* __restrict
   }
 }
 
-template <bool MIRROR, int TM, int BK, int ROLE, bool CLEAN = false>
+template <bool MIRROR, int TM, int BK, int ROLE>
 __global__ __launch_bounds__(256) void lg_gemm_sym_kernel(int N, const double* __restrict__ Ab, const double* __restrict__ Bb,
                                                           double alpha, double beta, const double* __restrict__ Eb,
                                                           double* __restrict__ Cb, int sb, SignArgs sg, const double* __restrict__ B2b) {
   __shared__ double smem[LgGemmCfg<MIRROR, TM, BK>::SMEM];
   __shared__ double red[16];
-  lg_gemm_sym_body<MIRROR, TM, BK, ROLE, CLEAN>(N, Ab, Bb, alpha, beta, Eb, Cb, sb, sg, B2b, (int)blockIdx.y, (int)blockIdx.x, (int)gridDim.x, smem, red);
+  lg_gemm_sym_body<MIRROR, TM, BK, ROLE>(N, Ab, Bb, alpha, beta, Eb, Cb, sb, sg, B2b, (int)blockIdx.y, (int)blockIdx.x, (int)gridDim.x, smem, red);
 }
 
 // ---- a handful of mid-size blocks: the WHOLE sign iteration in one launch --------------------------------------------------
@@ -430,7 +389,7 @@ constexpr int LG_CS_ROWS = 32;       // row chunks of the column sums of |X| (lg
 constexpr int kClusterMaxWgs = 224;       // default of psd_lg_cluster_wgs
 constexpr int kClusterXccStride = 1024;   // ints per table of d_xcc (the option's upper bound + slack)
 struct ClusterArgs {
-  double *S, *T, *Y, *X0, *M;
+  double *S, *T, *Y, *X0;
   unsigned* bar;            // per member, zeroed by lg_state_init_kernel
   int* xcc;                 // [member][tile]: the XCD every workgroup found itself on
   int* fail;
@@ -441,7 +400,7 @@ struct ClusterArgs {
   // prologue alone was 23 us of a 320 us chain on PlanarHand_N=1)
   int fused;
   double* colsum;           // [member][LG_CS_ROWS][N]
-  unsigned* bar_other;      // the counters of the NEXT projection (two sets, alternating): zeroed by this one, since nobody zeroes this one's before it
+  unsigned* bar_other;      // FUSED: the counters of the NEXT projection (two sets, alternating): zeroed by this one, since nobody zeroes this one's before it
 };
 // Several groups (different padded sizes N) in one launch: workgroup and member ranges per group.  A relaxation with blocks of 126 and
 // of 252 (taha1a) would otherwise run its two one-launch groups one after the other, each a few workgroups deep and bound by its barriers.
@@ -488,7 +447,7 @@ __device__ __forceinline__ bool lg_member_barrier(unsigned* bar, unsigned target
 // publishes the XCD it really runs on (HW_REG_XCC_ID), and after a first (agent-scope) barrier each checks that its member's are equal
 // -- only then the light barrier is used.  (Measured and rejected: workgroup-scope read-modify-writes on the counter, hoping they
 // would be served by the shared L2 -- they are not coherent between CUs: the waiters time out.)
-template <int TM, int BK, bool CLEAN>
+template <int TM, int BK>
 __global__ __launch_bounds__(256) void lg_sign_cluster_kernel(ClusterMulti cm) {
   __shared__ double smem[LgGemmCfg<true, TM, BK>::SMEM];
   __shared__ double red[16];
@@ -590,9 +549,9 @@ __global__ __launch_bounds__(256) void lg_sign_cluster_kernel(ClusterMulti cm) {
     sg.step = step;
     // done_at is written by this member's writer workgroup during the second product of the step before: ordered by the barrier
     if (__hip_atomic_load(&sg.done[member].done_at, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) <= step) break;
-    lg_gemm_sym_body<true, TM, BK, 1, CLEAN, false>(N, s, s, 1.0, 0.0, nullptr, ca.Y, 0, sg, ca.M, member, tile, (int)ntiles, smem, red, true);
+    lg_gemm_sym_body<true, TM, BK, 1, false>(N, s, s, 1.0, 0.0, nullptr, ca.Y, 0, sg, nullptr, member, tile, (int)ntiles, smem, red, true);
     if (!lg_member_barrier(bar, ntiles * ++phase, local)) { if (threadIdx.x == 0 && ca.fail) atomicAdd(ca.fail, 1); return; }
-    lg_gemm_sym_body<true, TM, BK, 2, CLEAN, false>(N, s, ca.Y, 0.0, 0.0, s, t, 0, sg, ca.M, member, tile, (int)ntiles, smem, red, true);
+    lg_gemm_sym_body<true, TM, BK, 2, false>(N, s, ca.Y, 0.0, 0.0, s, t, 0, sg, nullptr, member, tile, (int)ntiles, smem, red, true);
     if (!lg_member_barrier(bar, ntiles * ++phase, local)) { if (threadIdx.x == 0 && ca.fail) atomicAdd(ca.fail, 1); return; }
     if (local) {
       // the light barrier stands on "same XCD", established once at the start: a workgroup that finds itself elsewhere (a preempted
@@ -809,15 +768,10 @@ static int lg_gemm_mirror(int N, int count, const double* A, const double* B, do
                           hipStream_t st, const SignArgs& sa, const double* B2, int tile_force = 0) {
   const bool small_tiles = lg_small_tiles(true, N, count, tile_force);
   const int nb = small_tiles ? N / 32 : N / 64;
-  constexpr bool kCanClean = ROLE == 1 || ROLE == 2 || ROLE == 4;
   if (count == 1 && nb >= 16) {
     const int sb = (nb + 7) / 8;                               // 8x8-tile super-blocks per direction
-    if (sa.clean) { set_error("psd sign path: a clean mega-lift group on the super-block order (N = %d)", N); return CUADMM_ERR_INVALID; }
     if (small_tiles) hipLaunchKernelGGL((lg_gemm_sym_kernel<true, 32, 32, ROLE>), dim3(sb * (sb + 1) / 2 * 64), dim3(256), 0, st, N, A, B, alpha, beta, E, C, sb, sa, B2);
     else hipLaunchKernelGGL((lg_gemm_sym_kernel<true, 64, 16, ROLE>), dim3(sb * (sb + 1) / 2 * 64), dim3(256), 0, st, N, A, B, alpha, beta, E, C, sb, sa, B2);
-  } else if (kCanClean && sa.clean) {
-    if (small_tiles) hipLaunchKernelGGL((lg_gemm_sym_kernel<true, 32, 32, ROLE, kCanClean>), dim3(nb * (nb + 1) / 2, count), dim3(256), 0, st, N, A, B, alpha, beta, E, C, 0, sa, B2);
-    else hipLaunchKernelGGL((lg_gemm_sym_kernel<true, 64, 16, ROLE, kCanClean>), dim3(nb * (nb + 1) / 2, count), dim3(256), 0, st, N, A, B, alpha, beta, E, C, 0, sa, B2);
   } else {
     if (small_tiles) hipLaunchKernelGGL((lg_gemm_sym_kernel<true, 32, 32, ROLE>), dim3(nb * (nb + 1) / 2, count), dim3(256), 0, st, N, A, B, alpha, beta, E, C, 0, sa, B2);
     else hipLaunchKernelGGL((lg_gemm_sym_kernel<true, 64, 16, ROLE>), dim3(nb * (nb + 1) / 2, count), dim3(256), 0, st, N, A, B, alpha, beta, E, C, 0, sa, B2);
@@ -858,8 +812,7 @@ int SignPsd::build(const int* blk, const std::vector<int>& members) {
   std::map<int, std::vector<int>> by_pad;
   for (int k : members) by_pad[lg_pad(blk[k])].push_back(k);
   std::vector<int> ids;
-  size_t max_elems = 0, max_cols = 0;
-  int max_count = 0;
+  size_t max_cols = 0;
   for (auto& kv : by_pad) {
     int N = kv.first;
     const size_t per = (size_t)N * N * sizeof(double) * 4;
@@ -881,23 +834,21 @@ int SignPsd::build(const int* blk, const std::vector<int>& members) {
       g.begin = (int)ids.size();
       g.count = (int)std::min<size_t>((size_t)chunk, kv.second.size() - b);
       for (int i = 0; i < g.count; ++i) ids.push_back(kv.second[b + i]);
-      max_elems = std::max(max_elems, (size_t)g.count * N * N);
       max_cols = std::max(max_cols, (size_t)g.count * N * LG_CS_ROWS);
-      max_count = std::max(max_count, g.count);
       groups.push_back(g);
     }
   }
   // One-launch groups of DIFFERENT padded sizes (a relaxation with blocks of 126 and of 252: taha1a) share ONE launch
   // (ClusterMulti), each with a workspace of its own, while all of them together stay within the co-residency bound of such a
-  // launch.  Everything else runs one group after the other in the shared region.  (First attempt: side streams.  A plain side
+  // launch.  Everything else runs one group after the other in the shared workspace.  (First attempt: side streams.  A plain side
   // stream landed on the caller's hardware queue -- no overlap at all; a high-priority one overlapped, and every small kernel of the
   // caller's stream took 40 us instead of 5.)
   auto part_of = [](const Group& g) { return (size_t)g.count * 2 * (size_t)(g.N / 32) * (size_t)(g.N / 32 + 1) / 2; };
-  size_t max_part = 0, side_elems = 0, side_part = 0;
-  int side_members = 0, n_merged = 0, wgs = 0;
+  size_t max_elems = 0, max_part = 0, side_elems = 0, side_part = 0;
+  int n_merged = 0, wgs = 0;
   // per-XCD load of the merged launch: member q of a non-spread group sits on XCD q % 8 (every group's first workgroup is a
-  // multiple of 8), a spread group's workgroups go round the XCDs.  lg_path bounds one group's share of an XCD (96 workgroups, the
-  // XCD's CUs hold ~128); several groups must respect it TOGETHER, or a later group's workgroups wait for CUs while the resident
+  // multiple of 8), a spread group's workgroups go round the XCDs.  lg_path bounds one group's share of an XCD (96 workgroups: all the
+  // XCD's CUs hold); several groups must respect it TOGETHER, or a later group's workgroups wait for CUs while the resident
   // ones spin in lg_member_barrier (no deadlock -- barriers are per member -- but serial, and the ~2 s give-up budget runs)
   int xcd_load[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   for (Group& g : groups) {
@@ -920,44 +871,34 @@ int SignPsd::build(const int* blk, const std::vector<int>& members) {
   if (n_merged < 2)                             // nothing to merge: the plain path
     for (Group& g : groups) { g.merged = false; g.slot = 0; }
   if (n_merged < 2) n_merged = 0;
-  max_elems = 0; max_count = 0;                 // the shared region: the groups of the caller's stream only
-  for (const Group& g : groups)
+  for (const Group& g : groups)                 // the shared workspace: the groups of the caller's stream only
     if (!g.merged) {
       max_elems = std::max(max_elems, (size_t)g.count * g.N * g.N);
-      max_count = std::max(max_count, g.count);
       max_part = std::max(max_part, part_of(g));
     }
   for (Group& g : groups)
-    if (g.merged) {                             // behind the shared region
+    if (g.merged) {                             // behind the shared workspace
       g.ws_off = max_elems + side_elems;
-      g.mem_off = max_count + side_members;
       g.part_off = max_part + side_part;
       side_elems += (size_t)g.count * g.N * g.N;
-      side_members += g.count;
       side_part += part_of(g);
     }
-  const size_t elems = std::max<size_t>(max_elems + side_elems, 1), members_cap = std::max<size_t>((size_t)max_count + (size_t)side_members, 1);
+  size_t n_members = 0;                         // per-member state: every group its own range
+  for (Group& g : groups) { g.mem_off = (int)n_members; n_members += (size_t)g.count; }
+  const size_t elems = std::max<size_t>(max_elems + side_elems, 1), members_cap = std::max<size_t>(n_members, 1);
   CUADMM_HIP_TRY(hipMalloc(&d_ids, sizeof(int) * ids.size()));
   { int rc_ = staged_h2d(d_ids, ids.data(), sizeof(int) * ids.size()); if (rc_) return rc_; }
   CUADMM_HIP_TRY(hipMalloc(&X0, sizeof(double) * elems));
   CUADMM_HIP_TRY(hipMalloc(&S, sizeof(double) * elems));
   CUADMM_HIP_TRY(hipMalloc(&Y, sizeof(double) * elems));
   CUADMM_HIP_TRY(hipMalloc(&T, sizeof(double) * elems));
-  {
-    bool any_clean = false;
-    for (const Group& g : groups) any_clean = any_clean || (opt.lg_clean != 0 && g.N <= clean_max_n);
-    if (any_clean) {
-      CUADMM_HIP_TRY(hipMalloc(&Mw, sizeof(double) * elems));
-      CUADMM_HIP_TRY(hipMalloc(&d_cont, sizeof(int) * 2 * members_cap));
-    }
-  }
   CUADMM_HIP_TRY(hipMalloc(&colsum, sizeof(double) * std::max<size_t>(max_cols, 1)));
-  CUADMM_HIP_TRY(hipMalloc(&scale, sizeof(double) * std::max<size_t>(members_cap, 1)));
+  CUADMM_HIP_TRY(hipMalloc(&scale, sizeof(double) * members_cap));
   CUADMM_HIP_TRY(hipMalloc(&d_state, sizeof(SignDevState) * 2 * members_cap));
   CUADMM_HIP_TRY(hipMalloc(&d_done, sizeof(SignDone) * members_cap));
   CUADMM_HIP_TRY(hipMalloc(&d_group, sizeof(int) * 2 * (size_t)(1 + n_merged)));
-  CUADMM_HIP_TRY(hipMalloc(&d_bar, sizeof(unsigned) * 3 * members_cap));      // sets 0 / 1: fused projections, alternating; set 2: the others (zeroed at their start)
-  CUADMM_HIP_TRY(hipMemset(d_bar, 0, sizeof(unsigned) * 3 * members_cap));
+  CUADMM_HIP_TRY(hipMalloc(&d_bar, sizeof(unsigned) * 2 * members_cap));
+  CUADMM_HIP_TRY(hipMemset(d_bar, 0, sizeof(unsigned) * 2 * members_cap));
   bar_stride = members_cap;
   {
     size_t cs_total = 0;
@@ -972,43 +913,14 @@ int SignPsd::build(const int* blk, const std::vector<int>& members) {
 }
 
 void SignPsd::release() {
-  if (graph_exec) { hipError_t e = hipGraphExecDestroy(graph_exec); (void)e; graph_exec = nullptr; }
-  for (void* p : {(void*)d_ids, (void*)X0, (void*)S, (void*)Y, (void*)T, (void*)colsum, (void*)scale, (void*)d_state, (void*)d_part, (void*)d_done, (void*)d_bar, (void*)d_xcc, (void*)Mw, (void*)d_cont, (void*)colsum_f})
+  for (void* p : {(void*)d_ids, (void*)X0, (void*)S, (void*)Y, (void*)T, (void*)colsum, (void*)scale, (void*)d_state, (void*)d_part, (void*)d_done, (void*)d_bar, (void*)d_xcc, (void*)colsum_f})
     if (p) { hipError_t e = hipFree(p); (void)e; }
   if (d_group) { hipError_t e = hipFree(d_group); (void)e; d_group = nullptr; }
   if (h_group) { hipError_t e = hipHostFree(h_group); (void)e; h_group = nullptr; }
   d_ids = nullptr; d_state = nullptr; d_part = nullptr; d_done = nullptr; d_bar = nullptr; d_xcc = nullptr;
   X0 = S = Y = T = colsum = scale = nullptr;
-  Mw = nullptr; d_cont = nullptr; colsum_f = nullptr;
+  colsum_f = nullptr;
   groups.clear();
-}
-
-// out = svec(P_+(smat(in))) for every member block; boff / bn are the plan's device arrays (all blocks).  Asynchronous.
-// The fixed schedule is ~95 dependent launches per group (1.0 ms for a handful of N = 128 blocks, ~10 us per dependent
-// kernel).  Replaying them from a hipGraph was measured and does NOT help (1.835 vs 1.814 ms per PlanarHand projection):
-// the cost is the device-side drain/flush between dependent kernels, not host launch overhead.  Kept behind
-// CUADMM_PSD_GRAPH=1 for re-measurement on other ROCm versions.
-int SignPsd::project(const double* in, double* out, const long long* boff, const int* bn, int* d_fail, hipStream_t st) {
-  const bool use_graph = opt.graph == 1 && !opt.debug;
-  if (!use_graph || !allow_graph || st == nullptr || groups.empty()) return project_launch(in, out, boff, bn, d_fail, st);
-  if (graph_exec && (g_in != in || g_out != out || g_boff != boff || g_bn != bn || g_fail != d_fail)) {
-    hipError_t e = hipGraphExecDestroy(graph_exec); (void)e;
-    graph_exec = nullptr;
-  }
-  if (!graph_exec) {
-    hipGraph_t graph = nullptr;
-    CUADMM_HIP_TRY(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-    int rc = project_launch(in, out, boff, bn, d_fail, st);
-    hipError_t e = hipStreamEndCapture(st, &graph);
-    if (rc) { if (graph) { hipError_t e2 = hipGraphDestroy(graph); (void)e2; } return rc; }
-    if (e != hipSuccess) { set_error("psd sign path: graph capture failed: %s", hipGetErrorString(e)); return CUADMM_ERR_INVALID; }
-    e = hipGraphInstantiate(&graph_exec, graph, nullptr, nullptr, 0);
-    { hipError_t e2 = hipGraphDestroy(graph); (void)e2; }
-    if (e != hipSuccess) { graph_exec = nullptr; set_error("psd sign path: graph instantiate failed: %s", hipGetErrorString(e)); return CUADMM_ERR_INVALID; }
-    g_in = in; g_out = out; g_boff = boff; g_bn = bn; g_fail = d_fail;
-  }
-  CUADMM_HIP_TRY(hipGraphLaunch(graph_exec, st));
-  return CUADMM_OK;
 }
 
 static LgPath lg_path(const PsdOptions& opt, int N, int cnt) {
@@ -1020,14 +932,18 @@ static LgPath lg_path(const PsdOptions& opt, int N, int cnt) {
   p.decide_kernel = opt.lg_decide ? opt.lg_decide == 2 : p.ntiles > 300;
   // a handful of mid-size blocks: every step and the final product in ONE launch (lg_sign_cluster_kernel)
   p.cluster = opt.lg_cluster != 0 && !p.decide_kernel && lg_small_tiles(true, N, cnt, opt.lg_tile) && (long long)p.ntiles * cnt <= std::max(opt.lg_cluster_wgs, 8);
-  // one XCD has 32 CUs x 4 workgroups of this kernel: a member's workgroups go to ONE XCD only while everything mapped there stays
-  // co-resident with room to spare; else plain order over the whole chip (agent-scope barriers)
+  // one XCD has 32 CUs x 3 workgroups of this kernel: a member's workgroups go to ONE XCD only while everything mapped there stays
+  // co-resident; else plain order over the whole chip (agent-scope barriers)
   p.spread = ((cnt + 7) / 8) * p.ntiles > 96 ? 1 : 0;
   p.cluster_wgs = p.spread ? cnt * p.ntiles : 8 * ((cnt + 7) / 8) * p.ntiles;
   return p;
 }
 
-int SignPsd::project_launch(const double* in, double* out, const long long* boff, const int* bn, int* d_fail, hipStream_t st) {
+// out = svec(P_+(smat(in))) for every member block; boff / bn are the plan's device arrays (all blocks).  Asynchronous.
+// The fixed schedule is ~95 dependent launches per group (1.0 ms for a handful of N = 128 blocks, ~10 us per dependent
+// kernel).  Replaying them from a captured graph was measured and does NOT help (1.835 vs 1.814 ms per PlanarHand projection):
+// the cost is the device-side drain/flush between dependent kernels, not host launch overhead.
+int SignPsd::project(const double* in, double* out, const long long* boff, const int* bn, int* d_fail, hipStream_t st) {
   const bool sync_ok = opt.sign_sync != 0;
   hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
   if (st) { hipError_t e = hipStreamIsCapturing(st, &cap); (void)e; }
@@ -1059,21 +975,16 @@ void SignPsd::cluster_add(ClusterMulti& cm, const Group& g, int* d_fail, int max
   sa.ids = d_ids + g.begin;
   sa.count = g.count;
   sa.step = 0;
-  // fused prologue / epilogue (psd_lg_fuse; not under a graph capture's replay -- the counter set alternates per projection -- and only where the
-  // one-launch prologue applies at all, N <= 512): this projection counts in set bar_par and zeroes the other one
-  const bool fused = opt.lg_fuse != 0 && opt.graph != 1 && !opt.debug && g.N <= 512;
-  // (the groups that run one after the other share the region at offset 0 and with it the counters: ONE alternation for all of them)
-  int& bar_par = g.merged ? g.bar_par : shared_bar_par;
-  const int par = fused ? bar_par : 2;          // (a projection that is not fused zeroes its counters itself, in a set of its own: it must not dirty the alternating ones)
-  if (fused) bar_par ^= 1;
+  // fused prologue / epilogue (psd_lg_fuse; only where the one-launch prologue applies at all, N <= 512): this projection counts in set
+  // g.bar_par of the group's counters and zeroes the other one.  A run that is not fused counts in set 0 and zeroes it at its start.
+  const bool fused = opt.lg_fuse != 0 && !opt.debug && g.N <= 512;
+  const int par = fused ? g.bar_par : 0;
+  if (fused) g.bar_par ^= 1;
   sa.bar = d_bar + (size_t)par * bar_stride + g.mem_off;
-  sa.clean = (Mw && opt.lg_clean != 0 && g.N <= clean_max_n) ? 1 : 0;
-  sa.cont = sa.clean ? d_cont + 2 * (size_t)g.mem_off : nullptr;
-  sa.cap = max_steps;
   // psd_lg_cluster = 2: agent-scope barriers always (A/B, tests)
-  cm.ca[i] = ClusterArgs{S + g.ws_off, T + g.ws_off, Y + g.ws_off, X0 + g.ws_off, sa.clean ? Mw + g.ws_off : nullptr, sa.bar,
+  cm.ca[i] = ClusterArgs{S + g.ws_off, T + g.ws_off, Y + g.ws_off, X0 + g.ws_off, sa.bar,
                          d_xcc + (size_t)kClusterXccStride * (size_t)g.slot, d_fail, g.N, max_steps, g.count, opt.lg_cluster == 2 ? 1 : 0, path.spread,
-                         fused ? 1 : 0, colsum_f + g.cs_off, d_bar + (size_t)(fused ? par ^ 1 : 2) * bar_stride + g.mem_off};
+                         fused ? 1 : 0, colsum_f + g.cs_off, fused ? d_bar + (size_t)(par ^ 1) * bar_stride + g.mem_off : nullptr};
   cm.wg_begin[i + 1] = cm.wg_begin[i] + (path.cluster_wgs + 7) / 8 * 8;
   cm.mem_begin[i + 1] = cm.mem_begin[i] + g.count;
 }
@@ -1092,10 +1003,7 @@ int SignPsd::cluster_run(ClusterMulti& cm, bool prologue, const double* in, doub
     if (lds_prep > 48 * 1024) CUADMM_HIP_TRY(once(reinterpret_cast<const void*>(lg_prep_kernel)));
     hipLaunchKernelGGL(lg_prep_kernel, dim3(cm.mem_begin[cm.n]), dim3(1024), lds_prep, st, in, boff, bn, cm);
   }
-  bool any_clean = false;                      // (the instantiation without the clean mega-lift's second slot when no group takes one: not a register more)
-  for (int i = 0; i < cm.n; ++i) any_clean = any_clean || cm.sg[i].clean != 0;
-  if (any_clean) hipLaunchKernelGGL((lg_sign_cluster_kernel<32, 32, true>), dim3(cm.wg_begin[cm.n]), dim3(256), 0, st, cm);
-  else hipLaunchKernelGGL((lg_sign_cluster_kernel<32, 32, false>), dim3(cm.wg_begin[cm.n]), dim3(256), 0, st, cm);
+  hipLaunchKernelGGL((lg_sign_cluster_kernel<32, 32>), dim3(cm.wg_begin[cm.n]), dim3(256), 0, st, cm);
   for (int i = 0; i < cm.n; ++i) cm.sg[i].step = cm.ca[i].max_steps;          // the steps enqueued
   const unsigned gx = (unsigned)std::min<size_t>(((size_t)maxN * maxN / 2 + 255) / 256, 1024);
   if (!fused) hipLaunchKernelGGL(lg_pack_steps_kernel, dim3(gx, cm.mem_begin[cm.n]), dim3(256), 0, st, boff, bn, out, d_fail, d_steps, cm);
@@ -1122,7 +1030,7 @@ int SignPsd::launch_group(Group& g, const double* in, double* out, const long lo
     double* const T = this->T + g.ws_off;
     double* const scale = this->scale + g.mem_off;
     int* const d_group = this->d_group + 2 * g.slot;
-    unsigned* const d_bar = this->d_bar + 2 * bar_stride + g.mem_off;      // (set 2: cluster_add's choice for a projection that is not fused)
+    unsigned* const d_bar = this->d_bar + g.mem_off;       // (set 0: cluster_add's choice for a projection that is not fused)
     SignArgs sa{};
     sa.st = static_cast<SignDevState*>(d_state) + 2 * (size_t)g.mem_off;
     sa.done = static_cast<SignDone*>(d_done) + g.mem_off;
@@ -1134,10 +1042,6 @@ int SignPsd::launch_group(Group& g, const double* in, double* out, const long lo
     sa.count = cnt;
     sa.step = 0;
     sa.bar = d_bar;
-    sa.clean = (Mw && opt.lg_clean != 0 && g.N <= clean_max_n) ? 1 : 0;
-    sa.cont = sa.clean ? d_cont + 2 * (size_t)g.mem_off : nullptr;
-    sa.cap = max_steps;
-    double* const M = sa.clean ? Mw + g.ws_off : nullptr;
     ClusterMulti cm{};
     if (cluster) cluster_add(cm, g, d_fail, max_steps);
     if (!(cluster && N <= 512)) {              // else: the one-launch variant's own prologue (cluster_run)
@@ -1167,12 +1071,12 @@ int SignPsd::launch_group(Group& g, const double* in, double* out, const long lo
       for (int it = 0; it < chunk && enq < max_steps; ++it, ++enq) {
         // Y = S*S ; [decision] ; T = 1.5 mu S - 0.5 mu^3 S*Y ; finished members return at once
         sa.step = enq;
-        if ((rc = lg_gemm_mirror<1>(N, cnt, s, s, 1.0, 0.0, nullptr, Y, st, sa, M, opt.lg_tile))) return rc;
+        if ((rc = lg_gemm_mirror<1>(N, cnt, s, s, 1.0, 0.0, nullptr, Y, st, sa, nullptr, opt.lg_tile))) return rc;
         if (decide_kernel) {
           hipLaunchKernelGGL(lg_decide_kernel, dim3(cnt), dim3(256), 0, st, sa, ntiles);
-          if ((rc = lg_gemm_mirror<4>(N, cnt, s, Y, 0.0, 0.0, s, t, st, sa, M, opt.lg_tile))) return rc;
+          if ((rc = lg_gemm_mirror<4>(N, cnt, s, Y, 0.0, 0.0, s, t, st, sa, nullptr, opt.lg_tile))) return rc;
         } else {
-          if ((rc = lg_gemm_mirror<2>(N, cnt, s, Y, 0.0, 0.0, s, t, st, sa, M, opt.lg_tile))) return rc;
+          if ((rc = lg_gemm_mirror<2>(N, cnt, s, Y, 0.0, 0.0, s, t, st, sa, nullptr, opt.lg_tile))) return rc;
         }
         std::swap(s, t);
       }

@@ -23,34 +23,33 @@ struct PsdOptions {
   int lg_pad32 = 1;        // psd_lg_pad32: groups on 32 x 32 tiles pad to a multiple of 32
   int lg_decide = 0;       // psd_lg_decide: 0 = by tile count, 1 = decisions inside the product kernels, 2 = a separate kernel
   int lg_merge = 1;        // psd_lg_merge: one-launch groups of different padded sizes share ONE launch (workspaces of their own)
-  int lg_clean = 0;        // psd_lg_clean: 1 = groups padded to at most 512 take the CLEAN mega-lift where it pays (sign_sched.h: two step slots, no cap).  Built, parity-green and OFF: on the shipped inputs it never pays (NOTEBOOK.md "Round 6")
   int lg_fuse = 1;         // psd_lg_fuse: the one-launch kernel does its own prologue (svec -> X0, column sums, S, state) and epilogue (svec store): one launch instead of three
-  int lg_cluster_wgs = 224;  // psd_lg_cluster_wgs: the largest grid the one-launch sign kernel takes (its workgroups must be co-resident: four of them fit a CU)
+  int lg_cluster_wgs = 224;  // psd_lg_cluster_wgs: the largest grid the one-launch sign kernel takes (its workgroups must be co-resident: three of them fit a CU, 119 VGPRs + 16 AGPRs)
   int lg_cluster = 1;      // psd_lg_cluster: a handful of mid-size blocks run their whole sign iteration in one launch (per-member barriers)
-  int graph = 0;           // psd_graph: replay the launch sequence from a hipGraph (measured: no gain)
   int sign_maxsteps = 0;   // psd_sign_maxsteps: cap of the schedule (0: SignSched::kCap)
   int sign_sync = 1;       // psd_sign_sync: poll "members not finished" between chunks of steps
   int sign_ws_mb = 8192;   // psd_sign_ws_mb: workspace bound of a group
   int debug = 0;           // developer aid: CUADMM_PSD_DEBUG (phase ticks of the kernels on stderr; serialises the classes)
 
-  // the defaults: each option's environment variable (round 1 / 2 names) is consulted ONCE here, per plan -- never cached
+  // the defaults: each option's environment variable (round 1 / 2 names) is consulted ONCE here, per plan -- never cached -- and
+  // goes through set() like a value from cuadmm_set_option
   static PsdOptions from_env() {
     PsdOptions o;
-    struct { const char* name; int* field; } tab[] = {
-        {"CUADMM_PSD_DEBUG", &o.debug},           {"CUADMM_PSD_WAVE4_MIN", &o.wave4_min}, {"CUADMM_PSD_SIGN_MIN", &o.sign_min},
-        {"CUADMM_PSD_W32_OCC", &o.w32_occ},       {"CUADMM_PSD_CU_OCC", &o.cu_occ},       {"CUADMM_PSD_OVERLAP", &o.overlap},
-        {"CUADMM_PSD_N16", &o.n16_sign},    {"CUADMM_PSD_N32", &o.n32_sign},
-        {"CUADMM_PSD_MID", &o.mid},             {"CUADMM_PSD_LG_CLUSTER", &o.lg_cluster}, {"CUADMM_PSD_LDS_TRIPLE", &o.lds_triple},
-        {"CUADMM_PSD_LG_MERGE", &o.lg_merge},   {"CUADMM_PSD_LG_CLEAN", &o.lg_clean},
-        {"CUADMM_PSD_LG_FUSE", &o.lg_fuse},     {"CUADMM_PSD_LG_CLUSTER_WGS", &o.lg_cluster_wgs}};
-    for (auto& t : tab)
-      if (const char* e = getenv(t.name)) {
+    static const struct { const char* env; const char* key; } tab[] = {
+        {"CUADMM_PSD_DEBUG", "psd_debug"},           {"CUADMM_PSD_WAVE4_MIN", "psd_wave4_min"}, {"CUADMM_PSD_SIGN_MIN", "psd_sign_min"},
+        {"CUADMM_PSD_W32_OCC", "psd_w32_occ"},       {"CUADMM_PSD_CU_OCC", "psd_cu_occ"},       {"CUADMM_PSD_OVERLAP", "psd_overlap"},
+        {"CUADMM_PSD_N16", "psd_n16"},               {"CUADMM_PSD_N32", "psd_n32"},             {"CUADMM_PSD_MID", "psd_mid"},
+        {"CUADMM_PSD_LG_CLUSTER", "psd_lg_cluster"}, {"CUADMM_PSD_LDS_TRIPLE", "psd_lds_triple"}, {"CUADMM_PSD_LG_MERGE", "psd_lg_merge"},
+        {"CUADMM_PSD_LG_FUSE", "psd_lg_fuse"},       {"CUADMM_PSD_LG_CLUSTER_WGS", "psd_lg_cluster_wgs"}};
+    for (const auto& t : tab)
+      if (const char* e = getenv(t.env)) {
         // historical spellings: N16 / N32 = "eig" (register eigensolver), MID = "eig" | "lds"
-        if (!strcmp(e, "eig")) *t.field = (t.field == &o.mid) ? 1 : 0;
-        else if (!strcmp(e, "lds")) *t.field = 2;
-        else *t.field = atoi(e);
+        int v;
+        if (!strcmp(e, "eig")) v = strcmp(t.key, "psd_mid") ? 0 : 1;
+        else if (!strcmp(e, "lds")) v = 2;
+        else v = atoi(e);
+        o.set(t.key, v);
       }
-    if (o.debug < 0) o.debug = 0;
     return o;
   }
   // returns false when the key is not one of this struct's
@@ -70,14 +69,12 @@ struct PsdOptions {
     else if (k == "psd_lg_decide") lg_decide = v;
     else if (k == "psd_lg_cluster") lg_cluster = v;
     else if (k == "psd_lg_merge") lg_merge = v;
-    else if (k == "psd_lg_clean") lg_clean = v;
     else if (k == "psd_lg_fuse") lg_fuse = v;
     else if (k == "psd_lg_cluster_wgs") lg_cluster_wgs = v < 8 ? 8 : (v > 960 ? 960 : v);
-    else if (k == "psd_graph") graph = v;
     else if (k == "psd_sign_maxsteps") sign_maxsteps = v;
     else if (k == "psd_sign_sync") sign_sync = v;
     else if (k == "psd_sign_ws_mb") sign_ws_mb = v < 1 ? 1 : v;
-    else if (k == "psd_debug") debug = v;
+    else if (k == "psd_debug") debug = v < 0 ? 0 : v;
     else return false;
     return true;
   }

@@ -75,8 +75,6 @@ void cuadmm_destroy(cuadmm_solver* s);
  *                   flight beyond the current one (0 ... 3, default 1), rows per barrier (0 = by size).  A/B switches: the same solve to the last few bits.
  *   "psd_lg_fuse"   1 (default) = a handful of blocks of 65 <= n <= 512 run their whole projection -- svec -> dense, norm, every step of the matrix-sign
  *                   iteration, final product, svec store -- in ONE launch; 0 = prologue and epilogue as launches of their own (bit-identical)
- *   "psd_lg_clean"  1 = the uncapped ("clean") mega-lift of the sign schedule for groups padded to <= 480 (csrc/sign_sched.h); default 0: measured slower
- *                   on every shipped input
  *   "duo_share_device", "duo_exchange"   the in-process group of cuadmm_duo_init(device_num_requested = N): all engines on the
  *                   caller's device; all-reduce through device memory (1), host staging (0), chosen by peer accessibility (-1, default)
  *   (every other switch: INTEGRATION.md section 6)

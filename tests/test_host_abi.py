@@ -604,18 +604,21 @@ def test_ordering_and_tail_plan_of_the_fixtures_are_pinned(name, m, nnzL, tail_k
         lib.cuadmm_aat_free(h)
 
 
-def test_engine_options_are_validated_without_a_device():
+def test_engine_options_are_validated_and_retired_keys_refused_without_a_device():
     """cuadmm_set_option on a fresh handle touches no device: known keys are accepted, the one-pass kernel's ring depth is range-checked
-    (csrc/engine.hip: tail_depth 0 ... 3), an unknown key is an error with a message."""
+    (csrc/engine.hip: tail_depth 0 ... 3), an unknown key is an error with a message -- the keys of the removed sign-path variants
+    (psd_lg_clean, psd_graph) included."""
     import ctypes as C
     lib = cuadmm_amd.load()
     h = C.c_void_p()
     assert lib.cuadmm_create(C.byref(h)) == 0
     try:
-        for key, val in (("tail_order", 0), ("tail_zreg", 0), ("tail_rb", 2), ("tail_depth", 3), ("psd_lg_clean", 1), ("tail_pivot", 1)):
+        for key, val in (("tail_order", 0), ("tail_zreg", 0), ("tail_rb", 2), ("tail_depth", 3), ("psd_lg_fuse", 1), ("tail_pivot", 1)):
             assert lib.cuadmm_set_option(h, key.encode(), C.c_double(val)) == 0, key
         assert lib.cuadmm_set_option(h, b"tail_depth", C.c_double(4)) != 0
         assert b"tail_depth" in lib.cuadmm_last_error()
-        assert lib.cuadmm_set_option(h, b"no_such_option", C.c_double(1)) != 0
+        for key in (b"no_such_option", b"psd_lg_clean", b"psd_graph"):
+            assert lib.cuadmm_set_option(h, key, C.c_double(1)) != 0, key
+            assert key in lib.cuadmm_last_error()
     finally:
         lib.cuadmm_destroy(h)
