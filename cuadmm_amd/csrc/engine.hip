@@ -6,10 +6,13 @@
 //   At_csr  : rows = local svec slots, columns = constraints in the factor's PERMUTED order
 //   A_csr   : rows = constraints in permuted order, columns = local svec slots
 //   out     : [A*X (m) | sum Rd^2 | sum C.X | A*(S-C) (m)]  -> one D2H per (half-)iteration
-// The constraint-space vectors (y, b, Rp, rhs; length m) live on the host in permuted order, next
-// to the host LDL^T factor of P(AA^T + eps I)P^T, so the reference's two scatter kernels per solve
-// (perform_permutation, solver.cu:487,500) disappear: permutation is folded into the matrices.
-// Host<->device traffic per iteration: m doubles up (y), 2m+2 doubles down (ADMM phase).
+// The constraint-space vectors (y, b, normA; length m) are kept in the PERMUTED order of the LDL^T factor of P(AA^T + eps I)P^T, so the
+// reference's two scatter kernels per solve (perform_permutation, solver.cu:487,500) disappear: the permutation is folded into the
+// matrices.  The factor is computed once on the host; the solve runs on the device whenever the plan allows it (every shipped input):
+// level sweeps over the shallow rest of the elimination forest, packed inverses of the tree tops, and the dense tail W = inv(L22) applied
+// in one pass (lead_solve.hip, tail_solve.hip; DESIGN.md sections 3 - 4).  y then never leaves the device: the host fetches the four
+// scalars of the stopping test per iteration through a mapped pinned buffer.  With the solve on the host (option host_solve, or a probe
+// that rejects the explicit inverse) the traffic per iteration is m doubles up (y), 2m+2 doubles down (ADMM phase).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -248,24 +251,13 @@ struct cuadmm_solver {
     int tail_one_pass = 1;        // "tail_one_pass": the GPU tail applied in one pass over inv(L22) (0: two triangular GEMVs)
     int solve_next = 1;           // "solve_next": the y-solve of iteration k + 1 is enqueued before the host waits for iteration k (fetch_out)
     int tail_max_k = 32768;       // "tail_max_k": cap of the planner's GPU tail (<= 65 536: 3 x 8 K^2 bytes while it is built, 2 x 8 K^2 afterwards)
-    int tail_dd = 0;              // "tail_dd": experiment (tail_solve.h)
     int tail_refine = 0;          // "tail_refine": accuracy mode of the tail (tail_solve.h)
     int tail_pivot = 1;           // "tail_pivot": the tail's dense LDL^T with diagonal pivoting (0: unpivoted, rounds 2 - 5)
-    int tail_fat = 0;             // "tail_fat": the one-pass kernel on 512-thread workgroups with twice the rows in flight for K <= 10 240 (measured: slower; A/B)
-    int tail_depth = 1;           // "tail_depth" / "tail_order": ring depth and row walk of the tail's one-pass kernel (tail_solve.hip)
-    int tail_order = 2;
-    int tail_group_pf = 0;        // "tail_group_pf": see TailSolve::group_pf (measured slower, off)
-    int tail_zreg = 1;            // "tail_zreg": z in registers in that kernel where it fits
-    int tail_rb = 0;              // "tail_rb": rows per barrier of that kernel (0: by size)
-    int tail_prefetch = 1;        // "tail_prefetch": the tail's one-pass kernel keeps the next rows in flight across its barrier (0: rounds 3 - 5; A/B)
     int tail_shard = 1;           // "tail_shard": world > 1, replicated solve: every rank applies 1 / world of the tail's rows, the K partial
                                   // results are all-reduced (0: every rank applies the whole tail)
     int l21_device = 1;           // "l21_device": hybrid y-solve allowed (L21 on the device beside the tail when the forest is too deep; 0: host, 2: whenever the sweeps stay on the host)
     int lead_debug = 0;           // "lead_debug": statistics of the leading elimination forest on stderr at init (developer aid)
-    double tail_pinv_tol = 0.0;   // "tail_pinv_tol": experiment (tail_solve.h)
-    double pinv_tol = 0.0;        // "pinv_tol": the same for EVERY pivot of the device-side solve (tail, tree tops, leading sweeps): experiment (lead_solve.h)
     int lead_small_kb = 0;        // "lead_small_kb": LDS bound of the trees that share a workgroup in fours (lead_solve.h; 0 = chosen at build from 4 / 8 / 16)
-    int lead_tops_refine = 0;     // "lead_tops_refine": one refinement step per direction in the dense tree tops (A/B: measured, no effect -- lead_solve.h)
     int lead_tops = -1;           // "lead_tops": dense tree tops (lead_solve.h): -1 = when the forest is too deep for the sweeps, 0 = never, L = always, cut at height L
     int debug_eig = 0;            // developer aid
   } sw;
@@ -787,7 +779,8 @@ static int init_factor(Solver* s, const InitIn& in, InitCtx& c) {
   CUADMM_INIT_STAGE_PROLOGUE
   // --- factor of A A^T + 1e-15 I (solver.cu:91-96, cholesky_cpu.h:62-141): ordering, symbolic analysis and the sparse
   // leading columns on the host; when the cost model finds a dense tail, its Schur complement is factored (dense
-  // LDL^T) and inverted on the GPU and applied as two GEMVs per solve (tail_solve.hip).
+  // LDL^T with diagonal pivoting) and inverted on the GPU, and x = W^T D^-1 W z is applied in ONE pass over W = inv(L22)
+  // per solve (tail_solve.hip; the two triangular GEMVs remain as the fallback and behind option tail_one_pass = 0).
   // CUADMM_TAIL_K: 0 = everything on the host, k > 0 forces the tail size (A/B measurements).
   {
     int max_k = std::max(64, std::min(s->sw.tail_max_k, 65536));
@@ -807,17 +800,8 @@ static int init_factor(Solver* s, const InitIn& in, InitCtx& c) {
       const int64_t* srp; const int* sci; const double* sv;
       rc = cuadmm_aat_tail_schur(s->fac, &srp, &sci, &sv);
       s->tail.one_pass = s->sw.tail_one_pass != 0;
-      s->tail.prefetch = s->sw.tail_prefetch != 0;
-      s->tail.depth = s->sw.tail_depth;
-      s->tail.order = s->sw.tail_order;
-      s->tail.rows_per_group = s->sw.tail_rb;
-      s->tail.zreg = s->sw.tail_zreg != 0;
-      s->tail.group_pf = s->sw.tail_group_pf != 0;
-      s->tail.fat = s->sw.tail_fat != 0;
-      s->tail.dd_dot = s->sw.tail_dd != 0;
       s->tail.refine = s->sw.tail_refine != 0;
       s->tail.pivot = s->sw.tail_pivot != 0;
-      s->tail.pinv_tol = std::max(s->sw.tail_pinv_tol, s->sw.pinv_tol);
       if (!rc) rc = s->tail.build_from_schur(reinterpret_cast<const long long*>(srp), sci, sv, tk, s->st);
       // The tail is applied as an explicit inverse built without pivoting (tail_solve.hip); with (nearly) dependent
       // constraints the pivots approach the regularisation 1e-15 and inv(L22) could lose accuracy silently.  Probe it with
@@ -1165,10 +1149,8 @@ static int init_solve_plan(Solver* s, const InitIn& in, InitCtx& c) {
     const int64_t* Lp; const int* Li; const double* Lx; const double* D;
     if ((rc = cuadmm_aat_factor_arrays(s->fac, &Lp, &Li, &Lx, &D))) return rc;
     s->lead.stream_only = s->sw.lead_stream != 0;
-    s->lead.pinv_tol = s->sw.pinv_tol;
     s->lead.debug = s->sw.lead_debug != 0;
     s->lead.force_hybrid = s->sw.l21_device == 2;
-    s->lead.tops_refine = s->sw.lead_tops_refine != 0;
     s->lead.small_kb = std::max(0, std::min(s->sw.lead_small_kb, 36));
     s->lead.tops_level = s->sw.l21_device == 2 ? 0 : (s->sw.lead_tops >= 0 ? s->sw.lead_tops : (cuadmm_aat_tail_tops(s->fac) > 0 ? cuadmm_aat_tail_tops(s->fac) : -1));
     if ((rc = s->lead.build(m, s->tail.k, Lp, Li, Lx, D, s->sw.l21_device != 0))) return rc;
@@ -1408,21 +1390,10 @@ int cuadmm_set_option(cuadmm_solver* s, const char* key, double value) {
   else if (k == "lead_stream") s->sw.lead_stream = (int)value;
   else if (k == "lead_debug") s->sw.lead_debug = (int)value;
   else if (k == "lead_tops") s->sw.lead_tops = (int)value;
-  else if (k == "lead_tops_refine") s->sw.lead_tops_refine = (int)value;
   else if (k == "lead_small_kb") s->sw.lead_small_kb = (int)value;
-  else if (k == "tail_pinv_tol") s->sw.tail_pinv_tol = value;
-  else if (k == "pinv_tol") s->sw.pinv_tol = value;
   else if (k == "l21_device") s->sw.l21_device = (int)value;
   else if (k == "tail_one_pass") s->sw.tail_one_pass = (int)value;
   else if (k == "tail_shard") s->sw.tail_shard = (int)value;
-  else if (k == "tail_prefetch") s->sw.tail_prefetch = (int)value;
-  else if (k == "tail_depth") { if (value < 0 || value > 3) { set_error("set_option: tail_depth must be 0 .. 3"); return CUADMM_ERR_INVALID; } s->sw.tail_depth = (int)value; }
-  else if (k == "tail_order") s->sw.tail_order = value == 2 ? 2 : (value != 0 ? 1 : 0);
-  else if (k == "tail_rb") s->sw.tail_rb = (int)value;
-  else if (k == "tail_zreg") s->sw.tail_zreg = (int)value;
-  else if (k == "tail_group_pf") s->sw.tail_group_pf = (int)value;
-  else if (k == "tail_fat") s->sw.tail_fat = (int)value;
-  else if (k == "tail_dd") s->sw.tail_dd = (int)value;
   else if (k == "tail_refine") s->sw.tail_refine = (int)value;
   else if (k == "tail_pivot") s->sw.tail_pivot = (int)value;
   else if (k == "tail_max_k") s->sw.tail_max_k = (int)value;
@@ -1430,14 +1401,13 @@ int cuadmm_set_option(cuadmm_solver* s, const char* key, double value) {
   else if (k == "debug_eig") s->sw.debug_eig = (int)value;
   else if (s->plan.opt.set(k, value)) {}                      // "psd_*": the projection planner's switches (psd_options.h)
   else if (k == "batch_mixed") s->bt.allow_mixed = value != 0;
-  else if (k == "lazy_unscale") s->lazy_unscale = (int)value;
-  else if (k == "psd_hint") s->opt_hint = (int)value;
+  else if (k == "lazy_unscale") s->lazy_unscale = (int)value;            // 0: unscale X, y, S at the end of every solve
+  else if (k == "psd_hint") s->opt_hint = (int)value;                    // schedule warm start (before init)
   else if (k == "duo_cpu_eig_on_gpu") s->duo_cpu_eig_on_gpu = (int)value;
   else if (k == "duo_share_device") s->duo_share_device = (int)value;   // duo_init(device_num_requested = N) from one process: all N engines on this solver's device
-  else if (k == "tiny_sign") s->opt_tiny_sign = (int)value;                               // n <= 8 on the sign kernel (before init)                                     // schedule warm start (before init)                            // 0: unscale X, y, S at the end of every solve
+  else if (k == "tiny_sign") s->opt_tiny_sign = (int)value;              // n <= 8 on the sign kernel (before init)
   else if (k == "duo_exchange") s->duo_exchange = (int)value;           // in-process group: -1 choose, 0 host-staged, 1 device-side exchange
   else if (k == "duo_inject_fail") { s->duo_inject = (long long)value; if (s->group) duo_group_inject(s->group, s->duo_inject); }   // test hook
-  else if (k == "graph") {}
   else { s->option_log.pop_back(); set_error("set_option: unknown key '%s'", key); return CUADMM_ERR_INVALID; }
   // a group handle: every rank follows -- AFTER the key has been validated on the leader; a child that refuses leaves the option
   // out of the log (it is not replayed on later children) and the error with the caller

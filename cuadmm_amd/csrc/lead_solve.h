@@ -47,7 +47,6 @@ struct LeadSolve {
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
   bool debug = false;           // option lead_debug: forest statistics on stderr at build
   int small_kb = 0;             // option lead_small_kb: trees that need at most this much LDS share a workgroup in fours (one wavefront each); 0: chosen at build
-  double pinv_tol = 0.0;        // option pinv_tol (experiment): leading pivots below it in magnitude are treated as infinite (1 / d := 0), like the tail's
   bool stream_only = false;     // option lead_stream = 1: every tree on the streaming kernels (A/B, tests)
   bool ready = false;
   double est_us = 0;            // cost model used to decide (per solve)
@@ -92,15 +91,8 @@ struct LeadSolve {
   long long *kt_rp = nullptr, *tk_cp = nullptr;          // L_KT by tail rows (CSR) and by T columns (CSC), T-local / tail-local indices
   int *kt_ci = nullptr, *tk_ri = nullptr;
   double *kt_v = nullptr, *tk_v = nullptr;
-  // optional: one step of iterative refinement per direction with the SPARSE L_TT (z = W r; z += W (r - L z)).  Built to test whether the
-  // explicit inverses are what moves PushBox_N=50's primal objective by 9e-8 from the oracle's at a tail of 8 448 columns: they are not --
-  // with and without the step 8.0e-8 / 9.2e-8, and 9.0e-8 with the WHOLE leading part swept on the host at that tail (profiles/
-  // r05_tops_deviation.txt).  The inverses are benign (max |W| = 2.3); the deviation follows the tail's boundary among the 9 301 pivots
-  // at the regularisation (1e-15: dependent constraints; 5e-9 at 8 192 columns, 4e-8 at 8 704).  Off by default.
-  long long *tt_rp = nullptr, *tt_cp = nullptr;          // L_TT strictly lower by rows (CSR) and by columns (CSC), T-local
-  int *tt_ci = nullptr, *tt_ri = nullptr;
-  double *tt_v = nullptr, *tt_cv = nullptr;
-  bool tops_refine = false;     // option lead_tops_refine
+  // (One step of iterative refinement per direction against the sparse L_TT was built to test whether the explicit inverses move PushBox_N=50's
+  // primal objective: they do not -- profiles/r05_tops_deviation.txt; the step and its option were removed after commit aed57d4.)
   long long tops_bytes = 0;
   int tops_blocks = 0, tops_max = 0;
   int solve_tops(const double* ax, const double* asmc, const double* b, double isig, double* y, TailSolve& tail, hipStream_t st) const;

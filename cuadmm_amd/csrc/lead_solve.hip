@@ -12,7 +12,6 @@
 #include <cmath>
 #include <cstdio>
 #include <atomic>
-#include <limits>
 #include <new>
 #include <numeric>
 #include <vector>
@@ -407,7 +406,7 @@ __global__ __launch_bounds__(256) void lead_ext_rhs_kernel(int kext, int n1, con
 // out[i] = sum_c vals[off[i] + c] * in[start + c], c < len: a packed row of W_T (start = beg[i], the row ends at i) or of W_T^T (start = i,
 // len[i] entries); one wavefront per row, lanes stride the row (coalesced), xor butterfly: a fixed order
 __global__ __launch_bounds__(256) void tops_gemv_kernel(int nrows, const long long* __restrict__ off, const int* __restrict__ beg, const int* __restrict__ len,
-                                                        const double* __restrict__ vals, const double* __restrict__ in, double* __restrict__ out, int acc) {
+                                                        const double* __restrict__ vals, const double* __restrict__ in, double* __restrict__ out) {
   const int i = (int)blockIdx.x * 4 + ((int)threadIdx.x >> 6), lane = (int)threadIdx.x & 63;
   if (i >= nrows) return;
   const int start = beg ? beg[i] : i, n = beg ? i - start + 1 : len[i];
@@ -420,21 +419,7 @@ __global__ __launch_bounds__(256) void tops_gemv_kernel(int nrows, const long lo
   double s = s0 + s1;
 #pragma unroll
   for (int o = 32; o >= 1; o >>= 1) s += __shfl_xor(s, o, 64);
-  if (lane == 0) out[i] = acc ? out[i] + s : s;
-}
-
-// residual of the unit triangular system of the tops: out[i] = rhs[i] - x[i] - sum_c T[i][c] x[c], T = the strict part of L_TT by rows
-// (forward) or of L_TT^T by rows (backward: the CSC arrays); 32 lanes per row
-__global__ __launch_bounds__(256) void tops_resid_kernel(int n, const long long* __restrict__ rp, const int* __restrict__ ci, const double* __restrict__ v,
-                                                         const double* __restrict__ x, const double* __restrict__ rhs, double* __restrict__ out) {
-  const int gt = (int)(blockIdx.x * blockDim.x + threadIdx.x);
-  const int i = gt >> 5, sub = gt & 31;
-  if (i >= n) return;
-  double s = 0.0;
-  for (long long q = rp[i] + sub; q < rp[i + 1]; q += 32) s += v[q] * x[ci[q]];
-#pragma unroll
-  for (int o = 16; o >= 1; o >>= 1) s += __shfl_xor(s, o, 64);
-  if (sub == 0) out[i] = rhs[i] - x[i] - s;
+  if (lane == 0) out[i] = s;
 }
 
 // the tail's right-hand side: out[i] = zK[i] - sum_c L_KT[i][c] z_T[c]   (one wavefront per tail row: several hundred entries each)
@@ -489,11 +474,10 @@ void LeadSolve::release() {
   if (aux) { hipError_t e = hipStreamDestroy(aux); (void)e; e = hipEventDestroy(ev_fork); (void)e; e = hipEventDestroy(ev_join); (void)e; aux = nullptr; ev_fork = ev_join = nullptr; }
   desc_small_f = desc_small_b = desc_big_f = desc_big_b = nullptr; trees_stream = nullptr; n_small = n_big = n_stream = 0;
   for (void* p : {(void*)rid, (void*)xp, (void*)zext, (void*)xext, (void*)zT, (void*)uT, (void*)DT, (void*)Wf, (void*)Wb, (void*)wf_off, (void*)wb_off,
-                  (void*)wf_beg, (void*)wb_len, (void*)kt_rp, (void*)tk_cp, (void*)kt_ci, (void*)tk_ri, (void*)kt_v, (void*)tk_v, (void*)tt_rp, (void*)tt_cp,
-                  (void*)tt_ci, (void*)tt_ri, (void*)tt_v, (void*)tt_cv})
+                  (void*)wf_beg, (void*)wb_len, (void*)kt_rp, (void*)tk_cp, (void*)kt_ci, (void*)tk_ri, (void*)kt_v, (void*)tk_v})
     if (p) { hipError_t e = hipFree(p); (void)e; }
   rid = wf_beg = wb_len = kt_ci = tk_ri = nullptr; xp = zext = xext = zT = uT = DT = Wf = Wb = kt_v = tk_v = nullptr;
-  wf_off = wb_off = kt_rp = tk_cp = tt_rp = tt_cp = nullptr; tt_ci = tt_ri = nullptr; tt_v = tt_cv = nullptr;
+  wf_off = wb_off = kt_rp = tk_cp = nullptr;
   tops = false; nT = 0; k_tail = 0; tops_bytes = 0; tops_blocks = tops_max = 0;
   if (long_cols_d) { hipError_t e = hipFree(long_cols_d); (void)e; long_cols_d = nullptr; }
   n_long = 0;
@@ -582,15 +566,6 @@ int LeadSolve::build(int m_, int k_, const int64_t* Lp, const int* Li, const dou
     }
   }
   return build_core(m_, k_, Lp, Li, Lx, D, allow_hybrid);
-}
-
-// experiment (option pinv_tol, NOTEBOOK.md "Round 6"): pivots below the tolerance in magnitude become
-// +infinity -- the kernels divide by D, so the component along such a direction is dropped (1 / d := 0), here as in the tail's dinv
-static std::vector<double> pinv_pivots(const double* D, int n, double tol) {
-  std::vector<double> out(D, D + n);
-  if (tol > 0.0)
-    for (auto& d : out) if (std::fabs(d) < tol) d = std::numeric_limits<double>::infinity();
-  return out;
 }
 
 int LeadSolve::build_core(int m_, int k_, const int64_t* Lp, const int* Li, const double* Lx, const double* D, bool allow_hybrid) {
@@ -842,7 +817,7 @@ int LeadSolve::build_core(int m_, int k_, const int64_t* Lp, const int* Li, cons
       (rc = to_device(fptr, fp)) || (rc = to_device(fci, fc)) || (rc = to_device(fv_, fv)) ||
       (rc = to_device(bptr, bp)) || (rc = to_device(bci, bc)) || (rc = to_device(bv_, bv)) ||
       (rc = to_device(tptr, tp)) || (rc = to_device(tri, tr)) || (rc = to_device(tv_, tv)) || (rc = to_device(long_cols_d, long_cols)) ||
-      (rc = to_device(D1, pinv_pivots(D, n1, pinv_tol))) || (rc = to_device(nodes_f, nf)) || (rc = to_device(nodes_b, nb)) ||
+      (rc = to_device(D1, std::vector<double>(D, D + n1))) || (rc = to_device(nodes_f, nf)) || (rc = to_device(nodes_b, nb)) ||
       (rc = to_device(lvl_ptr_f, lpf)) || (rc = to_device(lvl_ptr_b, lpb)) || (rc = to_device(lvl_off_f, lof)) || (rc = to_device(lvl_off_b, lob)) ||
       (rc = to_device(lvl_g_f, lgf)) || (rc = to_device(lvl_g_b, lgb)))
     return rc;
@@ -1026,21 +1001,6 @@ int LeadSolve::build_tops(int m_, int k_, const int64_t* Lp, const int* Li, cons
   if (bad.load() > 0) { set_error("lead_solve: %d of %d dense tree tops fail the check of their inverse", bad.load(), nblk); return CUADMM_ERR_FACTOR; }
   std::vector<double> dt((size_t)nt);
   for (int t = 0; t < nt; ++t) dt[t] = D[tnodes[t]];
-  dt = pinv_pivots(dt.data(), nt, pinv_tol);
-  // L_TT by columns for the refinement of the backward solve (the rows of L_TT^T)
-  std::vector<long long> cpt((size_t)nt + 1, 0);
-  for (long long e = 0; e < rpt[nt]; ++e) cpt[(size_t)cit[(size_t)e] + 1]++;
-  for (int t = 0; t < nt; ++t) cpt[(size_t)t + 1] += cpt[t];
-  std::vector<int> rit((size_t)rpt[nt]);
-  std::vector<double> vct((size_t)rpt[nt]);
-  {
-    std::vector<long long> fc(cpt.begin(), cpt.end() - 1);
-    for (int r = 0; r < nt; ++r)
-      for (long long e = rpt[r]; e < rpt[(size_t)r + 1]; ++e) { const long long q = fc[(size_t)cit[(size_t)e]]++; rit[(size_t)q] = r; vct[(size_t)q] = vt[(size_t)e]; }
-  }
-  if ((rc = to_device(tt_rp, rpt)) || (rc = to_device(tt_ci, cit)) || (rc = to_device(tt_v, vt)) || (rc = to_device(tt_cp, cpt)) || (rc = to_device(tt_ri, rit)) ||
-      (rc = to_device(tt_cv, vct)))
-    return rc;
   if ((rc = to_device(rid, ridh)) || (rc = to_device(Wf, wf)) || (rc = to_device(Wb, wb)) || (rc = to_device(wf_off, offf)) || (rc = to_device(wb_off, offb)) ||
       (rc = to_device(wf_beg, begf)) || (rc = to_device(wb_len, lenb)) || (rc = to_device(kt_rp, krp)) || (rc = to_device(kt_ci, kci)) || (rc = to_device(kt_v, kv)) ||
       (rc = to_device(tk_cp, kcp)) || (rc = to_device(tk_ri, kri)) || (rc = to_device(tk_v, kcv)) || (rc = to_device(DT, dt)))
@@ -1132,11 +1092,7 @@ int LeadSolve::solve_tops(const double* ax, const double* asmc, const double* b,
   launch_sweeps(*this, false, ax, asmc, b, isig, xp, st);                                                       // z_B
   hipLaunchKernelGGL(lead_ext_rhs_kernel<32>, dim3((unsigned)(((long long)kext * 32 + 255) / 256)), dim3(256), 0, st, kext, n1, rp21, ci21, v21, ax, asmc, b, isig, rid,
                      xp, zext);                                                                                  // r_T - L_TB z_B | r_K - L_KB z_B
-  hipLaunchKernelGGL(tops_gemv_kernel, dim3((unsigned)((nT + 3) / 4)), dim3(256), 0, st, nT, wf_off, wf_beg, (const int*)nullptr, Wf, zext, zT, 0);   // z_T = W_T (...)
-  if (tops_refine) {                                                                                             // z_T += W_T (r - L_TT z_T)
-    hipLaunchKernelGGL(tops_resid_kernel, dim3((unsigned)(((long long)nT * 32 + 255) / 256)), dim3(256), 0, st, nT, tt_rp, tt_ci, tt_v, zT, zext, uT);
-    hipLaunchKernelGGL(tops_gemv_kernel, dim3((unsigned)((nT + 3) / 4)), dim3(256), 0, st, nT, wf_off, wf_beg, (const int*)nullptr, Wf, uT, zT, 1);
-  }
+  hipLaunchKernelGGL(tops_gemv_kernel, dim3((unsigned)((nT + 3) / 4)), dim3(256), 0, st, nT, wf_off, wf_beg, (const int*)nullptr, Wf, zext, zT);   // z_T = W_T (...)
   const int* pz = tail.z_scatter();                   // the tail reads z in its factor's pivoting order: written there, not gathered
   hipLaunchKernelGGL(tops_k_rhs_kernel, dim3((unsigned)((kt + 3) / 4)), dim3(256), 0, st, kt, kt_rp, kt_ci, kt_v, zT, zext + nT, tail.vin, pz);   // z_K -= L_KT z_T
   CUADMM_HIP_TRY(hipGetLastError());
@@ -1145,11 +1101,7 @@ int LeadSolve::solve_tops(const double* ax, const double* asmc, const double* b,
   if (rc) return rc;
   hipLaunchKernelGGL(tops_u_kernel, dim3((unsigned)((nT + 3) / 4 + (kt + 255) / 256)), dim3(256), 0, st, nT, tk_cp, tk_ri, tk_v, tail.vin, zT, DT, uT, xext + nT,
                      kt);                                                                                        // D_T^-1 z_T - L_KT^T x_K;  x_K beside x_T
-  hipLaunchKernelGGL(tops_gemv_kernel, dim3((unsigned)((nT + 3) / 4)), dim3(256), 0, st, nT, wb_off, (const int*)nullptr, wb_len, Wb, uT, xext, 0);  // x_T = W_T^T (...)
-  if (tops_refine) {                                                                                             // x_T += W_T^T (u - L_TT^T x_T); zext's T part is free by now
-    hipLaunchKernelGGL(tops_resid_kernel, dim3((unsigned)(((long long)nT * 32 + 255) / 256)), dim3(256), 0, st, nT, tt_cp, tt_ri, tt_cv, xext, uT, zext);
-    hipLaunchKernelGGL(tops_gemv_kernel, dim3((unsigned)((nT + 3) / 4)), dim3(256), 0, st, nT, wb_off, (const int*)nullptr, wb_len, Wb, zext, xext, 1);
-  }
+  hipLaunchKernelGGL(tops_gemv_kernel, dim3((unsigned)((nT + 3) / 4)), dim3(256), 0, st, nT, wb_off, (const int*)nullptr, wb_len, Wb, uT, xext);  // x_T = W_T^T (...)
   // w = [L_TB; L_KB]^T [x_T; x_K] -- and [x_T | x_K] into y in the caller's order on the way; the backward sweeps then write x_B straight into y
   // (round 6: the scatter kernel behind them is gone when there are leading columns to sweep)
   const bool direct = launch_l21t(n1, tptr, tri, tv_, xext, wvec, n_long, long_cols_d, st, y, kext, rid + n1);

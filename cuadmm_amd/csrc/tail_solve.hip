@@ -236,21 +236,6 @@ struct TsRows {
     }
   }
 };
-// error-free transformations for the compensated variant of u_i = W_i z (option tail_dd, an experiment: NOTEBOOK.md "Round 6", "pivots near the
-// regularisation"): (hi, lo) <- (hi, lo) + a b with the rounding errors of the product and of the sum collected in lo
-__device__ __forceinline__ void dd_fma_acc(double& hi, double& lo, double a, double b) {
-#pragma clang fp contract(off)               // the transformations are exact only with every operation rounded on its own
-  const double pr = a * b, pe = __fma_rn(a, b, -pr);
-  const double s = hi + pr, bb = s - hi;
-  lo += ((hi - (s - bb)) + (pr - bb)) + pe;
-  hi = s;
-}
-__device__ __forceinline__ void dd_add(double& hi, double& lo, double h2, double l2) {
-#pragma clang fp contract(off)
-  const double s = hi + h2, bb = s - hi;
-  lo += ((hi - (s - bb)) + (h2 - bb)) + l2;
-  hi = s;
-}
 // the sum of the sixteen wavefronts' parts, in every lane: lane l takes part l & 15, four butterfly steps on the DPP crossbar inside each row of
 // 16 lanes -- the tree (((0+1)+(2+3))+((4+5)+(6+7))) + (((8+9)+(10+11))+((12+13)+(14+15))) of rounds 3 - 6, bit for bit (every step adds a pair
 // that the old expression added, in one order or the other), for ONE LDS read per wavefront instead of eight 16-byte broadcasts and fifteen adds
@@ -265,12 +250,10 @@ __device__ __forceinline__ double ts_sum16(const double* rr, int lane) {
 // ZREG: the thread's NC entries of z live in registers (zr) instead of LDS.  They are the same for every row -- the LDS copy only existed for the
 // registers' sake -- and reading them back cost 64 NC bytes of LDS traffic per row and wavefront: with the sixteen wavefronts of a CU behind one
 // LDS port, a third of a row's time (tools/ubench/tri_stream.hip, MODE 3: the tick stamps of wavefront 0).
-template <int NC, int RB, bool DD, int NW = 16, bool TIGHT = false, bool ZREG = false>
-__device__ __forceinline__ void ts_rows_apply(const TsRows<NC, RB>& R, const double* zs, const double2 (&zr)[ZREG ? NC / 2 : 1], double (*red)[RB][DD ? 32 : 16],
+template <int NC, int RB, bool TIGHT, bool ZREG>
+__device__ __forceinline__ void ts_rows_apply(const TsRows<NC, RB>& R, const double* zs, const double2 (&zr)[ZREG ? NC / 2 : 1], double (*red)[RB][16],
                                               int it, int lane, int wave, int seg0, int K, int r0, int r_end, const double* __restrict__ dinv,
                                               double2 (&xa)[NC / 2]) {
-  static_assert(NW == 16 || NW == 8, "wavefronts per workgroup");
-  static_assert(!DD || NW == 16, "the compensated variant exists for 1024 threads only");
   double part[RB], dv[RB];
   bool busy[RB];                             // wave-uniform: the wavefront's segment reaches into row q (ts_seg_class: INSIDE or CROSSING)
 #pragma unroll
@@ -282,57 +265,30 @@ __device__ __forceinline__ void ts_rows_apply(const TsRows<NC, RB>& R, const dou
 #pragma unroll
   for (int q = 0; q < RB; ++q) {
     part[q] = 0.0;
-    if constexpr (DD) {
-      double lo = 0.0;
-      if (busy[q]) {
+    if (busy[q]) {
 #pragma unroll
-        for (int p = 0; p < NC / 2; ++p) {
-          const double2 zz = *reinterpret_cast<const double2*>(zs + 128 * p);
-          dd_fma_acc(part[q], lo, R.w[q][p].x, zz.x);
-          dd_fma_acc(part[q], lo, R.w[q][p].y, zz.y);
-        }
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) dd_add(part[q], lo, __shfl_xor(part[q], o, 64), __shfl_xor(lo, o, 64));
+      for (int p = 0; p < NC / 2; ++p) {
+        double2 zz;
+        if constexpr (ZREG) zz = zr[p]; else zz = *reinterpret_cast<const double2*>(zs + 128 * p);
+        part[q] += R.w[q][p].x * zz.x;
+        part[q] += R.w[q][p].y * zz.y;
+        // (TIGHT: at the register budget's edge the scheduler otherwise reads every z pair of the row up front -- 2 NC registers -- and spills)
+        if (TIGHT && (p & 1) == 1) __builtin_amdgcn_sched_barrier(0);
       }
-      if (lane == 0) { red[it & 1][q][wave] = part[q]; red[it & 1][q][16 + wave] = lo; }
-    } else {
-      if (busy[q]) {
-#pragma unroll
-        for (int p = 0; p < NC / 2; ++p) {
-          double2 zz;
-          if constexpr (ZREG) zz = zr[p]; else zz = *reinterpret_cast<const double2*>(zs + 128 * p);
-          part[q] += R.w[q][p].x * zz.x;
-          part[q] += R.w[q][p].y * zz.y;
-          // (TIGHT: at the register budget's edge the scheduler otherwise reads every z pair of the row up front -- 2 NC registers -- and spills)
-          if (TIGHT && (p & 1) == 1) __builtin_amdgcn_sched_barrier(0);
-        }
-        part[q] = wave_sum(part[q]);
-      }
-      if (lane == 0) red[it & 1][q][wave] = part[q];
+      part[q] = wave_sum(part[q]);
     }
+    if (lane == 0) red[it & 1][q][wave] = part[q];
   }
   __syncthreads();
 #pragma unroll
   for (int q = 0; q < RB; ++q) {
     if (!busy[q]) continue;                  // every entry of the row in this wavefront's columns is an exact zero
-    const double* rr = red[it & 1][q];
-    double u;
-    if constexpr (DD) {
-      double hi = rr[0], lo = rr[16];
-#pragma unroll
-      for (int w = 1; w < 16; ++w) dd_add(hi, lo, rr[w], rr[16 + w]);
-      u = hi + lo;
-    } else if constexpr (NW == 8) {
-      u = ((rr[0] + rr[1]) + (rr[2] + rr[3])) + ((rr[4] + rr[5]) + (rr[6] + rr[7]));
-    } else {
-      u = ts_sum16(rr, lane);
-    }
-    const double vq = u * dv[q];
+    const double vq = ts_sum16(red[it & 1][q], lane) * dv[q];
 #pragma unroll
     for (int p = 0; p < NC / 2; ++p) { xa[p].x += vq * R.w[q][p].x; xa[p].y += vq * R.w[q][p].y; }
   }
 }
-// NT threads: 1024 (sixteen wavefronts, <= 128 VGPRs each) or 512 -- "fewer, fatter threads", option tail_fat, measured slower and off.
+// 1024 threads: sixteen wavefronts of <= 128 VGPRs each.
 // WHAT BOUNDS THIS KERNEL (round 6, tools/ubench/tri_stream.hip + the kernel traces profiles/r06_tail_onepass_study.txt): at K = 9 216 it takes
 // 76.8 us for 340 MB whatever is changed inside it -- rows per barrier (1 / 2), groups in flight (0 ... 3), the walk, z in LDS or in registers,
 // the above-diagonal wavefronts idle or busy, 8- or 16-wavefront workgroups: 76.8 - 78.5 us every time.  A FLAT 16-byte-per-lane read of the same
@@ -344,18 +300,20 @@ __device__ __forceinline__ void ts_rows_apply(const TsRows<NC, RB>& R, const dou
 // D: row groups in flight BEYOND the one being applied (a ring of D + 1 register buffers; 0: load, apply, load ...).  With one group ahead
 // the wait at the top of a group still sees a whole memory round trip minus the ~0.3 us a group takes to apply: a row per round trip,
 // whatever its length -- the short rows of the triangle's tip are latency-bound (tools/ubench/tri_stream.hip).
-// ORDER 1: a workgroup walks its rows alternately from the long and from the short end (ORDER 2, the default: odd workgroups start at the short
-// end -- 77.7 -> 72.3 / 78.2 -> 75.2 us at K = 9 216, 45.5 -> 44.3 at 7 168 in the kernel trace), so the chip streams the same mix of long and short
-// rows from the first microsecond to the last (ORDER 0, rounds 3 - 6: longest first -- every workgroup reaches the tip at the same time and
-// the bytes in flight collapse together).  The partial sums associate in the walk's order: the last bits differ between orders, deterministically.
-template <int NC, int RB, int D, bool DD = false, int NT = 1024, int ORDER = 0, bool ZREG = false>
-__global__ __launch_bounds__(NT) void ts_onepass_kernel(const double* __restrict__ W, long long ld, int K, const double* __restrict__ z,
-                                                        const double* __restrict__ dinv, double* __restrict__ P, int r_begin, int r_end,
-                                                        const int* __restrict__ perm) {
-  constexpr int NW = NT / 64;
-  constexpr bool TIGHT = NT == 1024 && !ZREG && NC * RB * (D + 1) + NC >= 40;      // doubles of row data and accumulators per thread: 80 of the 128 registers
+// THE WALK: a workgroup takes its rows alternately from the long and from the short end, and odd workgroups start at the short end (77.7 -> 72.3 /
+// 78.2 -> 75.2 us at K = 9 216, 45.5 -> 44.3 at 7 168 in the kernel trace), so the chip streams the same mix of long and short rows from the first
+// microsecond to the last (longest first, rounds 3 - 6: every workgroup reaches the tip at the same time and the bytes in flight collapse
+// together).  The partial sums associate in the walk's order.
+// Which (NC, RB, D, ZREG) exist: the table in TailSolve::apply_rows.  The other settings of that study (walks, rows per barrier, up to three groups
+// ahead, 512-thread workgroups, a double-double dot product) were options until commit aed57d4; their measurements are in NOTEBOOK.md "Round 6".
+template <int NC, int RB, int D, bool ZREG>
+__global__ __launch_bounds__(1024) void ts_onepass_kernel(const double* __restrict__ W, long long ld, int K, const double* __restrict__ z,
+                                                          const double* __restrict__ dinv, double* __restrict__ P, int r_begin, int r_end,
+                                                          const int* __restrict__ perm) {
+  constexpr int NT = 1024;
+  constexpr bool TIGHT = !ZREG && NC * RB * (D + 1) + NC >= 40;           // doubles of row data and accumulators per thread: 80 of the 128 registers
   extern __shared__ __attribute__((aligned(16))) double ts_zs[];          // z, K doubles (zero beyond K up to NT NC)
-  __shared__ double red[2][RB][DD ? 32 : 16];
+  __shared__ double red[2][RB][16];
   const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int col0 = wave * (64 * NC) + 2 * lane;
   const int seg0 = __builtin_amdgcn_readfirstlane(wave) * (64 * NC);      // first column of the wavefront's segment, wave-uniform (ts_seg_class)
@@ -371,7 +329,8 @@ __global__ __launch_bounds__(NT) void ts_onepass_kernel(const double* __restrict
   // first row of the j-th group of the walk (beyond the last group: the last group again -- rows this rank holds; ts_rows_apply is not called for it)
   auto group_row = [&](int j) -> int {
     j = j < count ? j : count - 1;
-    if (ORDER >= 1) { const int h = j >> 1; j = (((j & 1) != 0) != (ORDER == 2 && (g & 1) != 0)) ? count - 1 - h : h; }      // ORDER 2: odd workgroups start at the short end
+    const int h = j >> 1;
+    j = (((j & 1) != 0) != ((g & 1) != 0)) ? count - 1 - h : h;      // alternately from both ends; odd workgroups start at the short end
     return first + j * step;
   };
   TsRows<NC, RB> buf[D + 1];
@@ -396,7 +355,7 @@ __global__ __launch_bounds__(NT) void ts_onepass_kernel(const double* __restrict
   if constexpr (D == 0) {                    // one group in flight (the registers of a second one would spill)
     for (int j = 0; j < count; ++j) {
       if (j) buf[0].load(W, ld, K, col0, seg0, group_row(j), r_end);
-      ts_rows_apply<NC, RB, DD, NW, TIGHT, ZREG>(buf[0], zs, zr, red, it++, lane, wave, seg0, K, group_row(j), r_end, dinv, xa);
+      ts_rows_apply<NC, RB, TIGHT, ZREG>(buf[0], zs, zr, red, it++, lane, wave, seg0, K, group_row(j), r_end, dinv, xa);
     }
   } else {
     int j = 0;
@@ -405,7 +364,7 @@ __global__ __launch_bounds__(NT) void ts_onepass_kernel(const double* __restrict
       for (int s = 0; s <= D; ++s) {
         if (j < count) {
           buf[(s + D) % (D + 1)].load(W, ld, K, col0, seg0, group_row(j + D), r_end);
-          ts_rows_apply<NC, RB, DD, NW, TIGHT, ZREG>(buf[s], zs, zr, red, it++, lane, wave, seg0, K, group_row(j), r_end, dinv, xa);
+          ts_rows_apply<NC, RB, TIGHT, ZREG>(buf[s], zs, zr, red, it++, lane, wave, seg0, K, group_row(j), r_end, dinv, xa);
           ++j;
         }
       }
@@ -439,11 +398,11 @@ __global__ void ts_fill_u64_kernel(unsigned long long* p, size_t n, unsigned lon
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) p[i] = v;
 }
-template <int NC, int Q, int RB, int OCC = 8, bool PF = false>
+template <int NC, int Q, int RB, int OCC>
 __global__ __launch_bounds__(1024, OCC) void ts_onepass_group_kernel(const double* __restrict__ W, long long ld, int K, const double* __restrict__ z,
                                                                    const double* __restrict__ dinv, double* __restrict__ P,
                                                                    unsigned long long* __restrict__ part, int* __restrict__ fail, int r_begin, int r_end,
-                                                                   const int* __restrict__ perm, int order) {
+                                                                   const int* __restrict__ perm) {
   extern __shared__ double ts_zs[];          // z of this thread's own columns: word (c * 1024 + tid); nobody else reads it
   __shared__ double red[2][RB][16];
   __shared__ double ush[2][RB];
@@ -478,12 +437,12 @@ __global__ __launch_bounds__(1024, OCC) void ts_onepass_group_kernel(const doubl
   double2 xa[NP];
 #pragma unroll
   for (int p = 0; p < NP; ++p) xa[p] = make_double2(0.0, 0.0);
-  // the group's row groups, walked longest first (order 0) or alternately from the long and the short end (order 1, ts_onepass_kernel): the
-  // members of a group share `group` and `count`, so they walk the same sequence and meet in the same exchange slots
+  // the group's row groups, walked alternately from the long and the short end, odd groups starting at the short end (the walk of
+  // ts_onepass_kernel): the members of a group share `group` and `count`, so they walk the same sequence and meet in the same exchange slots
   const int first = r_begin + group * RB, stride = G * RB;
   const int count = first < r_end ? (r_end - first + stride - 1) / stride : 0;
   auto row_of = [&](int it) -> int {
-    const int jw = order ? ((((it & 1) != 0) != (order == 2 && (group & 1) != 0)) ? count - 1 - (it >> 1) : (it >> 1)) : it;
+    const int jw = (((it & 1) != 0) != ((group & 1) != 0)) ? count - 1 - (it >> 1) : (it >> 1);
     return first + jw * stride;
   };
   // the rows of one group into registers (w), and everything behind the loads (process)
@@ -573,23 +532,11 @@ __global__ __launch_bounds__(1024, OCC) void ts_onepass_group_kernel(const doubl
 #pragma unroll
       for (int p = 0; p < NP; ++p) { xa[p].x += vq * w[q][p].x; xa[p].y += vq * w[q][p].y; }
     }
-    };
-  if constexpr (!PF) {
-    double2 w[RB][NP];
-    for (int it = 0; it < count; ++it) { load_group(w, row_of(it)); process(w, row_of(it), it); }
-  } else {
-    // PF: the NEXT group's rows travel while this group's parts go round the members -- the ~2 us exchange no longer stands between two loads
-    // (two register buffers: half the rows per exchange of the variant without, the same registers)
-    double2 wA[RB][NP], wB[RB][NP];
-    if (count > 0) load_group(wA, row_of(0));
-    for (int it = 0; it < count; it += 2) {
-      if (it + 1 < count) load_group(wB, row_of(it + 1));
-      process(wA, row_of(it), it);
-      if (it + 1 >= count) break;
-      if (it + 2 < count) load_group(wA, row_of(it + 2));
-      process(wB, row_of(it + 1), it + 1);
-    }
-  }
+  };
+  // (the next group's rows in flight across the exchange -- two register buffers, half the rows per exchange -- was measured slower, 4.25 ->
+  // 4.47 ms per iteration of PlanarHand N = 10, and removed after commit aed57d4: NOTEBOOK.md "Round 6")
+  double2 w[RB][NP];
+  for (int it = 0; it < count; ++it) { load_group(w, row_of(it)); process(w, row_of(it), it); }
 #pragma unroll
   for (int p = 0; p < NP; ++p) { const int col = col0 + 128 * p; if (col < K) *reinterpret_cast<double2*>(P + (size_t)group * K + col) = xa[p]; }
 }
@@ -879,10 +826,9 @@ int ts_ldlt_factor_pivoted(double* dS, int K, int k, double* dd, double* Yp, dou
   return CUADMM_OK;
 }
 
-// pinv_tol > 0 (option tail_pinv_tol, an experiment: see tail_solve.h): a pivot below it in magnitude counts as zero
-__global__ void ts_dinv_kernel(const double* __restrict__ d, double* __restrict__ dinv, int K, double pinv_tol) {
+__global__ void ts_dinv_kernel(const double* __restrict__ d, double* __restrict__ dinv, int K) {
   const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
-  if (i < K) dinv[i] = fabs(d[i]) < pinv_tol ? 0.0 : 1.0 / d[i];
+  if (i < K) dinv[i] = 1.0 / d[i];
 }
 
 int ts_gemm(int M, int N, int Kd, double alpha, const double* A, long long lda, long long sA, const double* B, long long ldb,
@@ -1071,7 +1017,7 @@ int TailSolve::build_from_schur(const long long* row_ptr, const int* col, const 
     { hipError_t e2 = hipFree(dg); (void)e2; }
     if (rc) { cleanup(); release(); return rc; }
   } else if ((rc = ts_ldlt_factor(dS, K, dd, Yp, dflag, st))) { cleanup(); release(); return rc; }
-  hipLaunchKernelGGL(ts_dinv_kernel, dim3((K + 255) / 256), dim3(256), 0, st, dd, dinv, K, pinv_tol);
+  hipLaunchKernelGGL(ts_dinv_kernel, dim3((K + 255) / 256), dim3(256), 0, st, dd, dinv, K);
   int hflag = 0;
   e = hipGetLastError();
   if (e == hipSuccess && staged_d2h(&hflag, dflag, sizeof(int), st)) e = hipErrorUnknown;      // staged: never a runtime copy into pageable memory
@@ -1155,7 +1101,7 @@ bool TailSolve::linear_z_ok() const {
   if (!perm_d || !pinv_d || !one_pass || !xpart || (refine && Lm)) return false;
   const int nc = (K + 1023) / 1024;
   const size_t lds = sizeof(double) * 1024 * (size_t)(nc + (nc & 1));
-  if (lds <= kMaxLdsBytes - 1024 && nc <= 20) return true;
+  if (lds <= kMaxLdsBytes - 1024) return true;
   return part && K <= 65536 && !group_retired;
 }
 // where entry i of z goes when the producer writes it for the next solve_device (null: in place, the kernels gather).  The producer that
@@ -1215,40 +1161,6 @@ int TailSolve::apply_refined(double* vin, hipStream_t st) {      // (vin: the ve
   return CUADMM_OK;
 }
 
-// Which (NC, RB, D) exist: RB NC (D + 1) doubles of row buffers + NC accumulators per thread within ~104 of the 128 registers a 1024-thread
-// workgroup leaves a wavefront (the rest: z pairs in flight, addresses, the reduction).  Measured by the compiler's own count, not guessed:
-// every instantiation below builds without scratch (tools: -Rpass-analysis=kernel-resource-usage).
-template <int NC, int RB, int D, bool ZREG>
-constexpr bool ts_onepass_fits = (D <= 1 || (RB == 1 && D <= 3 && NC <= 10)) && NC * RB * (D + 1) + NC + (ZREG ? NC : 0) <= 52;
-template <int NC, int RB, int D, class L>
-static int ts_onepass_launch_one(int order, bool zreg, L& launch) {
-  if constexpr (ts_onepass_fits<NC, RB, D, true>) {
-    if (zreg) return order == 2 ? launch(ts_onepass_kernel<NC, RB, D, false, 1024, 2, true>) : order ? launch(ts_onepass_kernel<NC, RB, D, false, 1024, 1, true>) : launch(ts_onepass_kernel<NC, RB, D, false, 1024, 0, true>);
-  }
-  if constexpr (ts_onepass_fits<NC, RB, D, false>) {
-    return order == 2 ? launch(ts_onepass_kernel<NC, RB, D, false, 1024, 2>) : order ? launch(ts_onepass_kernel<NC, RB, D, false, 1024, 1>) : launch(ts_onepass_kernel<NC, RB, D, false, 1024, 0>);
-  } else {
-    (void)order; (void)launch; (void)zreg;
-    return -1;
-  }
-}
-template <int NC, class L>
-static int ts_onepass_launch(int rb, int dep, int order, bool zreg, L& launch) {
-  if (rb == 2) {
-    switch (dep) {
-      case 0: return ts_onepass_launch_one<NC, 2, 0>(order, zreg, launch);
-      case 1: return ts_onepass_launch_one<NC, 2, 1>(order, zreg, launch);
-      default: return ts_onepass_launch_one<NC, 2, 2>(order, zreg, launch);
-    }
-  }
-  switch (dep) {
-    case 0: return ts_onepass_launch_one<NC, 1, 0>(order, zreg, launch);
-    case 1: return ts_onepass_launch_one<NC, 1, 1>(order, zreg, launch);
-    case 2: return ts_onepass_launch_one<NC, 1, 2>(order, zreg, launch);
-    default: return ts_onepass_launch_one<NC, 1, 3>(order, zreg, launch);
-  }
-}
-
 // vin <- W^T diag(dinv) W vin
 int TailSolve::apply(hipStream_t st) {
   // (refined: every rank of a sharded engine applies the WHOLE tail -- the result is replicated, no reduction)
@@ -1290,7 +1202,7 @@ int TailSolve::apply_rows(hipStream_t st, int r_begin, int r_end) {
   vin_pivot = false;
   const int* perm_in = z_pivot ? nullptr : perm_d;
   if (z_pivot && !linear_z_ok()) { set_error("tail_solve: z was written in the factor's order but the pass that reads it that way is gone"); return CUADMM_ERR_INVALID; }
-  if (one_pass && xpart && lds <= kMaxLdsBytes - 1024 && nc <= 20) {
+  if (one_pass && xpart && lds <= kMaxLdsBytes - 1024) {
     auto launch = [&](auto kern) -> int {
       if (lds > 48 * 1024 && !attr_set) {      // once per object: K, and with it the instantiation, never changes
         CUADMM_HIP_TRY(allow_max_dynamic_lds(reinterpret_cast<const void*>(kern)));   // process-wide per kernel: the maximum
@@ -1299,50 +1211,23 @@ int TailSolve::apply_rows(hipStream_t st, int r_begin, int r_end) {
       hipLaunchKernelGGL(kern, dim3(n_wg), dim3(1024), lds, st, W, ldw, K, vin, dinv, xpart, r_begin, r_end, perm_in);
       return CUADMM_OK;
     };
+    // NC columns per thread (1024 NC >= K, in pairs), RB rows per barrier, D row groups in flight beyond the current one, z in registers (ZREG) or
+    // in LDS: the largest grouping whose RB NC (D + 1) doubles of row buffers, NC accumulators and (ZREG) NC entries of z stay within ~104 of the
+    // 128 registers a 1024-thread workgroup leaves a wavefront (the rest: z pairs in flight, addresses, the reduction).  Measured by the
+    // compiler's own count, not guessed: every instantiation below builds without scratch (tools: -Rpass-analysis=kernel-resource-usage).
+    // The LDS test above admits nc <= 18 (K <= 18 432), so the table is complete.  Same column ownership in every row of it.
     int rc;
-    // K <= 10 240: eight fat wavefronts, two rows per group, two groups in flight (above ts_onepass_kernel); NC = columns per thread in steps of 4
-    auto launch512 = [&](auto kern, int ncol) -> int {
-      const size_t lds5 = sizeof(double) * 512 * (size_t)ncol;
-      if (lds5 > 48 * 1024 && !attr_set) { CUADMM_HIP_TRY(allow_max_dynamic_lds(reinterpret_cast<const void*>(kern))); attr_set = true; }
-      hipLaunchKernelGGL(kern, dim3(n_wg), dim3(512), lds5, st, W, ldw, K, vin, dinv, xpart, r_begin, r_end, perm_in);
-      return CUADMM_OK;
-    };
-    if (prefetch && fat && !dd_dot && K <= 10240) {
-      switch ((K + 2047) / 2048) {
-        case 1: rc = launch512(ts_onepass_kernel<4, 2, 1, false, 512>, 4); break;
-        case 2: rc = launch512(ts_onepass_kernel<8, 2, 1, false, 512>, 8); break;
-        case 3: rc = launch512(ts_onepass_kernel<12, 2, 1, false, 512>, 12); break;
-        case 4: rc = launch512(ts_onepass_kernel<16, 2, 1, false, 512>, 16); break;
-        default: rc = launch512(ts_onepass_kernel<20, 2, 1, false, 512>, 20); break;
-      }
-    } else
-    // NC columns per thread (1024 NC >= K), RB rows per group, D groups in flight beyond the current one during its barrier
-    // ((D + 1) register buffers of RB NC doubles + NC accumulators within 128 VGPRs).  Option tail_depth: 0 = one group in flight everywhere
-    // (rounds 3 - 5), 1 = one ahead (two rows per group up to NC = 8, one up to NC = 16, none beyond), 2 / 3 = two / three single rows ahead
-    // where the registers allow (NC <= 12 / NC <= 8).  Option tail_order: the walk of ts_onepass_kernel.  Same column ownership everywhere;
-    // the row grouping and the walk -- and with them the last bits -- differ between the settings.
-    if (dd_dot && (nc == 9 || nc == 10)) rc = launch(ts_onepass_kernel<10, 1, 1, true>);      // experiment (option tail_dd): compensated u = W z
-    else if (dd_dot && (nc == 15 || nc == 16)) rc = launch(ts_onepass_kernel<16, 1, 0, true>);
-    else {
-      // the requested grouping, degraded until the instantiation exists (ts_onepass_fits: the row buffers and accumulators within the budget)
-      int rb_ = rows_per_group, dep = prefetch ? depth : 0;
-      if (rb_ != 1 && rb_ != 2) rb_ = nc <= 8 ? 2 : 1;                    // rounds 3 - 6: two rows per group up to NC = 8
-      rc = -1;
-      while (rc == -1) {
-        switch ((nc + 1) / 2) {
-          case 1: rc = ts_onepass_launch<2>(rb_, dep, order, zreg, launch); break;
-          case 2: rc = ts_onepass_launch<4>(rb_, dep, order, zreg, launch); break;
-          case 3: rc = ts_onepass_launch<6>(rb_, dep, order, zreg, launch); break;
-          case 4: rc = ts_onepass_launch<8>(rb_, dep, order, zreg, launch); break;
-          case 5: rc = ts_onepass_launch<10>(rb_, dep, order, zreg, launch); break;
-          case 6: rc = ts_onepass_launch<12>(rb_, dep, order, zreg, launch); break;
-          case 7: rc = ts_onepass_launch<14>(rb_, dep, order, zreg, launch); break;
-          case 8: rc = ts_onepass_launch<16>(rb_, dep, order, zreg, launch); break;
-          case 9: rc = ts_onepass_launch<18>(rb_, dep, order, zreg, launch); break;
-          default: rc = ts_onepass_launch<20>(rb_, dep, order, zreg, launch); break;
-        }
-        if (rc == -1) { if (dep > 0) --dep; else rb_ = 1; }              // (one row, nothing ahead: exists for every NC)
-      }
+    switch ((nc + 1) / 2) {              //                  NC RB  D  ZREG
+      case 1: rc = launch(ts_onepass_kernel<2, 2, 1, true>); break;
+      case 2: rc = launch(ts_onepass_kernel<4, 2, 1, true>); break;
+      case 3: rc = launch(ts_onepass_kernel<6, 2, 1, true>); break;
+      case 4: rc = launch(ts_onepass_kernel<8, 2, 1, true>); break;
+      case 5: rc = launch(ts_onepass_kernel<10, 1, 1, true>); break;
+      case 6: rc = launch(ts_onepass_kernel<12, 1, 1, true>); break;
+      case 7: rc = launch(ts_onepass_kernel<14, 1, 1, false>); break;
+      case 8: rc = launch(ts_onepass_kernel<16, 1, 1, false>); break;
+      case 9: rc = launch(ts_onepass_kernel<18, 1, 0, false>); break;
+      default: set_error("tail_solve: no one-pass kernel for %d columns", K); return CUADMM_ERR_INVALID;
     }
     if (rc) return rc;
     hipLaunchKernelGGL(ts_onepass_reduce_kernel, dim3((K + 31) / 32), dim3(256), 0, st, xpart, K, n_wg, vin, (unsigned long long*)nullptr, 0, perm_d);
@@ -1353,7 +1238,7 @@ int TailSolve::apply_rows(hipStream_t st, int r_begin, int r_end) {
     const int G = std::max(8, 2 * n_wg / Q / 8 * 8);
     auto kern = ts_onepass_group_kernel<8, Q, 4, 4>;
     if (!attr_set) { CUADMM_HIP_TRY(allow_max_dynamic_lds(reinterpret_cast<const void*>(kern))); attr_set = true; }
-    hipLaunchKernelGGL(kern, dim3(G * Q), dim3(1024), lds2, st, W, ldw, K, vin, dinv, xpart, part, d_fail, r_begin, r_end, perm_in, order);
+    hipLaunchKernelGGL(kern, dim3(G * Q), dim3(1024), lds2, st, W, ldw, K, vin, dinv, xpart, part, d_fail, r_begin, r_end, perm_in);
     hipLaunchKernelGGL(ts_onepass_reduce_kernel, dim3((K + 31) / 32), dim3(256), 0, st, xpart, K, G, vin, part, Q, perm_d);
   } else if (one_pass && xpart && part && K <= 32768 && !group_retired) {
     constexpr int Q = 4;
@@ -1366,11 +1251,10 @@ int TailSolve::apply_rows(hipStream_t st, int r_begin, int r_end) {
     const int G = std::max(8, 2 * n_wg / Q / 8 * 8);            // groups: two workgroups per CU, whole octets (member m of a group: + 8 m)
     auto launch = [&](auto kern) -> int {
       if (lds2 > 48 * 1024 && !attr_set) { CUADMM_HIP_TRY(allow_max_dynamic_lds(reinterpret_cast<const void*>(kern))); attr_set = true; }
-      hipLaunchKernelGGL(kern, dim3(G * Q), dim3(1024), lds2, st, W, ldw, K, vin, dinv, xpart, part, d_fail, r_begin, r_end, perm_in, order);
+      hipLaunchKernelGGL(kern, dim3(G * Q), dim3(1024), lds2, st, W, ldw, K, vin, dinv, xpart, part, d_fail, r_begin, r_end, perm_in);
       return CUADMM_OK;
     };
-    // (group_pf: two rows per exchange and the next group's rows in flight across it, instead of four rows and nothing in flight)
-    int rc = small ? launch(ts_onepass_group_kernel<6, Q, 2, 8>) : group_pf ? launch(ts_onepass_group_kernel<8, Q, 2, 4, true>) : launch(ts_onepass_group_kernel<8, Q, 4, 4>);
+    int rc = small ? launch(ts_onepass_group_kernel<6, Q, 2, 8>) : launch(ts_onepass_group_kernel<8, Q, 4, 4>);
     if (rc) return rc;
     hipLaunchKernelGGL(ts_onepass_reduce_kernel, dim3((K + 31) / 32), dim3(256), 0, st, xpart, K, G, vin, part, Q, perm_d);
   } else {

@@ -60,7 +60,6 @@ void cuadmm_destroy(cuadmm_solver* s);
  *                   set before cuadmm_init (every block then takes the eigensolver kernels)
  *   "psd_steps"     1 = record how many Newton-Schulz steps the adaptive matrix-sign projection took per block
  *                   (cuadmm_get_psd_steps); set before cuadmm_init
- *   "graph"         reserved
  *   "tail_shard"    world > 1, coupled constraints: 1 (default) = each rank applies 1 / world of the rows of the dense GPU tail of the
  *                   replicated y-solve and the K partial results are all-reduced; 0 = every rank applies the whole tail
  *   "tail_pivot"    1 (default) = the dense LDL^T of the y-solve's GPU tail pivots on the diagonal (P S P^T = L D L^T, |L_ij| <= 1): its explicit inverse stays
@@ -70,9 +69,6 @@ void cuadmm_destroy(cuadmm_solver* s);
  *                   nearly singular Schur complement (large moment relaxations) otherwise leaves 1e-8 ... 1e-7 in the primal objective against an exact
  *                   LDL^T solve (the reference's contract, include/cuadmm/cholesky_cpu.h:146-155).  Costs 6x the tail's bytes per solve and two more
  *                   K x K matrices; default 0.  cuadmm_get_tail_info [4] reports the measured accuracy of the explicit inverse.
- *   "tail_order", "tail_zreg", "tail_depth", "tail_rb"   the tail's one pass over inv(L22) (csrc/tail_solve.hip): the workgroups' row walk (2, default:
- *                   alternately from the long and the short end, odd workgroups starting short; 0 = longest first), z in registers (1) or LDS (0), row groups in
- *                   flight beyond the current one (0 ... 3, default 1), rows per barrier (0 = by size).  A/B switches: the same solve to the last few bits.
  *   "psd_lg_fuse"   1 (default) = a handful of blocks of 65 <= n <= 512 run their whole projection -- svec -> dense, norm, every step of the matrix-sign
  *                   iteration, final product, svec store -- in ONE launch; 0 = prologue and epilogue as launches of their own (bit-identical)
  *   "duo_share_device", "duo_exchange"   the in-process group of cuadmm_duo_init(device_num_requested = N): all engines on the

@@ -186,12 +186,21 @@ def test_gemm_sym_op_fp64_mfma(n):
         check(lib.cuadmm_op_gemm_sym(100, dA.ptr, dB.ptr, 1.0, 0.0, None, dC.ptr, None))
 
 
-@pytest.mark.parametrize("k", [1, 50, 64, 100, 192, 1000, 2500])
+@pytest.mark.parametrize("k", [1, 50, 64, 100, 192, 1000, 2500, 5000, 7168, 9216, 11500, 13500, 15360, 17500, 18432])
 def test_tail_solve_op_vs_triangular_solves(k):
-    """z <- L^-T D^-1 L^-1 z with inv(L) from recursive doubling on the matrix cores (tail_solve.hip), ragged sizes."""
+    """z <- L^-T D^-1 L^-1 z with inv(L) from recursive doubling on the matrix cores (tail_solve.hip), ragged sizes.  The sizes reach every
+    row of the one-pass kernel's table (TailSolve::apply_rows), NC = 2 * ceil(ceil(k / 64) / 32) columns per thread: 2 (k <= 1 000), 4 (2 500),
+    6 (5 000), 8 (7 168), 10 (9 216), 12 (11 500), 14 (13 500), 16 (15 360), 18 (17 500 and 18 432, the last size before the row-sharing kernel)."""
     import scipy.linalg as sl
     rng = np.random.default_rng(k)
-    L = np.tril(rng.standard_normal((k, k)) * (0.5 / np.sqrt(k)), -1) + np.eye(k)
+    if k <= 2500:
+        L = np.tril(rng.standard_normal((k, k)) * (0.5 / np.sqrt(k)), -1) + np.eye(k)
+    else:                                     # (the float32 generator of the sizes beyond one workgroup's reach below: host time stays small)
+        L = rng.random((k, k), dtype=np.float32).astype(np.float64)
+        L -= 0.5
+        L *= 1.0 / np.sqrt(k)
+        L = np.tril(L, -1)
+        L[np.diag_indices(k)] = 1.0
     D = rng.uniform(0.1, 2.0, k) * rng.choice([1.0, 1.0, 1.0, -1.0], k)       # LDL^T pivots may be negative
     z = rng.standard_normal((3, k))
     ref = np.stack([sl.solve_triangular(L.T, sl.solve_triangular(L, zi, lower=True, unit_diagonal=True) / D,

@@ -605,19 +605,19 @@ def test_ordering_and_tail_plan_of_the_fixtures_are_pinned(name, m, nnzL, tail_k
 
 
 def test_engine_options_are_validated_and_retired_keys_refused_without_a_device():
-    """cuadmm_set_option on a fresh handle touches no device: known keys are accepted, the one-pass kernel's ring depth is range-checked
-    (csrc/engine.hip: tail_depth 0 ... 3), an unknown key is an error with a message -- the keys of the removed sign-path variants
-    (psd_lg_clean, psd_graph) included."""
+    """cuadmm_set_option on a fresh handle touches no device: known keys are accepted, an unknown key is an error with a message that names
+    it -- the keys of the removed sign-path variants (psd_lg_clean, psd_graph), of the closed study of the tail's one-pass kernel and of the
+    finished experiments around it (csrc/tail_solve.hip, csrc/lead_solve.hip; NOTEBOOK.md "Round 6"), and the former no-op "graph" included."""
     import ctypes as C
     lib = cuadmm_amd.load()
     h = C.c_void_p()
     assert lib.cuadmm_create(C.byref(h)) == 0
     try:
-        for key, val in (("tail_order", 0), ("tail_zreg", 0), ("tail_rb", 2), ("tail_depth", 3), ("psd_lg_fuse", 1), ("tail_pivot", 1)):
+        for key, val in (("psd_lg_fuse", 1), ("tail_pivot", 1), ("tail_one_pass", 1), ("tail_refine", 0), ("lead_tops", -1), ("tail_k", -1), ("tail_max_k", 32768),
+                         ("tail_shard", 1), ("lead_stream", 0), ("lead_small_kb", 0), ("l21_device", 1)):
             assert lib.cuadmm_set_option(h, key.encode(), C.c_double(val)) == 0, key
-        assert lib.cuadmm_set_option(h, b"tail_depth", C.c_double(4)) != 0
-        assert b"tail_depth" in lib.cuadmm_last_error()
-        for key in (b"no_such_option", b"psd_lg_clean", b"psd_graph"):
+        for key in (b"no_such_option", b"psd_lg_clean", b"psd_graph", b"tail_prefetch", b"tail_depth", b"tail_order", b"tail_rb", b"tail_zreg", b"tail_group_pf",
+                    b"tail_fat", b"tail_dd", b"tail_pinv_tol", b"pinv_tol", b"lead_tops_refine", b"graph"):
             assert lib.cuadmm_set_option(h, key, C.c_double(1)) != 0, key
             assert key in lib.cuadmm_last_error()
     finally:
