@@ -122,6 +122,13 @@ PROTOTYPES = {
     "cuadmm_op_tail_solve_sharded": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "cuadmm_tail_shard_bounds": (C.c_int, [C.c_int, C.c_int, C.c_void_p]),
     "cuadmm_op_tail_solve_drill": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cuadmm_op_lead_solve": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_int,
+                                        C.c_void_p, C.c_void_p]),
+    "cuadmm_op_forest_solve": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p]),
+    "cuadmm_op_aty_xb": (C.c_int, [C.c_int64, C.c_int] + [C.c_void_p] * 6 + [C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cuadmm_op_post": (C.c_int, [C.c_int, C.c_int64] + [C.c_void_p] * 5 + [C.c_double, C.c_double, C.c_void_p, C.c_int] + [C.c_void_p] * 5),
+    "cuadmm_op_spmv_rows": (C.c_int, [C.c_int, C.c_int] + [C.c_void_p] * 6 + [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cuadmm_op_rp_stats": (C.c_int, [C.c_int] + [C.c_void_p] * 4 + [C.c_double, C.c_void_p, C.c_void_p]),
     "cuadmm_op_batch_eig": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "cuadmm_op_max_zero": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p]),
     "cuadmm_op_mul_diag_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),

@@ -967,8 +967,8 @@ static int init_matrices(Solver* s, const InitIn& in, InitCtx& c) {
       }
       arp[pidx + 1] = (int)aci.size();
     }
-    s->A_avg_nnz = m > 0 ? (double)aci.size() / m : 1.0;
     if ((rc = s->A_long.build(m, arp.data()))) return rc;
+    s->A_avg_nnz = spmv_avg_nnz(m, arp.data(), s->A_long);   // long rows count with their capped part only
     // fused iteration: needs the one-wavefront-per-block sign kernels and no long rows of A^T (they are summed by their own kernel)
     s->fuse = s->plan.fusable() && s->At_long.nlong == 0 && !s->sw.debug_eig && s->sw.fuse != 0;
     s->lrows.active = false; s->lrows.nlocal = s->lrows.nrest = 0;
@@ -1046,11 +1046,6 @@ static int init_matrices(Solver* s, const InitIn& in, InitCtx& c) {
         }
         lr.active = true;
       }
-    }
-    if (s->A_long.nlong > 0) {   // the average that picks the threads-per-row of the main kernel should not count the capped tails
-      long long capped = 0;
-      for (int i = 0; i < m; ++i) capped += std::min(arp[i + 1] - arp[i], s->A_long.cap);
-      s->A_avg_nnz = (double)capped / m;
     }
     if ((rc = s->A_rp.from(arp)) || (rc = s->A_ci.alloc(std::max<size_t>(aci.size(), 1))) || (rc = s->A_v.alloc(std::max<size_t>(av.size(), 1)))) return rc;
     if ((rc = s->A_ci.upload(aci.data(), aci.size())) || (rc = s->A_v.upload(av.data(), av.size()))) return rc;
@@ -2217,6 +2212,85 @@ int cuadmm_op_tail_solve_drill(const double* L22_host, const double* D2_host, in
   counts[1] = t.take_failure(nullptr);
   counts[2] = t.group_retired ? 1 : 0;
   return t.solve(out_host + 3 * (size_t)k, nullptr);
+}
+
+// Test hook only: the device y-solve around the GPU tail on its own.  The tail and the leading sweeps are built from the split factor the
+// way init_factor / init_solve_plan build them (the tail from the Schur complement with the engine's default switches; LeadSolve with the
+// switches given), and whatever build() made ready runs -- the engine's cost-model veto (est_us against the host's sweeps) is NOT applied.
+// force_hybrid: the engine's hybrid sequence (host sweeps over L11, apply_l21 between them), demoting ready sweeps if need be.
+// ax / asmc / b: nrhs x m (factor's order), y_out likewise; one pair of objects serves all right-hand sides in turn.  y is filled with NaN
+// before every solve, so a row no kernel wrote comes back as NaN.  The factor keeps its Schur complement (the caller may read it).
+// info11 = {ntrees, max_levels, n_small, n_big, n_stream, n_micro, n_long, tops, nT, hybrid, ready}.
+int cuadmm_op_lead_solve(const cuadmm_aat* f, int m, int stream_only, int small_kb, int tops_level, int force_hybrid, const double* ax,
+                         const double* asmc, const double* b, double isig, int nrhs, double* y_out, int* info11) {
+  if (!f || m < 1 || !ax || !asmc || !b || !y_out || !info11 || nrhs < 0) { set_error("op_lead_solve: bad arguments"); return CUADMM_ERR_INVALID; }
+  const int k = cuadmm_aat_tail_k(f);
+  if (k < 1 || k > m) { set_error("op_lead_solve: a split factor of %d rows (tail %d)", m, k); return CUADMM_ERR_INVALID; }
+  const int64_t *srp, *Lp; const int *sci, *Li; const double *sv, *Lx, *D;
+  int rc;
+  if ((rc = cuadmm_aat_tail_schur(f, &srp, &sci, &sv)) || (rc = cuadmm_aat_factor_arrays(f, &Lp, &Li, &Lx, &D))) return rc;
+  TailSolve tail;
+  if ((rc = tail.build_from_schur(reinterpret_cast<const long long*>(srp), sci, sv, k, nullptr))) return rc;
+  LeadSolve lead;
+  lead.stream_only = stream_only != 0;
+  lead.force_hybrid = force_hybrid != 0;
+  lead.small_kb = std::max(0, std::min(small_kb, 36));
+  lead.tops_level = force_hybrid ? 0 : tops_level;
+  if ((rc = lead.build(m, k, Lp, Li, Lx, D, true))) return rc;
+  if (force_hybrid && !lead.hybrid && !(lead.ready && lead.demote_to_hybrid())) { set_error("op_lead_solve: no hybrid solve for this factor"); return CUADMM_ERR_INVALID; }
+  if (!lead.ready && !lead.hybrid) { set_error("op_lead_solve: neither the device sweeps nor the hybrid solve could be built"); return CUADMM_ERR_INVALID; }
+  const int info[11] = {lead.ntrees, lead.max_levels, lead.n_small, lead.n_big, lead.n_stream, lead.n_micro, lead.n_long, lead.tops ? 1 : 0, lead.nT,
+                        lead.hybrid ? 1 : 0, lead.ready ? 1 : 0};
+  std::copy(info, info + 11, info11);
+  DevBuf<double> ax_d, asmc_d, b_d, y_d;
+  if ((rc = ax_d.alloc(m)) || (rc = asmc_d.alloc(m)) || (rc = b_d.alloc(m)) || (rc = y_d.alloc(m))) return rc;
+  std::vector<double> yh((size_t)m);
+  for (int r = 0; r < nrhs; ++r) {
+    const double *axr = ax + (size_t)r * m, *asr = asmc + (size_t)r * m, *br = b + (size_t)r * m;
+    double* yr = y_out + (size_t)r * m;
+    if (lead.hybrid) {
+      for (int i = 0; i < m; ++i) yh[i] = -asr[i] + isig * (-axr[i] + br[i]);       // host_solve()'s right-hand side
+      if ((rc = cuadmm_aat_solve_leading_forward11(f, k, yh.data())) || (rc = lead.apply_l21(yh.data(), false, tail, nullptr)) ||
+          (rc = cuadmm_aat_solve_leading_backward11(f, k, yh.data(), lead.h_w)))
+        return rc;
+      std::copy(yh.begin(), yh.end(), yr);
+    } else {
+      if ((rc = ax_d.upload(axr, m)) || (rc = asmc_d.upload(asr, m)) || (rc = b_d.upload(br, m))) return rc;
+      CUADMM_HIP_TRY(hipMemset(y_d.p, 0xff, sizeof(double) * (size_t)m));
+      if ((rc = lead.solve(ax_d.p, asmc_d.p, b_d.p, isig, y_d.p, tail, nullptr))) return rc;
+      CUADMM_HIP_TRY(hipStreamSynchronize(nullptr));
+      if ((rc = staged_d2h(yr, y_d.p, sizeof(double) * (size_t)m))) return rc;
+    }
+  }
+  const int lost = tail.fail_count(nullptr);
+  if (lost != 0) { set_error("op_lead_solve: %d row exchanges of the tail lost", lost); return CUADMM_ERR_FACTOR; }
+  return CUADMM_OK;
+}
+
+// Test hook only: one thread per tree of a one-piece factor's elimination forest (forest_solve_kernel), with the arrays the engine uploads
+// in init_solve_plan.  info2 = {trees, columns of the largest tree}.
+int cuadmm_op_forest_solve(cuadmm_aat* f, int m, const double* ax, const double* asmc, const double* b, double isig, double* y_out, int* info2) {
+  if (!f || m < 1 || !ax || !asmc || !b || !y_out || !info2) { set_error("op_forest_solve: bad arguments"); return CUADMM_ERR_INVALID; }
+  if (cuadmm_aat_tail_k(f) != 0) { set_error("op_forest_solve: a one-piece factor"); return CUADMM_ERR_INVALID; }
+  int ntrees = 0, maxc = 0, rc;
+  const int *tp = nullptr, *tc = nullptr;
+  const int64_t* Lp; const int* Li; const double* Lx; const double* D;
+  if ((rc = cuadmm_aat_forest(f, &ntrees, &maxc, &tp, &tc)) || (rc = cuadmm_aat_factor_arrays(f, &Lp, &Li, &Lx, &D))) return rc;
+  const size_t lnz = (size_t)Lp[m];
+  DevBuf<int> d_tp, d_tc, d_Li;
+  DevBuf<long long> d_Lp;
+  DevBuf<double> d_Lx, d_D, ax_d, asmc_d, b_d, y_d;
+  if ((rc = d_tp.from(std::vector<int>(tp, tp + ntrees + 1))) || (rc = d_tc.from(std::vector<int>(tc, tc + m))) ||
+      (rc = d_Lp.from(std::vector<long long>(Lp, Lp + m + 1))) || (rc = d_Li.from(std::vector<int>(Li, Li + lnz))) ||
+      (rc = d_Lx.from(std::vector<double>(Lx, Lx + lnz))) || (rc = d_D.from(std::vector<double>(D, D + m))) ||
+      (rc = ax_d.from(std::vector<double>(ax, ax + m))) || (rc = asmc_d.from(std::vector<double>(asmc, asmc + m))) ||
+      (rc = b_d.from(std::vector<double>(b, b + m))) || (rc = y_d.alloc(m)))
+    return rc;
+  CUADMM_HIP_TRY(hipMemset(y_d.p, 0xff, sizeof(double) * (size_t)m));
+  if ((rc = launch_forest_solve(ntrees, d_tp.p, d_tc.p, d_Lp.p, d_Li.p, d_Lx.p, d_D.p, ax_d.p, asmc_d.p, b_d.p, isig, y_d.p, nullptr))) return rc;
+  CUADMM_HIP_TRY(hipStreamSynchronize(nullptr));
+  info2[0] = ntrees; info2[1] = maxc;
+  return staged_d2h(y_out, y_d.p, sizeof(double) * (size_t)m);
 }
 
 int cuadmm_op_psd_project(const double* Xb, double* Xproj, const int* blk_host, int mat_num, void* stream) {

@@ -58,6 +58,9 @@ struct SpmvLongRows {
   ~SpmvLongRows() { release(); }
 };
 
+// avg_nnz of launch_spmv_rows for the rows of A and their long-row list (the engine's init and the op-level test hook share it)
+double spmv_avg_nnz(int rows, const int* rp_host, const SpmvLongRows& lr);
+
 // outX = A*X, outS = A*(S-C) over the rows of A (either output may be null)
 int launch_spmv_rows(int rows, double avg_nnz, const int* rp, const int* ci, const double* av, const double* X,
                      const double* S, const double* C, double* outX, double* outS, hipStream_t st,

@@ -408,30 +408,34 @@ int launch_rp_stats(int m, const double* ax, const double* b, const double* norm
 // THREAD per tree.  The sweeps of a solve never leave a tree, and inside a tree this is the serial host algorithm
 // (aat_ldlt.cpp: columns ascending, x[i] -= L[i][j] x[j]; then x[j] / D[j] and the transposed sweep) with unfused
 // multiply-subtract, so y is bit-identical to the host solve.  y stays in HBM: no m-vector crosses PCIe in an iteration.
+// (Contraction is switched off for the kernel's body by pragma: __dmul_rn / __dsub_rn are plain operators to this compiler and were
+// fused into v_fma_f64 / v_fmac_f64 after inlining -- tests/test_gpu_iter_kernels.py compares with the host solve bit for bit.)
 // ------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kVecThreads) void forest_solve_kernel(int ntrees, const int* __restrict__ tree_ptr, const int* __restrict__ tree_cols,
                                                                    const long long* __restrict__ Lp, const int* __restrict__ Li,
                                                                    const double* __restrict__ Lx, const double* __restrict__ D,
                                                                    const double* __restrict__ ax, const double* __restrict__ asmc,
                                                                    const double* __restrict__ b, double isig, double* __restrict__ x) {
+#pragma clang fp contract(off)
   const int t = (int)(blockIdx.x * blockDim.x + threadIdx.x);
   if (t >= ntrees) return;
   const int c0 = tree_ptr[t], c1 = tree_ptr[t + 1];
   for (int q = c0; q < c1; ++q) {
     const int j = tree_cols[q];
-    const double rp = __dadd_rn(-ax[j], b[j]);                       // Rp = -A X + b
-    x[j] = __dadd_rn(-asmc[j], __dmul_rn(isig, rp));                 // rhs = -A(S-C) + Rp / sigma
+    const double rp = -ax[j] + b[j];                                 // Rp = -A X + b
+    const double scaled = isig * rp;
+    x[j] = -asmc[j] + scaled;                                        // rhs = -A(S-C) + Rp / sigma
   }
   for (int q = c0; q < c1; ++q) {                                    // L z = rhs
     const int j = tree_cols[q];
     const double xj = x[j];
     if (xj != 0.0)
-      for (long long p = Lp[j]; p < Lp[j + 1]; ++p) x[Li[p]] = __dsub_rn(x[Li[p]], __dmul_rn(Lx[p], xj));
+      for (long long p = Lp[j]; p < Lp[j + 1]; ++p) { const double u = Lx[p] * xj; x[Li[p]] = x[Li[p]] - u; }
   }
   for (int q = c1 - 1; q >= c0; --q) {                               // D^-1, then L^T y = z
     const int j = tree_cols[q];
     double s = x[j] / D[j];
-    for (long long p = Lp[j]; p < Lp[j + 1]; ++p) s = __dsub_rn(s, __dmul_rn(Lx[p], x[Li[p]]));
+    for (long long p = Lp[j]; p < Lp[j + 1]; ++p) { const double u = Lx[p] * x[Li[p]]; s = s - u; }
     x[j] = s;
   }
 }
@@ -668,6 +672,15 @@ int SpmvLongRows::build(int rows, const int* rp_host) {
   { int rc_ = staged_h2d(seg_end, se.data(), sizeof(int) * se.size()); if (rc_) return rc_; }
   return CUADMM_OK;
 }
+// average row length that picks the lanes per row of spmv_rows_kernel: with long rows only the part the main kernel sums counts
+// (their capped tails go to the segment kernels)
+double spmv_avg_nnz(int rows, const int* rp_host, const SpmvLongRows& lr) {
+  if (rows <= 0) return 1.0;
+  if (lr.nlong == 0) return (double)(rp_host[rows] - rp_host[0]) / rows;
+  long long capped = 0;
+  for (int i = 0; i < rows; ++i) capped += std::min(rp_host[i + 1] - rp_host[i], lr.cap);
+  return (double)capped / rows;
+}
 void SpmvLongRows::release() {
   for (void* p : {(void*)long_row, (void*)long_seg0, (void*)seg_begin, (void*)seg_end, (void*)partial}) if (p) { hipError_t e = hipFree(p); (void)e; }
   long_row = long_seg0 = seg_begin = seg_end = nullptr;
@@ -875,6 +888,26 @@ using namespace cuadmm;
     }                                                                                       \
   } while (0)
 
+namespace {
+template <class T>
+struct HookBuf {
+  T* p = nullptr;
+  int from(const T* h, size_t n) {
+    CUADMM_HIP_TRY(hipMalloc(&p, sizeof(T) * std::max<size_t>(n, 1)));
+    return (n && h) ? staged_h2d(p, h, sizeof(T) * n) : CUADMM_OK;
+  }
+  int to(T* h, size_t n) const { return n ? staged_d2h(h, p, sizeof(T) * n) : CUADMM_OK; }
+  ~HookBuf() { if (p) { hipError_t e = hipFree(p); (void)e; } }
+};
+bool csr_ok(long long rows, long long cols, const int* rp, const int* ci) {
+  if (rows < 0 || !rp || rp[0] != 0) return false;
+  for (long long i = 0; i < rows; ++i) if (rp[i + 1] < rp[i]) return false;
+  if (rp[rows] > 0 && !ci) return false;
+  for (int p = 0; p < rp[rows]; ++p) if (ci[p] < 0 || ci[p] >= cols) return false;
+  return true;
+}
+}  // namespace
+
 extern "C" {
 
 int cuadmm_op_vector_to_matrices(const double* Xb, double* large_mat, double* small_mat, const int* map_B,
@@ -946,6 +979,100 @@ int cuadmm_op_norm2(const double* v, int64_t n, double* host_out, void* stream) 
   CUADMM_HIP_TRY(e);
   *host_out = sqrt(h[0]);
   return CUADMM_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// Test hooks only: the iteration's own kernels as ops (host pointers; copies through the staged buffers).  Every index array is
+// checked before anything is launched, so a malformed input is an error code, never an out-of-range access.
+// ------------------------------------------------------------------------------------------
+
+int cuadmm_op_aty_xb(int64_t L, int m, const int* rp, const int* ci, const double* av, const double* y, const double* C, const double* X,
+                     double sig, int write_xb, double* Rd1, double* Xb, int* info2) {
+  if (L < 1 || m < 1 || !av || !y || !C || !X || !Rd1 || !Xb || !info2 || !csr_ok(L, m, rp, ci)) { set_error("op_aty_xb: bad arguments"); return CUADMM_ERR_INVALID; }
+  const size_t nnz = (size_t)rp[L];
+  AtyLongRows lr;
+  int rc = lr.build(L, rp);
+  if (rc) return rc;
+  HookBuf<int> d_rp, d_ci;
+  HookBuf<double> d_av, d_y, d_C, d_X, d_Rd1, d_Xb;
+  if ((rc = d_rp.from(rp, (size_t)L + 1)) || (rc = d_ci.from(ci, nnz)) || (rc = d_av.from(av, nnz)) || (rc = d_y.from(y, (size_t)m)) || (rc = d_C.from(C, (size_t)L)) ||
+      (rc = d_X.from(X, (size_t)L)) || (rc = d_Rd1.from(Rd1, (size_t)L)) || (rc = d_Xb.from(Xb, (size_t)L)))
+    return rc;
+  if ((rc = launch_aty_xb(write_xb != 0, L, d_rp.p, d_ci.p, d_av.p, d_y.p, d_C.p, d_X.p, sig, d_Rd1.p, d_Xb.p, nullptr, &lr))) return rc;
+  CUADMM_HIP_TRY(hipStreamSynchronize(nullptr));
+  if ((rc = d_Rd1.to(Rd1, (size_t)L)) || (rc = d_Xb.to(Xb, (size_t)L))) return rc;
+  info2[0] = lr.nlong; info2[1] = lr.max_short;
+  return CUADMM_OK;
+}
+
+int cuadmm_op_post(int mode, int64_t L, const double* Xproj, const double* Rd1, const double* C, double* X, double* S, double inv_sig, double tau_sig,
+                   double* sums2, int m, const int* rp, const int* ci, const double* av, const double* y, int* nparts_out) {
+  if (mode < 0 || mode > 3 || L < 1 || !C || !X || !S || !sums2) { set_error("op_post: bad arguments"); return CUADMM_ERR_INVALID; }
+  if (mode < 3 && (!Xproj || !Rd1)) { set_error("op_post: modes 0 - 2 take Xproj and Rd1"); return CUADMM_ERR_INVALID; }
+  if (mode == 3 && (m < 1 || !av || !y || !csr_ok(L, m, rp, ci))) { set_error("op_post: mode 3 takes A^T by svec rows and y"); return CUADMM_ERR_INVALID; }
+  const int grid = post_grid(L);
+  int rc;
+  HookBuf<double> d_Xp, d_Rd1, d_C, d_X, d_S, d_part, d_sums, d_av, d_y;
+  HookBuf<int> d_rp, d_ci;
+  if ((rc = d_C.from(C, (size_t)L)) || (rc = d_X.from(X, (size_t)L)) || (rc = d_S.from(S, (size_t)L)) || (rc = d_part.from(nullptr, 2 * (size_t)grid)) ||
+      (rc = d_sums.from(sums2, 2)))
+    return rc;
+  if (mode < 3) {
+    if ((rc = d_Xp.from(Xproj, (size_t)L)) || (rc = d_Rd1.from(Rd1, (size_t)L))) return rc;
+    rc = launch_post(mode, L, d_Xp.p, d_Rd1.p, d_C.p, d_X.p, d_S.p, inv_sig, tau_sig, d_part.p, d_sums.p, nullptr);
+  } else {
+    const size_t nnz = (size_t)rp[L];
+    if ((rc = d_rp.from(rp, (size_t)L + 1)) || (rc = d_ci.from(ci, nnz)) || (rc = d_av.from(av, nnz)) || (rc = d_y.from(y, (size_t)m))) return rc;
+    rc = launch_aty_post2(L, d_rp.p, d_ci.p, d_av.p, d_y.p, d_C.p, d_S.p, d_X.p, tau_sig, d_part.p, d_sums.p, nullptr);
+  }
+  if (rc) return rc;
+  CUADMM_HIP_TRY(hipStreamSynchronize(nullptr));
+  if ((rc = d_X.to(X, (size_t)L)) || (rc = d_S.to(S, (size_t)L)) || (rc = d_sums.to(sums2, 2))) return rc;
+  if (nparts_out) *nparts_out = grid;
+  return CUADMM_OK;
+}
+
+int cuadmm_op_spmv_rows(int rows, int ncols, const int* rp, const int* ci, const double* av, const double* X, const double* S, const double* C,
+                        int want_x, int want_s, const int* rowmap, int out_len, double* outX, double* outS, int* info4) {
+  if (rows < 1 || ncols < 1 || !av || !X || !S || !C || !outX || !outS || !info4 || out_len < 1 || !csr_ok(rows, ncols, rp, ci) || (!rowmap && out_len != rows)) {
+    set_error("op_spmv_rows: bad arguments");
+    return CUADMM_ERR_INVALID;
+  }
+  if (rowmap)
+    for (int r = 0; r < rows; ++r) if (rowmap[r] < 0 || rowmap[r] >= out_len) { set_error("op_spmv_rows: rowmap[%d] out of range", r); return CUADMM_ERR_INVALID; }
+  const size_t nnz = (size_t)rp[rows];
+  int rc;
+  SpmvLongRows lr;
+  // a compact row list has no long rows (engine: the rows left over by the fused blocks; the finish kernel writes by row number)
+  if (!rowmap && (rc = lr.build(rows, rp))) return rc;
+  const double avg = spmv_avg_nnz(rows, rp, lr);
+  HookBuf<int> d_rp, d_ci, d_map;
+  HookBuf<double> d_av, d_X, d_S, d_C, d_oX, d_oS;
+  if ((rc = d_rp.from(rp, (size_t)rows + 1)) || (rc = d_ci.from(ci, nnz)) || (rc = d_av.from(av, nnz)) || (rc = d_X.from(X, (size_t)ncols)) ||
+      (rc = d_S.from(S, (size_t)ncols)) || (rc = d_C.from(C, (size_t)ncols)) || (rc = d_oX.from(outX, (size_t)out_len)) || (rc = d_oS.from(outS, (size_t)out_len)) ||
+      (rowmap && (rc = d_map.from(rowmap, (size_t)rows))))
+    return rc;
+  if ((rc = launch_spmv_rows(rows, avg, d_rp.p, d_ci.p, d_av.p, d_X.p, d_S.p, d_C.p, want_x ? d_oX.p : nullptr, want_s ? d_oS.p : nullptr, nullptr,
+                             rowmap ? nullptr : &lr, rowmap ? d_map.p : nullptr)))
+    return rc;
+  CUADMM_HIP_TRY(hipStreamSynchronize(nullptr));
+  if ((rc = d_oX.to(outX, (size_t)out_len)) || (rc = d_oS.to(outS, (size_t)out_len))) return rc;
+  int T = 1;
+  while (T < 64 && T < avg) T <<= 1;                 // launch_spmv_rows' own choice
+  info4[0] = T; info4[1] = lr.cap; info4[2] = lr.nlong; info4[3] = lr.nseg;
+  return CUADMM_OK;
+}
+
+int cuadmm_op_rp_stats(int m, const double* ax, const double* b, const double* normA, const double* y, double bscale, const double* sums2, double* out4) {
+  if (m < 1 || !ax || !b || !normA || !y || !sums2 || !out4) { set_error("op_rp_stats: bad arguments"); return CUADMM_ERR_INVALID; }
+  int rc;
+  HookBuf<double> d_ax, d_b, d_n, d_y, d_sums, d_part, d_out;
+  if ((rc = d_ax.from(ax, (size_t)m)) || (rc = d_b.from(b, (size_t)m)) || (rc = d_n.from(normA, (size_t)m)) || (rc = d_y.from(y, (size_t)m)) ||
+      (rc = d_sums.from(sums2, 2)) || (rc = d_part.from(nullptr, 128)) || (rc = d_out.from(out4, 4)))
+    return rc;
+  if ((rc = launch_rp_stats(m, d_ax.p, d_b.p, d_n.p, d_y.p, bscale, d_sums.p, d_part.p, d_out.p, nullptr))) return rc;
+  CUADMM_HIP_TRY(hipStreamSynchronize(nullptr));
+  return d_out.to(out4, 4);
 }
 
 }  // extern "C"

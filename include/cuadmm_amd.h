@@ -371,6 +371,32 @@ int cuadmm_op_tail_solve_sharded(const double* L22_host, const double* D2_host, 
  * counter raised beforehand (NaN), the solve after the object retired to the two-pass kernels; counts[3] = {exchanges lost by the
  * poisoned solve (0), count found and cleared after the third solve (>= 1), retired flag (1)}. */
 int cuadmm_op_tail_solve_drill(const double* L22_host, const double* D2_host, int k, const double* z_host, double* out_host, int* counts);
+/* Test hook only: the device y-solve of a SPLIT factor (cuadmm_aat_create_split; its Schur complement not yet released) on its own: the GPU
+ * tail and the leading sweeps built as the engine builds them, with the engine's switches of the sweeps -- stream_only (option "lead_stream"),
+ * small_kb ("lead_small_kb"), tops_level ("lead_tops": -1 automatic, 0 never, L > 0 cut at height L), force_hybrid ("l21_device" = 2: host
+ * sweeps over L11, L21 and the tail on the device).  What was built runs; the engine's cost model is not asked.  ax, asmc, b: nrhs x m host
+ * doubles in the factor's order, y_out[r] = (L D L^T)^-1 (-asmc[r] + (b[r] - ax[r]) * isig), solved one after the other on the same objects.
+ * info11 = {ntrees, max_levels, n_small, n_big, n_stream, n_micro, n_long, tops, nT, hybrid, ready}: which kernels served the forest. */
+int cuadmm_op_lead_solve(const cuadmm_aat* f, int m, int stream_only, int small_kb, int tops_level, int force_hybrid, const double* ax,
+                         const double* asmc, const double* b, double isig, int nrhs, double* y_out, int* info11);
+/* Test hook only: the same solve by one GPU thread per tree of a ONE-PIECE factor's elimination forest (what the engine runs for a
+ * block-diagonal A A^T); info2 = {trees, columns of the largest tree}. */
+int cuadmm_op_forest_solve(cuadmm_aat* f, int m, const double* ax, const double* asmc, const double* b, double isig, double* y_out, int* info2);
+/* Test hooks only: the kernels of an ADMM iteration as ops.  Every pointer is a HOST pointer; in/out arrays are uploaded as given, so what a
+ * kernel leaves untouched comes back bit for bit.
+ *   aty_xb   : Rd1 = At y - C and, with write_xb, Xb = X + sig Rd1; At in CSR over the L svec rows (m columns); info2 = {long rows, longest short row}
+ *   post     : mode 0 / 1 / 2 = the three update steps behind the projection (X, S in/out, sums2 = {sum Rd^2, <C, X>} in/out); mode 3 = the one-pass
+ *              second half of an sGS iteration (takes At, y and m instead of Xproj and Rd1); *nparts_out = partial pairs the final reduction summed
+ *   spmv_rows: outX = A X, outS = A (S - C) over the rows of A (CSR, ncols columns) where want_x / want_s; with rowmap (compact row -> slot of an
+ *              out_len vector) the engine's compact-list variant, else out_len = rows; info4 = {lanes per row, long-row cap, long rows, segments}
+ *   rp_stats : out4 = {sum (normA (b - ax) bscale)^2, b . y, sums2[0], sums2[1]} */
+int cuadmm_op_aty_xb(int64_t L, int m, const int* row_ptrs, const int* col_ids, const double* vals, const double* y, const double* C, const double* X,
+                     double sig, int write_xb, double* Rd1, double* Xb, int* info2);
+int cuadmm_op_post(int mode, int64_t L, const double* Xproj, const double* Rd1, const double* C, double* X, double* S, double inv_sig, double tau_sig,
+                   double* sums2, int m, const int* row_ptrs, const int* col_ids, const double* vals, const double* y, int* nparts_out);
+int cuadmm_op_spmv_rows(int rows, int ncols, const int* row_ptrs, const int* col_ids, const double* vals, const double* X, const double* S, const double* C,
+                        int want_x, int want_s, const int* rowmap, int out_len, double* outX, double* outS, int* info4);
+int cuadmm_op_rp_stats(int m, const double* ax, const double* b, const double* normA, const double* y, double bscale, const double* sums2, double* out4);
 /* Same with the factorisation on the GPU too: z <- S^-1 z for a symmetric S given by its lower triangle with
  * diagonal (CSR over k rows, host pointers), dense LDL^T without pivoting (what cuadmm_aat_create_split hands over). */
 int cuadmm_op_tail_factor_solve(const int64_t* row_ptr, const int* col, const double* val, int k, double* z_host, int nrhs);
