@@ -55,6 +55,7 @@ PROTOTYPES = {
     "cuadmm_get_y": (C.c_int, [C.c_void_p, C.c_void_p]),
     "cuadmm_get_S": (C.c_int, [C.c_void_p, C.c_void_p]),
     "cuadmm_set_XyS": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double]),
+    "cuadmm_update_bC": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double]),
     "cuadmm_get_device_ptrs": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     "cuadmm_get_shard": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), c_int_p, c_int_p]),
     "cuadmm_aat_factor_arrays": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_void_p)] * 4),
@@ -89,6 +90,7 @@ PROTOTYPES = {
     "cuadmm_problem_free": (None, [C.c_void_p]),
     "cuadmm_coo_to_csc": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
     "cuadmm_read_blk": (C.c_int, [C.c_char_p, C.c_void_p, C.c_void_p, C.c_int]),
+    "cuadmm_read_sparse_vec_txt": (C.c_int, [C.c_char_p, C.c_void_p, C.c_void_p, C.c_int]),
     "cuadmm_write_dense_txt": (C.c_int, [C.c_char_p, C.c_void_p, C.c_int64]),
     "cuadmm_is_large_mat": (C.c_int, [C.c_int, C.c_int]),
     "cuadmm_analyze_blk": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]),

@@ -8,6 +8,11 @@
 //   --json=<file>: a sidecar with the run's figures (iterations, residuals, iters/s, per-phase milliseconds, the projection's
 //   nominal TFLOP/s = 10.67 sum n^3 per projection and the vector kernels' algorithmic GB/s: SURVEY.md 8d); switches the
 //   engine's per-phase HIP-event timers on (option "profile").  Nothing is written unless asked for: the reference writes X_opt.txt only.
+//   --then=<dir2/> (repeatable): after the solve, read ONLY b.txt and C.txt from <dir2/> (either may be absent: unchanged), replace
+//   them on the factored solver (cuadmm_update_bC, warm start), solve with the same parameters and write <dir2/>X_opt.txt; one
+//   sidecar per stage: <file>, <file>.1, ...  A receding-horizon sequence pays for the ordering and the factor once.
+#include <dirent.h>
+
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -55,6 +60,19 @@ static bool write_sidecar(const std::string& path, const std::string& prefix, cu
   return fclose(f) == 0;
 }
 
+// b.txt / C.txt of a --then stage; absent: nnz = -1 (unchanged)
+static bool read_then_vec(const std::string& fn, std::vector<int>& idx, std::vector<double>& vals, int& nnz) {
+  nnz = -1;
+  FILE* f = fopen(fn.c_str(), "r");
+  if (!f) return true;
+  fclose(f);
+  const int n = cuadmm_read_sparse_vec_txt(fn.c_str(), nullptr, nullptr, 0);
+  if (n < 0) return false;
+  idx.assign((size_t)n + 1, 0); vals.assign((size_t)n + 1, 0.0);
+  nnz = cuadmm_read_sparse_vec_txt(fn.c_str(), idx.data(), vals.data(), n);
+  return nnz == n;
+}
+
 int main(int argc, char* argv[]) {
   if (argc < 2) {
     std::cerr << "usage: cuadmm_exe <problem_dir/> [--key=value ...]" << std::endl;
@@ -66,8 +84,10 @@ int main(int argc, char* argv[]) {
          sig = 1e0, device = 0;
   bool quiet = false;
   std::string json_path;
+  std::vector<std::string> then_dirs;
   for (int i = 2; i < argc; ++i) {
     if (strncmp(argv[i], "--json=", 7) == 0) { json_path = argv[i] + 7; continue; }
+    if (strncmp(argv[i], "--then=", 7) == 0) { then_dirs.push_back(argv[i] + 7); continue; }
     if (opt(argv[i], "--max_iter", max_iter) || opt(argv[i], "--stop_tol", stop_tol) || opt(argv[i], "--threshold", threshold) ||
         opt(argv[i], "--stage1", stage1) || opt(argv[i], "--stage2", stage2) || opt(argv[i], "--switch_admm", switch_admm) ||
         opt(argv[i], "--sigscale", sigscale) || opt(argv[i], "--sig", sig) || opt(argv[i], "--device", device))
@@ -75,6 +95,12 @@ int main(int argc, char* argv[]) {
     if (strcmp(argv[i], "--quiet") == 0) { quiet = true; continue; }
     std::cerr << "unknown option " << argv[i] << std::endl;
     return 1;
+  }
+
+  for (const std::string& d : then_dirs) {   // before any work: a stage that cannot be read must not cost the stages before it
+    DIR* dp = d.empty() ? nullptr : opendir(d.c_str());
+    if (!dp) { std::cerr << "cannot read --then directory '" << d << "'" << std::endl; return 1; }
+    closedir(dp);
   }
 
   cuadmm_problem* prob = nullptr;
@@ -103,6 +129,19 @@ int main(int argc, char* argv[]) {
   std::vector<double> X((size_t)v.vec_len);
   if (cuadmm_get_X(solver, X.data()) == CUADMM_OK) cuadmm_write_dense_txt((prefix + "X_opt.txt").c_str(), X.data(), v.vec_len);
   if (!json_path.empty() && !write_sidecar(json_path, prefix, solver, v)) std::cerr << "cannot write " << json_path << std::endl;
+  for (size_t k = 0; k < then_dirs.size() && rc == CUADMM_OK; ++k) {
+    const std::string& d = then_dirs[k];
+    std::vector<int> bi, ci;
+    std::vector<double> bv, cv;
+    int bn = -1, cn = -1;
+    if (!read_then_vec(d + "b.txt", bi, bv, bn) || !read_then_vec(d + "C.txt", ci, cv, cn)) { std::cerr << cuadmm_last_error() << std::endl; rc = CUADMM_ERR_IO; break; }
+    rc = cuadmm_update_bC(solver, bi.data(), bv.data(), bn, ci.data(), cv.data(), cn, 1, 0.0);
+    if (rc == CUADMM_OK) rc = cuadmm_solve(solver, (int)max_iter, stop_tol, (int)threshold, (int)stage1, (int)stage2, (int)switch_admm, sigscale, 1);
+    if (rc != CUADMM_OK) { std::cerr << cuadmm_last_error() << std::endl; break; }
+    if (cuadmm_get_X(solver, X.data()) == CUADMM_OK) cuadmm_write_dense_txt((d + "X_opt.txt").c_str(), X.data(), v.vec_len);
+    const std::string side = json_path + "." + std::to_string(k + 1);
+    if (!json_path.empty() && !write_sidecar(side, d, solver, v)) std::cerr << "cannot write " << side << std::endl;
+  }
   cuadmm_destroy(solver);
   cuadmm_problem_free(prob);
   return rc == CUADMM_OK ? 0 : 1;

@@ -234,6 +234,9 @@ struct cuadmm_solver {
   // if_first = false then simply continues, instead of unscaling and rescaling three vectors and recomputing A X, A (S - C)
   bool pending_unscale = false;
   int lazy_unscale = 1;
+  // cuadmm_update_bC rescaled y on the device (y-solve there): y_p is behind y_d until somebody on the host needs it (sync_y_host)
+  bool y_host_stale = false;
+  std::vector<double> normA_all;      // owned constraints: max(1, ||column||) of EVERY constraint (bscale of a new b runs over all of them)
   // Behavioural switches (cuadmm_set_option, before init).  The environment variables of round 1 / 2 only give the DEFAULTS, read
   // once per solver in its constructor: two solvers in a process can choose differently, and tests reach every variant.
   struct Switches {
@@ -666,6 +669,7 @@ struct cuadmm_solver {
   }
   // X, S, y back in the caller's units (solver.cu:814-816); a no-op unless a solve left them scaled
   int materialise();
+  int sync_y_host();
 
   int launch_post_mode(int mode, double tau) {
     prof_begin(K_POST);
@@ -1286,6 +1290,7 @@ static int init_closed(Solver* s, const InitIn& in, InitCtx& c) {
   return rc;
 }
 
+static int init_residuals(Solver* s, bool y_resident);
 // stage: device copies of b / normA for the device-side scalars, mapped result buffers, initial residuals (solver.cu:195-228)
 static int init_finish(Solver* s, const InitIn& in, InitCtx& c) {
   CUADMM_INIT_STAGE_PROLOGUE
@@ -1302,8 +1307,16 @@ static int init_finish(Solver* s, const InitIn& in, InitCtx& c) {
     else { hipError_t e = hipGetLastError(); (void)e; }
   }
 
-  // --- initial residuals (solver.cu:195-228)
-  if ((rc = s->upload_y(true))) return rc;
+  return init_residuals(s, false);
+}
+
+// last stage of init, and of cuadmm_update_bC: initial A X, A (S - C) and residual scalars (solver.cu:195-228) from the scaled X, y, S.
+// y_resident: y_d already holds y (the update rescaled it there), nothing to upload
+static int init_residuals(Solver* s, bool y_resident) {
+  const int m = s->m;
+  const long long L = s->L;
+  int rc = CUADMM_OK;
+  if (!y_resident && (rc = s->upload_y(true))) return rc;
   if ((rc = s->launch_aty(false))) return rc;                               // Rd1 = At*y - C
   if ((rc = launch_post(2, L, s->Xproj.p, s->Rd1.p, s->C.p, s->X.p, s->S.p, 1.0, 0.0, s->partials.p,
                         s->out_w + (size_t)m, s->st)))                      // Rd = Rd1 + S, sums (X untouched)
@@ -1522,6 +1535,12 @@ int cuadmm_init(cuadmm_solver* s, int eig_stream_num_per_gpu, int cpu_eig_thread
       s->m_full = con_num; s->cons_local = cons; s->sv_off = lo; s->blk_off = first[me];
       s->L_caller = vec_len; s->nblk_caller = mat_num;
       s->ov_nb = nb; s->ov_nc = nc; s->ov_nb2 = nb2;
+      s->normA_all.assign((size_t)con_num, 1.0);            // what a later cuadmm_update_bC divides the whole new b by
+      for (int j = 0; j < con_num; ++j) {
+        double cn = 0;
+        for (int p = At_cp[j]; p < At_cp[j + 1]; ++p) cn += At_vx[p] * At_vx[p];
+        s->normA_all[j] = std::max(1.0, std::sqrt(cn));
+      }
       s->world = 1; s->rank = 0;
       if (s->comm_rank != 0) s->verbose = 0;      // one console table per job
       int one = 0;
@@ -1592,6 +1611,7 @@ int cuadmm_solve(cuadmm_solver* s, int max_iter, double stop_tol, int sig_update
     // the previous solve left X, y, S scaled and [A X | A (S - C)], Rp as its last iteration formed them: nothing to redo
     s->pending_unscale = false;
   } else if (!if_first) {   // solver.cu:385-409: X,y,S currently hold UNSCALED values
+    if ((rc = s->sync_y_host())) return rc;
     for (int i = 0; i < m; ++i) s->y_p[i] = (s->y_p[i] * s->normA_p[i]) * (1 / s->Cscale);
     if (s->dev_solve && (rc = s->upload_y(true))) return rc;
     if ((rc = launch_scale(s->X.p, L, 1 / s->bscale, s->st))) return rc;
@@ -1873,9 +1893,23 @@ int cuadmm_solve(cuadmm_solver* s, int max_iter, double stop_tol, int sig_update
   return CUADMM_OK;
 }
 
+// y_d -> y_p after cuadmm_update_bC left the rescaled y on the device only
+int cuadmm_solver::sync_y_host() {
+  if (!y_host_stale) return CUADMM_OK;
+  y_host_stale = false;
+  if (m <= 0) return CUADMM_OK;
+  int rc;
+  if ((rc = check_device(device))) return rc;
+  CUADMM_HIP_TRY(hipMemcpyAsync(h_y.p, y_d.p, sizeof(double) * (size_t)m, hipMemcpyDeviceToHost, st));
+  CUADMM_HIP_TRY(hipStreamSynchronize(st));
+  std::memcpy(y_p.data(), h_y.p, sizeof(double) * (size_t)m);
+  return CUADMM_OK;
+}
+
 int cuadmm_solver::materialise() {
-  if (!pending_unscale) return CUADMM_OK;
+  if (!pending_unscale) return sync_y_host();
   pending_unscale = false;
+  y_host_stale = false;                 // y_d is copied down below
   int rc;
   if ((rc = check_device(device))) return rc;
   if ((rc = launch_scale(X.p, L, bscale, st))) return rc;
@@ -2044,6 +2078,152 @@ int cuadmm_set_XyS(cuadmm_solver* s, const double* X, const double* y, const dou
   if (y) for (int i = 0; i < s->m; ++i) s->y_p[i] = s->local_mode ? y[s->cons_local[s->perm[i]]] : y[s->perm[i]];
   if (sig > 0) s->sig = sig;
   return CUADMM_OK;
+}
+
+// New b and / or C on a factored solver.  Nothing that depends on A alone is touched: ordering, factor, GPU tail, tree tops, CSR
+// matrices, projection plan.  What changes: the scaling constants, b (host, device, the closed blocks' records), C, the units of the
+// resident X, y, S -- rescaled where they live, with the rounded operations of materialise() followed by init's scaling -- and the
+// per-solve bookkeeping, which goes back to what init leaves.  The last stage of init (init_residuals) then runs as it does there.
+int cuadmm_update_bC(cuadmm_solver* s, const int* b_idx, const double* b_vals, int b_nnz, const int* C_idx, const double* C_vals, int C_nnz,
+                     int keep_iterate, double sig) {
+  if (!s || !s->initialised) { set_error("update_bC: solver not initialised"); return CUADMM_ERR_INVALID; }
+  const bool new_b = b_nnz >= 0, new_C = C_nnz >= 0;
+  if ((b_nnz > 0 && (!b_idx || !b_vals)) || (C_nnz > 0 && (!C_idx || !C_vals))) { set_error("update_bC: entries without their index / value arrays"); return CUADMM_ERR_INVALID; }
+  // --- every check before anything changes (the caller's numbering; the rules of init_vectors, over the whole of b and C on every rank)
+  const int m_call = s->local_mode ? s->m_full : s->m;
+  const long long L_call = s->local_mode ? s->L_caller : s->L_full;
+  if (new_b) {
+    std::vector<char> seen((size_t)m_call, 0);
+    for (int i = 0; i < b_nnz; ++i) {
+      if (b_idx[i] < 0 || b_idx[i] >= m_call) { set_error("update_bC: b index %d out of range", b_idx[i]); return CUADMM_ERR_INVALID; }
+      if (seen[b_idx[i]]) { set_error("update_bC: b index %d appears twice", b_idx[i]); return CUADMM_ERR_INVALID; }
+      seen[b_idx[i]] = 1;
+    }
+  }
+  if (new_C) {
+    std::vector<char> seen((size_t)L_call, 0);
+    for (int i = 0; i < C_nnz; ++i) {
+      if (C_idx[i] < 0 || C_idx[i] >= L_call) { set_error("update_bC: C index %d out of range", C_idx[i]); return CUADMM_ERR_INVALID; }
+      if (seen[C_idx[i]]) { set_error("update_bC: C index %d appears twice", C_idx[i]); return CUADMM_ERR_INVALID; }
+      seen[C_idx[i]] = 1;
+    }
+  }
+  if (s->group && !s->in_group_call) {      // every rank takes the full b and C, as with init; their residual stage meets in the group's all-reduce
+    DeviceGuard keep_device;
+    return duo_group_run(s->group, [&](cuadmm_solver* q, int) {
+      q->in_group_call = true;
+      int r2 = cuadmm_update_bC(q, b_idx, b_vals, b_nnz, C_idx, C_vals, C_nnz, keep_iterate, sig);
+      q->in_group_call = false;
+      return r2;
+    });
+  }
+  int rc = check_device(s->device);
+  if (rc) return rc;
+  const double t_begin = wall_s();
+  const int m = s->m;
+  const long long L = s->L;
+
+  // --- this rank's entries, in the engine's numbering: b by position in the factor's order and divided by normA (sparse_dense.cu:11-20),
+  // C by local svec slot; the norms over the WHOLE of b and C (owned constraints: from the full inputs every rank holds)
+  double nb = 0, nb2 = 0, nc = 0;
+  std::vector<int> bi, ci;
+  std::vector<double> bv, cv;
+  std::vector<double> bfull;
+  if (new_b) {
+    bfull.assign((size_t)m, 0.0);
+    std::vector<int> g2l;
+    if (s->local_mode) { g2l.assign((size_t)s->m_full, -1); for (int q = 0; q < m; ++q) g2l[s->cons_local[q]] = q; }
+    for (int i = 0; i < b_nnz; ++i) {
+      nb += b_vals[i] * b_vals[i];
+      if (s->local_mode) { const double v = b_vals[i] / s->normA_all[b_idx[i]]; nb2 += v * v; }
+      const int j = s->local_mode ? g2l[b_idx[i]] : b_idx[i];
+      if (j < 0) continue;
+      const double v = b_vals[i] / s->normA[j];
+      bfull[j] = v;
+      if (!s->local_mode) nb2 += v * v;
+      bi.push_back(s->perm_inv[j]); bv.push_back(v);
+    }
+  }
+  if (new_C) {
+    const long long lo = s->sv_off + s->sv_begin, hi = s->sv_off + s->sv_end;
+    for (int i = 0; i < C_nnz; ++i) {
+      nc += C_vals[i] * C_vals[i];
+      if (C_idx[i] >= lo && C_idx[i] < hi) { ci.push_back((int)(C_idx[i] - lo)); cv.push_back(C_vals[i]); }
+    }
+  }
+  // the sparse entries are all that crosses to the device
+  DevBuf<int> bi_d, ci_d;
+  DevBuf<double> bv_d, cv_d;
+  const bool b_on_device = new_b && s->b_d.p != nullptr;
+  s->prof_begin(K_COPY);
+  if (b_on_device && !bi.empty() && ((rc = bi_d.from(bi)) || (rc = bv_d.from(bv)))) return rc;
+  if (!ci.empty() && ((rc = ci_d.from(ci)) || (rc = cv_d.from(cv)))) return rc;
+  s->prof_end(K_COPY, 12.0 * ((b_on_device ? (double)bi.size() : 0.0) + (double)ci.size()));
+
+  // --- from here on the solver changes.  A solve left X, y, S scaled (pending): their way back to the caller's units is folded into
+  // the rescaling; otherwise they are taken as they stand, as init takes X0, y0, S0.
+  const bool pending = s->pending_unscale;
+  if (!pending && (rc = s->sync_y_host())) return rc;
+  const double bs_old = s->bscale, cs_old = s->Cscale;
+  if (new_b) {
+    s->norm_borg = 1 + std::sqrt(nb);
+    s->bscale = 1 + std::sqrt(nb2);
+    if (s->local_mode) { s->ov_nb = nb; s->ov_nb2 = nb2; }
+  }
+  if (new_C) {
+    s->norm_Corg = 1 + std::sqrt(nc);
+    s->Cscale = 1 + std::sqrt(nc);
+    if (s->local_mode) s->ov_nc = nc;
+  }
+  s->objscale = s->bscale * s->Cscale;
+  const double ibs = 1 / s->bscale, ics = 1 / s->Cscale;
+  if (new_b)
+    for (int pidx = 0; pidx < m; ++pidx) s->b_p[pidx] = bfull[s->perm[pidx]] * ibs;
+
+  // svec pass: X, S (and C <- 0), then C's entries
+  const bool keep = keep_iterate != 0;
+  s->prof_begin(K_POST);
+  if ((rc = launch_update_svec(s->X.p, s->S.p, new_C ? s->C.p : nullptr, L, !keep, pending ? bs_old : 1.0, ibs, pending ? cs_old : 1.0, ics, s->st))) return rc;
+  s->prof_end(K_POST, (new_C ? 40.0 : 32.0) * (double)L);
+  if (new_C && (rc = launch_scatter_scaled(s->C.p, ci_d.p, cv_d.p, (int)ci.size(), ics, s->st))) return rc;
+
+  // constraint pass: b_d and y where they live
+  const bool y_on_device = s->dev_solve && (pending || !keep);
+  if (y_on_device) {
+    if ((rc = launch_update_cons(m, b_on_device ? s->b_d.p : nullptr, s->y_d.p, s->normA_d.p, keep ? 2 : 1, cs_old, ics, s->st))) return rc;
+    if (!keep) std::fill(s->y_p.begin(), s->y_p.end(), 0.0);
+    s->y_host_stale = keep && m > 0;
+  } else {
+    if (pending && !s->dev_solve)      // the solve left y_p scaled
+      for (int i = 0; i < m; ++i) s->y_p[i] = s->y_p[i] / s->normA_p[i] * cs_old;
+    if (keep) for (int i = 0; i < m; ++i) s->y_p[i] = (s->y_p[i] * s->normA_p[i]) * ics;
+    else std::fill(s->y_p.begin(), s->y_p.end(), 0.0);
+    if (b_on_device && (rc = launch_update_cons(m, s->b_d.p, nullptr, nullptr, 0, cs_old, ics, s->st))) return rc;
+  }
+  if (b_on_device) {
+    if ((rc = launch_scatter_scaled(s->b_d.p, bi_d.p, bv_d.p, (int)bi.size(), ibs, s->st))) return rc;
+    if (s->closed.active && (rc = launch_closed_patch_b(s->closed.rec.p, s->plan.fused_blocks(), s->b_d.p, s->st))) return rc;
+  }
+  s->pending_unscale = false;
+  if (sig > 0) s->sig = sig;
+
+  // --- per-solve bookkeeping as init leaves it (profile counters, plans, the blocks' launch order stay)
+  for (auto& a : s->info) a.clear();
+  s->info_iter_num = 0;
+  s->t_init0 = t_begin; s->total_time = 0;
+  s->best_KKT = 0; s->sgs_KKT = 0; s->have_best = false; s->eig_fail_total = 0;
+  s->prim_win = 0; s->dual_win = 0; s->feasratio = 0; s->ratioconst = 1e0; s->sigmax = 1e3; s->sigmin = 1e-3;
+  s->y_early = false; s->stats_fused = false;
+  s->bt.len = s->bt.pos = 0; s->bt.have_ck = false;
+  s->closed.iters_done = 0; s->closed.out_dirty = true;
+  s->plan.n_project = 0;
+  if (s->hint_d.p) CUADMM_HIP_TRY(hipMemsetAsync(s->hint_d.p, 0, sizeof(int) * s->hint_d.n, s->st));     // the sign schedule's warm start
+  if (s->closed.cl_out.p) CUADMM_HIP_TRY(hipMemsetAsync(s->closed.cl_out.p, 0, sizeof(double) * s->closed.cl_out.n, s->st));
+  if (!s->dev_solve) std::fill(s->Rp_p.begin(), s->Rp_p.end(), 0.0);
+  s->y_full.clear();
+
+  // --- initial A X, A (S - C), residual scalars: init's own last stage (it ends with a stream synchronisation)
+  return init_residuals(s, y_on_device);
 }
 
 int cuadmm_get_device_ptrs(cuadmm_solver* s, double** X, double** y, double** S) {
@@ -2388,6 +2568,16 @@ int cuadmm_read_blk(const char* filename, char* types, int* sizes, int cap) {
   if (rc) return rc;
   for (size_t i = 0; i < sz.size() && (int)i < cap; ++i) { if (types) types[i] = t[i]; if (sizes) sizes[i] = sz[i]; }
   return (int)sz.size();
+}
+
+int cuadmm_read_sparse_vec_txt(const char* filename, int* indices, double* vals, int cap) {
+  if (!filename) { set_error("read_sparse_vec_txt: null"); return CUADMM_ERR_INVALID; }
+  std::vector<int> idx, zero;
+  std::vector<double> v;
+  int rc = read_triplets(filename, idx, zero, v, false);
+  if (rc) return rc;
+  for (size_t i = 0; i < v.size() && (int)i < cap; ++i) { if (indices) indices[i] = idx[i]; if (vals) vals[i] = v[i]; }
+  return (int)v.size();
 }
 
 int cuadmm_write_dense_txt(const char* filename, const double* vals, int64_t n) {

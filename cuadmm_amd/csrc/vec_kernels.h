@@ -70,6 +70,12 @@ int launch_scale(double* v, long long n, double s, hipStream_t st);
 int launch_copy(double* dst, const double* src, long long n, hipStream_t st);   // device to device, 16-byte aligned pointers
 struct CopyJobs { void* dst[6]; const void* src[6]; long long nbytes[6]; int count; };   // lengths: multiples of 4 bytes
 int launch_copy_multi(const CopyJobs& jobs, hipStream_t st);                    // all of them in one launch
+// cuadmm_update_bC: X <- (X x1) x2, S <- (S s1) s2 (zero: both <- 0) and, with C non-null, C <- 0, in one pass over the n elements
+int launch_update_svec(double* X, double* S, double* C, long long n, bool zero, double x1, double x2, double s1, double s2, hipStream_t st);
+// ... b <- 0 (non-null) and y by ymode (0 leave, 1 zero, 2 ((y / normA cs_old) normA) ics_new) in one pass over the m constraints
+int launch_update_cons(int m, double* b, double* y, const double* normA, int ymode, double cs_old, double ics_new, hipStream_t st);
+int launch_scatter_scaled(double* dst, const int* idx, const double* val, int n, double s, hipStream_t st);   // dst[idx[k]] = val[k] s
+int launch_closed_patch_b(ClosedRec* rec, int nslots, const double* b, hipStream_t st);                       // rec[slot].b[k] = b[rows[k]]
 // y = (L D L^T)^-1 (-A(S-C) + (b - A X) / sigma) on the device, one thread per tree of the elimination forest
 int launch_forest_solve(int ntrees, const int* tree_ptr, const int* tree_cols, const long long* Lp, const int* Li, const double* Lx,
                         const double* D, const double* ax, const double* asmc, const double* b, double isig, double* x, hipStream_t st);

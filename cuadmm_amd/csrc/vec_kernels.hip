@@ -751,6 +751,95 @@ int launch_scale(double* v, long long n, double s, hipStream_t st) {
 }
 
 // ------------------------------------------------------------------------------------------
+// cuadmm_update_bC (engine.hip): new b / C on a factored solver.  Every element goes through the rounded operations of
+// materialise() followed by init's scaling, in that order, so the updated solver holds the bits a fresh init would hold.
+// ------------------------------------------------------------------------------------------
+// One streaming pass over the rank's svec: X <- (X x1) x2, S <- (S s1) s2 (ZERO: both <- 0, a cold start), C <- 0 when it is
+// replaced (its entries are scattered behind this launch).  16 bytes per lane and access, two elements of every vector in flight;
+// 32 L bytes of traffic (+ 8 L with C); the pad behind the L elements is not touched.
+typedef double up_d2 __attribute__((ext_vector_type(2)));
+template <bool WRITE_C, bool ZERO>
+__global__ __launch_bounds__(kVecThreads) void update_svec_kernel(double* __restrict__ X, double* __restrict__ S, double* __restrict__ C, long long n,
+                                                                double x1, double x2, double s1, double s2) {
+  const long long n2 = n / 2, stride = (long long)gridDim.x * kVecThreads;
+  up_d2* __restrict__ X2 = reinterpret_cast<up_d2*>(X);
+  up_d2* __restrict__ S2 = reinterpret_cast<up_d2*>(S);
+  up_d2* __restrict__ C2 = reinterpret_cast<up_d2*>(C);
+  const up_d2 zero = {0.0, 0.0};
+  long long i = (long long)blockIdx.x * kVecThreads + threadIdx.x;
+  if (ZERO) {
+    for (; i < n2; i += stride) { X2[i] = zero; S2[i] = zero; if (WRITE_C) C2[i] = zero; }
+  } else {
+    for (; i + stride < n2; i += 2 * stride) {
+      const up_d2 xa = X2[i], xb = X2[i + stride], sa = S2[i], sb = S2[i + stride];
+      X2[i] = (xa * x1) * x2; X2[i + stride] = (xb * x1) * x2;
+      S2[i] = (sa * s1) * s2; S2[i + stride] = (sb * s1) * s2;
+      if (WRITE_C) { C2[i] = zero; C2[i + stride] = zero; }
+    }
+    for (; i < n2; i += stride) {
+      const up_d2 xa = X2[i], sa = S2[i];
+      X2[i] = (xa * x1) * x2; S2[i] = (sa * s1) * s2;
+      if (WRITE_C) C2[i] = zero;
+    }
+  }
+  if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+    X[n - 1] = ZERO ? 0.0 : (X[n - 1] * x1) * x2;
+    S[n - 1] = ZERO ? 0.0 : (S[n - 1] * s1) * s2;
+    if (WRITE_C) C[n - 1] = 0.0;
+  }
+}
+int launch_update_svec(double* X, double* S, double* C, long long n, bool zero, double x1, double x2, double s1, double s2, hipStream_t st) {
+  if (n <= 0) return CUADMM_OK;
+  const dim3 grid(grid_for(n / 2 + 1, kVecThreads * 2, 256 * 8)), block(kVecThreads);
+  if (C && zero) hipLaunchKernelGGL((update_svec_kernel<true, true>), grid, block, 0, st, X, S, C, n, x1, x2, s1, s2);
+  else if (C) hipLaunchKernelGGL((update_svec_kernel<true, false>), grid, block, 0, st, X, S, C, n, x1, x2, s1, s2);
+  else if (zero) hipLaunchKernelGGL((update_svec_kernel<false, true>), grid, block, 0, st, X, S, C, n, x1, x2, s1, s2);
+  else hipLaunchKernelGGL((update_svec_kernel<false, false>), grid, block, 0, st, X, S, C, n, x1, x2, s1, s2);
+  CUADMM_HIP_TRY(hipGetLastError());
+  return CUADMM_OK;
+}
+// One pass over the m constraints (the factor's order): b <- 0 when it is replaced (entries scattered behind this launch);
+// y by ymode: 0 leave, 1 <- 0, 2 <- ((y / normA cs_old) normA) ics_new  (materialise(), then init's y0 normA / Cscale)
+__global__ __launch_bounds__(kVecThreads) void update_cons_kernel(int m, double* __restrict__ b, double* __restrict__ y, const double* __restrict__ normA,
+                                                                int ymode, double cs_old, double ics_new) {
+  for (int i = blockIdx.x * kVecThreads + threadIdx.x; i < m; i += gridDim.x * kVecThreads) {
+    if (b) b[i] = 0.0;
+    if (ymode == 1) y[i] = 0.0;
+    else if (ymode == 2) { const double na = normA[i]; y[i] = ((y[i] / na * cs_old) * na) * ics_new; }
+  }
+}
+int launch_update_cons(int m, double* b, double* y, const double* normA, int ymode, double cs_old, double ics_new, hipStream_t st) {
+  if (m <= 0 || (!b && ymode == 0)) return CUADMM_OK;
+  hipLaunchKernelGGL(update_cons_kernel, dim3(grid_for(m, kVecThreads)), dim3(kVecThreads), 0, st, m, b, y, normA, ymode, cs_old, ics_new);
+  CUADMM_HIP_TRY(hipGetLastError());
+  return CUADMM_OK;
+}
+// dst[idx[k]] = val[k] * s: the entries of a sparse vector into its zero-filled dense form (distinct indices: no two lanes meet)
+__global__ __launch_bounds__(kVecThreads) void scatter_scaled_kernel(double* __restrict__ dst, const int* __restrict__ idx, const double* __restrict__ val, int n, double s) {
+  for (int k = blockIdx.x * kVecThreads + threadIdx.x; k < n; k += gridDim.x * kVecThreads) dst[idx[k]] = val[k] * s;
+}
+int launch_scatter_scaled(double* dst, const int* idx, const double* val, int n, double s, hipStream_t st) {
+  if (n <= 0) return CUADMM_OK;
+  hipLaunchKernelGGL(scatter_scaled_kernel, dim3(grid_for(n, kVecThreads)), dim3(kVecThreads), 0, st, dst, idx, val, n, s);
+  CUADMM_HIP_TRY(hipGetLastError());
+  return CUADMM_OK;
+}
+// closed blocks: the b entries of the per-block records from the by-row vector (nothing else in a record depends on b)
+__global__ __launch_bounds__(kVecThreads) void closed_patch_b_kernel(ClosedRec* __restrict__ rec, int nslots, const double* __restrict__ b) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  const int slot = (int)(i / kClosedMaxRows), k = (int)(i % kClosedMaxRows);
+  if (slot >= nslots || k >= rec[slot].nk) return;
+  rec[slot].b[k] = b[rec[slot].rows[k]];
+}
+int launch_closed_patch_b(ClosedRec* rec, int nslots, const double* b, hipStream_t st) {
+  if (nslots <= 0) return CUADMM_OK;
+  const long long n = (long long)nslots * kClosedMaxRows;
+  hipLaunchKernelGGL(closed_patch_b_kernel, dim3((unsigned)((n + kVecThreads - 1) / kVecThreads)), dim3(kVecThreads), 0, st, rec, nslots, b);
+  CUADMM_HIP_TRY(hipGetLastError());
+  return CUADMM_OK;
+}
+
+// ------------------------------------------------------------------------------------------
 // op-level kernels: one per reference kernel (same element-wise semantics)
 // ------------------------------------------------------------------------------------------
 // src/kernels/vec_mat_conversion.cu:11-34

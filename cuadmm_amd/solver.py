@@ -215,6 +215,19 @@ class SDPSolver:
         Sa = None if S is None else _f64(S)
         check(self._lib.cuadmm_set_XyS(self._h, _p(Xa), _p(ya), _p(Sa), float(sig)))
 
+    def update_bC(self, b_idx=None, b_val=None, C_idx=None, C_val=None, keep_iterate=True, sig=0.0):
+        """New b and / or C (the caller's numbering and units, as in init) on the factored solver; None leaves that one unchanged.
+        keep_iterate: the current X, y, S start the next solve (warm start), else zeros.  Nothing that depends on A is redone."""
+        if (b_idx is None) != (b_val is None) or (C_idx is None) != (C_val is None):
+            raise ValueError("update_bC: indices and values come together")
+        bi, bv = (None, None) if b_idx is None else (_i32(b_idx), _f64(b_val))
+        ci, cv = (None, None) if C_idx is None else (_i32(C_idx), _f64(C_val))
+        if (bi is not None and bi.size != bv.size) or (ci is not None and ci.size != cv.size):
+            raise ValueError("update_bC: as many indices as values")
+        check(self._lib.cuadmm_update_bC(self._h, _p(bi), _p(bv), -1 if bi is None else int(bi.size),
+                                         _p(ci), _p(cv), -1 if ci is None else int(ci.size), int(bool(keep_iterate)), float(sig)))
+        return self
+
     @property
     def info_iter_num(self):
         return int(self._lib.cuadmm_get_info_iter_num(self._h))

@@ -149,6 +149,17 @@ int cuadmm_get_S(cuadmm_solver* s, double* host_out /* vec_len */);
  * writing through X.vals/y.vals/S.vals before solve(..., if_first=false) (solver.cu:385-409);
  * NULL leaves that vector untouched */
 int cuadmm_set_XyS(cuadmm_solver* s, const double* X, const double* y, const double* S, double sig);
+/* Replace b and/or C of an initialised solver without touching anything that depends on A alone (ordering, factor, GPU tail,
+ * tree tops, plans).  b / C in the caller's numbering and units exactly as in cuadmm_init; b_nnz < 0 (or C_nnz < 0) leaves that
+ * one unchanged.  keep_iterate = 1: the current X, y, S (caller's units) become the start of the next solve (warm start);
+ * 0: zeros, as cuadmm_init with NULL X / y / S.  sig > 0 sets sigma, otherwise the current value stays.
+ * Afterwards the solver is in the state cuadmm_init(At, blk, same options, new b, new C, X0, y0, S0, sig) would have left:
+ * scaling constants, info arrays, total_time, best iterate and schedule hints as after init; profile counters and plans stay.
+ * Every index is checked before anything changes (range; no index twice, anywhere in b or C): a refused call returns
+ * CUADMM_ERR_INVALID and leaves the solver as it was.  Every rank of a sharded job calls it with the full b and C; the leader
+ * of an in-process group forwards it to its engines.  Not in the reference, whose only way to new data is a second init. */
+int cuadmm_update_bC(cuadmm_solver* s, const int* b_indices, const double* b_vals, int b_nnz,
+                     const int* C_indices, const double* C_vals, int C_nnz, int keep_iterate, double sig);
 /* device pointers of this rank's shard (scaled inside solve, unscaled after) */
 int cuadmm_get_device_ptrs(cuadmm_solver* s, double** X, double** y, double** S);
 /* svec range [begin,end) owned by this rank (whole vector when world==1) */
@@ -224,6 +235,8 @@ void cuadmm_problem_free(cuadmm_problem* p);
 int cuadmm_coo_to_csc(int* col_ptrs, int* col_ids, int* row_ids, double* vals, int nnz, int col_num);
 /* read_blk (io.cu:296-329): returns number of entries; types[i] in 'a'..'z','A'..'Z' */
 int cuadmm_read_blk(const char* filename, char* types, int* sizes, int cap);
+/* a sparse vector file (b.txt / C.txt: lines "idx 0 value"): returns the number of entries in the file and fills the first cap of them */
+int cuadmm_read_sparse_vec_txt(const char* filename, int* indices, double* vals, int cap);
 /* DeviceDenseVector::to_txt format (memory.h:278-294): one "%.32f\n" per entry */
 int cuadmm_write_dense_txt(const char* filename, const double* vals, int64_t n);
 

@@ -94,6 +94,12 @@ class SDPSolver {
     con_num = con_num_;
   }
 
+  // cuadmm_update_bC: new b and / or C on the factored solver (nnz < 0: unchanged); not in the reference
+  void update_bC(const int* cpu_b_indices, const double* cpu_b_vals, int b_nnz, const int* cpu_C_indices, const double* cpu_C_vals,
+                 int C_nnz, bool keep_iterate = true, double sig = 0.0) {
+    check(cuadmm_update_bC(h_, cpu_b_indices, cpu_b_vals, b_nnz, cpu_C_indices, cpu_C_vals, C_nnz, keep_iterate ? 1 : 0, sig));
+  }
+
   // SDPSolver::solve, same argument list and defaults (solver.h:236-244)
   void solve(int max_iter, double stop_tol, int sig_update_threshold = 500, int sig_update_stage_1 = 50,
              int sig_update_stage_2 = 100, int switch_admm = (int)1.1e4, double sigscale = 1.05, bool if_first = true) {
