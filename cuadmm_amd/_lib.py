@@ -85,6 +85,11 @@ PROTOTYPES = {
     "cuadmm_get_counters": (C.c_int, [C.c_void_p, C.c_void_p]),
     "cuadmm_get_group_info": (C.c_int, [C.c_void_p, C.c_void_p]),
     "cuadmm_get_tail_info": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "cuadmm_get_accel_info": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "cuadmm_accel_solve_ls": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_void_p]),
+    "cuadmm_op_accel_push": (C.c_int, [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 4),
+    "cuadmm_op_accel_gram": (C.c_int, [C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cuadmm_op_accel_combine": (C.c_int, [C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p]),
     "cuadmm_problem_from_txt": (C.c_int, [C.c_char_p, C.POINTER(C.c_void_p)]),
     "cuadmm_problem_view_get": (C.c_int, [C.c_void_p, C.POINTER(ProblemView)]),
     "cuadmm_problem_free": (None, [C.c_void_p]),

@@ -5,6 +5,8 @@
 // <dir/>{blk,con_num,At,b,C}.txt and writes <dir/>X_opt.txt with "%.32f" per line (memory.h:278-294).
 // Optional trailing --key=value arguments (not in the reference) override the solve parameters:
 //   --max_iter= --stop_tol= --threshold= --stage1= --stage2= --switch_admm= --sigscale= --sig= --device= --quiet
+//   --accel=M: safeguarded Anderson acceleration with memory M (option "accel"); prints "accel: taken a, accepted b, rejected c,
+//   restarts d" after the solve and adds the four numbers to the sidecar
 //   --json=<file>: a sidecar with the run's figures (iterations, residuals, iters/s, per-phase milliseconds, the projection's
 //   nominal TFLOP/s = 10.67 sum n^3 per projection and the vector kernels' algorithmic GB/s: SURVEY.md 8d); switches the
 //   engine's per-phase HIP-event timers on (option "profile").  Nothing is written unless asked for: the reference writes X_opt.txt only.
@@ -48,6 +50,10 @@ static bool write_sidecar(const std::string& path, const std::string& prefix, cu
   fprintf(f, " \"eig_not_converged\": %.17g,\n", st[11]);
   fprintf(f, " \"plan\": {\"fused\": %d, \"closed_blocks\": %d, \"device_solve\": %d, \"factor_gpu_tail\": %d, \"batched_launches\": %.0f, \"iterations_in_batches\": %.0f},\n",
           (int)cnt[4], (int)cnt[5], (int)cnt[6], (int)cnt[7], cnt[0], cnt[1]);
+  double acc[8] = {0};
+  cuadmm_get_accel_info(solver, acc);
+  if (acc[0] > 0)
+    fprintf(f, " \"accel\": {\"memory\": %.0f, \"taken\": %.0f, \"accepted\": %.0f, \"rejected\": %.0f, \"restarts\": %.0f},\n", acc[0], acc[1], acc[2], acc[3], acc[4]);
   fprintf(f, " \"phases\": {");
   for (int k = 0; k < CUADMM_NUM_KCLASS; ++k) {
     const double launches = prof[3 * k], ms = prof[3 * k + 1], bytes = prof[3 * k + 2];
@@ -81,7 +87,7 @@ int main(int argc, char* argv[]) {
   std::string prefix = argv[1];
   int eig_stream_num_per_gpu = 15, cpu_eig_thread_num = 30;
   double max_iter = 1e6, stop_tol = 1e-3, threshold = 0, stage1 = 50, stage2 = 100, switch_admm = 5000, sigscale = 1.05,
-         sig = 1e0, device = 0;
+         sig = 1e0, device = 0, accel = 0;
   bool quiet = false;
   std::string json_path;
   std::vector<std::string> then_dirs;
@@ -90,7 +96,7 @@ int main(int argc, char* argv[]) {
     if (strncmp(argv[i], "--then=", 7) == 0) { then_dirs.push_back(argv[i] + 7); continue; }
     if (opt(argv[i], "--max_iter", max_iter) || opt(argv[i], "--stop_tol", stop_tol) || opt(argv[i], "--threshold", threshold) ||
         opt(argv[i], "--stage1", stage1) || opt(argv[i], "--stage2", stage2) || opt(argv[i], "--switch_admm", switch_admm) ||
-        opt(argv[i], "--sigscale", sigscale) || opt(argv[i], "--sig", sig) || opt(argv[i], "--device", device))
+        opt(argv[i], "--sigscale", sigscale) || opt(argv[i], "--sig", sig) || opt(argv[i], "--device", device) || opt(argv[i], "--accel", accel))
       continue;
     if (strcmp(argv[i], "--quiet") == 0) { quiet = true; continue; }
     std::cerr << "unknown option " << argv[i] << std::endl;
@@ -116,6 +122,10 @@ int main(int argc, char* argv[]) {
   cuadmm_set_option(solver, "device", device);
   cuadmm_set_option(solver, "verbose", quiet ? 0 : 1);
   if (!json_path.empty()) cuadmm_set_option(solver, "profile", 1);
+  if (accel != 0 && cuadmm_set_option(solver, "accel", accel) != CUADMM_OK) {
+    std::cerr << cuadmm_last_error() << std::endl;
+    return 1;
+  }
   int rc = cuadmm_init(solver, eig_stream_num_per_gpu, cpu_eig_thread_num, v.vec_len, v.con_num, v.At_csc_col_ptrs,
                        v.At_csc_row_ids, v.At_csc_vals, v.At_nnz, v.b_indices, v.b_vals, v.b_nnz, v.C_indices, v.C_vals,
                        v.C_nnz, v.blk_vals, v.mat_num, nullptr, nullptr, nullptr, sig);
@@ -126,6 +136,11 @@ int main(int argc, char* argv[]) {
   rc = cuadmm_solve(solver, (int)max_iter, stop_tol, (int)threshold, (int)stage1, (int)stage2, (int)switch_admm, sigscale, 1);
   if (rc != CUADMM_OK) std::cerr << cuadmm_last_error() << std::endl;
 
+  if (accel != 0) {
+    double acc[8] = {0};
+    cuadmm_get_accel_info(solver, acc);
+    printf("accel: taken %.0f, accepted %.0f, rejected %.0f, restarts %.0f\n", acc[1], acc[2], acc[3], acc[4]);
+  }
   std::vector<double> X((size_t)v.vec_len);
   if (cuadmm_get_X(solver, X.data()) == CUADMM_OK) cuadmm_write_dense_txt((prefix + "X_opt.txt").c_str(), X.data(), v.vec_len);
   if (!json_path.empty() && !write_sidecar(json_path, prefix, solver, v)) std::cerr << "cannot write " << json_path << std::endl;

@@ -30,6 +30,7 @@
 #include "lead_solve.h"
 #include "vec_kernels.h"
 #include "duo_group.h"
+#include "accel.h"
 
 using namespace cuadmm;
 
@@ -322,6 +323,37 @@ struct cuadmm_solver {
   double A_avg_nnz = 1;
   PsdPlan plan;
 
+  // Safeguarded Anderson acceleration behind the iteration (option "accel" = memory; accel.h, DESIGN.md "Acceleration").  The state is
+  // u = (X, sigma S); fbuf holds f_k = (X, S) as the last plain iteration left them (the next iteration's u unless a candidate is
+  // taken, and what a rejected candidate falls back to), ubuf a candidate, gbuf g_k, the rings the last `cols` differences.
+  struct Accel {
+    int mem = 0;
+    double safeguard = 2.0, reg = 1e-10;
+    DevBuf<double> ring_dF, ring_dG, state[2], gbuf, partials, dots, fb_y, fb_out;
+    struct { double* p = nullptr; } fbuf, ubuf;      // the two state buffers by role (they trade places when a candidate is accepted)
+    PinnedBuf<double> h_dots;
+    DevBuf<int> fb_hint;              // the sign schedule's warm start is part of what an iteration reads and writes (as in batch_copy)
+    unsigned fb_nproj = 0;
+    long long fb_iters_done = 0;
+    std::vector<double> h_fb_out, h_fb_Rp, h_fb_y;
+    long long hs = 0;                 // distance of the S half from the X half: L rounded up to an even number
+    int cols = 0, head = 0;           // columns held, ring slot the next column goes to
+    bool have_prev = false;           // fbuf / gbuf hold the previous pair (f, g) of the current map
+    bool pending = false;             // the iteration under way started from a candidate
+    double gnorm2_prev = 0;           // ||g_k||^2 of the iteration the pending candidate was formed behind
+    double G[kAccelMaxMem][kAccelMaxMem] = {};   // Gram matrix of the dG columns, by ring slot
+    double sc[8] = {};                // host scalars of f_k beside a pending candidate
+    int sc_win[2] = {0, 0};
+    long long taken = 0, accepted = 0, rejected = 0, restarts = 0;
+    double ms = 0;
+    hipEvent_t ev[4] = {};
+    ~Accel() { for (auto& e : ev) if (e) { hipError_t r = hipEventDestroy(e); (void)r; } }
+  } aa;
+  bool accel_on() const { return aa.mem > 0 && L > 0; }
+  void accel_clear() { aa.cols = 0; aa.head = 0; aa.have_prev = false; aa.pending = false; }
+  int accel_begin_solve();
+  int accel_step(int iter, int max_iter, double stop_tol, int switch_admm, double tau, bool sig_changed, bool next_sig_may_change);
+
   // profiling
   hipEvent_t ev0[K_NUM][2] = {}, ev1[K_NUM][2] = {};
   int ev_used[K_NUM] = {0};
@@ -586,7 +618,7 @@ struct cuadmm_solver {
   }
   // --- several iterations per launch ---------------------------------------------------------------------------------
   bool can_batch() const {
-    return can_batch_local() && bt.peers_agree;
+    return can_batch_local() && bt.peers_agree && aa.mem == 0;
   }
   bool can_batch_local() const {
     return bt.max_iters >= 2 && fuse && closed.active && dev_solve && !lead.ready && plan.n_rest == 0 && eig_rank == 0 && !out_mapped &&
@@ -1415,6 +1447,14 @@ int cuadmm_set_option(cuadmm_solver* s, const char* key, double value) {
   else if (k == "duo_share_device") s->duo_share_device = (int)value;   // duo_init(device_num_requested = N) from one process: all N engines on this solver's device
   else if (k == "tiny_sign") s->opt_tiny_sign = (int)value;              // n <= 8 on the sign kernel (before init)
   else if (k == "duo_exchange") s->duo_exchange = (int)value;           // in-process group: -1 choose, 0 host-staged, 1 device-side exchange
+  else if (k == "accel") {                                              // memory of the Anderson acceleration (0: off), before init
+    if (!(value >= 0 && value <= kAccelMaxMem && value == std::floor(value))) {
+      s->option_log.pop_back(); set_error("set_option: accel must be an integer from 0 (off) to %d", kAccelMaxMem); return CUADMM_ERR_INVALID;
+    }
+    s->aa.mem = (int)value;
+  }
+  else if (k == "accel_safeguard") s->aa.safeguard = value;             // a candidate is rejected when ||g|| grows by more than this factor (<= 0: always)
+  else if (k == "accel_reg") s->aa.reg = value;                         // relative Tikhonov term of the least-squares solve
   else if (k == "duo_inject_fail") { s->duo_inject = (long long)value; if (s->group) duo_group_inject(s->group, s->duo_inject); }   // test hook
   else { s->option_log.pop_back(); set_error("set_option: unknown key '%s'", key); return CUADMM_ERR_INVALID; }
   // a group handle: every rank follows -- AFTER the key has been validated on the leader; a child that refuses leaves the option
@@ -1469,6 +1509,11 @@ int cuadmm_init(cuadmm_solver* s, int eig_stream_num_per_gpu, int cpu_eig_thread
     return CUADMM_ERR_INVALID;
   }
   if (s->world < 1 || s->rank < 0 || s->rank >= s->world) { set_error("init: bad rank/world %d/%d", s->rank, s->world); return CUADMM_ERR_INVALID; }
+  if (s->aa.mem > 0 && (s->world > 1 || s->eig_rank > 0 || s->group || s->in_group_call)) {
+    set_error("init: option accel works on one rank with the full projection (world = %d, eig_rank = %d%s): its Gram matrix is not all-reduced",
+              s->world, s->eig_rank, (s->group || s->in_group_call) ? ", in-process group" : "");
+    return CUADMM_ERR_INVALID;
+  }
   long long Lchk = 0;
   for (int k = 0; k < mat_num; ++k) {
     if (blk[k] == 0) { set_error("init: block %d has size 0", k); return CUADMM_ERR_INVALID; }
@@ -1627,6 +1672,7 @@ int cuadmm_solve(cuadmm_solver* s, int max_iter, double stop_tol, int sig_update
   }
 
   if ((rc = s->batch_agree())) return rc;
+  if (s->accel_on() && (rc = s->accel_begin_solve())) return rc;
   const bool lpt_enabled = s->sw.lpt != 0;
   long long& lpt_ev = s->lpt_next;             // counts iterations over all solve calls of this solver
   if (!lpt_enabled) lpt_ev = 0;
@@ -1688,7 +1734,8 @@ int cuadmm_solve(cuadmm_solver* s, int max_iter, double stop_tol, int sig_update
       s->sgs_KKT = std::max(s->maxfeas, s->relgap);
       s->best_KKT = s->sgs_KKT;
       snapshot = true;
-    } else if (iter > switch_admm && s->have_best && s->best_KKT > std::max(s->maxfeas, s->relgap)) {
+    } else if (iter > switch_admm && s->have_best && !s->aa.pending && s->best_KKT > std::max(s->maxfeas, s->relgap)) {
+      // (not in an iteration that started from a candidate of the acceleration: X, y, S there are not the iterate the scalars describe)
       s->best_KKT = std::max(s->maxfeas, s->relgap);                     // solver.cu:732-741
       snapshot = true;
     }
@@ -1739,7 +1786,7 @@ int cuadmm_solve(cuadmm_solver* s, int max_iter, double stop_tol, int sig_update
     // device and belongs to the engine (not to a closed block's kernel), sigma does not change in this iteration's step 5, nothing of a
     // batch is pending, and the per-class event timers (profile = 1) are off -- they are collected at the wait, before that solve ends
     const bool sig_may_change = (iter <= sig_update_threshold && iter % sig_update_stage_1 == 1) || (iter > sig_update_threshold && iter % sig_update_stage_2 == 1);
-    const bool solve_next_ok = s->sw.solve_next != 0 && s->dev_solve && !from_batch && !sig_may_change && !(s->fuse && s->closed.active) && s->profile != 1;
+    const bool solve_next_ok = s->sw.solve_next != 0 && !s->accel_on() && s->dev_solve && !from_batch && !sig_may_change && !(s->fuse && s->closed.active) && s->profile != 1;
     if (from_batch) {
       // consumed below (Step 5) from bt.h
     } else if ((rc = s->upload_y())) return rc;
@@ -1810,6 +1857,7 @@ int cuadmm_solve(cuadmm_solver* s, int max_iter, double stop_tol, int sig_update
     }
 
     // ---- Step 5 (solver.cu:764-799)
+    const double sig_of_iter = s->sig;
     {
       double t0 = wall_s();
       double nr = 0, bty = 0;
@@ -1874,6 +1922,12 @@ int cuadmm_solve(cuadmm_solver* s, int max_iter, double stop_tol, int sig_update
       if ((rc = s->plan.reorder_by_steps(s->steps_h.data(), s->st))) return rc;
       lpt_ev *= 8;
     }
+    // ---- acceleration: behind the iteration, on every path (the scalars above are those of the plain iterate f_k)
+    if (s->accel_on()) {
+      const int nx = iter + 1;
+      const bool next_sig_may_change = (nx <= sig_update_threshold && nx % sig_update_stage_1 == 1) || (nx > sig_update_threshold && nx % sig_update_stage_2 == 1);
+      if ((rc = s->accel_step(iter, max_iter, stop_tol, switch_admm, tau, s->sig != sig_of_iter, next_sig_may_change))) return rc;
+    }
   }
 
   // unscale (solver.cu:814-816) -- deferred until somebody reads or replaces X, y, S (materialise): a following
@@ -1937,6 +1991,151 @@ int cuadmm_solver::materialise() {
   return CUADMM_OK;
 }
 
+// ------------------------------------------------------------------------------------------
+// Acceleration (option "accel"): DESIGN.md, "Acceleration"
+// ------------------------------------------------------------------------------------------
+// start of every solve: buffers on first use, empty memory, u_0 = the state the first iteration starts from
+int cuadmm_solver::accel_begin_solve() {
+  int rc;
+  if (!aa.fbuf.p) {
+    aa.hs = (L + 1) & ~1LL;
+    const size_t n2 = 2 * (size_t)aa.hs;
+    if ((rc = aa.ring_dF.alloc(n2 * aa.mem)) || (rc = aa.ring_dG.alloc(n2 * aa.mem)) || (rc = aa.state[0].alloc(n2)) || (rc = aa.gbuf.alloc(n2)) ||
+        (rc = aa.state[1].alloc(n2)) || (rc = aa.partials.alloc(kAccelPartials)) || (rc = aa.dots.alloc(kAccelDots)) || (rc = aa.h_dots.alloc(kAccelDots)) ||
+        (rc = aa.fb_y.alloc(std::max(m, 1))) || (rc = aa.fb_out.alloc(2 * (size_t)m + 2)))
+      return rc;
+    aa.fbuf.p = aa.state[0].p; aa.ubuf.p = aa.state[1].p;
+    // the pad element of an odd L is never read, but a column is copied whole nowhere either: zero once, for tidy dumps
+    CUADMM_HIP_TRY(hipMemsetAsync(aa.ubuf.p, 0, sizeof(double) * n2, st));
+    CUADMM_HIP_TRY(hipMemsetAsync(aa.fbuf.p, 0, sizeof(double) * n2, st));
+    CUADMM_HIP_TRY(hipMemsetAsync(aa.gbuf.p, 0, sizeof(double) * n2, st));
+    if (profile) for (auto& e : aa.ev) CUADMM_HIP_TRY(hipEventCreate(&e));
+  }
+  accel_clear();
+  CUADMM_HIP_TRY(hipMemcpyAsync(aa.fbuf.p, X.p, sizeof(double) * (size_t)L, hipMemcpyDeviceToDevice, st));
+  CUADMM_HIP_TRY(hipMemcpyAsync(aa.fbuf.p + aa.hs, S.p, sizeof(double) * (size_t)L, hipMemcpyDeviceToDevice, st));
+  return CUADMM_OK;
+}
+
+// End of iteration `iter` (its scalars are recorded, sigma may have changed in its step 5).  X, S hold f_k = F(u_k).
+int cuadmm_solver::accel_step(int iter, int max_iter, double stop_tol, int switch_admm, double tau, bool sig_changed, bool next_sig_may_change) {
+  int rc;
+  const size_t n2 = 2 * (size_t)aa.hs;
+  const bool timed = profile != 0 && aa.ev[0];
+  auto elapsed = [&](int a) {   // after a synchronisation behind ev[a + 1]
+    float t = 0;
+    if (timed && hipEventElapsedTime(&t, aa.ev[a], aa.ev[a + 1]) == hipSuccess) aa.ms += t;
+  };
+  // the map changed under this iteration's feet (sigma in step 5): nothing held describes the new map.  (No candidate is ever
+  // pending here: none is taken in front of an iteration that may change sigma.)
+  if (sig_changed) {
+    accel_clear();
+    aa.restarts++;
+    CUADMM_HIP_TRY(hipMemcpyAsync(aa.fbuf.p, X.p, sizeof(double) * (size_t)L, hipMemcpyDeviceToDevice, st));
+    CUADMM_HIP_TRY(hipMemcpyAsync(aa.fbuf.p + aa.hs, S.p, sizeof(double) * (size_t)L, hipMemcpyDeviceToDevice, st));
+    return CUADMM_OK;
+  }
+  // g_k, the new columns, f_k.  Behind a candidate u_k is ubuf and f_k goes there too, so that fbuf still holds the fallback.
+  const bool was_pending = aa.pending;
+  const bool have_col = aa.have_prev;
+  const int slot = aa.head;
+  double* const u = was_pending ? aa.ubuf.p : aa.fbuf.p;
+  if (timed) CUADMM_HIP_TRY(hipEventRecord(aa.ev[0], st));
+  if ((rc = launch_aa_push(L, aa.hs, u, X.p, S.p, sig, aa.fbuf.p, aa.gbuf.p, have_col ? 1 : 0, aa.gbuf.p, u, aa.ring_dF.p + (size_t)slot * n2,
+                           aa.ring_dG.p + (size_t)slot * n2, aa.partials.p, aa.dots.p + 2 * kAccelMaxMem, st)))
+    return rc;
+  int cols_new = aa.cols;
+  if (have_col) {
+    cols_new = std::min(aa.cols + 1, aa.mem);
+    if ((rc = launch_aa_gram(L, aa.hs, (long long)n2, cols_new, slot, aa.ring_dG.p, aa.gbuf.p, aa.partials.p, aa.dots.p, st))) return rc;
+  }
+  if (timed) CUADMM_HIP_TRY(hipEventRecord(aa.ev[1], st));
+  CUADMM_HIP_TRY(hipMemcpyAsync(aa.h_dots.p, aa.dots.p, sizeof(double) * kAccelDots, hipMemcpyDeviceToHost, st));
+  CUADMM_HIP_TRY(hipStreamSynchronize(st));
+  elapsed(0);
+  const double gnorm2 = aa.h_dots.p[2 * kAccelMaxMem];
+
+  if (was_pending) {
+    aa.pending = false;
+    const bool reject = !(aa.safeguard > 0) || !(std::sqrt(gnorm2) <= aa.safeguard * std::sqrt(aa.gnorm2_prev));
+    if (reject) {
+      // back to f_k, bit for bit: X, S, y, the fetched vectors, the scalars of the stopping test.  The wasted iteration stays recorded.
+      CUADMM_HIP_TRY(hipMemcpyAsync(X.p, aa.fbuf.p, sizeof(double) * (size_t)L, hipMemcpyDeviceToDevice, st));
+      CUADMM_HIP_TRY(hipMemcpyAsync(S.p, aa.fbuf.p + aa.hs, sizeof(double) * (size_t)L, hipMemcpyDeviceToDevice, st));
+      if (dev_solve) CUADMM_HIP_TRY(hipMemcpyAsync(y_d.p, aa.fb_y.p, sizeof(double) * (size_t)m, hipMemcpyDeviceToDevice, st));
+      else { std::copy(aa.h_fb_y.begin(), aa.h_fb_y.end(), y_p.begin()); std::copy(aa.h_fb_Rp.begin(), aa.h_fb_Rp.end(), Rp_p.begin()); }
+      if (!out_mapped) CUADMM_HIP_TRY(hipMemcpyAsync(out_d.p, aa.fb_out.p, sizeof(double) * (2 * (size_t)m + 2), hipMemcpyDeviceToDevice, st));
+      if (hint_d.p) CUADMM_HIP_TRY(hipMemcpyAsync(hint_d.p, aa.fb_hint.p, sizeof(int) * hint_d.n, hipMemcpyDeviceToDevice, st));
+      plan.n_project = aa.fb_nproj; closed.iters_done = aa.fb_iters_done;
+      CUADMM_HIP_TRY(hipStreamSynchronize(st));
+      std::copy(aa.h_fb_out.begin(), aa.h_fb_out.end(), h_out.p);
+      closed.out_dirty = true;
+      errRp = aa.sc[0]; errRd = aa.sc[1]; maxfeas = aa.sc[2]; pobj = aa.sc[3]; dobj = aa.sc[4]; relgap = aa.sc[5]; feasratio = aa.sc[6];
+      prim_win = aa.sc_win[0]; dual_win = aa.sc_win[1];
+      accel_clear();
+      aa.rejected++;
+      return CUADMM_OK;
+    }
+    aa.accepted++;
+    std::swap(aa.fbuf.p, aa.ubuf.p);      // f_k was written over the candidate
+  }
+  if (have_col) {
+    // the Gram matrix by ring slot: row and column `slot` are the new column's
+    for (int j = 0; j < cols_new; ++j) aa.G[slot][j] = aa.G[j][slot] = aa.h_dots.p[j];
+    aa.cols = cols_new;
+    aa.head = (slot + 1) % aa.mem;
+  }
+  aa.have_prev = true;
+
+  // what the next iteration will be
+  const int nx = iter + 1;
+  double tau_next = (nx < switch_admm) ? 1.95 : 1.618;
+  if (errRd < stop_tol) tau_next = std::max(1.618, tau_next / 1.1);
+  if (tau_next != tau || nx == switch_admm) {     // another map from the next iteration on
+    accel_clear();
+    aa.restarts++;
+    return CUADMM_OK;
+  }
+  // no candidate in front of the pass that stops (the result is a plain iterate), nor in front of a possible sigma update
+  if (nx > max_iter || std::max(maxfeas, relgap) < stop_tol || next_sig_may_change || aa.cols < 2) return CUADMM_OK;
+
+  double gram[kAccelMaxMem * kAccelMaxMem], rhs[kAccelMaxMem], gamma[kAccelMaxMem];
+  for (int i = 0; i < aa.cols; ++i) {
+    rhs[i] = aa.h_dots.p[cols_new + i];
+    for (int j = 0; j < aa.cols; ++j) gram[i * aa.cols + j] = aa.G[i][j];
+  }
+  if (accel_solve_ls(gram, rhs, aa.cols, aa.reg, gamma) != CUADMM_OK) {     // degenerate columns: start the memory afresh
+    accel_clear();
+    aa.restarts++;
+    return CUADMM_OK;
+  }
+  // the fallback beside fbuf: y, the fetched vectors, the host scalars
+  if (dev_solve) CUADMM_HIP_TRY(hipMemcpyAsync(aa.fb_y.p, y_d.p, sizeof(double) * (size_t)m, hipMemcpyDeviceToDevice, st));
+  else { aa.h_fb_y = y_p; aa.h_fb_Rp = Rp_p; }
+  if (!out_mapped) CUADMM_HIP_TRY(hipMemcpyAsync(aa.fb_out.p, out_d.p, sizeof(double) * (2 * (size_t)m + 2), hipMemcpyDeviceToDevice, st));
+  if (hint_d.p) {
+    if (!aa.fb_hint.p && (rc = aa.fb_hint.alloc(hint_d.n))) return rc;
+    CUADMM_HIP_TRY(hipMemcpyAsync(aa.fb_hint.p, hint_d.p, sizeof(int) * hint_d.n, hipMemcpyDeviceToDevice, st));
+  }
+  aa.fb_nproj = plan.n_project; aa.fb_iters_done = closed.iters_done;
+  aa.h_fb_out.assign(h_out.p, h_out.p + 2 * (size_t)m + 2);
+  aa.sc[0] = errRp; aa.sc[1] = errRd; aa.sc[2] = maxfeas; aa.sc[3] = pobj; aa.sc[4] = dobj; aa.sc[5] = relgap; aa.sc[6] = feasratio;
+  aa.sc_win[0] = prim_win; aa.sc_win[1] = dual_win;
+  aa.gnorm2_prev = gnorm2;
+
+  if (timed) CUADMM_HIP_TRY(hipEventRecord(aa.ev[2], st));
+  if ((rc = launch_aa_combine(L, aa.hs, (long long)n2, aa.cols, aa.ring_dF.p, gamma, sig, X.p, S.p, aa.ubuf.p, st))) return rc;
+  if (timed) CUADMM_HIP_TRY(hipEventRecord(aa.ev[3], st));
+  // X and S were overwritten: [A X | sums | A (S - C)] and Rp again, as a continued solve forms them
+  if ((rc = launch_spmv(true, true))) return rc;
+  if ((rc = fetch_out(0, 2 * (size_t)m + 2))) return rc;
+  for (int i = 0; i < m && !dev_solve; ++i) Rp_p[i] = -h_out.p[i] + b_p[i];
+  elapsed(2);
+  aa.pending = true;
+  aa.taken++;
+  return CUADMM_OK;
+}
+
 // SDPDuoSolver front (duo_solver.h:236-276): exactly two block sizes, then the generic engine.
 int cuadmm_duo_init(cuadmm_solver* s, int if_gpu_eig_mom, int device_num_requested, int eig_stream_num_per_gpu,
                     int cpu_eig_thread_num, int vec_len, int con_num, const int* At_cp, const int* At_ri, const double* At_vx,
@@ -1955,6 +2154,10 @@ int cuadmm_duo_init(cuadmm_solver* s, int if_gpu_eig_mom, int device_num_request
   // check_gpus.cu:29-43).  Here a GPU is a rank of the block-sharded engine: with rank / world already set by the caller (one
   // process per GPU) the request must agree with them; from a single process (world = 1) the handle becomes rank 0 of a GROUP of
   // N engines on N host threads with an in-process all-reduce (duo_group.hip).
+  if (device_num_requested > 1 && s->aa.mem > 0) {
+    set_error("duo_init: option accel works on one engine (device_num_requested = %d): its Gram matrix is not all-reduced", device_num_requested);
+    return CUADMM_ERR_INVALID;
+  }
   if (device_num_requested > 1 && s->world == 1 && !s->in_group_call) {
     if (s->group) { set_error("duo_init: this handle already leads a group of %d engines", duo_group_world(s->group)); return CUADMM_ERR_INVALID; }
     if (s->initialised) { set_error("duo_init: already initialised"); return CUADMM_ERR_INVALID; }
@@ -2289,6 +2492,15 @@ int cuadmm_get_counters(const cuadmm_solver* s, double o[8]) {
   o[4] = s->fuse ? 1 : 0; o[5] = s->closed.active ? 1 : 0; o[6] = s->dev_solve ? (s->lead.tops ? 3 : 1) : (s->lead.hybrid ? 2 : 0); o[7] = (double)s->tail.k;
   return CUADMM_OK;
 }
+int cuadmm_get_accel_info(const cuadmm_solver* s, double o[8]) {
+  if (!s || !o) { set_error("get_accel_info: null"); return CUADMM_ERR_INVALID; }
+  o[0] = (double)s->aa.mem; o[1] = (double)s->aa.taken; o[2] = (double)s->aa.accepted; o[3] = (double)s->aa.rejected; o[4] = (double)s->aa.restarts;
+  o[5] = (double)s->aa.cols; o[6] = s->profile ? s->aa.ms : 0.0; o[7] = (double)(s->aa.ring_dF.n + s->aa.ring_dG.n) * sizeof(double);
+  return CUADMM_OK;
+}
+int cuadmm_accel_solve_ls(const double* gram, const double* rhs, int cols, double reg, double* gamma_out) {
+  return accel_solve_ls(gram, rhs, cols, reg, gamma_out);
+}
 int cuadmm_get_tail_info(const cuadmm_solver* s, double o[6]) {
   if (!s || !o) { set_error("get_tail_info: null"); return CUADMM_ERR_INVALID; }
   o[0] = (double)s->tail.k; o[1] = s->tail.shard_bytes; o[2] = (double)s->tail.shard_rows; o[3] = s->tail.resident_bytes;
@@ -2517,6 +2729,52 @@ int cuadmm_psd_plan_project(cuadmm_psd_plan* p, const double* Xb, double* Xproj,
   return p->plan.project(Xb, Xproj, (hipStream_t)stream);
 }
 void cuadmm_psd_plan_destroy(cuadmm_psd_plan* p) { delete p; }
+
+// ---- the acceleration kernels on host arrays (tests).  State vectors have 2 L entries, the S half right behind the X half: for an
+// odd L the S half is then not 16-byte aligned and takes the kernels' one-double path; the engine itself pads (accel.h).
+namespace {
+struct HookBuf {
+  DevBuf<double> d;
+  int up(const double* h, size_t n) { int rc = d.alloc(std::max<size_t>(n, 1)); return (rc || !h || !n) ? rc : d.upload(h, n); }
+  int down(double* h, size_t n) { return (h && n) ? staged_d2h(h, d.p, sizeof(double) * n) : CUADMM_OK; }
+};
+}  // namespace
+int cuadmm_op_accel_push(int64_t L, const double* u_prev, const double* X, const double* S, double sig, double* f_prev, const double* g_prev, int have_prev,
+                         double* g_out, double* dF_out, double* dG_out, double* gnorm2_out) {
+  if (L < 1 || !u_prev || !X || !S || !f_prev || !g_out || !gnorm2_out || (have_prev && (!g_prev || !dF_out || !dG_out))) { set_error("op_accel_push: invalid argument"); return CUADMM_ERR_INVALID; }
+  int rc = check_device(0);
+  if (rc) return rc;
+  const size_t n2 = 2 * (size_t)L;
+  HookBuf u, x, sv, f, g, dF, dG, part, out;
+  if ((rc = u.up(u_prev, n2)) || (rc = x.up(X, L)) || (rc = sv.up(S, L)) || (rc = f.up(f_prev, n2)) || (rc = g.up(have_prev ? g_prev : nullptr, n2)) ||
+      (rc = dF.up(dF_out, n2)) || (rc = dG.up(dG_out, n2)) || (rc = part.up(nullptr, kAccelPartials)) || (rc = out.up(nullptr, 1)))
+    return rc;
+  if ((rc = launch_aa_push(L, L, u.d.p, x.d.p, sv.d.p, sig, f.d.p, g.d.p, have_prev, g.d.p, f.d.p, dF.d.p, dG.d.p, part.d.p, out.d.p, nullptr))) return rc;
+  CUADMM_HIP_TRY(hipDeviceSynchronize());
+  if ((rc = g.down(g_out, n2)) || (rc = f.down(f_prev, n2)) || (rc = dF.down(dF_out, n2)) || (rc = dG.down(dG_out, n2)) || (rc = out.down(gnorm2_out, 1))) return rc;
+  return CUADMM_OK;
+}
+int cuadmm_op_accel_gram(int64_t L2, int cols, int newest, const double* ring_dG, const double* g, double* out) {
+  if (L2 < 2 || (L2 & 1) || cols < 1 || cols > kAccelMaxMem || newest < 0 || newest >= cols || !ring_dG || !g || !out) { set_error("op_accel_gram: invalid argument"); return CUADMM_ERR_INVALID; }
+  int rc = check_device(0);
+  if (rc) return rc;
+  HookBuf ring, gv, part, dots;
+  if ((rc = ring.up(ring_dG, (size_t)L2 * cols)) || (rc = gv.up(g, L2)) || (rc = part.up(nullptr, kAccelPartials)) || (rc = dots.up(nullptr, kAccelDots))) return rc;
+  if ((rc = launch_aa_gram(L2 / 2, L2 / 2, L2, cols, newest, ring.d.p, gv.d.p, part.d.p, dots.d.p, nullptr))) return rc;
+  CUADMM_HIP_TRY(hipDeviceSynchronize());
+  return dots.down(out, 2 * (size_t)cols);
+}
+int cuadmm_op_accel_combine(int64_t L, int cols, const double* ring_dF, const double* gamma, double sig, double* X_inout, double* S_inout) {
+  if (L < 1 || cols < 1 || cols > kAccelMaxMem || !ring_dF || !gamma || !X_inout || !S_inout) { set_error("op_accel_combine: invalid argument"); return CUADMM_ERR_INVALID; }
+  int rc = check_device(0);
+  if (rc) return rc;
+  HookBuf ring, x, sv, u;
+  if ((rc = ring.up(ring_dF, 2 * (size_t)L * cols)) || (rc = x.up(X_inout, L)) || (rc = sv.up(S_inout, L)) || (rc = u.up(nullptr, 2 * (size_t)L))) return rc;
+  if ((rc = launch_aa_combine(L, L, 2 * L, cols, ring.d.p, gamma, sig, x.d.p, sv.d.p, u.d.p, nullptr))) return rc;
+  CUADMM_HIP_TRY(hipDeviceSynchronize());
+  if ((rc = x.down(X_inout, L)) || (rc = sv.down(S_inout, L))) return rc;
+  return CUADMM_OK;
+}
 
 int cuadmm_dev_malloc(void** ptr, size_t bytes) { CUADMM_HIP_TRY(hipMalloc(ptr, bytes ? bytes : 8)); return CUADMM_OK; }
 int cuadmm_dev_free(void* ptr) { if (ptr) CUADMM_HIP_TRY(hipFree(ptr)); return CUADMM_OK; }

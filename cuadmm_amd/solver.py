@@ -119,6 +119,13 @@ class SDPSolver:
         return {"tail_k": int(o[0]), "bytes_read_per_solve": float(o[1]), "rows": int(o[2]), "bytes_resident": float(o[3]),
                 "inverse_residual": float(o[4]), "refined": bool(o[5])}
 
+    def accel_info(self):
+        """Option "accel" (cuadmm_get_accel_info): what the safeguarded Anderson acceleration did so far."""
+        o = np.zeros(8)
+        check(self._lib.cuadmm_get_accel_info(self._h, _p(o)))
+        return {"memory": int(o[0]), "taken": int(o[1]), "accepted": int(o[2]), "rejected": int(o[3]), "restarts": int(o[4]),
+                "columns": int(o[5]), "ms": float(o[6]), "ring_bytes": float(o[7])}
+
     def set_allreduce(self, fn):
         """fn(dev_ptr:int, count:int, hip_stream:int) -> None : in-place sum over ranks on that stream."""
         def tramp(_user, buf, count, stream):

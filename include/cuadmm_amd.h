@@ -73,6 +73,14 @@ void cuadmm_destroy(cuadmm_solver* s);
  *                   iteration, final product, svec store -- in ONE launch; 0 = prologue and epilogue as launches of their own (bit-identical)
  *   "duo_share_device", "duo_exchange"   the in-process group of cuadmm_duo_init(device_num_requested = N): all engines on the
  *                   caller's device; all-reduce through device memory (1), host staging (0), chosen by peer accessibility (-1, default)
+ *   "accel"         memory m of the safeguarded Anderson acceleration of the iteration ("Acceleration"): 0 (default) = off,
+ *                   1 .. 16 = keep the last m differences of the fixed-point map (X, sigma S) -> (X+, sigma S+) and extrapolate behind every
+ *                   iteration; anything else is CUADMM_ERR_INVALID.  Costs (2 m + 3) 2 L doubles of device memory (two rings of m columns,
+ *                   u_k, g_k, the fallback copy).  Runs one iteration per launch (no batches, no early y-solve); refused at init together
+ *                   with world > 1, an in-process group or eig_rank > 0.  Set before cuadmm_init.
+ *   "accel_safeguard"   default 2.0: the candidate behind iteration k is rejected (the iterate goes back to the plain f_k, the memory is
+ *                   cleared, the iteration spent on it stays counted) when ||g_{k+1}|| > accel_safeguard ||g_k||; <= 0 rejects every candidate
+ *   "accel_reg"     default 1e-10: the least-squares system is (G + accel_reg tr(G) / cols I) gamma = rhs
  *   (every other switch: INTEGRATION.md section 6)
  */
 int cuadmm_set_option(cuadmm_solver* s, const char* key, double value);
@@ -204,6 +212,13 @@ int cuadmm_get_counters(const cuadmm_solver* s, double out8[8]);
  * || z - L22 (W z) ||_inf for a probe vector z of entries in [0.5, 1.5] (~ unit roundoff x cond(L22); -1: not measured), [5] 1 when option
  * "tail_refine" is on: every triangular solve of the tail takes one refinement step against the factor itself (6x the bytes per solve). */
 int cuadmm_get_tail_info(const cuadmm_solver* s, double out[6]);
+/* Option "accel": [0] memory m, [1] candidates taken, [2] accepted, [3] rejected, [4] restarts (the memory cleared because the map
+ * changed: sigma, tau, the switch to ADMM, a degenerate least-squares system), [5] columns held now, [6] total ms in the acceleration
+ * kernels when option "profile" is on (else 0; they are not part of cuadmm_get_profile), [7] bytes the two rings hold. */
+int cuadmm_get_accel_info(const cuadmm_solver* s, double out8[8]);
+/* The least-squares solve of the acceleration: (gram + reg tr(gram) / cols I) gamma = rhs, gram cols x cols row-major and symmetric,
+ * 1 <= cols <= 16, by Cholesky in long double.  Host only (no device needed).  CUADMM_ERR_FACTOR when a pivot is not positive. */
+int cuadmm_accel_solve_ls(const double* gram, const double* rhs, int cols, double reg, double* gamma_out);
 /* The in-process group a handle leads after cuadmm_duo_init(device_num_requested = N) from one process (reference
  * src/duo_solver.cu:487-577): [0] engines in the group (1: no group), [1] exchange of its all-reduce -- 1 = device side (each
  * rank's kernel adds the N staging buffers out of its peers' memory: one shared device, or peer access over xGMI as
@@ -407,6 +422,15 @@ int cuadmm_op_aty_xb(int64_t L, int m, const int* row_ptrs, const int* col_ids, 
                      double sig, int write_xb, double* Rd1, double* Xb, int* info2);
 int cuadmm_op_post(int mode, int64_t L, const double* Xproj, const double* Rd1, const double* C, double* X, double* S, double inv_sig, double tau_sig,
                    double* sums2, int m, const int* row_ptrs, const int* col_ids, const double* vals, const double* y, int* nparts_out);
+/* The acceleration kernels on host arrays (csrc/accel.hip).  State vectors have 2 L entries, X part then S part.
+ *   push:    g_out = (X - u_X, sig (S - u_S)); with have_prev also dF_out = (X - f_X, sig (S - f_S)) and dG_out = g - g_prev (else both are
+ *            left as they were); f_prev is in / out and returns (X, S); gnorm2_out[0] = ||g||^2
+ *   gram:    out[j] = <dG_newest, dG_j>, out[cols + j] = <dG_j, g>, j < cols; ring_dG holds cols columns of L2 entries (L2 even)
+ *   combine: X <- X - sum_j gamma_j dF_j[X], S <- (sig S - sum_j gamma_j dF_j[S]) / sig; ring_dF holds cols columns of 2 L entries */
+int cuadmm_op_accel_push(int64_t L, const double* u_prev, const double* X, const double* S, double sig, double* f_prev, const double* g_prev, int have_prev,
+                         double* g_out, double* dF_out, double* dG_out, double* gnorm2_out);
+int cuadmm_op_accel_gram(int64_t L2, int cols, int newest, const double* ring_dG, const double* g, double* out /* 2 cols */);
+int cuadmm_op_accel_combine(int64_t L, int cols, const double* ring_dF, const double* gamma, double sig, double* X_inout, double* S_inout);
 int cuadmm_op_spmv_rows(int rows, int ncols, const int* row_ptrs, const int* col_ids, const double* vals, const double* X, const double* S, const double* C,
                         int want_x, int want_s, const int* rowmap, int out_len, double* outX, double* outS, int* info4);
 int cuadmm_op_rp_stats(int m, const double* ax, const double* b, const double* normA, const double* y, double bscale, const double* sums2, double* out4);

@@ -94,6 +94,14 @@ class SDPSolver {
     con_num = con_num_;
   }
 
+  // option "accel" (set_option before init): [memory, taken, accepted, rejected, restarts, columns, ms, ring bytes]; not in the reference
+  struct AccelInfo { int memory; long long taken, accepted, rejected, restarts; int columns; double ms, ring_bytes; };
+  AccelInfo accel_info() const {
+    double o[8] = {0};
+    check(cuadmm_get_accel_info(h_, o));
+    return AccelInfo{(int)o[0], (long long)o[1], (long long)o[2], (long long)o[3], (long long)o[4], (int)o[5], o[6], o[7]};
+  }
+
   // cuadmm_update_bC: new b and / or C on the factored solver (nnz < 0: unchanged); not in the reference
   void update_bC(const int* cpu_b_indices, const double* cpu_b_vals, int b_nnz, const int* cpu_C_indices, const double* cpu_C_vals,
                  int C_nnz, bool keep_iterate = true, double sig = 0.0) {
