@@ -85,6 +85,10 @@ PROTOTYPES = {
     "cuadmm_get_counters": (C.c_int, [C.c_void_p, C.c_void_p]),
     "cuadmm_get_group_info": (C.c_int, [C.c_void_p, C.c_void_p]),
     "cuadmm_get_tail_info": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "cuadmm_update_A": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double]),
+    "cuadmm_get_update_info": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "cuadmm_get_update_pass_info": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "cuadmm_op_gather_vals": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p]),
     "cuadmm_get_accel_info": (C.c_int, [C.c_void_p, C.c_void_p]),
     "cuadmm_accel_solve_ls": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_void_p]),
     "cuadmm_op_accel_push": (C.c_int, [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 4),
@@ -121,6 +125,9 @@ PROTOTYPES = {
     "cuadmm_aat_solve_leading_forward11": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "cuadmm_aat_solve_leading_backward11": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "cuadmm_aat_free": (None, [C.c_void_p]),
+    "cuadmm_aat_refactor": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "cuadmm_aat_valid": (C.c_int, [C.c_void_p]),
+    "cuadmm_aat_pattern_nnz": (C.c_int64, [C.c_void_p]),
     "cuadmm_op_vector_to_matrices": (C.c_int, [C.c_void_p] * 6 + [C.c_int, C.c_void_p]),
     "cuadmm_op_matrices_to_vector": (C.c_int, [C.c_void_p] * 6 + [C.c_int, C.c_void_p]),
     "cuadmm_op_gemm_sym": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -64,6 +64,15 @@ struct cuadmm_aat {
   // ascending; the sweeps of a solve never leave a tree
   std::vector<int> forest_ptr, forest_cols;
   int forest_max = 0;
+  // What the analysis leaves for cuadmm_aat_refactor (new values of A on the same pattern): the pattern of A by columns as given and by
+  // rows (Rsrc: position of every row entry in the caller's value array), the upper triangle of P B P^T by columns (Cp / Ci; its values
+  // are formed again from A), the elimination tree.  Index arrays only: the values of B and of P B P^T are released as before.
+  int L = 0;
+  double eps = 0;
+  std::vector<int> Acp, Ari, Rc, Rsrc, Ci, parent;
+  std::vector<int64_t> Rp, Cp;
+  bool valid = false;        // false while a refactorisation that hit a zero pivot has left Lx / D half written
+  int refactors = 0;
 };
 
 namespace {
@@ -557,6 +566,33 @@ int plan_tail(const int64_t* Lp, int m, int max_k, const int* parent = nullptr, 
 }
 
 int aat_create_impl(int m, int L, const int* Acp, const int* Ari, const double* Ax, double eps, int split_max_k, cuadmm_aat** out);
+struct NumStat { double t_lead = 0; long long upd = 0; };
+int aat_numeric(cuadmm_aat* f, const std::vector<double>& Cx, double t0, NumStat& ns);
+
+// Row i of B = A A^T + eps I with the accumulation order of the factor's first build: cuadmm_aat_create and cuadmm_aat_refactor both
+// form B through this one function, so the values agree bit for bit.  `touched`: the columns of the row, ascending; acc[j] their values.
+struct BRow {
+  std::vector<int> where, touched;
+  std::vector<double> acc;
+  explicit BRow(int m) : where(m, -1), acc(m, 0.0) {}
+  void row(int i, const cuadmm_aat& f, const double* Ax) {
+    touched.clear();
+    const int* Acp = f.Acp.data();
+    const int* Ari = f.Ari.data();
+    for (int64_t p = f.Rp[i]; p < f.Rp[i + 1]; ++p) {
+      const int k = f.Rc[p];
+      const double a = Ax[f.Rsrc[p]];
+      for (int64_t q = Acp[k]; q < Acp[k + 1]; ++q) {
+        const int j = Ari[q];
+        if (where[j] != i) { where[j] = i; acc[j] = 0.0; touched.push_back(j); }
+        acc[j] += a * Ax[q];
+      }
+    }
+    if (where[i] != i) { where[i] = i; acc[i] = 0.0; touched.push_back(i); }
+    acc[i] += f.eps;
+    std::sort(touched.begin(), touched.end());
+  }
+};
 
 }  // namespace
 
@@ -576,133 +612,27 @@ int cuadmm_aat_create_split(int m, int L, const int* Acp, const int* Ari, const 
 
 namespace {
 
-int aat_create_impl(int m, int L, const int* Acp, const int* Ari, const double* Ax, double eps, int split_max_k, cuadmm_aat** out) {
-  if (!out || m < 0 || L < 0 || !Acp) { set_error("aat_create: bad arguments"); return CUADMM_ERR_INVALID; }
-  *out = nullptr;
-  double t0 = now_s();
-  const int64_t nnz = Acp[L];
-  // rows of A (CSR) from its columns (CSC)
-  std::vector<int64_t> Rp((size_t)m + 1, 0);
-  for (int64_t p = 0; p < nnz; ++p) {
-    if (Ari[p] < 0 || Ari[p] >= m) { set_error("aat_create: row index %d out of range", Ari[p]); return CUADMM_ERR_INVALID; }
-    Rp[(size_t)Ari[p] + 1]++;
-  }
-  for (int i = 0; i < m; ++i) Rp[i + 1] += Rp[i];
-  std::vector<int> Rc((size_t)nnz);
-  std::vector<double> Rx((size_t)nnz);
-  {
-    std::vector<int64_t> pos(Rp.begin(), Rp.end() - 1);
-    for (int k = 0; k < L; ++k)
-      for (int64_t p = Acp[k]; p < Acp[k + 1]; ++p) {
-        int64_t q = pos[Ari[p]]++;
-        Rc[q] = k; Rx[q] = Ax[p];
-      }
-  }
-  // B = A A^T + eps I, full symmetric pattern, one row at a time
-  std::vector<int64_t> Bp((size_t)m + 1, 0);
-  std::vector<int> Bi;
-  std::vector<double> Bx;
-  {
-    std::vector<int> where(m, -1);
-    std::vector<double> acc(m, 0.0);
-    std::vector<int> touched;
-    for (int i = 0; i < m; ++i) {
-      touched.clear();
-      for (int64_t p = Rp[i]; p < Rp[i + 1]; ++p) {
-        int k = Rc[p];
-        double a = Rx[p];
-        for (int64_t q = Acp[k]; q < Acp[k + 1]; ++q) {
-          int j = Ari[q];
-          if (where[j] != i) { where[j] = i; acc[j] = 0.0; touched.push_back(j); }
-          acc[j] += a * Ax[q];
-        }
-      }
-      if (where[i] != i) { where[i] = i; acc[i] = 0.0; touched.push_back(i); }
-      acc[i] += eps;
-      std::sort(touched.begin(), touched.end());
-      for (int j : touched) { Bi.push_back(j); Bx.push_back(acc[j]); }
-      Bp[i + 1] = (int64_t)Bi.size();
-    }
-  }
-  cuadmm_aat* f = new cuadmm_aat();
-  f->m = m;
-  double t_b = now_s();
-  min_degree_order(m, Bp, Bi, f->perm);
-  if (getenv("CUADMM_AAT_TIMING")) fprintf(stderr, "[aat] build B %.3fs (nnz %lld), ordering %.3fs\n", t_b - t0, (long long)Bi.size(), now_s() - t_b);
-  f->iperm.resize(m);
-  for (int i = 0; i < m; ++i) f->iperm[f->perm[i]] = i;
-
-  // C = P B P^T, upper triangle by columns (column k holds rows i <= k)
-  std::vector<int64_t> Cp((size_t)m + 1, 0);
-  for (int i = 0; i < m; ++i) {
-    int pi = f->iperm[i];
-    for (int64_t p = Bp[i]; p < Bp[i + 1]; ++p) {
-      int pj = f->iperm[Bi[p]];
-      if (pi <= pj) Cp[(size_t)pj + 1]++;
-    }
-  }
-  for (int i = 0; i < m; ++i) Cp[i + 1] += Cp[i];
-  std::vector<int> Ci((size_t)Cp[m]);
-  std::vector<double> Cx((size_t)Cp[m]);
-  {
-    std::vector<int64_t> pos(Cp.begin(), Cp.end() - 1);
-    for (int i = 0; i < m; ++i) {
-      int pi = f->iperm[i];
-      for (int64_t p = Bp[i]; p < Bp[i + 1]; ++p) {
-        int pj = f->iperm[Bi[p]];
-        if (pi <= pj) { int64_t q = pos[pj]++; Ci[q] = pi; Cx[q] = Bx[p]; }
-      }
-    }
-  }
-  std::vector<int64_t>().swap(Bp); std::vector<int>().swap(Bi); std::vector<double>().swap(Bx);
-
-  // symbolic: elimination tree and column counts of L
-  std::vector<int> parent(m, -1), flag(m, -1);
-  std::vector<int64_t> Lnz(m, 0);
-  for (int k = 0; k < m; ++k) {
-    flag[k] = k;
-    for (int64_t p = Cp[k]; p < Cp[k + 1]; ++p) {
-      int i = Ci[p];
-      while (i < k && flag[i] != k) {
-        if (parent[i] < 0) parent[i] = k;
-        Lnz[i]++;
-        flag[i] = k;
-        i = parent[i];
-      }
-    }
-  }
-  f->Lp.assign((size_t)m + 1, 0);
-  for (int k = 0; k < m; ++k) f->Lp[k + 1] = f->Lp[k] + Lnz[k];
-  f->analyze_s = now_s() - t0;
-  t0 = now_s();
-  const int tail_k = split_max_k > 0 ? plan_tail(f->Lp.data(), m, split_max_k, parent.data(), &f->plan_tops) : std::min(m, -split_max_k);
-  const int n1 = m - tail_k;                     // rows / columns >= n1 belong to the unfactored tail
-  f->tail_k = tail_k;
-  try {
-    // the tail columns keep their symbolic counts in Lp (cuadmm_aat_factor_nnz reports the whole factor) but get no
-    // storage: Li / Lx end at Lp[n1]
-    f->Li.resize((size_t)f->Lp[n1]);
-    f->Lx.resize((size_t)f->Lp[n1]);
-    if (tail_k > 0) {
-      f->schur_ptr.assign((size_t)tail_k + 1, 0);
-      f->schur_col.reserve((size_t)(f->Lp[m] - f->Lp[n1]) + (size_t)tail_k);
-      f->schur_val.reserve((size_t)(f->Lp[m] - f->Lp[n1]) + (size_t)tail_k);
-    }
-  } catch (const std::bad_alloc&) {
-    set_error("aat_create: factor with %lld nonzeros does not fit in host memory", (long long)f->Lp[m]);
-    delete f;
-    return CUADMM_ERR_FACTOR;
-  }
+// The numeric part: leading columns of the up-looking LDL^T and the Schur complement of the tail, from the values Cx of the upper triangle
+// of P B P^T on the analysis f holds (Cp / Ci, parent, Lp, tail_k).  cuadmm_aat_create and cuadmm_aat_refactor both end here, so a
+// refactorisation repeats the arithmetic of a fresh factor entry by entry.  Li is written again with the indices it holds.
+int aat_numeric(cuadmm_aat* f, const std::vector<double>& Cx, double t0, NumStat& ns) {
+  const int m = f->m, tail_k = f->tail_k, n1 = m - tail_k;
+  const std::vector<int64_t>& Cp = f->Cp;
+  const std::vector<int>& Ci = f->Ci;
+  const std::vector<int>& parent = f->parent;
+  f->valid = false;
   f->D.assign(m, 0.0);
-
+  if (tail_k > 0) {
+    f->schur_ptr.assign((size_t)tail_k + 1, 0);
+    f->schur_col.clear(); f->schur_val.clear();
+  }
   // numeric: up-looking LDL^T, row k of L from the reach of column k of C in the etree
   std::vector<double> Y(m, 0.0);
   std::vector<int> pattern(m);
-  std::fill(flag.begin(), flag.end(), -1);
-  std::fill(Lnz.begin(), Lnz.end(), 0);
-  double t_lead = 0;
-  const double t_alloc = now_s() - t0;
-  long long upd = 0;
+  std::vector<int> flag(m, -1);
+  std::vector<int64_t> Lnz(m, 0);
+  double& t_lead = ns.t_lead;
+  long long& upd = ns.upd;
   // The TAIL rows on the host pool (round 4).  Row k >= n1 of the up-looking factorisation needs the leading factor (complete
   // after row n1 - 1) and, for its Schur-complement entries, the L21 entries of the tail rows before it.  Two parallel phases with
   // the serial arithmetic, entry by entry:
@@ -759,7 +689,6 @@ int aat_create_impl(int m, int L, const int* Acp, const int* Ari, const double* 
     }
     if (dk == 0.0 || !std::isfinite(dk)) {
       set_error("Factorization fails! (zero or non-finite pivot at permuted row %d)", k);
-      delete f;
       return CUADMM_ERR_FACTOR;
     }
     f->D[k] = dk;
@@ -869,9 +798,126 @@ int aat_create_impl(int m, int L, const int* Acp, const int* Ari, const double* 
     }
   } catch (const std::bad_alloc&) {
     set_error("aat_create: the working set of the %d tail rows of the factor (%lld nonzeros) does not fit in host memory", tail_k, (long long)f->Lp[m]);
+    return CUADMM_ERR_FACTOR;
+  }
+  f->valid = true;
+  return CUADMM_OK;
+}
+
+int aat_create_impl(int m, int L, const int* Acp, const int* Ari, const double* Ax, double eps, int split_max_k, cuadmm_aat** out) {
+  if (!out || m < 0 || L < 0 || !Acp) { set_error("aat_create: bad arguments"); return CUADMM_ERR_INVALID; }
+  *out = nullptr;
+  double t0 = now_s();
+  const int64_t nnz = Acp[L];
+  cuadmm_aat* f = new cuadmm_aat();
+  f->m = m; f->L = L; f->eps = eps;
+  // rows of A (CSR) from its columns (CSC); Rsrc: where every row entry sits in the caller's value array
+  std::vector<int64_t>& Rp = f->Rp;
+  Rp.assign((size_t)m + 1, 0);
+  for (int64_t p = 0; p < nnz; ++p) {
+    if (Ari[p] < 0 || Ari[p] >= m) { set_error("aat_create: row index %d out of range", Ari[p]); delete f; return CUADMM_ERR_INVALID; }
+    Rp[(size_t)Ari[p] + 1]++;
+  }
+  for (int i = 0; i < m; ++i) Rp[i + 1] += Rp[i];
+  f->Rc.resize((size_t)nnz); f->Rsrc.resize((size_t)nnz);
+  {
+    std::vector<int64_t> pos(Rp.begin(), Rp.end() - 1);
+    for (int k = 0; k < L; ++k)
+      for (int64_t p = Acp[k]; p < Acp[k + 1]; ++p) {
+        int64_t q = pos[Ari[p]]++;
+        f->Rc[q] = k; f->Rsrc[q] = (int)p;
+      }
+  }
+  f->Acp.assign(Acp, Acp + L + 1);
+  f->Ari.assign(Ari, Ari + nnz);
+  // B = A A^T + eps I, full symmetric pattern, one row at a time
+  std::vector<int64_t> Bp((size_t)m + 1, 0);
+  std::vector<int> Bi;
+  std::vector<double> Bx;
+  {
+    BRow w(m);
+    for (int i = 0; i < m; ++i) {
+      w.row(i, *f, Ax);
+      for (int j : w.touched) { Bi.push_back(j); Bx.push_back(w.acc[j]); }
+      Bp[i + 1] = (int64_t)Bi.size();
+    }
+  }
+  double t_b = now_s();
+  min_degree_order(m, Bp, Bi, f->perm);
+  if (getenv("CUADMM_AAT_TIMING")) fprintf(stderr, "[aat] build B %.3fs (nnz %lld), ordering %.3fs\n", t_b - t0, (long long)Bi.size(), now_s() - t_b);
+  f->iperm.resize(m);
+  for (int i = 0; i < m; ++i) f->iperm[f->perm[i]] = i;
+
+  // C = P B P^T, upper triangle by columns (column k holds rows i <= k)
+  std::vector<int64_t>& Cp = f->Cp;
+  Cp.assign((size_t)m + 1, 0);
+  for (int i = 0; i < m; ++i) {
+    int pi = f->iperm[i];
+    for (int64_t p = Bp[i]; p < Bp[i + 1]; ++p) {
+      int pj = f->iperm[Bi[p]];
+      if (pi <= pj) Cp[(size_t)pj + 1]++;
+    }
+  }
+  for (int i = 0; i < m; ++i) Cp[i + 1] += Cp[i];
+  std::vector<int>& Ci = f->Ci;
+  Ci.resize((size_t)Cp[m]);
+  std::vector<double> Cx((size_t)Cp[m]);
+  {
+    std::vector<int64_t> pos(Cp.begin(), Cp.end() - 1);
+    for (int i = 0; i < m; ++i) {
+      int pi = f->iperm[i];
+      for (int64_t p = Bp[i]; p < Bp[i + 1]; ++p) {
+        int pj = f->iperm[Bi[p]];
+        if (pi <= pj) { int64_t q = pos[pj]++; Ci[q] = pi; Cx[q] = Bx[p]; }
+      }
+    }
+  }
+  std::vector<int64_t>().swap(Bp); std::vector<int>().swap(Bi); std::vector<double>().swap(Bx);
+
+  // symbolic: elimination tree and column counts of L
+  std::vector<int>& parent = f->parent;
+  parent.assign(m, -1);
+  std::vector<int> flag(m, -1);
+  std::vector<int64_t> Lnz(m, 0);
+  for (int k = 0; k < m; ++k) {
+    flag[k] = k;
+    for (int64_t p = Cp[k]; p < Cp[k + 1]; ++p) {
+      int i = Ci[p];
+      while (i < k && flag[i] != k) {
+        if (parent[i] < 0) parent[i] = k;
+        Lnz[i]++;
+        flag[i] = k;
+        i = parent[i];
+      }
+    }
+  }
+  f->Lp.assign((size_t)m + 1, 0);
+  for (int k = 0; k < m; ++k) f->Lp[k + 1] = f->Lp[k] + Lnz[k];
+  f->analyze_s = now_s() - t0;
+  t0 = now_s();
+  const int tail_k = split_max_k > 0 ? plan_tail(f->Lp.data(), m, split_max_k, parent.data(), &f->plan_tops) : std::min(m, -split_max_k);
+  const int n1 = m - tail_k;                     // rows / columns >= n1 belong to the unfactored tail
+  f->tail_k = tail_k;
+  try {
+    // the tail columns keep their symbolic counts in Lp (cuadmm_aat_factor_nnz reports the whole factor) but get no
+    // storage: Li / Lx end at Lp[n1]
+    f->Li.resize((size_t)f->Lp[n1]);
+    f->Lx.resize((size_t)f->Lp[n1]);
+    if (tail_k > 0) {
+      f->schur_ptr.assign((size_t)tail_k + 1, 0);
+      f->schur_col.reserve((size_t)(f->Lp[m] - f->Lp[n1]) + (size_t)tail_k);
+      f->schur_val.reserve((size_t)(f->Lp[m] - f->Lp[n1]) + (size_t)tail_k);
+    }
+  } catch (const std::bad_alloc&) {
+    set_error("aat_create: factor with %lld nonzeros does not fit in host memory", (long long)f->Lp[m]);
     delete f;
     return CUADMM_ERR_FACTOR;
   }
+  const double t_alloc = now_s() - t0;
+  NumStat ns;
+  if (int rcn = aat_numeric(f, Cx, t0, ns)) { delete f; return rcn; }
+  const double t_lead = ns.t_lead;
+  const long long upd = ns.upd;
   for (int j = 0; j < n1; ++j) if (f->Lp[j + 1] > f->Lp[j]) f->nzcols.push_back(j);
   if (tail_k > 0) {
     f->lead_mid.resize((size_t)n1);
@@ -1210,6 +1256,52 @@ int cuadmm_aat_solve_leading_backward11(const cuadmm_aat* f, int k, double* x, c
 }
 
 void cuadmm_aat_free(cuadmm_aat* f) { delete f; }
+
+// Numeric refactorisation: new values of A (the caller's order at create) on the analysis f holds -- pattern of B, ordering, elimination
+// tree, Lp / Li, tail cut and tops plan stay; B's values, the leading columns and the Schur complement of the tail (released or not) are
+// formed again by the code a fresh create runs, in its order.  Refused (factor untouched) for a non-finite value.  CUADMM_ERR_FACTOR on a
+// zero or non-finite pivot: the factor then holds no usable values (cuadmm_aat_valid) until a later refactorisation succeeds.
+int cuadmm_aat_refactor(cuadmm_aat* f, const double* A_vals) {
+  if (!f || (!A_vals && !f->Ari.empty())) { set_error("aat_refactor: null argument"); return CUADMM_ERR_INVALID; }
+  const int m = f->m;
+  const int64_t nnz = (int64_t)f->Ari.size();
+  for (int64_t p = 0; p < nnz; ++p)
+    if (!std::isfinite(A_vals[p])) { set_error("aat_refactor: value %lld is not finite", (long long)p); return CUADMM_ERR_INVALID; }
+  const double t0 = now_s();
+  std::vector<double> Cx;
+  try {
+    Cx.resize((size_t)f->Cp[m]);
+    std::vector<int64_t> pos(f->Cp.begin(), f->Cp.end() - 1);
+    BRow w(m);
+    for (int i = 0; i < m; ++i) {
+      w.row(i, *f, A_vals);
+      const int pi = f->iperm[i];
+      for (int j : w.touched) {
+        const int pj = f->iperm[j];
+        if (pi <= pj) Cx[(size_t)pos[pj]++] = w.acc[j];
+      }
+    }
+    if (f->tail_k > 0) {
+      const int n1 = m - f->tail_k;
+      f->schur_col.reserve((size_t)(f->Lp[m] - f->Lp[n1]) + (size_t)f->tail_k);
+      f->schur_val.reserve((size_t)(f->Lp[m] - f->Lp[n1]) + (size_t)f->tail_k);
+    }
+  } catch (const std::bad_alloc&) {
+    set_error("aat_refactor: the values of A A^T do not fit in host memory");
+    return CUADMM_ERR_FACTOR;
+  }
+  const double t_b = now_s();
+  NumStat ns;
+  const int rc = aat_numeric(f, Cx, t_b, ns);
+  f->factor_s = now_s() - t0;
+  f->refactors++;
+  if (getenv("CUADMM_AAT_TIMING"))
+    fprintf(stderr, "[aat] refactor: values of B %.3fs, numeric %.3fs (leading rows until %.3fs, %lld updates); no ordering, no symbolic analysis\n", t_b - t0,
+            now_s() - t_b, ns.t_lead, ns.upd);
+  return rc;
+}
+int cuadmm_aat_valid(const cuadmm_aat* f) { return f && f->valid ? 1 : 0; }
+int64_t cuadmm_aat_pattern_nnz(const cuadmm_aat* f) { return f ? (int64_t)f->Ari.size() : 0; }
 
 // how many ranks share this node's CPUs (before the pool's first use; later calls are ignored)
 void cuadmm_host_pool_hint(int ranks_on_node) { if (ranks_on_node > 0) g_pool_ranks_hint.store(ranks_on_node); }

@@ -13,6 +13,10 @@
 //   --then=<dir2/> (repeatable): after the solve, read ONLY b.txt and C.txt from <dir2/> (either may be absent: unchanged), replace
 //   them on the factored solver (cuadmm_update_bC, warm start), solve with the same parameters and write <dir2/>X_opt.txt; one
 //   sidecar per stage: <file>, <file>.1, ...  A receding-horizon sequence pays for the ordering and the factor once.
+//   --then-A=<dir2/> (repeatable, in order with --then=): <dir2/> holds a whole problem on the SAME sparsity pattern of A (blk, con_num
+//   and the index columns of At.txt identical, checked before anything changes); its values of A replace the solver's
+//   (cuadmm_update_A: refactorisation on the analysis of the first init, warm start), then its b and C as with --then=, solve, write
+//   <dir2/>X_opt.txt.
 #include <dirent.h>
 
 #include <cstdio>
@@ -91,9 +95,11 @@ int main(int argc, char* argv[]) {
   bool quiet = false;
   std::string json_path;
   std::vector<std::string> then_dirs;
+  std::vector<char> then_is_A;
   for (int i = 2; i < argc; ++i) {
     if (strncmp(argv[i], "--json=", 7) == 0) { json_path = argv[i] + 7; continue; }
-    if (strncmp(argv[i], "--then=", 7) == 0) { then_dirs.push_back(argv[i] + 7); continue; }
+    if (strncmp(argv[i], "--then=", 7) == 0) { then_dirs.push_back(argv[i] + 7); then_is_A.push_back(0); continue; }
+    if (strncmp(argv[i], "--then-A=", 9) == 0) { then_dirs.push_back(argv[i] + 9); then_is_A.push_back(1); continue; }
     if (opt(argv[i], "--max_iter", max_iter) || opt(argv[i], "--stop_tol", stop_tol) || opt(argv[i], "--threshold", threshold) ||
         opt(argv[i], "--stage1", stage1) || opt(argv[i], "--stage2", stage2) || opt(argv[i], "--switch_admm", switch_admm) ||
         opt(argv[i], "--sigscale", sigscale) || opt(argv[i], "--sig", sig) || opt(argv[i], "--device", device) || opt(argv[i], "--accel", accel))
@@ -103,9 +109,10 @@ int main(int argc, char* argv[]) {
     return 1;
   }
 
-  for (const std::string& d : then_dirs) {   // before any work: a stage that cannot be read must not cost the stages before it
+  for (size_t k = 0; k < then_dirs.size(); ++k) {   // before any work: a stage that cannot be read must not cost the stages before it
+    const std::string& d = then_dirs[k];
     DIR* dp = d.empty() ? nullptr : opendir(d.c_str());
-    if (!dp) { std::cerr << "cannot read --then directory '" << d << "'" << std::endl; return 1; }
+    if (!dp) { std::cerr << "cannot read " << (then_is_A[k] ? "--then-A" : "--then") << " directory '" << d << "'" << std::endl; return 1; }
     closedir(dp);
   }
 
@@ -149,6 +156,20 @@ int main(int argc, char* argv[]) {
     std::vector<int> bi, ci;
     std::vector<double> bv, cv;
     int bn = -1, cn = -1;
+    if (then_is_A[k]) {
+      cuadmm_problem* p2 = nullptr;
+      if (cuadmm_problem_from_txt(d.c_str(), &p2) != CUADMM_OK) { std::cerr << cuadmm_last_error() << std::endl; rc = CUADMM_ERR_IO; break; }
+      cuadmm_problem_view w;
+      cuadmm_problem_view_get(p2, &w);
+      bool same = w.vec_len == v.vec_len && w.con_num == v.con_num && w.At_nnz == v.At_nnz && w.mat_num == v.mat_num;
+      for (int j = 0; same && j <= v.con_num; ++j) same = w.At_csc_col_ptrs[j] == v.At_csc_col_ptrs[j];
+      for (int q = 0; same && q < v.At_nnz; ++q) same = w.At_csc_row_ids[q] == v.At_csc_row_ids[q];
+      for (int q = 0; same && q < v.mat_num; ++q) same = w.blk_vals[q] == v.blk_vals[q];
+      if (!same) { std::cerr << "--then-A: the problem in '" << d << "' does not have the sparsity pattern of A (or the blocks) of '" << prefix << "'" << std::endl; rc = CUADMM_ERR_INVALID; }
+      else rc = cuadmm_update_A(solver, w.At_csc_vals, w.At_nnz, 1, 0.0);
+      cuadmm_problem_free(p2);
+      if (rc != CUADMM_OK) { if (same) std::cerr << cuadmm_last_error() << std::endl; break; }
+    }
     if (!read_then_vec(d + "b.txt", bi, bv, bn) || !read_then_vec(d + "C.txt", ci, cv, cn)) { std::cerr << cuadmm_last_error() << std::endl; rc = CUADMM_ERR_IO; break; }
     rc = cuadmm_update_bC(solver, bi.data(), bv.data(), bn, ci.data(), cv.data(), cn, 1, 0.0);
     if (rc == CUADMM_OK) rc = cuadmm_solve(solver, (int)max_iter, stop_tol, (int)threshold, (int)stage1, (int)stage2, (int)switch_admm, sigscale, 1);

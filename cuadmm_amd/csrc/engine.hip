@@ -238,6 +238,32 @@ struct cuadmm_solver {
   // cuadmm_update_bC rescaled y on the device (y-solve there): y_p is behind y_d until somebody on the host needs it (sync_y_host)
   bool y_host_stale = false;
   std::vector<double> normA_all;      // owned constraints: max(1, ||column||) of EVERY constraint (bscale of a new b runs over all of them)
+  // cuadmm_update_A (new values of A on the pattern of init).  Kept since init: the caller's pattern of A^T and b in the caller's units
+  // and entry order (b is divided by the new column norms, bscale summed in that order; cuadmm_update_bC replaces them).  Built at
+  // the first update: the two index maps of the value pass (CSR slot -> position in the caller's value array) and the host's row
+  // pointers of A.  factor_bad: the last update could not factor the new A A^T; solve refuses until an update succeeds.
+  struct UpdateA {
+    std::vector<int> cp, ri, b_idx;
+    std::vector<double> b_val;
+    // owned constraints: the caller's column pointers, where this rank's entries sit in the caller's value array, and the whole b
+    // (the column norms of EVERY constraint and bscale over all of b are formed again from the full inputs, as in init)
+    std::vector<int> g_cp, g_from, bg_idx;
+    std::vector<double> bg_val;
+    bool maps = false, in_update = false, tail_fellback = false;
+    int inject_fail = 0;      // test hook (option "update_A_inject_fail"): the NEXT update fails as a broken factorisation would, 1: behind the
+                              // host refactorisation, 2: behind the rebuilt GPU tail and y-solve streams; cleared by that update
+    std::vector<int> h_fromA, h_fromAt, h_arp;
+    DevBuf<int> fromA, fromAt;
+    DevBuf<double> src;
+    long long count = 0, orderings = 0;
+    double wall_ms = 0, host_ms = 0, dev_ms = 0, bytes = 0;
+    // option profile: the two streaming passes of the last update timed by events of their own (the K_COPY / K_POST classes also hold what the
+    // residual stage behind them does): [0, 1] around the value pass's kernel, [2, 3] around the svec pass
+    hipEvent_t ev[4] = {};
+    double pass_ms[2] = {0, 0}, pass_bytes[2] = {0, 0};
+    ~UpdateA() { for (auto& e : ev) if (e) { hipError_t r = hipEventDestroy(e); (void)r; } }
+  } upa;
+  bool factor_bad = false;
   // Behavioural switches (cuadmm_set_option, before init).  The environment variables of round 1 / 2 only give the DEFAULTS, read
   // once per solver in its constructor: two solvers in a process can choose differently, and tests reach every variant.
   struct Switches {
@@ -784,6 +810,7 @@ static int init_normalise(Solver* s, const InitIn& in, InitCtx& c) {
   CUADMM_INIT_STAGE_PROLOGUE
   // --- get_normA (sparse_matrix_norm.cu:11-31): norm_j = max(1,||col j||), column scaled in place
   vals.assign(At_vx, At_vx + At_nnz);
+  if (!s->upa.in_update) { s->upa.cp.assign(At_cp, At_cp + m + 1); s->upa.ri.assign(At_ri, At_ri + At_nnz); }
   s->normA.assign(m, 1.0);
   for (int j = 0; j < m; ++j) {
     double nrm = 0.0;
@@ -810,6 +837,33 @@ static int init_normalise(Solver* s, const InitIn& in, InitCtx& c) {
   return rc;
 }
 
+// The probe solve of a freshly built GPU tail (init, and cuadmm_update_A after it rebuilt the tail): see init_factor
+static int tail_probe(Solver* s, const int64_t* srp, const int* sci, const double* sv, int tk, bool& tail_ok) {
+  int rc = CUADMM_OK;
+  std::vector<double> x((size_t)tk), z((size_t)tk, 0.0), r((size_t)tk, 0.0);
+  unsigned long long seed = 0x9e3779b97f4a7c15ull;
+  for (int i = 0; i < tk; ++i) { seed = seed * 6364136223846793005ull + 1442695040888963407ull; x[i] = 0.5 + (double)(seed >> 11) * (1.0 / 9007199254740992.0); }
+  auto apply_S = [&](const std::vector<double>& in, std::vector<double>& out) {
+    std::fill(out.begin(), out.end(), 0.0);
+    for (int i = 0; i < tk; ++i)
+      for (int64_t q = srp[i]; q < srp[i + 1]; ++q) {
+        const int j = sci[q];
+        out[i] += sv[q] * in[j];
+        if (j != i) out[j] += sv[q] * in[i];
+      }
+  };
+  apply_S(x, z);
+  std::vector<double> xh = z;
+  rc = s->tail.solve(xh.data(), s->st);
+  apply_S(xh, r);
+  double err = 0, zn = 0;
+  for (int i = 0; i < tk; ++i) { err = std::max(err, std::fabs(r[i] - z[i])); zn = std::max(zn, std::fabs(z[i])); }
+  tail_ok = rc == CUADMM_OK && err <= 1e-6 * zn;
+  if (!tail_ok && rc == CUADMM_OK && s->verbose)
+    printf("\n A*A^T factor: the GPU tail of size %d fails its probe solve (backward error %.1e): falling back to the host-only factor\n", tk, err / std::max(zn, 1e-300));
+  return rc;
+}
+
 // stage: A A^T + eps I: ordering, host factor, GPU tail of the Schur complement with its probe solve, permutation
 static int init_factor(Solver* s, const InitIn& in, InitCtx& c) {
   CUADMM_INIT_STAGE_PROLOGUE
@@ -822,6 +876,7 @@ static int init_factor(Solver* s, const InitIn& in, InitCtx& c) {
     int max_k = std::max(64, std::min(s->sw.tail_max_k, 65536));
     if (s->sw.tail_k >= 0) max_k = -std::min(std::min(s->sw.tail_k, m), 65536);
     double t0 = wall_s();
+    s->upa.orderings++;
     if (max_k == 0) rc = cuadmm_aat_create(m, vec_len, rp.data(), rci.data(), rv.data(), 1e-15, &s->fac);
     else {
       // the planner may choose a (smaller) tail for the solve with dense tree tops unless the options rule that solve out
@@ -846,35 +901,14 @@ static int init_factor(Solver* s, const InitIn& in, InitCtx& c) {
       // relaxations have numerically singular S: no solver recovers x, and the ADMM iteration only needs a small residual).
       // On failure fall back to the host-only factor (CHOLMOD-style substitution, no explicit inverse).
       bool tail_ok = rc == CUADMM_OK;
-      if (rc == CUADMM_OK) {
-        std::vector<double> x((size_t)tk), z((size_t)tk, 0.0), r((size_t)tk, 0.0);
-        unsigned long long seed = 0x9e3779b97f4a7c15ull;
-        for (int i = 0; i < tk; ++i) { seed = seed * 6364136223846793005ull + 1442695040888963407ull; x[i] = 0.5 + (double)(seed >> 11) * (1.0 / 9007199254740992.0); }
-        auto apply_S = [&](const std::vector<double>& in, std::vector<double>& out) {
-          std::fill(out.begin(), out.end(), 0.0);
-          for (int i = 0; i < tk; ++i)
-            for (int64_t q = srp[i]; q < srp[i + 1]; ++q) {
-              const int j = sci[q];
-              out[i] += sv[q] * in[j];
-              if (j != i) out[j] += sv[q] * in[i];
-            }
-        };
-        apply_S(x, z);
-        std::vector<double> xh = z;
-        rc = s->tail.solve(xh.data(), s->st);
-        apply_S(xh, r);
-        double err = 0, zn = 0;
-        for (int i = 0; i < tk; ++i) { err = std::max(err, std::fabs(r[i] - z[i])); zn = std::max(zn, std::fabs(z[i])); }
-        tail_ok = rc == CUADMM_OK && err <= 1e-6 * zn;
-        if (!tail_ok && rc == CUADMM_OK && s->verbose)
-          printf("\n A*A^T factor: the GPU tail of size %d fails its probe solve (backward error %.1e): falling back to the host-only factor\n", tk, err / std::max(zn, 1e-300));
-      }
+      if (rc == CUADMM_OK) rc = tail_probe(s, srp, sci, sv, tk, tail_ok);
       cuadmm_aat_tail_schur_release(s->fac);
       if (rc && rc != CUADMM_ERR_FACTOR) return rc;
       if (!tail_ok) {
         s->tail.release();
         cuadmm_aat_free(s->fac);
         s->fac = nullptr;
+        s->upa.orderings++; s->upa.tail_fellback = true;
         if ((rc = cuadmm_aat_create(m, vec_len, rp.data(), rci.data(), rv.data(), 1e-15, &s->fac))) return rc;
       }
     }
@@ -1101,6 +1135,7 @@ static int init_vectors(Solver* s, const InitIn& in, InitCtx& c) {
   if (s->local_mode) { nb = s->ov_nb; nc = s->ov_nc; }      // norms over ALL constraints / the whole C
   s->norm_borg = 1 + std::sqrt(nb);
   s->norm_Corg = 1 + std::sqrt(nc);
+  s->upa.b_idx.assign(b_idx, b_idx + b_nnz); s->upa.b_val.assign(b_vals, b_vals + b_nnz);
   std::vector<double> bfull(m, 0.0);
   std::vector<char> seen_b((size_t)m, 0);
   double nb2 = 0;
@@ -1302,7 +1337,14 @@ static int init_closed(Solver* s, const InitIn& in, InitCtx& c) {
           R.nrounds = maxmult;
         }
       }
-      if (ok) {
+      if (ok && s->upa.in_update) {
+        // cuadmm_update_A: the same records with the new rows of A, normA, D, dense factor and b, into the allocation of init in one copy
+        // (headers, nk / nnz / rounds, depend on the pattern alone: the descriptors' aux words stay)
+        if (s->closed.rec.n != recs.size()) { set_error("update_A: the closed-block records changed their number"); return CUADMM_ERR_INTERNAL; }
+        if ((rc = s->closed.rec.upload(recs.data(), recs.size()))) return rc;
+        s->upa.bytes += (double)(sizeof(ClosedRec) * recs.size());
+        s->closed.active = true;
+      } else if (ok) {
         if ((rc = s->closed.rec.from(recs)) || (rc = s->closed.cl_out.alloc(16 * recs.size())) ||
             (rc = s->closed.partials2.alloc(2 * (size_t)s->plan.fused_blocks() + 2)))
           return rc;
@@ -1455,6 +1497,7 @@ int cuadmm_set_option(cuadmm_solver* s, const char* key, double value) {
   }
   else if (k == "accel_safeguard") s->aa.safeguard = value;             // a candidate is rejected when ||g|| grows by more than this factor (<= 0: always)
   else if (k == "accel_reg") s->aa.reg = value;                         // relative Tikhonov term of the least-squares solve
+  else if (k == "update_A_inject_fail") s->upa.inject_fail = (int)value;   // test hook
   else if (k == "duo_inject_fail") { s->duo_inject = (long long)value; if (s->group) duo_group_inject(s->group, s->duo_inject); }   // test hook
   else { s->option_log.pop_back(); set_error("set_option: unknown key '%s'", key); return CUADMM_ERR_INVALID; }
   // a group handle: every rank follows -- AFTER the key has been validated on the leader; a child that refuses leaves the option
@@ -1586,6 +1629,11 @@ int cuadmm_init(cuadmm_solver* s, int eig_stream_num_per_gpu, int cpu_eig_thread
         for (int p = At_cp[j]; p < At_cp[j + 1]; ++p) cn += At_vx[p] * At_vx[p];
         s->normA_all[j] = std::max(1.0, std::sqrt(cn));
       }
+      s->upa.g_cp.assign(At_cp, At_cp + con_num + 1);
+      s->upa.g_from.clear();
+      for (size_t q = 0; q < cons.size(); ++q)
+        for (int p = At_cp[cons[q]]; p < At_cp[cons[q] + 1]; ++p) s->upa.g_from.push_back(p);
+      s->upa.bg_idx.assign(b_idx, b_idx + b_nnz); s->upa.bg_val.assign(b_vals, b_vals + b_nnz);
       s->world = 1; s->rank = 0;
       if (s->comm_rank != 0) s->verbose = 0;      // one console table per job
       int one = 0;
@@ -1616,6 +1664,7 @@ int cuadmm_init(cuadmm_solver* s, int eig_stream_num_per_gpu, int cpu_eig_thread
 int cuadmm_solve(cuadmm_solver* s, int max_iter, double stop_tol, int sig_update_threshold, int sig_update_stage_1,
                  int sig_update_stage_2, int switch_admm, double sigscale, int if_first) {
   if (!s || !s->initialised) { set_error("solve: solver not initialised"); return CUADMM_ERR_INVALID; }
+  if (s->factor_bad) { set_error("solve: the last cuadmm_update_A could not factor the new A A^T; the solver needs a successful cuadmm_update_A first"); return CUADMM_ERR_FACTOR; }
   if (sig_update_stage_1 <= 0 || sig_update_stage_2 <= 0) { set_error("solve: sig_update stages must be positive"); return CUADMM_ERR_INVALID; }
   if (s->group && !s->in_group_call) {    // the leader of an in-process group (duo_group.hip): every rank solves, on its own host thread
     DeviceGuard keep_device;
@@ -2290,6 +2339,7 @@ int cuadmm_set_XyS(cuadmm_solver* s, const double* X, const double* y, const dou
 int cuadmm_update_bC(cuadmm_solver* s, const int* b_idx, const double* b_vals, int b_nnz, const int* C_idx, const double* C_vals, int C_nnz,
                      int keep_iterate, double sig) {
   if (!s || !s->initialised) { set_error("update_bC: solver not initialised"); return CUADMM_ERR_INVALID; }
+  if (s->factor_bad) { set_error("update_bC: the last cuadmm_update_A could not factor the new A A^T; the solver needs a successful cuadmm_update_A first"); return CUADMM_ERR_FACTOR; }
   const bool new_b = b_nnz >= 0, new_C = C_nnz >= 0;
   if ((b_nnz > 0 && (!b_idx || !b_vals)) || (C_nnz > 0 && (!C_idx || !C_vals))) { set_error("update_bC: entries without their index / value arrays"); return CUADMM_ERR_INVALID; }
   // --- every check before anything changes (the caller's numbering; the rules of init_vectors, over the whole of b and C on every rank)
@@ -2369,6 +2419,14 @@ int cuadmm_update_bC(cuadmm_solver* s, const int* b_idx, const double* b_vals, i
   if (!pending && (rc = s->sync_y_host())) return rc;
   const double bs_old = s->bscale, cs_old = s->Cscale;
   if (new_b) {
+    if (!s->local_mode) { s->upa.b_idx.assign(b_idx, b_idx + b_nnz); s->upa.b_val.assign(b_vals, b_vals + b_nnz); }   // what a later cuadmm_update_A rescales
+    else {
+      s->upa.bg_idx.assign(b_idx, b_idx + b_nnz); s->upa.bg_val.assign(b_vals, b_vals + b_nnz);
+      s->upa.b_idx.clear(); s->upa.b_val.clear();
+      std::vector<int> g2l2((size_t)s->m_full, -1);
+      for (int q = 0; q < m; ++q) g2l2[s->cons_local[q]] = q;
+      for (int i = 0; i < b_nnz; ++i) if (g2l2[b_idx[i]] >= 0) { s->upa.b_idx.push_back(g2l2[b_idx[i]]); s->upa.b_val.push_back(b_vals[i]); }
+    }
     s->norm_borg = 1 + std::sqrt(nb);
     s->bscale = 1 + std::sqrt(nb2);
     if (s->local_mode) { s->ov_nb = nb; s->ov_nb2 = nb2; }
@@ -2427,6 +2485,274 @@ int cuadmm_update_bC(cuadmm_solver* s, const int* b_idx, const double* b_vals, i
 
   // --- initial A X, A (S - C), residual scalars: init's own last stage (it ends with a stream synchronisation)
   return init_residuals(s, y_on_device);
+}
+
+
+// New values of A on the pattern of init.  Everything that depends on the pattern alone stays: the pattern of A A^T, the ordering, the
+// elimination tree and column counts, the tail cut and the tops plan, the projection plan, the closed-block and fused-row
+// classification, the index arrays of both device matrices.  What is formed again, by the routines of init in their arithmetic order:
+// the column norms and the normalised values, the host factor (cuadmm_aat_refactor), the GPU tail with its probe solve, the streams of the
+// device-side y-solve, the value arrays of A and A^T (one upload of the normalised values, one kernel through two index maps), the
+// closed blocks' records, b and the scaling constants, the units of X, y, S.  Decisions of init that depend on VALUES are taken again
+// (DESIGN.md section 7 lists them); where one comes out differently the handle would need another plan, which only an init builds:
+// the call then fails like a factorisation that broke down and the solver refuses to solve until an update succeeds.
+int cuadmm_update_A(cuadmm_solver* s, const double* At_vals, int At_nnz, int keep_iterate, double sig) {
+  if (!s || !s->initialised) { set_error("update_A: solver not initialised"); return CUADMM_ERR_INVALID; }
+  // --- every check before anything changes
+  const int nnz_init = s->local_mode ? s->upa.g_cp.back() : (int)s->upa.ri.size();
+  if (At_nnz != nnz_init) { set_error("update_A: %d values, the pattern given to init has %d entries", At_nnz, nnz_init); return CUADMM_ERR_INVALID; }
+  if (At_nnz > 0 && !At_vals) { set_error("update_A: null values"); return CUADMM_ERR_INVALID; }
+  for (int p = 0; p < At_nnz; ++p)
+    if (!std::isfinite(At_vals[p])) { set_error("update_A: value %d is not finite", p); return CUADMM_ERR_INVALID; }
+  // (init keeps explicit zeros in the pattern -- of A, of A A^T and of the factor --, so a value of exactly 0 is as good as any other)
+  if (s->group && !s->in_group_call) {      // every rank takes the full value array, as with init
+    DeviceGuard keep_device;
+    return duo_group_run(s->group, [&](cuadmm_solver* q, int) {
+      q->in_group_call = true;
+      int r2 = cuadmm_update_A(q, At_vals, At_nnz, keep_iterate, sig);
+      q->in_group_call = false;
+      return r2;
+    });
+  }
+  if (s->upa.tail_fellback) {
+    set_error("update_A: init fell back from the GPU tail to the host-only factor on the values it was given; whether new values would take the tail is a decision only an init can take");
+    return CUADMM_ERR_INVALID;
+  }
+  int rc = check_device(s->device);
+  if (rc) return rc;
+  const double t_begin = wall_s();
+  const int m = s->m;
+  const long long L = s->L;
+  const bool keep = keep_iterate != 0;
+  s->upa.bytes = 0;
+
+  // X, y, S to the caller's units where a solve left them scaled (the rounded operations a caller reading them would have seen)
+  if ((rc = s->materialise())) return rc;
+
+  // owned constraints: the norms of EVERY constraint and the sum behind bscale from the full inputs, then this rank's own values
+  std::vector<double> local_vals;
+  if (s->local_mode) {
+    const int* gcp = s->upa.g_cp.data();
+    for (int j = 0; j < s->m_full; ++j) {
+      double cn = 0;
+      for (int p = gcp[j]; p < gcp[j + 1]; ++p) cn += At_vals[p] * At_vals[p];
+      s->normA_all[j] = std::max(1.0, std::sqrt(cn));
+    }
+    double nb2 = 0;
+    for (size_t i = 0; i < s->upa.bg_idx.size(); ++i) { const double v = s->upa.bg_val[i] / s->normA_all[s->upa.bg_idx[i]]; nb2 += v * v; }
+    s->ov_nb2 = nb2;
+    local_vals.resize(s->upa.g_from.size());
+    for (size_t p = 0; p < local_vals.size(); ++p) local_vals[p] = At_vals[s->upa.g_from[p]];
+    At_vals = local_vals.data();
+    At_nnz = (int)local_vals.size();
+  }
+  // --- column norms, normalised values, A^T by svec rows: init's own stage
+  s->upa.in_update = true;
+  struct Leave { cuadmm_solver* s; int verbose; ~Leave() { s->upa.in_update = false; s->verbose = verbose; } } leave{s, s->verbose};
+  s->verbose = 0;                                              // the stages of init print their plans; they are not new
+  InitIn in{s->L_full, m, At_nnz, (int)s->upa.b_idx.size(), 0, (int)s->blk_local.size(), s->upa.cp.data(), s->upa.ri.data(), s->upa.b_idx.data(), nullptr,
+            s->blk_local.data(), At_vals, s->upa.b_val.data(), nullptr, nullptr, nullptr, nullptr, s->sig};
+  InitCtx ctx;
+  const std::vector<double> normA_old = s->normA;
+  if ((rc = init_normalise(s, in, ctx))) return rc;
+
+  // --- host factor on the analysis of init, then the GPU tail from the new Schur complement through init's routine and probe
+  s->factor_bad = true;                                        // until every stage below has gone through
+  auto fail = [&](int code) { s->normA = normA_old; return code; };
+  const double t_f0 = wall_s();
+  double t_f1 = t_f0;
+  auto factor_stage = [&]() -> int {
+    int rc = CUADMM_OK;
+    if ((rc = cuadmm_aat_refactor(s->fac, ctx.rv.data()))) return (rc);
+    t_f1 = wall_s();
+    const int inject = s->upa.inject_fail;
+    s->upa.inject_fail = 0;
+    if (inject == 1) { set_error("update_A: injected failure behind the host refactorisation (test hook)"); return CUADMM_ERR_FACTOR; }
+    if (s->tail.k > 0) {
+      const int tk = cuadmm_aat_tail_k(s->fac);
+      const int64_t* srp; const int* sci; const double* sv;
+      if ((rc = cuadmm_aat_tail_schur(s->fac, &srp, &sci, &sv))) return (rc);
+      s->tail.shard_rank = 0; s->tail.shard_world = 1; s->tail.reduce_fn = nullptr;      // as at init: the probe applies the whole tail; solve sets the shard again
+      rc = s->tail.build_from_schur(reinterpret_cast<const long long*>(srp), sci, sv, tk, s->st);
+      bool tail_ok = rc == CUADMM_OK;
+      if (rc == CUADMM_OK) rc = tail_probe(s, srp, sci, sv, tk, tail_ok);
+      s->upa.bytes += 20.0 * (double)srp[tk];
+      cuadmm_aat_tail_schur_release(s->fac);
+      if (rc && rc != CUADMM_ERR_FACTOR) return (rc);
+      if (!tail_ok) {
+        set_error("update_A: the GPU tail of %d columns fails its factorisation or its probe solve on the new values (an init would fall back to the host-only factor)", tk);
+        return (CUADMM_ERR_FACTOR);
+      }
+      if (s->world > 1 && !s->local_mode && s->sw.tail_shard != 0 && !s->sw.tail_refine && (rc = s->tail.keep_shard(s->rank, s->world, s->st))) return (rc);
+    }
+    // --- where the y-solve runs: init's stage again (the streams of the leading sweeps, the tree tops' inverses, L21), and its decisions
+    if (s->tail.k > 0 && !s->sw.host_solve) {
+      const bool o_dev = s->dev_solve, o_ready = s->lead.ready, o_tops = s->lead.tops, o_hyb = s->lead.hybrid;
+      if ((rc = init_solve_plan(s, in, ctx))) return (rc);
+      if (o_dev != s->dev_solve || o_ready != s->lead.ready || o_tops != s->lead.tops || o_hyb != s->lead.hybrid) {
+        set_error("update_A: with the new values the y-solve would be planned differently (device %d -> %d, sweeps %d -> %d, tree tops %d -> %d, hybrid %d -> %d); only an init builds another plan",
+                  (int)o_dev, (int)s->dev_solve, (int)o_ready, (int)s->lead.ready, (int)o_tops, (int)s->lead.tops, (int)o_hyb, (int)s->lead.hybrid);
+        return (CUADMM_ERR_FACTOR);
+      }
+    } else if (s->forest_trees > 0) {
+      const int64_t* Lp; const int* Li; const double* Lx; const double* D;
+      if ((rc = cuadmm_aat_factor_arrays(s->fac, &Lp, &Li, &Lx, &D))) return (rc);
+      if ((rc = s->f_Lx.upload(Lx, (size_t)Lp[m])) || (rc = s->f_D.upload(D, (size_t)m))) return (rc);
+      s->upa.bytes += 8.0 * ((double)Lp[m] + (double)m);
+    }
+    if (inject == 2) { set_error("update_A: injected failure behind the rebuilt y-solve (test hook)"); return CUADMM_ERR_FACTOR; }
+    return CUADMM_OK;
+  };
+  rc = factor_stage();
+  if (s->local_mode && s->comm_world > 1) {
+    // owned constraints: every rank factors its own A A^T.  The ranks agree on the outcome before the residual stage's collectives: one
+    // rank that failed fails the call on all of them
+    double bad[1] = {rc ? 1.0 : 0.0};
+    int rc2 = s->allreduce_scalars(bad, 1);
+    if (!rc && rc2) rc = rc2;
+    if (!rc && bad[0] > 0) { set_error("update_A: another rank could not factor its share of the new A A^T"); rc = CUADMM_ERR_FACTOR; }
+  }
+  if (rc) return fail(rc);
+  const double t_f2 = wall_s();
+
+  // --- the value arrays of A and A^T: the maps at the first update, then one upload and one kernel
+  if (!s->upa.maps) {
+    auto& u = s->upa;
+    const int* cp = u.cp.data();
+    const int* ri = u.ri.data();
+    // A^T by svec rows: slot q of the rank's share <- caller's position (the fill order of init_normalise)
+    std::vector<int> from_rows((size_t)At_nnz);
+    {
+      std::vector<int> pos(ctx.rp.begin(), ctx.rp.end() - 1);
+      for (int j = 0; j < m; ++j)
+        for (int p = cp[j]; p < cp[j + 1]; ++p) from_rows[(size_t)pos[ri[p]]++] = p;
+    }
+    const int base = ctx.rp[s->sv_begin], cnt = ctx.rp[s->sv_end] - base;
+    u.h_fromAt.assign(from_rows.begin() + base, from_rows.begin() + base + cnt);
+    // A by permuted rows, local columns (the fill order of init_matrices)
+    u.h_fromA.clear(); u.h_fromA.reserve((size_t)cnt);
+    u.h_arp.assign((size_t)m + 1, 0);
+    for (int pidx = 0; pidx < m; ++pidx) {
+      const int j = s->perm[pidx];
+      for (int p = cp[j]; p < cp[j + 1]; ++p)
+        if (ri[p] >= s->sv_begin && ri[p] < s->sv_end) u.h_fromA.push_back(p);
+      u.h_arp[(size_t)pidx + 1] = (int)u.h_fromA.size();
+    }
+    if (u.h_fromA.size() != s->A_v.n || (size_t)cnt != s->At_v.n) { set_error("update_A: the index maps do not match the device matrices"); return fail(CUADMM_ERR_INTERNAL); }
+    if ((rc = u.fromA.from(u.h_fromA)) || (rc = u.fromAt.from(u.h_fromAt)) || (rc = u.src.alloc(std::max(At_nnz, 1)))) return fail(rc);
+    u.maps = true;
+  }
+  if ((rc = s->upa.src.upload(ctx.vals.data(), (size_t)At_nnz))) return fail(rc);
+  const bool timed = s->profile == 1;
+  if (timed) for (auto& e : s->upa.ev) if (!e) CUADMM_HIP_TRY(hipEventCreate(&e));
+  if (timed) CUADMM_HIP_TRY(hipEventRecord(s->upa.ev[0], s->st));      // the kernel alone: the upload above is a blocking copy of its own
+  if ((rc = launch_gather_vals(s->A_v.p, s->upa.fromA.p, (long long)s->upa.h_fromA.size(), s->At_v.p, s->upa.fromAt.p, (long long)s->upa.h_fromAt.size(), s->upa.src.p, s->st)))
+    return fail(rc);
+  if (timed) CUADMM_HIP_TRY(hipEventRecord(s->upa.ev[1], s->st));
+  s->upa.pass_bytes[0] = 20.0 * ((double)s->upa.h_fromA.size() + (double)s->upa.h_fromAt.size());      // per slot: 4 of map, 8 gathered, 8 stored
+  s->upa.bytes += 8.0 * At_nnz;
+  if (s->lrows.active) {
+    // the rows evaluated inside the fused blocks' kernels keep copies of their values (and the compact matrix of the others its own)
+    auto& lr = s->lrows;
+    const auto& arp = s->upa.h_arp;
+    const auto& fA = s->upa.h_fromA;
+    std::vector<char> local((size_t)m, 0);
+    size_t z = 0;
+    for (int q = 0; q < lr.nlocal; ++q) {
+      const int r = lr.h_row[q];
+      local[r] = 1;
+      for (int p = arp[r]; p < arp[r + 1]; ++p) lr.h_v[z++] = ctx.vals[fA[p]];
+    }
+    if ((rc = lr.v.upload(lr.h_v.data(), lr.h_v.size()))) return fail(rc);
+    s->upa.bytes += 8.0 * (double)lr.h_v.size();
+    if (lr.nrest > 0) {
+      std::vector<double> rv2;
+      for (int r = 0; r < m; ++r) {
+        if (local[r]) continue;
+        for (int p = arp[r]; p < arp[r + 1]; ++p) rv2.push_back(ctx.vals[fA[p]]);
+      }
+      if ((rc = lr.rest_v.upload(rv2.data(), rv2.size()))) return fail(rc);
+      s->upa.bytes += 8.0 * (double)rv2.size();
+    }
+  }
+
+  // --- scaling constants, b, and the iterate in the new units (init_vectors; b and C themselves are the caller's of before)
+  double ibs = 1, ics = 1;
+  {
+    double nb2 = 0;
+    std::vector<double> bfull((size_t)m, 0.0);
+    for (size_t i = 0; i < s->upa.b_idx.size(); ++i) {
+      const double v = s->upa.b_val[i] / s->normA[s->upa.b_idx[i]];
+      bfull[s->upa.b_idx[i]] = v;
+      nb2 += v * v;
+    }
+    if (s->local_mode) nb2 = s->ov_nb2;
+    s->bscale = 1 + std::sqrt(nb2);
+    s->objscale = s->bscale * s->Cscale;
+    ibs = 1 / s->bscale; ics = 1 / s->Cscale;
+    for (int pidx = 0; pidx < m; ++pidx) {
+      const int j = s->perm[pidx];
+      s->normA_p[pidx] = s->normA[j];
+      s->b_p[pidx] = bfull[j] * ibs;
+    }
+    if (s->b_d.p) {
+      if ((rc = s->b_d.upload(s->b_p.data(), (size_t)m)) || (rc = s->normA_d.upload(s->normA_p.data(), (size_t)m))) return fail(rc);
+      s->upa.bytes += 16.0 * (double)m;
+    }
+  }
+  // --- closed blocks: init's routine, into the records of init
+  if (s->closed.active) {
+    if ((rc = init_closed(s, in, ctx))) return fail(rc);
+    if (!s->closed.active) { set_error("update_A: the closed-block records could not be rebuilt on the new factor"); return fail(CUADMM_ERR_FACTOR); }
+  }
+  // (the iterate last: a call that failed above has left X, y, S in the caller's units, where a later update finds them)
+  for (int pidx = 0; pidx < m; ++pidx) s->y_p[pidx] = keep ? (s->y_p[pidx] * s->normA_p[pidx]) * ics : 0.0;
+  if (timed) CUADMM_HIP_TRY(hipEventRecord(s->upa.ev[2], s->st));
+  if ((rc = launch_update_svec(s->X.p, s->S.p, nullptr, L, !keep, 1.0, ibs, 1.0, ics, s->st))) return fail(rc);
+  if (timed) CUADMM_HIP_TRY(hipEventRecord(s->upa.ev[3], s->st));
+  s->upa.pass_bytes[1] = (keep ? 32.0 : 16.0) * (double)L;
+  if (sig > 0) s->sig = sig;
+  s->factor_bad = false;
+
+  // --- per-solve bookkeeping as init leaves it (profile counters, plans, the blocks' launch order stay)
+  for (auto& a : s->info) a.clear();
+  s->info_iter_num = 0;
+  s->t_init0 = t_begin; s->total_time = 0;
+  s->best_KKT = 0; s->sgs_KKT = 0; s->have_best = false; s->eig_fail_total = 0;
+  s->prim_win = 0; s->dual_win = 0; s->feasratio = 0; s->ratioconst = 1e0; s->sigmax = 1e3; s->sigmin = 1e-3;
+  s->y_early = false; s->stats_fused = false;
+  s->bt.len = s->bt.pos = 0; s->bt.have_ck = false;
+  s->closed.iters_done = 0; s->closed.out_dirty = true;
+  s->plan.n_project = 0;
+  if (s->hint_d.p) CUADMM_HIP_TRY(hipMemsetAsync(s->hint_d.p, 0, sizeof(int) * s->hint_d.n, s->st));
+  if (s->closed.cl_out.p) CUADMM_HIP_TRY(hipMemsetAsync(s->closed.cl_out.p, 0, sizeof(double) * s->closed.cl_out.n, s->st));
+  if (!s->dev_solve) std::fill(s->Rp_p.begin(), s->Rp_p.end(), 0.0);
+  s->y_full.clear();
+  s->y_host_stale = false;
+  s->pending_unscale = false;
+  s->upa.bytes += 8.0 * (double)m;                             // y, uploaded by the residual stage
+
+  rc = init_residuals(s, false);                               // (ends with a stream synchronisation)
+  s->upa.pass_ms[0] = s->upa.pass_ms[1] = 0;
+  if (timed && !rc)
+    for (int q = 0; q < 2; ++q) { float ms = 0; if (hipEventElapsedTime(&ms, s->upa.ev[2 * q], s->upa.ev[2 * q + 1]) == hipSuccess) s->upa.pass_ms[q] = ms; else (void)hipGetLastError(); }
+  s->upa.count++;
+  s->upa.host_ms = (t_f1 - t_f0) * 1e3;
+  s->upa.dev_ms = (t_f2 - t_f1) * 1e3;
+  s->upa.wall_ms = (wall_s() - t_begin) * 1e3;
+  return rc;
+}
+
+int cuadmm_get_update_info(const cuadmm_solver* s, double o[6]) {
+  if (!s || !o) { set_error("get_update_info: null"); return CUADMM_ERR_INVALID; }
+  o[0] = (double)s->upa.count; o[1] = s->upa.wall_ms; o[2] = s->upa.host_ms; o[3] = s->upa.dev_ms; o[4] = (double)s->upa.orderings; o[5] = s->upa.bytes;
+  return CUADMM_OK;
+}
+
+int cuadmm_get_update_pass_info(const cuadmm_solver* s, double o[4]) {
+  if (!s || !o) { set_error("get_update_pass_info: null"); return CUADMM_ERR_INVALID; }
+  o[0] = s->upa.pass_ms[0]; o[1] = s->upa.pass_bytes[0]; o[2] = s->upa.pass_ms[1]; o[3] = s->upa.pass_bytes[1];
+  return CUADMM_OK;
 }
 
 int cuadmm_get_device_ptrs(cuadmm_solver* s, double** X, double** y, double** S) {
@@ -2683,6 +3009,27 @@ int cuadmm_op_forest_solve(cuadmm_aat* f, int m, const double* ax, const double*
   CUADMM_HIP_TRY(hipStreamSynchronize(nullptr));
   info2[0] = ntrees; info2[1] = maxc;
   return staged_d2h(y_out, y_d.p, sizeof(double) * (size_t)m);
+}
+
+// op-level hook of the value pass of cuadmm_update_A: outA[offA + q] = src[fromA[q]], outAt[offAt + q] = src[fromAt[q]]; the targets are
+// device arrays of nA + offA + 2 (nAt + offAt + 2) doubles filled with `fill` first, returned whole (what the kernel must leave alone included)
+int cuadmm_op_gather_vals(const double* src, int n_src, const int* fromA, int nA, int offA, const int* fromAt, int nAt, int offAt, double fill,
+                          double* outA, double* outAt) {
+  if (!src || n_src < 1 || nA < 0 || nAt < 0 || offA < 0 || offAt < 0 || (nA > 0 && !fromA) || (nAt > 0 && !fromAt) || !outA || !outAt) { set_error("op_gather_vals: bad arguments"); return CUADMM_ERR_INVALID; }
+  for (int q = 0; q < nA; ++q) if (fromA[q] < 0 || fromA[q] >= n_src) { set_error("op_gather_vals: index out of range"); return CUADMM_ERR_INVALID; }
+  for (int q = 0; q < nAt; ++q) if (fromAt[q] < 0 || fromAt[q] >= n_src) { set_error("op_gather_vals: index out of range"); return CUADMM_ERR_INVALID; }
+  int rc;
+  DevBuf<double> d_src, dA, dAt;
+  DevBuf<int> d_fA, d_fAt;
+  const size_t lenA = (size_t)nA + offA + 2, lenAt = (size_t)nAt + offAt + 2;
+  std::vector<double> hA(lenA, fill), hAt(lenAt, fill);
+  if ((rc = d_src.from(std::vector<double>(src, src + n_src))) || (rc = dA.from(hA)) || (rc = dAt.from(hAt)) ||
+      (rc = d_fA.from(std::vector<int>(fromA, fromA + nA))) || (rc = d_fAt.from(std::vector<int>(fromAt, fromAt + nAt))))
+    return rc;
+  if ((rc = launch_gather_vals(dA.p + offA, d_fA.p, nA, dAt.p + offAt, d_fAt.p, nAt, d_src.p, nullptr))) return rc;
+  CUADMM_HIP_TRY(hipDeviceSynchronize());
+  if ((rc = staged_d2h(outA, dA.p, sizeof(double) * lenA)) || (rc = staged_d2h(outAt, dAt.p, sizeof(double) * lenAt))) return rc;
+  return CUADMM_OK;
 }
 
 int cuadmm_op_psd_project(const double* Xb, double* Xproj, const int* blk_host, int mat_num, void* stream) {

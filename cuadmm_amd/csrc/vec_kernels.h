@@ -76,6 +76,9 @@ int launch_update_svec(double* X, double* S, double* C, long long n, bool zero, 
 int launch_update_cons(int m, double* b, double* y, const double* normA, int ymode, double cs_old, double ics_new, hipStream_t st);
 int launch_scatter_scaled(double* dst, const int* idx, const double* val, int n, double s, hipStream_t st);   // dst[idx[k]] = val[k] s
 int launch_closed_patch_b(ClosedRec* rec, int nslots, const double* b, hipStream_t st);                       // rec[slot].b[k] = b[rows[k]]
+// cuadmm_update_A: the value arrays of A (CSR, permuted rows) and A^T (CSR over the svec rows) from this rank's normalised values in the
+// caller's order: vA[q] = src[fromA[q]] (q < nA), vAt[q] = src[fromAt[q]] (q < nAt), both in one launch
+int launch_gather_vals(double* vA, const int* fromA, long long nA, double* vAt, const int* fromAt, long long nAt, const double* src, hipStream_t st);
 // y = (L D L^T)^-1 (-A(S-C) + (b - A X) / sigma) on the device, one thread per tree of the elimination forest
 int launch_forest_solve(int ntrees, const int* tree_ptr, const int* tree_cols, const long long* Lp, const int* Li, const double* Lx,
                         const double* D, const double* ax, const double* asmc, const double* b, double isig, double* x, hipStream_t st);

@@ -840,6 +840,43 @@ int launch_closed_patch_b(ClosedRec* rec, int nslots, const double* b, hipStream
 }
 
 // ------------------------------------------------------------------------------------------
+// cuadmm_update_A (engine.hip): new values of A on the pattern of init.  The host normalises this rank's values with init's arithmetic
+// and uploads them once, in the caller's order; this kernel writes the value arrays of both device matrices from them through two index
+// maps (CSR slot -> position in the upload, built at the first update).  Stores are streaming and 16 bytes wide wherever the target is
+// 16-byte aligned (a leading element of a misaligned array and an odd last one go alone); the loads are the gather.  The long-row and
+// compact-row SpMV variants read these arrays too, so nothing else has to move.
+// ------------------------------------------------------------------------------------------
+__device__ __forceinline__ void gather_vals_range(double* __restrict__ dst, const int* __restrict__ from, long long n, const double* __restrict__ src,
+                                                  long long tid, long long stride) {
+  if (n <= 0) return;
+  const long long head = (reinterpret_cast<unsigned long long>(dst) & 8ull) ? 1 : 0;      // elements in front of the first 16-byte boundary
+  const long long n2 = (n - head) / 2;
+  up_d2* __restrict__ d2 = reinterpret_cast<up_d2*>(dst + head);
+  const int* __restrict__ f2 = from + head;
+  for (long long i = tid; i < n2; i += stride) {
+    up_d2 v;
+    v.x = src[f2[2 * i]]; v.y = src[f2[2 * i + 1]];
+    d2[i] = v;
+  }
+  if (tid == 0) {
+    if (head) dst[0] = src[from[0]];
+    if ((n - head) & 1) dst[n - 1] = src[from[n - 1]];
+  }
+}
+__global__ __launch_bounds__(kVecThreads) void gather_vals_kernel(double* __restrict__ vA, const int* __restrict__ fromA, long long nA, double* __restrict__ vAt,
+                                                                const int* __restrict__ fromAt, long long nAt, const double* __restrict__ src) {
+  const long long tid = (long long)blockIdx.x * kVecThreads + threadIdx.x, stride = (long long)gridDim.x * kVecThreads;
+  gather_vals_range(vA, fromA, nA, src, tid, stride);
+  gather_vals_range(vAt, fromAt, nAt, src, tid, stride);
+}
+int launch_gather_vals(double* vA, const int* fromA, long long nA, double* vAt, const int* fromAt, long long nAt, const double* src, hipStream_t st) {
+  if (nA <= 0 && nAt <= 0) return CUADMM_OK;
+  hipLaunchKernelGGL(gather_vals_kernel, dim3(grid_for(std::max(nA, nAt) / 2 + 1, kVecThreads, 256 * 8)), dim3(kVecThreads), 0, st, vA, fromA, nA, vAt, fromAt, nAt, src);
+  CUADMM_HIP_TRY(hipGetLastError());
+  return CUADMM_OK;
+}
+
+// ------------------------------------------------------------------------------------------
 // op-level kernels: one per reference kernel (same element-wise semantics)
 // ------------------------------------------------------------------------------------------
 // src/kernels/vec_mat_conversion.cu:11-34

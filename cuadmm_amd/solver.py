@@ -235,6 +235,26 @@ class SDPSolver:
                                          _p(ci), _p(cv), -1 if ci is None else int(ci.size), int(bool(keep_iterate)), float(sig)))
         return self
 
+    def update_A(self, vals, keep_iterate=True, sig=0.0):
+        """New values of A (At_csc_vals in the order given to init) on the sparsity pattern of init.  The ordering and the symbolic
+        analysis are kept; factor, device matrices, y-solve data and scaling are formed again as init would (cuadmm_update_A)."""
+        v = _f64(vals)
+        check(self._lib.cuadmm_update_A(self._h, _p(v), int(v.size), int(bool(keep_iterate)), float(sig)))
+        return self
+
+    def update_info(self):
+        """cuadmm_get_update_info: [updates so far, wall ms of the last one, host numeric factor ms, device part of the y-solve
+        rebuild ms, orderings run on this handle, bytes that crossed to the device in the last update]"""
+        o = np.zeros(6)
+        check(self._lib.cuadmm_get_update_info(self._h, _p(o)))
+        return o
+
+    def update_pass_info(self):
+        """cuadmm_get_update_pass_info (option profile = 1): [value pass ms, bytes, svec pass ms, bytes] of the last update_A"""
+        o = np.zeros(4)
+        check(self._lib.cuadmm_get_update_pass_info(self._h, _p(o)))
+        return o
+
     @property
     def info_iter_num(self):
         return int(self._lib.cuadmm_get_info_iter_num(self._h))

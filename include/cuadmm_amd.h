@@ -168,6 +168,32 @@ int cuadmm_set_XyS(cuadmm_solver* s, const double* X, const double* y, const dou
  * of an in-process group forwards it to its engines.  Not in the reference, whose only way to new data is a second init. */
 int cuadmm_update_bC(cuadmm_solver* s, const int* b_indices, const double* b_vals, int b_nnz,
                      const int* C_indices, const double* C_vals, int C_nnz, int keep_iterate, double sig);
+/* New values of A on the pattern given to cuadmm_init.  At_csc_vals has At_nnz entries in the caller's order at init (same
+ * col_ptrs / row_ids, not passed again).  b, C, options, block structure stay.  keep_iterate / sig as in cuadmm_update_bC.
+ * Afterwards the solver is in the state cuadmm_init(same pattern, blk, b, C, options; the new values; the current iterate in the
+ * caller's units or zeros) would have left, bit for bit: scaling constants, column norms, info arrays, total_time, best iterate, schedule
+ * hints and acceleration memory as after init; profile counters and plans stay.  The ordering and the symbolic analysis of A A^T do
+ * not run: the host factor is refactored on the analysis of init (cuadmm_aat_refactor), the GPU tail, the streams of the device-side
+ * y-solve, the value arrays of A and A^T, the closed blocks' records and b are formed again by the routines of init.
+ * Checked before anything changes (CUADMM_ERR_INVALID, solver as it was): At_nnz equals the count at init; every value is finite.
+ * EXPLICIT ZEROS: cuadmm_init keeps every entry it is given in the pattern, also one whose value is exactly 0 (nothing is dropped from A,
+ * from A A^T or from the factor), so a value of exactly 0 is accepted here like any other.
+ * If the new A A^T cannot be factored -- a zero or non-finite pivot, a GPU tail that fails its factorisation or probe solve, or a
+ * value-dependent decision of init that would come out differently -- the call returns CUADMM_ERR_FACTOR and
+ * cuadmm_solve / cuadmm_update_bC refuse with that code until a later cuadmm_update_A succeeds.  After CUADMM_ERR_FACTOR the handle
+ * holds a mixture of old and new data: only reading X, y, S (the caller's units, unchanged) and a further cuadmm_update_A are defined.
+ * Every rank of a sharded job calls it with the full value array, as with init; the leader of an in-process group forwards it to its
+ * engines.  With owned constraints a rank whose factorisation fails fails the call on every rank; a rank that returns earlier than
+ * that -- a HIP error while it brings X, y, S back to the caller's units -- does so alone, and the job must be ended as after any
+ * rank's HIP error.  Not in the reference. */
+int cuadmm_update_A(cuadmm_solver* s, const double* At_csc_vals, int At_nnz, int keep_iterate, double sig);
+/* [0] updates so far, [1] wall ms of the last one, [2] host numeric factor ms, [3] device part of the y-solve rebuild ms,
+ * [4] orderings run on this handle since create (stays 1; 2 on a handle whose init fell back from the GPU tail to the host-only factor,
+ * which refuses cuadmm_update_A), [5] bytes that crossed to the device in the last update */
+int cuadmm_get_update_info(const cuadmm_solver* s, double out6[6]);
+/* option profile = 1: the two streaming passes of the last cuadmm_update_A, each timed alone by events: [0] ms and [1] bytes (index
+ * maps read, values gathered and stored) of the value pass's kernel, [2] ms and [3] bytes of the svec pass over X and S */
+int cuadmm_get_update_pass_info(const cuadmm_solver* s, double out4[4]);
 /* device pointers of this rank's shard (scaled inside solve, unscaled after) */
 int cuadmm_get_device_ptrs(cuadmm_solver* s, double** X, double** y, double** S);
 /* svec range [begin,end) owned by this rank (whole vector when world==1) */
@@ -336,6 +362,16 @@ int cuadmm_aat_solve_leading_backward(const cuadmm_aat* f, int k, double* x);
  *   backward11: x1 <- L11^-T (D1^-1 x1 - w), w = L21^T x2 (m-k doubles, from the GPU); x[m-k..] is not read */
 int cuadmm_aat_solve_leading_forward11(const cuadmm_aat* f, int k, double* x);
 int cuadmm_aat_solve_leading_backward11(const cuadmm_aat* f, int k, double* x, const double* w);
+/* Numeric refactorisation on the analysis of an existing factor (one-piece or split): A_vals are new values of A on the pattern given
+ * to cuadmm_aat_create / _create_split, in that order (cuadmm_aat_pattern_nnz of them).  Ordering, elimination tree, Lp / Li, tail cut
+ * and tops plan stay; the values of A A^T, the leading columns and the Schur complement of the tail (recomputed also after
+ * _tail_schur_release) come from the code a fresh create runs, in its arithmetic order: the result equals a fresh create bit for bit.
+ * A non-finite value is refused before anything changes (CUADMM_ERR_INVALID).  A zero or non-finite pivot returns CUADMM_ERR_FACTOR and
+ * leaves a factor without usable values (cuadmm_aat_valid = 0) that a later successful refactorisation restores.  Single caller per
+ * factor, like the sweeps. */
+int cuadmm_aat_refactor(cuadmm_aat* f, const double* A_vals);
+int cuadmm_aat_valid(const cuadmm_aat* f);
+int64_t cuadmm_aat_pattern_nnz(const cuadmm_aat* f);
 void cuadmm_aat_free(cuadmm_aat* f);
 
 /* ------------------------------------------------------------------------------------ */
@@ -409,6 +445,10 @@ int cuadmm_op_lead_solve(const cuadmm_aat* f, int m, int stream_only, int small_
                          const double* asmc, const double* b, double isig, int nrhs, double* y_out, int* info11);
 /* Test hook only: the same solve by one GPU thread per tree of a ONE-PIECE factor's elimination forest (what the engine runs for a
  * block-diagonal A A^T); info2 = {trees, columns of the largest tree}. */
+/* value pass of cuadmm_update_A: outA[offA + q] = src[fromA[q]] (q < nA), outAt[offAt + q] = src[fromAt[q]] (q < nAt) on device arrays of
+ * nA + offA + 2 / nAt + offAt + 2 doubles filled with `fill` first and returned whole */
+int cuadmm_op_gather_vals(const double* src, int n_src, const int* fromA, int nA, int offA, const int* fromAt, int nAt, int offAt, double fill,
+                          double* outA, double* outAt);
 int cuadmm_op_forest_solve(cuadmm_aat* f, int m, const double* ax, const double* asmc, const double* b, double isig, double* y_out, int* info2);
 /* Test hooks only: the kernels of an ADMM iteration as ops.  Every pointer is a HOST pointer; in/out arrays are uploaded as given, so what a
  * kernel leaves untouched comes back bit for bit.

@@ -108,6 +108,17 @@ class SDPSolver {
     check(cuadmm_update_bC(h_, cpu_b_indices, cpu_b_vals, b_nnz, cpu_C_indices, cpu_C_vals, C_nnz, keep_iterate ? 1 : 0, sig));
   }
 
+  // cuadmm_update_A: new values of A on the pattern of init (the caller's order at init); not in the reference
+  void update_A(const double* cpu_At_csc_vals, int At_nnz, bool keep_iterate = true, double sig = 0.0) {
+    check(cuadmm_update_A(h_, cpu_At_csc_vals, At_nnz, keep_iterate ? 1 : 0, sig));
+  }
+  struct UpdateInfo { long long updates; double wall_ms, host_factor_ms, device_solve_ms; long long orderings; double bytes_to_device; };
+  UpdateInfo update_info() const {
+    double o[6] = {0};
+    check(cuadmm_get_update_info(h_, o));
+    return UpdateInfo{(long long)o[0], o[1], o[2], o[3], (long long)o[4], o[5]};
+  }
+
   // SDPSolver::solve, same argument list and defaults (solver.h:236-244)
   void solve(int max_iter, double stop_tol, int sig_update_threshold = 500, int sig_update_stage_1 = 50,
              int sig_update_stage_2 = 100, int switch_admm = (int)1.1e4, double sigscale = 1.05, bool if_first = true) {
