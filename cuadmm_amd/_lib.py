@@ -94,6 +94,10 @@ PROTOTYPES = {
     "cuadmm_op_accel_push": (C.c_int, [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 4),
     "cuadmm_op_accel_gram": (C.c_int, [C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "cuadmm_op_accel_combine": (C.c_int, [C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p]),
+    "cuadmm_get_status": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "cuadmm_get_certificate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cuadmm_infeas_decide": (C.c_int, [C.c_void_p, C.c_double, C.c_void_p, C.c_void_p]),
+    "cuadmm_op_infeas_roll": (C.c_int, [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "cuadmm_problem_from_txt": (C.c_int, [C.c_char_p, C.POINTER(C.c_void_p)]),
     "cuadmm_problem_view_get": (C.c_int, [C.c_void_p, C.POINTER(ProblemView)]),
     "cuadmm_problem_free": (None, [C.c_void_p]),

@@ -7,6 +7,9 @@
 //   --max_iter= --stop_tol= --threshold= --stage1= --stage2= --switch_admm= --sigscale= --sig= --device= --quiet
 //   --accel=M: safeguarded Anderson acceleration with memory M (option "accel"); prints "accel: taken a, accepted b, rejected c,
 //   restarts d" after the solve and adds the four numbers to the sidecar
+//   --infeas=P --infeas_tol=T: infeasibility check every P iterations (options "infeas_check", "infeas_tol"); a certificate ends that solve
+//   with "Solver ended: primal infeasible ..." in the summary, and a --then sequence goes on with its next stage.  The sidecar carries
+//   "status" ("converged", "iteration_limit", "primal_infeasible", "dual_infeasible") with or without the check
 //   --json=<file>: a sidecar with the run's figures (iterations, residuals, iters/s, per-phase milliseconds, the projection's
 //   nominal TFLOP/s = 10.67 sum n^3 per projection and the vector kernels' algorithmic GB/s: SURVEY.md 8d); switches the
 //   engine's per-phase HIP-event timers on (option "profile").  Nothing is written unless asked for: the reference writes X_opt.txt only.
@@ -19,6 +22,7 @@
 //   <dir2/>X_opt.txt.
 #include <dirent.h>
 
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -54,6 +58,14 @@ static bool write_sidecar(const std::string& path, const std::string& prefix, cu
   fprintf(f, " \"eig_not_converged\": %.17g,\n", st[11]);
   fprintf(f, " \"plan\": {\"fused\": %d, \"closed_blocks\": %d, \"device_solve\": %d, \"factor_gpu_tail\": %d, \"batched_launches\": %.0f, \"iterations_in_batches\": %.0f},\n",
           (int)cnt[4], (int)cnt[5], (int)cnt[6], (int)cnt[7], cnt[0], cnt[1]);
+  double fin[8] = {0};
+  cuadmm_get_status(solver, fin);
+  static const char* sname[5] = {"none", "converged", "iteration_limit", "primal_infeasible", "dual_infeasible"};
+  const int code = fin[0] >= 0 && fin[0] <= 4 ? (int)fin[0] : 0;
+  fprintf(f, " \"status\": \"%s\", \"status_iteration\": %.0f,\n", sname[code], fin[1]);
+  if (fin[2] > 0 || code >= 3)
+    fprintf(f, " \"infeas\": {\"checks\": %.0f, \"scalar\": %.17g, \"eta\": %.17g, \"radius\": %s%.17g%s, \"check_ms\": %.17g, \"bytes\": %.0f},\n", fin[2], fin[3], fin[4],
+            std::isfinite(fin[5]) ? "" : "\"", fin[5], std::isfinite(fin[5]) ? "" : "\"", fin[6], fin[7]);
   double acc[8] = {0};
   cuadmm_get_accel_info(solver, acc);
   if (acc[0] > 0)
@@ -91,7 +103,7 @@ int main(int argc, char* argv[]) {
   std::string prefix = argv[1];
   int eig_stream_num_per_gpu = 15, cpu_eig_thread_num = 30;
   double max_iter = 1e6, stop_tol = 1e-3, threshold = 0, stage1 = 50, stage2 = 100, switch_admm = 5000, sigscale = 1.05,
-         sig = 1e0, device = 0, accel = 0;
+         sig = 1e0, device = 0, accel = 0, infeas = 0, infeas_tol = -1;
   bool quiet = false;
   std::string json_path;
   std::vector<std::string> then_dirs;
@@ -102,7 +114,8 @@ int main(int argc, char* argv[]) {
     if (strncmp(argv[i], "--then-A=", 9) == 0) { then_dirs.push_back(argv[i] + 9); then_is_A.push_back(1); continue; }
     if (opt(argv[i], "--max_iter", max_iter) || opt(argv[i], "--stop_tol", stop_tol) || opt(argv[i], "--threshold", threshold) ||
         opt(argv[i], "--stage1", stage1) || opt(argv[i], "--stage2", stage2) || opt(argv[i], "--switch_admm", switch_admm) ||
-        opt(argv[i], "--sigscale", sigscale) || opt(argv[i], "--sig", sig) || opt(argv[i], "--device", device) || opt(argv[i], "--accel", accel))
+        opt(argv[i], "--sigscale", sigscale) || opt(argv[i], "--sig", sig) || opt(argv[i], "--device", device) || opt(argv[i], "--accel", accel) ||
+        opt(argv[i], "--infeas_tol", infeas_tol) || opt(argv[i], "--infeas", infeas))
       continue;
     if (strcmp(argv[i], "--quiet") == 0) { quiet = true; continue; }
     std::cerr << "unknown option " << argv[i] << std::endl;
@@ -130,6 +143,11 @@ int main(int argc, char* argv[]) {
   cuadmm_set_option(solver, "verbose", quiet ? 0 : 1);
   if (!json_path.empty()) cuadmm_set_option(solver, "profile", 1);
   if (accel != 0 && cuadmm_set_option(solver, "accel", accel) != CUADMM_OK) {
+    std::cerr << cuadmm_last_error() << std::endl;
+    return 1;
+  }
+  if ((infeas != 0 && cuadmm_set_option(solver, "infeas_check", infeas) != CUADMM_OK) ||
+      (infeas_tol >= 0 && cuadmm_set_option(solver, "infeas_tol", infeas_tol) != CUADMM_OK)) {
     std::cerr << cuadmm_last_error() << std::endl;
     return 1;
   }

@@ -31,6 +31,7 @@
 #include "vec_kernels.h"
 #include "duo_group.h"
 #include "accel.h"
+#include "infeas.h"
 
 using namespace cuadmm;
 
@@ -380,6 +381,35 @@ struct cuadmm_solver {
   int accel_begin_solve();
   int accel_step(int iter, int max_iter, double stop_tol, int switch_admm, double tau, bool sig_changed, bool next_sig_may_change);
 
+  // Infeasibility detection behind the iteration (option "infeas_check" = period p; infeas.h, DESIGN.md "Infeasibility certificates").
+  // Every p iterations the differences of y and X against the snapshot taken p iterations earlier are tested for the two certificates.
+  // The projections go through a plan of the check's own (plan2): the iteration's plan carries the sign schedule's warm start and the
+  // longest-block-first order from one iteration to the next, and a foreign matrix projected through it would change the trajectory.
+  struct Infeas {
+    int period = 0;
+    double tol = 1e-6;
+    DevBuf<double> xprev, yprev, dbuf, pbuf, dy, adx, bcopy, partials, stats_d;
+    PinnedBuf<double> h_stats;
+    PsdPlan* plan2 = nullptr;
+    std::vector<std::pair<long long, long long>> free_rng;   // svec ranges of the unconstrained blocks
+    bool have_snap = false;
+    // of the last solve
+    int status = 0, verdict_iter = 0;
+    long long checks = 0;
+    double scalar = 0, eta = 0, radius = 0, ms = 0;
+    std::vector<double> cert;         // the ray of a verdict, scaled space and internal order (y: m, X: L)
+    double plan2_bytes = 0;           // device memory the second plan took when it was built (estimate: free memory before - after)
+    hipEvent_t ev[2] = {};
+    double bytes() const {
+      return 8.0 * (double)(xprev.n + yprev.n + dbuf.n + pbuf.n + dy.n + adx.n + bcopy.n + partials.n + stats_d.n) + plan2_bytes;
+    }
+    ~Infeas() { for (auto& e : ev) if (e) { hipError_t r = hipEventDestroy(e); (void)r; } delete plan2; }
+  } inf;
+  bool infeas_on() const { return inf.period > 0 && L > 0; }
+  void infeas_reset() { inf.have_snap = false; inf.status = 0; inf.verdict_iter = 0; inf.checks = 0; inf.scalar = inf.eta = inf.radius = 0; inf.cert.clear(); }
+  int infeas_begin_solve();
+  int infeas_step(int iter, double stop_tol);
+
   // profiling
   hipEvent_t ev0[K_NUM][2] = {}, ev1[K_NUM][2] = {};
   int ev_used[K_NUM] = {0};
@@ -644,7 +674,7 @@ struct cuadmm_solver {
   }
   // --- several iterations per launch ---------------------------------------------------------------------------------
   bool can_batch() const {
-    return can_batch_local() && bt.peers_agree && aa.mem == 0;
+    return can_batch_local() && bt.peers_agree && aa.mem == 0 && inf.period == 0;
   }
   bool can_batch_local() const {
     return bt.max_iters >= 2 && fuse && closed.active && dev_solve && !lead.ready && plan.n_rest == 0 && eig_rank == 0 && !out_mapped &&
@@ -1497,6 +1527,17 @@ int cuadmm_set_option(cuadmm_solver* s, const char* key, double value) {
   }
   else if (k == "accel_safeguard") s->aa.safeguard = value;             // a candidate is rejected when ||g|| grows by more than this factor (<= 0: always)
   else if (k == "accel_reg") s->aa.reg = value;                         // relative Tikhonov term of the least-squares solve
+  else if (k == "infeas_check") {                                       // period of the infeasibility check (0: off), before init
+    if (!(value == 0 || (value >= 2 && value <= 1e6 && value == std::floor(value)))) {
+      s->option_log.pop_back(); set_error("set_option: infeas_check must be 0 (off) or an integer period from 2 to 1000000"); return CUADMM_ERR_INVALID;
+    }
+    if (s->initialised) { s->option_log.pop_back(); set_error("set_option: infeas_check is set before init"); return CUADMM_ERR_INVALID; }
+    s->inf.period = (int)value;
+  }
+  else if (k == "infeas_tol") {
+    if (!(value >= 0)) { s->option_log.pop_back(); set_error("set_option: infeas_tol must not be negative"); return CUADMM_ERR_INVALID; }
+    s->inf.tol = value;
+  }
   else if (k == "update_A_inject_fail") s->upa.inject_fail = (int)value;   // test hook
   else if (k == "duo_inject_fail") { s->duo_inject = (long long)value; if (s->group) duo_group_inject(s->group, s->duo_inject); }   // test hook
   else { s->option_log.pop_back(); set_error("set_option: unknown key '%s'", key); return CUADMM_ERR_INVALID; }
@@ -1555,6 +1596,12 @@ int cuadmm_init(cuadmm_solver* s, int eig_stream_num_per_gpu, int cpu_eig_thread
   if (s->aa.mem > 0 && (s->world > 1 || s->eig_rank > 0 || s->group || s->in_group_call)) {
     set_error("init: option accel works on one rank with the full projection (world = %d, eig_rank = %d%s): its Gram matrix is not all-reduced",
               s->world, s->eig_rank, (s->group || s->in_group_call) ? ", in-process group" : "");
+    return CUADMM_ERR_INVALID;
+  }
+  if (s->inf.period > 0 && (s->world > 1 || s->eig_rank > 0 || s->group || s->in_group_call || s->aa.mem > 0)) {
+    set_error("init: option infeas_check works on one rank with the full projection and the plain iteration (world = %d, eig_rank = %d, accel = %d%s): "
+              "its sums are not all-reduced, and differences of accelerated iterates are not the sequence its certificates come from",
+              s->world, s->eig_rank, s->aa.mem, (s->group || s->in_group_call) ? ", in-process group" : "");
     return CUADMM_ERR_INVALID;
   }
   long long Lchk = 0;
@@ -1722,6 +1769,8 @@ int cuadmm_solve(cuadmm_solver* s, int max_iter, double stop_tol, int sig_update
 
   if ((rc = s->batch_agree())) return rc;
   if (s->accel_on() && (rc = s->accel_begin_solve())) return rc;
+  s->inf.status = 0;
+  if (s->infeas_on() && (rc = s->infeas_begin_solve())) return rc;
   const bool lpt_enabled = s->sw.lpt != 0;
   long long& lpt_ev = s->lpt_next;             // counts iterations over all solve calls of this solver
   if (!lpt_enabled) lpt_ev = 0;
@@ -1729,6 +1778,15 @@ int cuadmm_solve(cuadmm_solver* s, int max_iter, double stop_tol, int sig_update
     // ---- Step 0 (solver.cu:419-467)
     if (std::max(s->maxfeas, s->relgap) < stop_tol) { breakyes = true; final_msg = "Solver ended: converged."; }
     if (iter > max_iter) { breakyes = true; final_msg = "Solver ended: maximum iteration reached"; }
+    if (s->inf.status >= 3) {             // a certificate behind the previous iteration (infeas_step)
+      breakyes = true;
+      char msg[128];
+      snprintf(msg, sizeof msg, "Solver ended: %s infeasible (certificate at iteration %d)", s->inf.status == 3 ? "primal" : "dual", s->inf.verdict_iter);
+      final_msg = msg;
+    } else if (breakyes) {
+      s->inf.status = iter > max_iter ? 2 : 1;
+      s->inf.verdict_iter = iter - 1;
+    }
     const double seconds = wall_s() - s->t_init0;
     if (verbose && (breakyes || (iter <= 200 && iter % 50 == 1) || (iter > 200 && iter % 100 == 1))) {
       printf(" %4d | %3.2e %3.2e | %- 5.4e %- 5.4e %3.2e | %5.1f | %2.1e |", iter - 1, s->errRp, s->errRd, s->pobj,
@@ -1757,7 +1815,7 @@ int cuadmm_solve(cuadmm_solver* s, int max_iter, double stop_tol, int sig_update
     else if (s->bt.len == 0 && (rc = s->host_solve(s->fuse && !breakyes))) return rc;
 
     if (breakyes) {   // solver.cu:567-576
-      if (iter > switch_admm && s->have_best) {
+      if (iter > switch_admm && s->have_best && s->inf.status < 3) {   // (a certificate describes the last iterate: no restore)
         CUADMM_HIP_TRY(hipMemcpyAsync(s->X.p, s->X_best.p, sizeof(double) * (size_t)L, hipMemcpyDeviceToDevice, s->st));
         CUADMM_HIP_TRY(hipMemcpyAsync(s->S.p, s->S_best.p, sizeof(double) * (size_t)L, hipMemcpyDeviceToDevice, s->st));
         CUADMM_HIP_TRY(hipStreamSynchronize(s->st));
@@ -1835,7 +1893,7 @@ int cuadmm_solve(cuadmm_solver* s, int max_iter, double stop_tol, int sig_update
     // device and belongs to the engine (not to a closed block's kernel), sigma does not change in this iteration's step 5, nothing of a
     // batch is pending, and the per-class event timers (profile = 1) are off -- they are collected at the wait, before that solve ends
     const bool sig_may_change = (iter <= sig_update_threshold && iter % sig_update_stage_1 == 1) || (iter > sig_update_threshold && iter % sig_update_stage_2 == 1);
-    const bool solve_next_ok = s->sw.solve_next != 0 && !s->accel_on() && s->dev_solve && !from_batch && !sig_may_change && !(s->fuse && s->closed.active) && s->profile != 1;
+    const bool solve_next_ok = s->sw.solve_next != 0 && !s->accel_on() && !s->infeas_on() && s->dev_solve && !from_batch && !sig_may_change && !(s->fuse && s->closed.active) && s->profile != 1;
     if (from_batch) {
       // consumed below (Step 5) from bt.h
     } else if ((rc = s->upload_y())) return rc;
@@ -1977,6 +2035,8 @@ int cuadmm_solve(cuadmm_solver* s, int max_iter, double stop_tol, int sig_update
       const bool next_sig_may_change = (nx <= sig_update_threshold && nx % sig_update_stage_1 == 1) || (nx > sig_update_threshold && nx % sig_update_stage_2 == 1);
       if ((rc = s->accel_step(iter, max_iter, stop_tol, switch_admm, tau, s->sig != sig_of_iter, next_sig_may_change))) return rc;
     }
+    // ---- infeasibility check: on the state at the end of the iteration, after the sigma update
+    if (s->infeas_on() && iter % s->inf.period == 0 && (rc = s->infeas_step(iter, stop_tol))) return rc;
   }
 
   // unscale (solver.cu:814-816) -- deferred until somebody reads or replaces X, y, S (materialise): a following
@@ -2185,6 +2245,114 @@ int cuadmm_solver::accel_step(int iter, int max_iter, double stop_tol, int switc
   return CUADMM_OK;
 }
 
+// ------------------------------------------------------------------------------------------
+// Infeasibility detection (option "infeas_check"): DESIGN.md, "Infeasibility certificates"
+// ------------------------------------------------------------------------------------------
+// start of every solve: buffers on first use, no snapshot, b on the device where the engine keeps none there
+int cuadmm_solver::infeas_begin_solve() {
+  int rc;
+  if (!inf.xprev.p) {
+    const size_t mm = (size_t)std::max(m, 1);
+    if ((rc = inf.xprev.alloc(L)) || (rc = inf.dbuf.alloc(L)) || (rc = inf.pbuf.alloc(L)) || (rc = inf.yprev.alloc(mm)) || (rc = inf.dy.alloc(mm)) ||
+        (rc = inf.adx.alloc(mm)) || (rc = inf.partials.alloc(kInfeasPartials)) || (rc = inf.stats_d.alloc(INF_NSTATS)) || (rc = inf.h_stats.alloc(INF_NSTATS)))
+      return rc;
+    if (!b_d.p && (rc = inf.bcopy.alloc(mm))) return rc;
+    for (auto& e : inf.ev) CUADMM_HIP_TRY(hipEventCreate(&e));
+    long long off = 0;
+    for (int n : blk_local) { if (n < 0) inf.free_rng.emplace_back(off, blk_svec_len(n)); off += blk_svec_len(n); }
+  }
+  if (inf.bcopy.p && m > 0 && (rc = staged_h2d(inf.bcopy.p, b_p.data(), sizeof(double) * (size_t)m, st))) return rc;
+  infeas_reset();
+  inf.ms = 0;
+  return CUADMM_OK;
+}
+
+// End of iteration `iter`, a multiple of the period.  y_d holds the y this iteration's A^T y kernel read (device y-solve: its result,
+// host y-solve: the uploaded copy), in the factor's order; X the new X.  The first call of a solve only copies the snapshot.
+int cuadmm_solver::infeas_step(int iter, double stop_tol) {
+  int rc;
+  if (std::max(maxfeas, relgap) < stop_tol) return CUADMM_OK;      // the loop is about to end as converged
+  if (!inf.have_snap) {          // the first multiple of the period: the snapshot alone
+    if (m > 0) CUADMM_HIP_TRY(hipMemcpyAsync(inf.yprev.p, y_d.p, sizeof(double) * (size_t)m, hipMemcpyDeviceToDevice, st));
+    CUADMM_HIP_TRY(hipMemcpyAsync(inf.xprev.p, X.p, sizeof(double) * (size_t)L, hipMemcpyDeviceToDevice, st));
+    inf.have_snap = true;
+    return CUADMM_OK;
+  }
+  const double* bw = b_d.p ? b_d.p : inf.bcopy.p;
+  CUADMM_HIP_TRY(hipEventRecord(inf.ev[0], st));
+  // d = cur - prev and prev <- cur in one pass each; the X difference is written negated: it is the input of P+(-dX), and the norm
+  // of A dX does not see the sign
+  if ((rc = launch_infeas_roll(m, y_d.p, inf.yprev.p, bw, inf.dy.p, 0, 0, nullptr, nullptr, inf.partials.p, inf.stats_d.p + INF_DY2, st))) return rc;
+  if ((rc = launch_infeas_roll(L, X.p, inf.xprev.p, C.p, inf.dbuf.p, 1, 0, nullptr, nullptr, inf.partials.p, inf.stats_d.p + INF_DX2, st))) return rc;
+  inf.checks++;
+  double* hs = inf.h_stats.p;
+  CUADMM_HIP_TRY(hipMemcpyAsync(hs, inf.stats_d.p, sizeof(double) * 4, hipMemcpyDeviceToHost, st));
+  CUADMM_HIP_TRY(hipStreamSynchronize(st));
+  // a test's SpMV and projection run only when its scalar has the sign a certificate needs
+  const bool try_dual = hs[INF_CDX] < 0 && hs[INF_DX2] > 0, try_primal = hs[INF_BDY] > 0 && hs[INF_DY2] > 0;
+  int verdict = 0;
+  double o3[3] = {0, 0, 0}, stats[INF_NSTATS];
+  const double nan = std::nan("");
+  if ((try_dual || try_primal) && !inf.plan2) {
+    size_t free0 = 0, free1 = 0, total = 0;
+    if (hipMemGetInfo(&free0, &total) != hipSuccess) { free0 = 0; (void)hipGetLastError(); }
+    inf.plan2 = new PsdPlan();
+    inf.plan2->opt = plan.opt;
+    inf.plan2->eig_rank = 0;
+    if ((rc = inf.plan2->build(blk_local.data(), (int)blk_local.size()))) { delete inf.plan2; inf.plan2 = nullptr; return rc; }
+    // what the build took from the device's free memory: an estimate (other users of the device and the allocator's caching move it)
+    if (hipMemGetInfo(&free1, &total) != hipSuccess) { free1 = free0; (void)hipGetLastError(); }
+    inf.plan2_bytes = free0 > free1 ? (double)(free0 - free1) : 0.0;
+  }
+  // The dual test first: its input -dX sits in dbuf, which the primal test overwrites.
+  if (try_dual) {      // A (-dX) over the whole svec; P+(-dX) with the unconstrained blocks' slices (copied through by the plan) left out
+    if ((rc = launch_spmv_rows(m, A_avg_nnz, A_rp.p, A_ci.p, A_v.p, inf.dbuf.p, S.p, C.p, inf.adx.p, nullptr, st, &A_long))) return rc;
+    if ((rc = launch_infeas_norm2(m, inf.adx.p, inf.partials.p, inf.stats_d.p + INF_ADX2, st))) return rc;
+    if ((rc = inf.plan2->project(inf.dbuf.p, inf.pbuf.p, st))) return rc;
+    for (auto& r : inf.free_rng) CUADMM_HIP_TRY(hipMemsetAsync(inf.pbuf.p + r.first, 0, sizeof(double) * (size_t)r.second, st));
+    if ((rc = launch_infeas_norm2(L, inf.pbuf.p, inf.partials.p, inf.stats_d.p + INF_PNEGDX2, st))) return rc;
+    CUADMM_HIP_TRY(hipMemcpyAsync(hs + INF_ADX2, inf.stats_d.p + INF_ADX2, sizeof(double) * 2, hipMemcpyDeviceToHost, st));
+    CUADMM_HIP_TRY(hipStreamSynchronize(st));
+    for (int q = 0; q < INF_NSTATS; ++q) stats[q] = hs[q];
+    stats[INF_DY2] = stats[INF_BDY] = stats[INF_PATY2] = nan; stats[INF_ATY2] = 0;
+    if ((rc = infeas_decide(stats, inf.tol, &verdict, o3))) return rc;
+  }
+  if (verdict == 0 && try_primal) {   // A^T dy (the kernel forms A^T y - C: pbuf, zeroed, stands in for C), its PSD part, its norm
+    CUADMM_HIP_TRY(hipMemsetAsync(inf.pbuf.p, 0, sizeof(double) * (size_t)L, st));
+    if ((rc = launch_aty_xb(false, L, At_rp.p, At_ci.p, At_v.p, inf.dy.p, inf.pbuf.p, X.p, 1.0, inf.dbuf.p, nullptr, st, &At_long))) return rc;
+    if ((rc = launch_infeas_norm2(L, inf.dbuf.p, inf.partials.p, inf.stats_d.p + INF_ATY2, st))) return rc;      // ||A^T dy||^2: the radius' rounding term
+    if ((rc = inf.plan2->project(inf.dbuf.p, inf.pbuf.p, st))) return rc;
+    if ((rc = launch_infeas_norm2(L, inf.pbuf.p, inf.partials.p, inf.stats_d.p + INF_PATY2, st))) return rc;
+    CUADMM_HIP_TRY(hipMemcpyAsync(hs + INF_PATY2, inf.stats_d.p + INF_PATY2, sizeof(double) * 4, hipMemcpyDeviceToHost, st));
+    CUADMM_HIP_TRY(hipStreamSynchronize(st));
+    for (int q = 0; q < INF_NSTATS; ++q) stats[q] = hs[q];
+    stats[INF_DX2] = stats[INF_CDX] = stats[INF_ADX2] = stats[INF_PNEGDX2] = nan;
+    if ((rc = infeas_decide(stats, inf.tol, &verdict, o3))) return rc;
+  }
+  CUADMM_HIP_TRY(hipEventRecord(inf.ev[1], st));
+  CUADMM_HIP_TRY(hipEventSynchronize(inf.ev[1]));
+  { float t = 0; if (hipEventElapsedTime(&t, inf.ev[0], inf.ev[1]) == hipSuccess) inf.ms += t; else (void)hipGetLastError(); }
+  if ((try_dual || try_primal) && inf.plan2->fail_count(st) > 0) {
+    set_error("solve: a block projection of the infeasibility check hit the QL sweep cap");
+    return CUADMM_ERR_EIG;
+  }
+  if (verdict == 0) return CUADMM_OK;
+  // the ray, as the check left it on the device (scaled space, the factor's order / the svec): dy, or -dX in dbuf
+  const size_t n = verdict == 3 ? (size_t)m : (size_t)L;
+  inf.cert.assign(n, 0.0);
+  if ((rc = staged_d2h(inf.cert.data(), verdict == 3 ? inf.dy.p : inf.dbuf.p, sizeof(double) * n, st))) return rc;
+  if (verdict == 4) for (double& v : inf.cert) v = -v;
+  inf.status = verdict; inf.verdict_iter = iter;
+  inf.scalar = o3[0]; inf.eta = o3[1];
+  // The reported radius is scalar / (eta + eta_fl): eta is the norm of a projection the kernels evaluate to 1e-12 ||M||_F per entry
+  // (M = A^T dy or -dX: the projection's contract), so the true violation may exceed eta by eta_fl = 1e-12 sqrt(L) ||M||_F / ||d||, and
+  // only the smaller radius is certified.  In the caller's units: X = bscale X_scaled (primal test); S = Cscale S_scaled,
+  // y = Cscale y_scaled / normA (dual test).
+  const double eta_fl = kInfeasProjErr * std::sqrt((double)L) * (verdict == 3 ? std::sqrt(stats[INF_ATY2] / stats[INF_DY2]) : 1.0);
+  inf.radius = o3[0] / (o3[1] + eta_fl) * (verdict == 3 ? bscale : Cscale);
+  return CUADMM_OK;
+}
+
 // SDPDuoSolver front (duo_solver.h:236-276): exactly two block sizes, then the generic engine.
 int cuadmm_duo_init(cuadmm_solver* s, int if_gpu_eig_mom, int device_num_requested, int eig_stream_num_per_gpu,
                     int cpu_eig_thread_num, int vec_len, int con_num, const int* At_cp, const int* At_ri, const double* At_vx,
@@ -2205,6 +2373,10 @@ int cuadmm_duo_init(cuadmm_solver* s, int if_gpu_eig_mom, int device_num_request
   // N engines on N host threads with an in-process all-reduce (duo_group.hip).
   if (device_num_requested > 1 && s->aa.mem > 0) {
     set_error("duo_init: option accel works on one engine (device_num_requested = %d): its Gram matrix is not all-reduced", device_num_requested);
+    return CUADMM_ERR_INVALID;
+  }
+  if (device_num_requested > 1 && s->inf.period > 0) {
+    set_error("duo_init: option infeas_check works on one engine (device_num_requested = %d): its sums are not all-reduced", device_num_requested);
     return CUADMM_ERR_INVALID;
   }
   if (device_num_requested > 1 && s->world == 1 && !s->in_group_call) {
@@ -2329,6 +2501,7 @@ int cuadmm_set_XyS(cuadmm_solver* s, const double* X, const double* y, const dou
   if (S && s->L > 0) { int rc2 = staged_h2d(s->S.p, S + s->sv_off + s->sv_begin, sizeof(double) * (size_t)s->L, s->st); if (rc2) return rc2; }
   if (y) for (int i = 0; i < s->m; ++i) s->y_p[i] = s->local_mode ? y[s->cons_local[s->perm[i]]] : y[s->perm[i]];
   if (sig > 0) s->sig = sig;
+  s->infeas_reset();                            // snapshots and status describe another iterate
   return CUADMM_OK;
 }
 
@@ -2477,6 +2650,7 @@ int cuadmm_update_bC(cuadmm_solver* s, const int* b_idx, const double* b_vals, i
   s->y_early = false; s->stats_fused = false;
   s->bt.len = s->bt.pos = 0; s->bt.have_ck = false;
   s->closed.iters_done = 0; s->closed.out_dirty = true;
+  s->infeas_reset();
   s->plan.n_project = 0;
   if (s->hint_d.p) CUADMM_HIP_TRY(hipMemsetAsync(s->hint_d.p, 0, sizeof(int) * s->hint_d.n, s->st));     // the sign schedule's warm start
   if (s->closed.cl_out.p) CUADMM_HIP_TRY(hipMemsetAsync(s->closed.cl_out.p, 0, sizeof(double) * s->closed.cl_out.n, s->st));
@@ -2723,6 +2897,7 @@ int cuadmm_update_A(cuadmm_solver* s, const double* At_vals, int At_nnz, int kee
   s->y_early = false; s->stats_fused = false;
   s->bt.len = s->bt.pos = 0; s->bt.have_ck = false;
   s->closed.iters_done = 0; s->closed.out_dirty = true;
+  s->infeas_reset();
   s->plan.n_project = 0;
   if (s->hint_d.p) CUADMM_HIP_TRY(hipMemsetAsync(s->hint_d.p, 0, sizeof(int) * s->hint_d.n, s->st));
   if (s->closed.cl_out.p) CUADMM_HIP_TRY(hipMemsetAsync(s->closed.cl_out.p, 0, sizeof(double) * s->closed.cl_out.n, s->st));
@@ -2826,6 +3001,41 @@ int cuadmm_get_accel_info(const cuadmm_solver* s, double o[8]) {
 }
 int cuadmm_accel_solve_ls(const double* gram, const double* rhs, int cols, double reg, double* gamma_out) {
   return accel_solve_ls(gram, rhs, cols, reg, gamma_out);
+}
+int cuadmm_get_status(const cuadmm_solver* s, double o[8]) {
+  if (!s || !o) { set_error("get_status: null"); return CUADMM_ERR_INVALID; }
+  o[0] = (double)s->inf.status; o[1] = (double)s->inf.verdict_iter; o[2] = (double)s->inf.checks; o[3] = s->inf.scalar; o[4] = s->inf.eta;
+  o[5] = s->inf.radius; o[6] = s->inf.ms; o[7] = s->inf.bytes();
+  return CUADMM_OK;
+}
+int cuadmm_get_certificate(cuadmm_solver* s, double* y_out, double* X_out) {
+  if (!s || !s->initialised) { set_error("get_certificate: solver not initialised"); return CUADMM_ERR_INVALID; }
+  if (s->inf.status != 3 && s->inf.status != 4) { set_error("get_certificate: the last solve found no certificate of infeasibility (status %d)", s->inf.status); return CUADMM_ERR_INVALID; }
+  const std::vector<double>& c = s->inf.cert;
+  if (s->inf.status == 3) {
+    if (!y_out) { set_error("get_certificate: status 3 returns a y ray: y_out is null"); return CUADMM_ERR_INVALID; }
+    // back to the caller's units and order as materialise / cuadmm_get_y map y, then b' y = 1 on the caller's b
+    for (int i = 0; i < s->m; ++i) y_out[s->perm[i]] = c[i] / s->normA_p[i];
+    long double t = 0;
+    for (size_t k = 0; k < s->upa.b_idx.size(); ++k) t += (long double)s->upa.b_val[k] * y_out[s->upa.b_idx[k]];
+    for (int i = 0; i < s->m; ++i) y_out[i] = (double)(y_out[i] / t);
+    return CUADMM_OK;
+  }
+  if (!X_out) { set_error("get_certificate: status 4 returns an X ray: X_out is null"); return CUADMM_ERR_INVALID; }
+  int rc = check_device(s->device);
+  if (rc) return rc;
+  std::vector<double> Ch((size_t)s->L);
+  if (s->L > 0 && (rc = staged_d2h(Ch.data(), s->C.p, sizeof(double) * (size_t)s->L, s->st))) return rc;
+  long double t = 0;
+  for (long long i = 0; i < s->L; ++i) t += (long double)(Ch[i] * s->Cscale) * c[i];      // <C, dX> in the caller's units of C
+  for (long long i = 0; i < s->L; ++i) X_out[i] = (double)(c[i] / -t);
+  return CUADMM_OK;
+}
+int cuadmm_infeas_decide(const double stats[8], double tol, int* verdict, double* radius) {
+  double o3[3];
+  int rc = infeas_decide(stats, tol, verdict, o3);
+  if (!rc && radius) *radius = o3[2];
+  return rc;
 }
 int cuadmm_get_tail_info(const cuadmm_solver* s, double o[6]) {
   if (!s || !o) { set_error("get_tail_info: null"); return CUADMM_ERR_INVALID; }
@@ -3120,6 +3330,39 @@ int cuadmm_op_accel_combine(int64_t L, int cols, const double* ring_dF, const do
   if ((rc = launch_aa_combine(L, L, 2 * L, cols, ring.d.p, gamma, sig, x.d.p, sv.d.p, u.d.p, nullptr))) return rc;
   CUADMM_HIP_TRY(hipDeviceSynchronize());
   if ((rc = x.down(X_inout, L)) || (rc = sv.down(S_inout, L))) return rc;
+  return CUADMM_OK;
+}
+
+// the roll kernel of the infeasibility check on host arrays (csrc/infeas.hip).  offset = 1 places every vector one double behind a
+// 16-byte boundary, so that the one-double path runs
+int cuadmm_op_infeas_roll(int64_t n, const double* cur, double* prev_inout, const double* w, int negate, int nz, const int64_t* zoff, const int64_t* zlen,
+                          int offset, double* d_out, double* sums2_out) {
+  if (n < 1 || !cur || !prev_inout || !w || !d_out || !sums2_out || nz < 0 || (nz > 0 && (!zoff || !zlen)) || offset < 0 || offset > 1) {
+    set_error("op_infeas_roll: invalid argument");
+    return CUADMM_ERR_INVALID;
+  }
+  for (int r = 0; r < nz; ++r)
+    if (zoff[r] < 0 || zlen[r] < 0 || zoff[r] + zlen[r] > n) { set_error("op_infeas_roll: range %d outside the vector", r); return CUADMM_ERR_INVALID; }
+  int rc = check_device(0);
+  if (rc) return rc;
+  const size_t N = (size_t)n + 2;
+  DevBuf<double> c, q, wv, out, part, sums;
+  DevBuf<long long> zo, zl;
+  if ((rc = c.alloc(N)) || (rc = q.alloc(N)) || (rc = wv.alloc(N)) || (rc = out.alloc(N)) || (rc = part.alloc(kInfeasPartials)) || (rc = sums.alloc(2)) ||
+      (rc = zo.alloc(std::max(nz, 1))) || (rc = zl.alloc(std::max(nz, 1))))
+    return rc;
+  if ((rc = staged_h2d(c.p + offset, cur, sizeof(double) * (size_t)n)) || (rc = staged_h2d(q.p + offset, prev_inout, sizeof(double) * (size_t)n)) ||
+      (rc = staged_h2d(wv.p + offset, w, sizeof(double) * (size_t)n)))
+    return rc;
+  if (nz > 0) {
+    std::vector<long long> a(zoff, zoff + nz), b(zlen, zlen + nz);
+    if ((rc = staged_h2d(zo.p, a.data(), sizeof(long long) * (size_t)nz)) || (rc = staged_h2d(zl.p, b.data(), sizeof(long long) * (size_t)nz))) return rc;
+  }
+  if ((rc = launch_infeas_roll(n, c.p + offset, q.p + offset, wv.p + offset, out.p + offset, negate, nz, zo.p, zl.p, part.p, sums.p, nullptr))) return rc;
+  CUADMM_HIP_TRY(hipDeviceSynchronize());
+  if ((rc = staged_d2h(prev_inout, q.p + offset, sizeof(double) * (size_t)n)) || (rc = staged_d2h(d_out, out.p + offset, sizeof(double) * (size_t)n)) ||
+      (rc = staged_d2h(sums2_out, sums.p, sizeof(double) * 2)))
+    return rc;
   return CUADMM_OK;
 }
 

@@ -126,6 +126,26 @@ class SDPSolver:
         return {"memory": int(o[0]), "taken": int(o[1]), "accepted": int(o[2]), "rejected": int(o[3]), "restarts": int(o[4]),
                 "columns": int(o[5]), "ms": float(o[6]), "ring_bytes": float(o[7])}
 
+    STATUS_NAMES = ("none", "converged", "iteration_limit", "primal_infeasible", "dual_infeasible")
+
+    def status(self):
+        """How the last solve ended (cuadmm_get_status); option "infeas_check" adds the two infeasible statuses."""
+        o = np.zeros(8)
+        check(self._lib.cuadmm_get_status(self._h, _p(o)))
+        return {"status": int(o[0]), "name": self.STATUS_NAMES[int(o[0])], "iteration": int(o[1]), "checks": int(o[2]), "scalar": float(o[3]),
+                "eta": float(o[4]), "radius": float(o[5]), "ms": float(o[6]), "bytes": float(o[7])}
+
+    def certificate(self):
+        """("primal", y) behind status primal_infeasible (b'y = 1), ("dual", X) behind dual_infeasible (<C, X> = -1)."""
+        st = self.status()["status"]
+        if st == 4:
+            X = np.zeros(self.vec_len)
+            check(self._lib.cuadmm_get_certificate(self._h, None, _p(X)))
+            return "dual", X
+        y = np.zeros(self.con_num)
+        check(self._lib.cuadmm_get_certificate(self._h, _p(y), None))      # any status but 3: the library's error
+        return "primal", y
+
     def set_allreduce(self, fn):
         """fn(dev_ptr:int, count:int, hip_stream:int) -> None : in-place sum over ranks on that stream."""
         def tramp(_user, buf, count, stream):

@@ -81,6 +81,13 @@ void cuadmm_destroy(cuadmm_solver* s);
  *   "accel_safeguard"   default 2.0: the candidate behind iteration k is rejected (the iterate goes back to the plain f_k, the memory is
  *                   cleared, the iteration spent on it stays counted) when ||g_{k+1}|| > accel_safeguard ||g_k||; <= 0 rejects every candidate
  *   "accel_reg"     default 1e-10: the least-squares system is (G + accel_reg tr(G) / cols I) gamma = rhs
+ *   "infeas_check"  period p of the infeasibility check ("Infeasibility certificates"): 0 (default) = off, an integer from 2 to
+ *                   1 000 000 = every p iterations the differences y_k - y_{k-p}, X_k - X_{k-p} are tested for a certificate of primal or
+ *                   dual infeasibility; a certificate ends the solve (cuadmm_get_status, cuadmm_get_certificate).  Anything else is
+ *                   CUADMM_ERR_INVALID.  Costs 3 L + 3 m doubles of device memory and, from the first check that needs a projection,
+ *                   a projection plan of its own.  Runs one iteration per launch (no batches, no early y-solve); refused at init together
+ *                   with world > 1, an in-process group, eig_rank > 0 or accel > 0.  Weak infeasibility is not detected.  Set before cuadmm_init.
+ *   "infeas_tol"    default 1e-6: a ray is a certificate when its violation eta is at most infeas_tol times its scalar (b'dy or -C'dx, per unit norm)
  *   (every other switch: INTEGRATION.md section 6)
  */
 int cuadmm_set_option(cuadmm_solver* s, const char* key, double value);
@@ -245,6 +252,25 @@ int cuadmm_get_accel_info(const cuadmm_solver* s, double out8[8]);
 /* The least-squares solve of the acceleration: (gram + reg tr(gram) / cols I) gamma = rhs, gram cols x cols row-major and symmetric,
  * 1 <= cols <= 16, by Cholesky in long double.  Host only (no device needed).  CUADMM_ERR_FACTOR when a pivot is not positive. */
 int cuadmm_accel_solve_ls(const double* gram, const double* rhs, int cols, double reg, double* gamma_out);
+/* How the last cuadmm_solve ended.  [0] status: 0 = no solve yet (or the problem / iterate was replaced since: cuadmm_update_bC,
+ * cuadmm_update_A, cuadmm_set_XyS), 1 = converged, 2 = iteration limit, 3 = primal infeasible, 4 = dual infeasible (primal unbounded);
+ * [1] iteration of the verdict; then, of option "infeas_check" (zeros while it is off): [2] checks run in that solve, [3] beta = b'dy / ||dy||
+ * (status 3) or gamma = -C'dX / ||dX|| (status 4) in the engine's scaled space, [4] eta = ||P+(A'dy)|| / ||dy|| (status 3) or
+ * max(||A dX||, ||P+(-dX)||) / ||dX|| (status 4), [5] the certified radius in the caller's units: status 3: no X >= 0 with A X = b has
+ * ||X||_F < [5]; status 4: no (y, S >= 0) with A'y + S = C has ||D y|| + ||S||_F < [5], D = diag(max(1, ||row_i of A||)) (infinite when
+ * eta = 0), [6] milliseconds of device time spent in the checks of that solve (HIP events), [7] bytes of device memory the check holds:
+ * its vectors exactly, plus an estimate of the second projection plan (the drop of the device's free memory around its build).
+ * Statuses 1 and 2 are reported with the option off too. */
+int cuadmm_get_status(const cuadmm_solver* s, double out8[8]);
+/* The ray behind status 3 or 4, in the caller's units and order.  Status 3: y_out (con_num doubles) with b'y = 1 and A'y <= 0 up to
+ * [4] / [3] of cuadmm_get_status; X_out may be null.  Status 4: X_out (vec_len doubles) with <C, X> = -1, A X = 0 and X >= 0 on the PSD
+ * blocks up to the same ratio (its slices of unconstrained blocks are free); y_out may be null.  Any other status: CUADMM_ERR_INVALID. */
+int cuadmm_get_certificate(cuadmm_solver* s, double* y_out, double* X_out);
+/* The rule of the infeasibility check on the statistics of one check: stats = [||dy||^2, b'dy, ||dX||^2, C'dX, ||P+(A'dy)||^2, ||A dX||^2,
+ * ||P+(-dX)||^2, unused].  verdict: 3 when b'dy > 0 and ||P+(A'dy)|| <= tol b'dy, else 4 when C'dX < 0 and max(||A dX||, ||P+(-dX)||) <=
+ * -tol C'dX, else 0 (a NaN in a test's numbers: no verdict from it); radius (may be null): scalar / eta in the scaled space, infinite when
+ * eta = 0.  Host only (no device needed). */
+int cuadmm_infeas_decide(const double stats[8], double tol, int* verdict, double* radius);
 /* The in-process group a handle leads after cuadmm_duo_init(device_num_requested = N) from one process (reference
  * src/duo_solver.cu:487-577): [0] engines in the group (1: no group), [1] exchange of its all-reduce -- 1 = device side (each
  * rank's kernel adds the N staging buffers out of its peers' memory: one shared device, or peer access over xGMI as
@@ -471,6 +497,11 @@ int cuadmm_op_accel_push(int64_t L, const double* u_prev, const double* X, const
                          double* g_out, double* dF_out, double* dG_out, double* gnorm2_out);
 int cuadmm_op_accel_gram(int64_t L2, int cols, int newest, const double* ring_dG, const double* g, double* out /* 2 cols */);
 int cuadmm_op_accel_combine(int64_t L, int cols, const double* ring_dF, const double* gamma, double sig, double* X_inout, double* S_inout);
+/* The roll kernel of the infeasibility check on host arrays (csrc/infeas.hip): d = cur - prev, prev_inout <- cur, d_out = d (negate: -d;
+ * 0 inside the nz ranges [zoff[r], zoff[r] + zlen[r])), sums2_out = [||d||^2, <w, d>].  offset = 1 places the device vectors one double
+ * behind a 16-byte boundary (the kernel's one-double path), 0 on one (two doubles per access). */
+int cuadmm_op_infeas_roll(int64_t n, const double* cur, double* prev_inout, const double* w, int negate, int nz, const int64_t* zoff, const int64_t* zlen,
+                          int offset, double* d_out, double* sums2_out);
 int cuadmm_op_spmv_rows(int rows, int ncols, const int* row_ptrs, const int* col_ids, const double* vals, const double* X, const double* S, const double* C,
                         int want_x, int want_s, const int* rowmap, int out_len, double* outX, double* outS, int* info4);
 int cuadmm_op_rp_stats(int m, const double* ax, const double* b, const double* normA, const double* y, double bscale, const double* sums2, double* out4);

@@ -102,6 +102,24 @@ class SDPSolver {
     return AccelInfo{(int)o[0], (long long)o[1], (long long)o[2], (long long)o[3], (long long)o[4], (int)o[5], o[6], o[7]};
   }
 
+  // how the last solve ended (cuadmm_get_status); option "infeas_check" adds the two infeasible statuses; not in the reference
+  enum Status { kNoSolve = 0, kConverged = 1, kIterationLimit = 2, kPrimalInfeasible = 3, kDualInfeasible = 4 };
+  struct StatusInfo { Status status; int iteration; long long checks; double scalar, eta, radius, ms, bytes; };
+  StatusInfo status() const {
+    double o[8] = {0};
+    check(cuadmm_get_status(h_, o));
+    return StatusInfo{(Status)(int)o[0], (int)o[1], (long long)o[2], o[3], o[4], o[5], o[6], o[7]};
+  }
+  // the ray behind kPrimalInfeasible (y, con_num entries, b'y = 1) or kDualInfeasible (X, vec_len entries, <C, X> = -1); throws otherwise
+  std::vector<double> certificate() {
+    const StatusInfo st = status();
+    int vl = 0, cn = 0, mn = 0;
+    check(cuadmm_get_dims(h_, &vl, &cn, &mn));
+    std::vector<double> ray((size_t)(st.status == kDualInfeasible ? vl : cn));
+    check(cuadmm_get_certificate(h_, st.status == kDualInfeasible ? nullptr : ray.data(), st.status == kDualInfeasible ? ray.data() : nullptr));
+    return ray;
+  }
+
   // cuadmm_update_bC: new b and / or C on the factored solver (nnz < 0: unchanged); not in the reference
   void update_bC(const int* cpu_b_indices, const double* cpu_b_vals, int b_nnz, const int* cpu_C_indices, const double* cpu_C_vals,
                  int C_nnz, bool keep_iterate = true, double sig = 0.0) {
