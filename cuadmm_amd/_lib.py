@@ -154,6 +154,9 @@ PROTOTYPES = {
     "cuadmm_psd_plan_create": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "cuadmm_psd_plan_project": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "cuadmm_psd_plan_destroy": (None, [C.c_void_p]),
+    "cuadmm_psd_plan_set_hint": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
+    "cuadmm_psd_plan_reorder": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
+    "cuadmm_psd_plan_project_ordered": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, c_int_p]),
     "cuadmm_op_psd_project": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "cuadmm_op_permute": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "cuadmm_op_get_normA": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),

@@ -3268,7 +3268,14 @@ int cuadmm_op_psd_project_ex(const double* Xb, double* Xproj, const int* blk_hos
   return CUADMM_OK;
 }
 
-struct cuadmm_psd_plan { PsdPlan plan; };
+// own: the test hooks' non-blocking stream (cuadmm_psd_plan_project_ordered), made on first use
+struct cuadmm_psd_plan {
+  PsdPlan plan;
+  hipStream_t own = nullptr;
+  ~cuadmm_psd_plan() {
+    if (own) { hipError_t e = hipStreamSynchronize(own); (void)e; e = hipStreamDestroy(own); (void)e; }   // idle before the plan's side streams and events go
+  }
+};
 int cuadmm_psd_plan_create(const int* blk_host, int mat_num, int eig_rank, cuadmm_psd_plan** out) {
   if (!blk_host || mat_num < 0 || eig_rank < 0 || !out) { set_error("psd_plan_create: bad arguments"); return CUADMM_ERR_INVALID; }
   cuadmm_psd_plan* p = new cuadmm_psd_plan();
@@ -3286,6 +3293,44 @@ int cuadmm_psd_plan_project(cuadmm_psd_plan* p, const double* Xb, double* Xproj,
   return p->plan.project(Xb, Xproj, (hipStream_t)stream);
 }
 void cuadmm_psd_plan_destroy(cuadmm_psd_plan* p) { delete p; }
+
+// ---- the plan in the state the engine keeps it in (tests): schedule hints, re-sorted descriptors, a non-blocking caller's stream
+static int psd_plan_stream(cuadmm_psd_plan* p, int own_stream, hipStream_t* st) {
+  if (own_stream && !p->own) CUADMM_HIP_TRY(hipStreamCreateWithFlags(&p->own, hipStreamNonBlocking));
+  *st = own_stream ? p->own : nullptr;
+  return CUADMM_OK;
+}
+int cuadmm_psd_plan_set_hint(cuadmm_psd_plan* p, int* hint_dev, int hint_max_n) {
+  if (!p) { set_error("psd_plan_set_hint: bad arguments"); return CUADMM_ERR_INVALID; }
+  p->plan.d_hint = hint_dev;
+  p->plan.sign.d_hint = hint_dev;
+  p->plan.sign.hint_max_n = hint_max_n;
+  return CUADMM_OK;
+}
+int cuadmm_psd_plan_reorder(cuadmm_psd_plan* p, const int* steps_host, int async, int own_stream) {
+  if (!p || !steps_host) { set_error("psd_plan_reorder: bad arguments"); return CUADMM_ERR_INVALID; }
+  hipStream_t st;
+  int rc = psd_plan_stream(p, own_stream, &st);
+  if (rc) return rc;
+  return async ? p->plan.reorder_by_steps_async(steps_host, st) : p->plan.reorder_by_steps(steps_host, st);
+}
+int cuadmm_psd_plan_project_ordered(cuadmm_psd_plan* p, const double* Xb, double* Xproj, double* snap_dev, int* steps_dev, int own_stream, int* fails_out) {
+  if (!p || !Xb || !Xproj) { set_error("psd_plan_project_ordered: bad arguments"); return CUADMM_ERR_INVALID; }
+  hipStream_t st;
+  int rc = psd_plan_stream(p, own_stream, &st);
+  if (rc) return rc;
+  p->plan.d_steps = steps_dev;
+  p->plan.sign.d_steps = steps_dev;
+  if ((rc = p->plan.project(Xb, Xproj, st))) return rc;
+  // the snapshot is a consumer ordered by `st` alone: what a class that was not joined has not written yet is missing from it (a
+  // device-wide synchronisation would wait for it); fail_count waits for `st` only
+  if (snap_dev && p->plan.vec_len > 0)
+    CUADMM_HIP_TRY(hipMemcpyAsync(snap_dev, Xproj, sizeof(double) * (size_t)p->plan.vec_len, hipMemcpyDeviceToDevice, st));
+  const int fails = p->plan.fail_count(st);
+  if (fails < 0) return CUADMM_ERR_INVALID;
+  if (fails_out) *fails_out = fails;
+  return CUADMM_OK;
+}
 
 // ---- the acceleration kernels on host arrays (tests).  State vectors have 2 L entries, the S half right behind the X half: for an
 // odd L the S half is then not 16-byte aligned and takes the kernels' one-double path; the engine itself pads (accel.h).

@@ -524,6 +524,17 @@ typedef struct cuadmm_psd_plan cuadmm_psd_plan;
 int cuadmm_psd_plan_create(const int* blk_host, int mat_num, int eig_rank, cuadmm_psd_plan** out);
 int cuadmm_psd_plan_project(cuadmm_psd_plan* plan, const double* Xb, double* Xproj, int* steps_dev /* may be NULL */, void* stream);
 void cuadmm_psd_plan_destroy(cuadmm_psd_plan* plan);
+/* The plan in the state the engine keeps it in (test hooks).  set_hint: the schedule warm start, a caller-owned device array of mat_num
+ * ints (lift steps of the previous projection, read and written by the sign kernels; aged every 16th projection), on the batched-GEMM
+ * path for the groups padded to at most hint_max_n; NULL switches it off.  reorder: longest block first -- the members of the
+ * one-wavefront classes re-sorted by steps_host[mat_num] (async: from a page-locked copy by a command queued on the stream).
+ * project_ordered: the projection on the null stream (own_stream = 0) or on a non-blocking stream of the plan's (1: size classes fork
+ * to side streams and join), a copy Xproj -> snap_dev (may be NULL) queued on that stream right behind it, and a synchronisation of
+ * that stream only; *fails_out = the plan's cumulative count of blocks that hit an iteration cap. */
+int cuadmm_psd_plan_set_hint(cuadmm_psd_plan* plan, int* hint_dev, int hint_max_n);
+int cuadmm_psd_plan_reorder(cuadmm_psd_plan* plan, const int* steps_host, int async, int own_stream);
+int cuadmm_psd_plan_project_ordered(cuadmm_psd_plan* plan, const double* Xb, double* Xproj, double* snap_dev /* may be NULL */, int* steps_dev /* may be NULL */,
+                                    int own_stream, int* fails_out /* may be NULL */);
 /* General form: blk[k] < 0 is an UNCONSTRAINED block of -blk[k] variables (blk.txt type 'u', reference README.md:55-64),
  * copied through; eig_rank > 0 keeps only the eig_rank largest eigenvalues of every PSD block: V diag(max(W,0) * mask) V^T with
  * the mask of get_eig_rank_mask.cu:13-37 (dense_scalar.cu:51-57) -- computed through the eigensolver kernels. */

@@ -246,3 +246,148 @@ def lead_solve_gpu(fac, ax, asmc, b, isig, stream_only=0, small_kb=0, tops_level
     check(fac.lib.cuadmm_op_lead_solve(fac.h, m, int(stream_only), int(small_kb), int(tops_level), int(force_hybrid), P(ax), P(asmc), P(b),
                                        float(isig), nrhs, P(y), P(info)))
     return y, dict(zip(LEAD_INFO, (int(v) for v in info)))
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# The PSD projection on a PERSISTENT plan in the state the engine keeps it in (tests/test_gpu_psd_plan_state.py): schedule
+# hints carried from projection to projection, descriptors re-sorted while the plan is live, a non-blocking caller's stream.
+# ----------------------------------------------------------------------------------------------------------------------
+class PlanHandle:
+    """cuadmm_psd_plan_* with its buffers.  Plan options come from the environment at creation (PsdOptions::from_env)."""
+
+    def __init__(self, blk):
+        self.lib = cuadmm_amd.load()
+        self.blk = np.ascontiguousarray(blk, dtype=np.int32)
+        self.nblk = int(self.blk.size)
+        n = self.blk.astype(np.int64)
+        self.L = int(np.sum(n * (n + 1) // 2))
+        self.h = C.c_void_p()
+        check(self.lib.cuadmm_psd_plan_create(self.blk.ctypes.data_as(C.c_void_p), self.nblk, 0, C.byref(self.h)))
+        self.din, self.dout, self.dsnap = (Dev(shape=(self.L,), dtype=np.float64) for _ in range(3))
+        self.dsteps = Dev(np.zeros(self.nblk, np.int32))
+        self.dhint = None
+        self._nan = np.full(self.L, np.nan)
+        self._zero = np.zeros(self.nblk, np.int32)
+        self.hints_on = False
+        self.hinted_projections = 0          # the plan ages its hints on every 16th of them
+
+    def _up(self, dev, arr):
+        arr = np.ascontiguousarray(arr, dtype=dev.dtype)
+        assert arr.shape == dev.shape
+        check(self.lib.cuadmm_memcpy_h2d(dev.ptr, arr.ctypes.data_as(C.c_void_p), dev.nbytes))
+
+    def set_hint(self, hints, hint_max_n=512):
+        """hints: mat_num ints uploaded into the plan's hint array, or None = hints off"""
+        if hints is None:
+            check(self.lib.cuadmm_psd_plan_set_hint(self.h, None, int(hint_max_n)))
+            self.hints_on = False
+            return
+        if self.dhint is None:
+            self.dhint = Dev(np.zeros(self.nblk, np.int32))
+        self._up(self.dhint, hints)
+        check(self.lib.cuadmm_psd_plan_set_hint(self.h, self.dhint.ptr, int(hint_max_n)))
+        self.hints_on = True
+
+    def get_hint(self):
+        return self.dhint.get()
+
+    def reorder(self, steps, async_=0, own_stream=0):
+        steps = np.ascontiguousarray(steps, dtype=np.int32)
+        assert steps.size == self.nblk
+        check(self.lib.cuadmm_psd_plan_reorder(self.h, steps.ctypes.data_as(C.c_void_p), int(async_), int(own_stream)))
+
+    def project(self, x, own_stream=0):
+        """-> (snap, Xproj, steps, fails): Xproj and the snapshot are prefilled with NaN and the steps with 0; `snap` is the copy of
+        Xproj queued on the projection's stream right behind it, Xproj itself is read after a device-wide synchronisation."""
+        self._up(self.din, x)
+        self._up(self.dout, self._nan)
+        self._up(self.dsnap, self._nan)
+        self._up(self.dsteps, self._zero)
+        fails = C.c_int(-1)
+        check(self.lib.cuadmm_psd_plan_project_ordered(self.h, self.din.ptr, self.dout.ptr, self.dsnap.ptr, self.dsteps.ptr, int(own_stream),
+                                                       C.byref(fails)))
+        self.hinted_projections += self.dhint is not None and self.hints_on
+        return self.dsnap.get(), self.dout.get(), self.dsteps.get(), fails.value
+
+    def project_back_to_back(self, xs, own_stream=0):
+        """The inputs one after the other into ONE output vector, as the engine does, with no upload or download between two projections (every buffer
+        is uploaded before the first); each call still waits for its own stream, and for that stream only: -> the snapshots, one per input, and the last fail count."""
+        dins = [Dev(np.ascontiguousarray(x, dtype=np.float64)) for x in xs]
+        snaps = [Dev(self._nan) for _ in xs]
+        self._up(self.dout, self._nan)
+        self._up(self.dsteps, self._zero)
+        fails = C.c_int(-1)
+        for din, snap in zip(dins, snaps):
+            check(self.lib.cuadmm_psd_plan_project_ordered(self.h, din.ptr, self.dout.ptr, snap.ptr, self.dsteps.ptr, int(own_stream),
+                                                           C.byref(fails)))
+            self.hinted_projections += self.dhint is not None and self.hints_on
+        return [s.get() for s in snaps], fails.value
+
+    def close(self):
+        if self.h:
+            check(self.lib.cuadmm_dev_sync())
+            self.lib.cuadmm_psd_plan_destroy(self.h)
+            self.h = None
+
+
+# The inputs of tests/test_gpu_psd_plan_state.py and of its CPU precondition (tests/test_sign_schedule.py): block lists, spectrum families
+# classes 0-4 and no sign path: the class of the largest blocks stays on the caller's stream, the others fork to a stream each
+NO_SIGN = [3] * 8 + [8] * 8 + [9, 12, 15, 16] * 3 + [17, 24, 31, 32] * 3 + [33, 40, 48] * 2 + [49, 56, 63, 64] * 2
+NO_SIGN = [int(n) for n in np.array(NO_SIGN)[np.random.default_rng(20240).permutation(len(NO_SIGN))]]
+# ... beside a sign path (n >= 65: three padded sizes): the small classes share one side stream
+WITH_SIGN = NO_SIGN + [65, 66, 91, 100, 120, 130, 200]
+WITH_600 = WITH_SIGN + [600]
+
+FAMILIES = ("randn", "lowrank", "graded", "psd", "nsd", "clustered", "moment")
+STALE_FAMILIES = ("moment", "graded", "psd", "clustered", "randn", "zero")
+
+
+def plan_matrix(n, kind, rng):
+    """the spectrum families of tests/test_gpu_psd.py plus "moment" (rank 3 plus symmetric noise at 1e-12: ~30 lift steps) and "zero" """
+    if kind == "zero":
+        return np.zeros((n, n))
+    if kind == "moment":
+        U = rng.standard_normal((n, 3)); G = rng.standard_normal((n, n))
+        return U @ U.T + 1e-12 * (G + G.T)
+    from tests.test_gpu_psd import _spectrum_matrix          # (that module imports this one)
+    return _spectrum_matrix(n, kind, rng)
+
+
+def block_scale(k):
+    return 0.5 + 0.25 * k          # distinct per block: a block in another block's svec range cannot pass
+
+
+_INPUTS = {}
+
+
+def plan_input(blocks, tag):
+    """-> (x, mats): tag = a family for every block, "mixed" = the seven families dealt round over the blocks (one zero block among them), or
+    "sides" = moment blocks (~40 steps) on the side streams and zero blocks (one step) on the caller's: the join must wait"""
+    key = (tuple(blocks), tag)
+    if key not in _INPUTS:
+        rng = np.random.default_rng(1000 + len(blocks) + sum(map(ord, tag)))
+        main_min = 65 if max(blocks) > 64 else 33
+        mats = []
+        for k, n in enumerate(blocks):
+            kind = tag
+            if tag == "mixed":
+                kind = "zero" if k == 5 else FAMILIES[k % len(FAMILIES)]
+            elif tag == "sides":
+                kind = "zero" if n >= main_min else "moment"
+            mats.append(block_scale(k) * plan_matrix(n, kind, rng))
+        x = np.concatenate([_orc().BlockIndex([M.shape[0]]).pack([M[None]]) for M in mats])
+        _INPUTS[key] = (x, mats)
+    return _INPUTS[key]
+
+
+def _orc():
+    from oracle import cuadmm_oracle
+    return cuadmm_oracle
+
+
+def plan_drift_input(blocks, k):
+    """input k of 20 of a slowly drifting sequence x_0 + 0.02 k d with a jump to -x_0 at k = 10 (x_0: the mixed input)"""
+    x0, _ = plan_input(blocks, "mixed")
+    n = np.asarray(blocks, dtype=np.int64)
+    d = np.random.default_rng(17).standard_normal(x0.size) * np.repeat([block_scale(q) for q in range(len(blocks))], n * (n + 1) // 2)
+    return x0 + 0.02 * k * d if k < 10 else -x0 + 0.02 * (k - 10) * d

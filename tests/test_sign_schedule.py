@@ -188,3 +188,41 @@ def test_mega_lift_jumps_a_gap_and_leaves_continuous_spectra_alone():
             same += a == b
     assert saved[0] >= 200 * 3 and saved[1] >= 200 * 3                # >= 3 steps per gapped block on average
     assert same >= 0.8 * 400                                          # ... but mostly not: same schedule as rounds 2-4
+
+
+def test_schedule_resolves_the_plan_state_inputs_for_every_hint():
+    """The precondition of tests/test_gpu_psd_plan_state.py, which projects these matrices on the device under arbitrary schedule hints:
+    the spectrum of every block of its inputs -- each family on every block size, the mixed input, the one with slow side streams, the
+    twenty drifting ones --
+    scaled as the kernels scale it (||X||_F on the one-wavefront kernels, ||X||_1 on the one-workgroup and batched-GEMM kernels: both
+    bound the spectral radius) meets this file's contract on the host model for EVERY lift0 in 0 ... 64, with decisions from the current
+    iterate (lag 0) and from the lagged statistics (lag 1).  A failure on the device is then the kernels', not the schedule's."""
+    from oracle import cuadmm_oracle as orc
+    from tests.helpers import STALE_FAMILIES, WITH_600, WITH_SIGN, plan_drift_input, plan_input
+    lib = cuadmm_amd.load()
+    err, lifts = C.c_double(), C.c_int()
+    worst = 0.0
+    seen = set()
+    inputs = [plan_input(WITH_600, tag)[1] for tag in STALE_FAMILIES + ("mixed", "sides")]      # the other block lists are prefixes of this one
+    bidx = orc.BlockIndex(WITH_SIGN)
+    for k in range(20):                                  # test_everything_together_as_the_engine_runs_it
+        inputs.append([M for G in bidx.unpack(plan_drift_input(WITH_SIGN, k)) for M in G])
+    for tag, mats in enumerate(inputs):
+        for M in mats:
+            n = M.shape[0]
+            w = np.abs(np.linalg.eigvalsh(M))
+            for nrm in (np.linalg.norm(M, "fro"), np.abs(M).sum(axis=0).max()):
+                spec = w / nrm if nrm > 0 else w
+                assert spec.max() <= 1.0 + 1e-12
+                key = (n, spec.tobytes())
+                if key in seen:
+                    continue
+                seen.add(key)
+                for lag in (0, 1):
+                    for lift0 in range(65):
+                        s = spec.copy()
+                        steps = lib.cuadmm_sign_sched_simulate_hint(s.ctypes.data_as(C.c_void_p), n, lag, lift0, C.byref(err), C.byref(lifts))
+                        assert 1 <= steps <= 64 and err.value <= 2.5e-13, (tag, n, lag, lift0, steps, err.value)
+                        assert 0 <= lifts.value <= 64
+                        worst = max(worst, err.value)
+    print("worst error relative to the scale: %.3e" % worst)
