@@ -98,6 +98,11 @@ PROTOTYPES = {
     "cuadmm_get_certificate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "cuadmm_infeas_decide": (C.c_int, [C.c_void_p, C.c_double, C.c_void_p, C.c_void_p]),
     "cuadmm_op_infeas_roll": (C.c_int, [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "cuadmm_set_trace_bounds": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
+    "cuadmm_lower_bound": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cuadmm_get_gap_info": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "cuadmm_trace_bounds_detect": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "cuadmm_op_lb_block_norms": (C.c_int, [C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "cuadmm_problem_from_txt": (C.c_int, [C.c_char_p, C.POINTER(C.c_void_p)]),
     "cuadmm_problem_view_get": (C.c_int, [C.c_void_p, C.POINTER(ProblemView)]),
     "cuadmm_problem_free": (None, [C.c_void_p]),

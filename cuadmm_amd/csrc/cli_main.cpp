@@ -10,6 +10,10 @@
 //   --infeas=P --infeas_tol=T: infeasibility check every P iterations (options "infeas_check", "infeas_tol"); a certificate ends that solve
 //   with "Solver ended: primal infeasible ..." in the summary, and a --then sequence goes on with its next stage.  The sidecar carries
 //   "status" ("converged", "iteration_limit", "primal_infeasible", "dual_infeasible") with or without the check
+//   --trace-bounds=FILE|auto: one number R_k per line of blk.txt (PSD block: tr X_k <= R_k, unconstrained: ||x_k|| <= R_k), or "auto":
+//   read off the constraints (cuadmm_trace_bounds_detect; an error when a block has none).  With them the sidecar carries "lower_bound"
+//   (cuadmm_lower_bound at the returned y) and "certified_gap"; without the flag it is what it was
+//   --gap=P --gap_tol=T: certified-gap check every P iterations (options "gap_check", "gap_tol"; needs --trace-bounds); status "certified_gap"
 //   --json=<file>: a sidecar with the run's figures (iterations, residuals, iters/s, per-phase milliseconds, the projection's
 //   nominal TFLOP/s = 10.67 sum n^3 per projection and the vector kernels' algorithmic GB/s: SURVEY.md 8d); switches the
 //   engine's per-phase HIP-event timers on (option "profile").  Nothing is written unless asked for: the reference writes X_opt.txt only.
@@ -39,7 +43,7 @@ static bool opt(const char* arg, const char* key, double& out) {
 }
 
 // --json=<file>: one object; every number printed with %.17g
-static bool write_sidecar(const std::string& path, const std::string& prefix, cuadmm_solver* solver, const cuadmm_problem_view& v) {
+static bool write_sidecar(const std::string& path, const std::string& prefix, cuadmm_solver* solver, const cuadmm_problem_view& v, bool have_bounds) {
   FILE* f = fopen(path.c_str(), "w");
   if (!f) return false;
   const int iters = cuadmm_get_info_iter_num(solver);
@@ -60,12 +64,23 @@ static bool write_sidecar(const std::string& path, const std::string& prefix, cu
           (int)cnt[4], (int)cnt[5], (int)cnt[6], (int)cnt[7], cnt[0], cnt[1]);
   double fin[8] = {0};
   cuadmm_get_status(solver, fin);
-  static const char* sname[5] = {"none", "converged", "iteration_limit", "primal_infeasible", "dual_infeasible"};
-  const int code = fin[0] >= 0 && fin[0] <= 4 ? (int)fin[0] : 0;
+  static const char* sname[6] = {"none", "converged", "iteration_limit", "primal_infeasible", "dual_infeasible", "certified_gap"};
+  const int code = fin[0] >= 0 && fin[0] <= 5 ? (int)fin[0] : 0;
   fprintf(f, " \"status\": \"%s\", \"status_iteration\": %.0f,\n", sname[code], fin[1]);
-  if (fin[2] > 0 || code >= 3)
+  if (fin[2] > 0 || code == 3 || code == 4)
     fprintf(f, " \"infeas\": {\"checks\": %.0f, \"scalar\": %.17g, \"eta\": %.17g, \"radius\": %s%.17g%s, \"check_ms\": %.17g, \"bytes\": %.0f},\n", fin[2], fin[3], fin[4],
             std::isfinite(fin[5]) ? "" : "\"", fin[5], std::isfinite(fin[5]) ? "" : "\"", fin[6], fin[7]);
+  if (have_bounds) {
+    double lb[8] = {0}, gi[8] = {0};
+    if (cuadmm_lower_bound(solver, lb, nullptr) == CUADMM_OK) {
+      cuadmm_get_gap_info(solver, gi);
+      fprintf(f, " \"lower_bound\": %.17g, \"certified_gap\": %.17g, \"lower_bound_parts\": {\"bty\": %.17g, \"penalty\": %.17g, \"worst_block\": %.0f, \"worst_term\": %.17g, \"ms\": %.17g},\n",
+              lb[0], lb[3], lb[1], lb[2], lb[4], lb[5], lb[6]);
+      if (gi[0] > 0)
+        fprintf(f, " \"gap_check\": {\"checks\": %.0f, \"best_lower_bound\": %.17g, \"best_iteration\": %.0f, \"last_gap\": %.17g, \"check_ms\": %.17g, \"bytes\": %.0f, \"verdict_iteration\": %.0f},\n",
+                gi[0], gi[1], gi[2], gi[4], gi[5], gi[6], gi[7]);
+    } else std::cerr << cuadmm_last_error() << std::endl;
+  }
   double acc[8] = {0};
   cuadmm_get_accel_info(solver, acc);
   if (acc[0] > 0)
@@ -103,19 +118,20 @@ int main(int argc, char* argv[]) {
   std::string prefix = argv[1];
   int eig_stream_num_per_gpu = 15, cpu_eig_thread_num = 30;
   double max_iter = 1e6, stop_tol = 1e-3, threshold = 0, stage1 = 50, stage2 = 100, switch_admm = 5000, sigscale = 1.05,
-         sig = 1e0, device = 0, accel = 0, infeas = 0, infeas_tol = -1;
+         sig = 1e0, device = 0, accel = 0, infeas = 0, infeas_tol = -1, gap = 0, gap_tol = -1;
   bool quiet = false;
-  std::string json_path;
+  std::string json_path, bounds_arg;
   std::vector<std::string> then_dirs;
   std::vector<char> then_is_A;
   for (int i = 2; i < argc; ++i) {
     if (strncmp(argv[i], "--json=", 7) == 0) { json_path = argv[i] + 7; continue; }
+    if (strncmp(argv[i], "--trace-bounds=", 15) == 0) { bounds_arg = argv[i] + 15; continue; }
     if (strncmp(argv[i], "--then=", 7) == 0) { then_dirs.push_back(argv[i] + 7); then_is_A.push_back(0); continue; }
     if (strncmp(argv[i], "--then-A=", 9) == 0) { then_dirs.push_back(argv[i] + 9); then_is_A.push_back(1); continue; }
     if (opt(argv[i], "--max_iter", max_iter) || opt(argv[i], "--stop_tol", stop_tol) || opt(argv[i], "--threshold", threshold) ||
         opt(argv[i], "--stage1", stage1) || opt(argv[i], "--stage2", stage2) || opt(argv[i], "--switch_admm", switch_admm) ||
         opt(argv[i], "--sigscale", sigscale) || opt(argv[i], "--sig", sig) || opt(argv[i], "--device", device) || opt(argv[i], "--accel", accel) ||
-        opt(argv[i], "--infeas_tol", infeas_tol) || opt(argv[i], "--infeas", infeas))
+        opt(argv[i], "--infeas_tol", infeas_tol) || opt(argv[i], "--infeas", infeas) || opt(argv[i], "--gap_tol", gap_tol) || opt(argv[i], "--gap", gap))
       continue;
     if (strcmp(argv[i], "--quiet") == 0) { quiet = true; continue; }
     std::cerr << "unknown option " << argv[i] << std::endl;
@@ -151,6 +167,31 @@ int main(int argc, char* argv[]) {
     std::cerr << cuadmm_last_error() << std::endl;
     return 1;
   }
+  if (!bounds_arg.empty()) {
+    std::vector<double> R((size_t)v.mat_num, -1.0);
+    if (bounds_arg == "auto") {
+      if (cuadmm_trace_bounds_detect(v.vec_len, v.con_num, v.At_csc_col_ptrs, v.At_csc_row_ids, v.At_csc_vals, v.b_indices, v.b_vals, v.b_nnz, v.blk_vals,
+                                     v.mat_num, R.data()) != CUADMM_OK) {
+        std::cerr << cuadmm_last_error() << std::endl;
+        return 1;
+      }
+      for (int k = 0; k < v.mat_num; ++k)
+        if (R[k] < 0) { std::cerr << "--trace-bounds=auto: the constraints give no bound for block " << k << " (size " << v.blk_vals[k] << ")" << std::endl; return 1; }
+    } else {
+      FILE* bf = fopen(bounds_arg.c_str(), "r");
+      int got = 0;
+      double x = 0;
+      while (bf && got < v.mat_num && fscanf(bf, "%lf", &x) == 1) R[got++] = x;
+      const bool more = bf && fscanf(bf, "%lf", &x) == 1;
+      if (bf) fclose(bf);
+      if (!bf || got != v.mat_num || more) { std::cerr << "--trace-bounds: '" << bounds_arg << "' must hold " << v.mat_num << " numbers, one per block" << std::endl; return 1; }
+    }
+    if (cuadmm_set_trace_bounds(solver, R.data(), v.mat_num) != CUADMM_OK) { std::cerr << cuadmm_last_error() << std::endl; return 1; }
+  }
+  if ((gap != 0 && cuadmm_set_option(solver, "gap_check", gap) != CUADMM_OK) || (gap_tol >= 0 && cuadmm_set_option(solver, "gap_tol", gap_tol) != CUADMM_OK)) {
+    std::cerr << cuadmm_last_error() << std::endl;
+    return 1;
+  }
   int rc = cuadmm_init(solver, eig_stream_num_per_gpu, cpu_eig_thread_num, v.vec_len, v.con_num, v.At_csc_col_ptrs,
                        v.At_csc_row_ids, v.At_csc_vals, v.At_nnz, v.b_indices, v.b_vals, v.b_nnz, v.C_indices, v.C_vals,
                        v.C_nnz, v.blk_vals, v.mat_num, nullptr, nullptr, nullptr, sig);
@@ -168,7 +209,7 @@ int main(int argc, char* argv[]) {
   }
   std::vector<double> X((size_t)v.vec_len);
   if (cuadmm_get_X(solver, X.data()) == CUADMM_OK) cuadmm_write_dense_txt((prefix + "X_opt.txt").c_str(), X.data(), v.vec_len);
-  if (!json_path.empty() && !write_sidecar(json_path, prefix, solver, v)) std::cerr << "cannot write " << json_path << std::endl;
+  if (!json_path.empty() && !write_sidecar(json_path, prefix, solver, v, !bounds_arg.empty())) std::cerr << "cannot write " << json_path << std::endl;
   for (size_t k = 0; k < then_dirs.size() && rc == CUADMM_OK; ++k) {
     const std::string& d = then_dirs[k];
     std::vector<int> bi, ci;
@@ -194,7 +235,7 @@ int main(int argc, char* argv[]) {
     if (rc != CUADMM_OK) { std::cerr << cuadmm_last_error() << std::endl; break; }
     if (cuadmm_get_X(solver, X.data()) == CUADMM_OK) cuadmm_write_dense_txt((d + "X_opt.txt").c_str(), X.data(), v.vec_len);
     const std::string side = json_path + "." + std::to_string(k + 1);
-    if (!json_path.empty() && !write_sidecar(side, d, solver, v)) std::cerr << "cannot write " << side << std::endl;
+    if (!json_path.empty() && !write_sidecar(side, d, solver, v, !bounds_arg.empty())) std::cerr << "cannot write " << side << std::endl;
   }
   cuadmm_destroy(solver);
   cuadmm_problem_free(prob);

@@ -32,6 +32,7 @@
 #include "duo_group.h"
 #include "accel.h"
 #include "infeas.h"
+#include "lower_bound.h"
 
 using namespace cuadmm;
 
@@ -410,6 +411,38 @@ struct cuadmm_solver {
   int infeas_begin_solve();
   int infeas_step(int iter, double stop_tol);
 
+  // Certified lower bound from trace bounds (cuadmm_set_trace_bounds, cuadmm_lower_bound, option "gap_check" = period p; lower_bound.h,
+  // DESIGN.md "Certified lower bound").  M = A'y - C (the iteration's kernel, into a vector of the bound's own), P = P+(M) through a plan
+  // of the bound's own as the infeasibility check has one, then one pass of per-block norms and a combine kernel: four doubles cross.
+  struct Lb {
+    int period = 0;
+    double tol = 0;                    // 0: the solve's stop_tol
+    std::vector<double> R;             // the caller's bounds, one per block (empty: none set)
+    bool R_dirty = false;
+    DevBuf<double> mbuf, pbuf, ybuf, bcopy, R_d, pairs, cpart, dpart, out_d;
+    DevBuf<long long> off_d, len_d;
+    DevBuf<int> blk_d, wave_d, chunk_d, large_d;
+    int nwave = 0, nchunk = 0, nlarge = 0;
+    PinnedBuf<double> h_out;
+    PsdPlan* plan2 = nullptr;
+    double plan2_bytes = 0;
+    hipEvent_t ev[2] = {};
+    // of the last solve with the option on
+    long long checks = 0;
+    int best_iter = 0, verdict_iter = 0;
+    double best_lb = 0, last_lb = 0, last_g = 0, ms = 0;
+    double bytes() const {
+      return 8.0 * (double)(mbuf.n + pbuf.n + ybuf.n + bcopy.n + R_d.n + pairs.n + cpart.n + dpart.n + out_d.n + off_d.n + len_d.n) +
+             4.0 * (double)(blk_d.n + wave_d.n + chunk_d.n + large_d.n) + plan2_bytes;
+    }
+    ~Lb() { for (auto& e : ev) if (e) { hipError_t r = hipEventDestroy(e); (void)r; } delete plan2; }
+  } lb;
+  bool gap_on() const { return lb.period > 0 && L > 0; }
+  void lb_reset() { lb.checks = 0; lb.best_iter = lb.verdict_iter = 0; lb.best_lb = lb.last_lb = lb.last_g = 0; }
+  int lb_prepare();
+  int lb_eval(const double* y_scaled_d, double out6[6], float* ms);
+  int lb_step(int iter, double stop_tol);
+
   // profiling
   hipEvent_t ev0[K_NUM][2] = {}, ev1[K_NUM][2] = {};
   int ev_used[K_NUM] = {0};
@@ -674,7 +707,7 @@ struct cuadmm_solver {
   }
   // --- several iterations per launch ---------------------------------------------------------------------------------
   bool can_batch() const {
-    return can_batch_local() && bt.peers_agree && aa.mem == 0 && inf.period == 0;
+    return can_batch_local() && bt.peers_agree && aa.mem == 0 && inf.period == 0 && lb.period == 0;
   }
   bool can_batch_local() const {
     return bt.max_iters >= 2 && fuse && closed.active && dev_solve && !lead.ready && plan.n_rest == 0 && eig_rank == 0 && !out_mapped &&
@@ -1538,6 +1571,17 @@ int cuadmm_set_option(cuadmm_solver* s, const char* key, double value) {
     if (!(value >= 0)) { s->option_log.pop_back(); set_error("set_option: infeas_tol must not be negative"); return CUADMM_ERR_INVALID; }
     s->inf.tol = value;
   }
+  else if (k == "gap_check") {                                          // period of the certified-gap check (0: off), before init
+    if (!(value == 0 || (value >= 2 && value <= 1e6 && value == std::floor(value)))) {
+      s->option_log.pop_back(); set_error("set_option: gap_check must be 0 (off) or an integer period from 2 to 1000000"); return CUADMM_ERR_INVALID;
+    }
+    if (s->initialised) { s->option_log.pop_back(); set_error("set_option: gap_check is set before init"); return CUADMM_ERR_INVALID; }
+    s->lb.period = (int)value;
+  }
+  else if (k == "gap_tol") {
+    if (!(value >= 0)) { s->option_log.pop_back(); set_error("set_option: gap_tol must not be negative"); return CUADMM_ERR_INVALID; }
+    s->lb.tol = value;
+  }
   else if (k == "update_A_inject_fail") s->upa.inject_fail = (int)value;   // test hook
   else if (k == "duo_inject_fail") { s->duo_inject = (long long)value; if (s->group) duo_group_inject(s->group, s->duo_inject); }   // test hook
   else { s->option_log.pop_back(); set_error("set_option: unknown key '%s'", key); return CUADMM_ERR_INVALID; }
@@ -1602,6 +1646,20 @@ int cuadmm_init(cuadmm_solver* s, int eig_stream_num_per_gpu, int cpu_eig_thread
     set_error("init: option infeas_check works on one rank with the full projection and the plain iteration (world = %d, eig_rank = %d, accel = %d%s): "
               "its sums are not all-reduced, and differences of accelerated iterates are not the sequence its certificates come from",
               s->world, s->eig_rank, s->aa.mem, (s->group || s->in_group_call) ? ", in-process group" : "");
+    return CUADMM_ERR_INVALID;
+  }
+  if (s->lb.period > 0 && (s->world > 1 || s->eig_rank > 0 || s->group || s->in_group_call || s->aa.mem > 0 || s->inf.period > 0)) {
+    set_error("init: option gap_check works on one rank with the full projection and the plain iteration, without another check behind it "
+              "(world = %d, eig_rank = %d, accel = %d, infeas_check = %d%s): its sums are not all-reduced, and one check at a time keeps the solve's end defined",
+              s->world, s->eig_rank, s->aa.mem, s->inf.period, (s->group || s->in_group_call) ? ", in-process group" : "");
+    return CUADMM_ERR_INVALID;
+  }
+  if (s->lb.period > 0 && s->lb.R.empty()) {
+    set_error("init: option gap_check needs trace bounds (cuadmm_set_trace_bounds before cuadmm_init): without them no lower bound exists");
+    return CUADMM_ERR_INVALID;
+  }
+  if (!s->lb.R.empty() && (int)s->lb.R.size() != mat_num) {
+    set_error("init: %d trace bounds were set, the problem has %d blocks", (int)s->lb.R.size(), mat_num);
     return CUADMM_ERR_INVALID;
   }
   long long Lchk = 0;
@@ -1771,6 +1829,9 @@ int cuadmm_solve(cuadmm_solver* s, int max_iter, double stop_tol, int sig_update
   if (s->accel_on() && (rc = s->accel_begin_solve())) return rc;
   s->inf.status = 0;
   if (s->infeas_on() && (rc = s->infeas_begin_solve())) return rc;
+  s->lb_reset();
+  s->lb.ms = 0;
+  if (s->gap_on() && (rc = s->lb_prepare())) return rc;
   const bool lpt_enabled = s->sw.lpt != 0;
   long long& lpt_ev = s->lpt_next;             // counts iterations over all solve calls of this solver
   if (!lpt_enabled) lpt_ev = 0;
@@ -1778,7 +1839,12 @@ int cuadmm_solve(cuadmm_solver* s, int max_iter, double stop_tol, int sig_update
     // ---- Step 0 (solver.cu:419-467)
     if (std::max(s->maxfeas, s->relgap) < stop_tol) { breakyes = true; final_msg = "Solver ended: converged."; }
     if (iter > max_iter) { breakyes = true; final_msg = "Solver ended: maximum iteration reached"; }
-    if (s->inf.status >= 3) {             // a certificate behind the previous iteration (infeas_step)
+    if (s->inf.status == 5) {             // the certified gap behind the previous iteration (lb_step)
+      breakyes = true;
+      char msg[160];
+      snprintf(msg, sizeof msg, "Solver ended: certified gap %.3e (lower bound %.10e at iteration %d)", s->lb.last_g, s->lb.last_lb, s->inf.verdict_iter);
+      final_msg = msg;
+    } else if (s->inf.status >= 3) {      // a certificate behind the previous iteration (infeas_step)
       breakyes = true;
       char msg[128];
       snprintf(msg, sizeof msg, "Solver ended: %s infeasible (certificate at iteration %d)", s->inf.status == 3 ? "primal" : "dual", s->inf.verdict_iter);
@@ -1812,6 +1878,7 @@ int cuadmm_solve(cuadmm_solver* s, int max_iter, double stop_tol, int sig_update
     // ---- Step 1 (solver.cu:478-500): y = (AA^T)^-1 (Rp/sig - A(S-C)); with closed blocks the fused projection of this
     // iteration solves it (not on the last pass through the loop, which stops before the projection)
     if (s->y_early) s->y_early = false;       // enqueued at the end of the previous iteration (fetch_out, solve_next)
+    else if (s->inf.status == 5) {}           // the bound was formed at the y the solve returns: no further y-solve behind the verdict
     else if (s->bt.len == 0 && (rc = s->host_solve(s->fuse && !breakyes))) return rc;
 
     if (breakyes) {   // solver.cu:567-576
@@ -1893,7 +1960,7 @@ int cuadmm_solve(cuadmm_solver* s, int max_iter, double stop_tol, int sig_update
     // device and belongs to the engine (not to a closed block's kernel), sigma does not change in this iteration's step 5, nothing of a
     // batch is pending, and the per-class event timers (profile = 1) are off -- they are collected at the wait, before that solve ends
     const bool sig_may_change = (iter <= sig_update_threshold && iter % sig_update_stage_1 == 1) || (iter > sig_update_threshold && iter % sig_update_stage_2 == 1);
-    const bool solve_next_ok = s->sw.solve_next != 0 && !s->accel_on() && !s->infeas_on() && s->dev_solve && !from_batch && !sig_may_change && !(s->fuse && s->closed.active) && s->profile != 1;
+    const bool solve_next_ok = s->sw.solve_next != 0 && !s->accel_on() && !s->infeas_on() && !s->gap_on() && s->dev_solve && !from_batch && !sig_may_change && !(s->fuse && s->closed.active) && s->profile != 1;
     if (from_batch) {
       // consumed below (Step 5) from bt.h
     } else if ((rc = s->upload_y())) return rc;
@@ -2037,6 +2104,8 @@ int cuadmm_solve(cuadmm_solver* s, int max_iter, double stop_tol, int sig_update
     }
     // ---- infeasibility check: on the state at the end of the iteration, after the sigma update
     if (s->infeas_on() && iter % s->inf.period == 0 && (rc = s->infeas_step(iter, stop_tol))) return rc;
+    // ---- certified-gap check: the lower bound at this iteration's y against this iteration's pobj
+    if (s->gap_on() && iter % s->lb.period == 0 && (rc = s->lb_step(iter, stop_tol))) return rc;
   }
 
   // unscale (solver.cu:814-816) -- deferred until somebody reads or replaces X, y, S (materialise): a following
@@ -2353,6 +2422,98 @@ int cuadmm_solver::infeas_step(int iter, double stop_tol) {
   return CUADMM_OK;
 }
 
+// ------------------------------------------------------------------------------------------
+// Certified lower bound from trace bounds (cuadmm_lower_bound, option "gap_check"): DESIGN.md, "Certified lower bound"
+// ------------------------------------------------------------------------------------------
+// vectors, task lists and events on first use; R and (where the engine keeps none on the device) b on every call: both may have changed
+int cuadmm_solver::lb_prepare() {
+  int rc;
+  const int nb = (int)blk_local.size();
+  if ((int)lb.R.size() != nb) { set_error("lower bound: %d trace bounds are set, the solver has %d blocks", (int)lb.R.size(), nb); return CUADMM_ERR_INVALID; }
+  if (!lb.out_d.p) {
+    const size_t mm = (size_t)std::max(m, 1);
+    std::vector<long long> off((size_t)nb), len((size_t)nb);
+    long long o = 0;
+    for (int k = 0; k < nb; ++k) { off[k] = o; len[k] = blk_svec_len(blk_local[k]); o += len[k]; }
+    LbTasks t;
+    if ((rc = lb_build_tasks(nb, len.data(), &t))) return rc;
+    if ((rc = lb.mbuf.alloc((size_t)L)) || (rc = lb.pbuf.alloc((size_t)L)) || (rc = lb.ybuf.alloc(mm)) || (rc = lb.R_d.alloc((size_t)nb)) ||
+        (rc = lb.pairs.alloc(2 * (size_t)nb)) || (rc = lb.dpart.alloc(kLbDotSlots)) || (rc = lb.h_out.alloc(4)) || (rc = lb.off_d.from(off)) ||
+        (rc = lb.len_d.from(len)) || (rc = lb.blk_d.from(blk_local)) || (rc = lb.wave_d.from(t.wave)) || (rc = lb.chunk_d.from(t.chunk)) ||
+        (rc = lb.large_d.from(t.large)) || (rc = lb.cpart.alloc(2 * (size_t)t.nchunk())))
+      return rc;
+    if (!b_d.p && (rc = lb.bcopy.alloc(mm))) return rc;
+    lb.nwave = t.nwave(); lb.nchunk = t.nchunk(); lb.nlarge = t.nlarge();
+    CUADMM_HIP_TRY(hipMemsetAsync(lb.pairs.p, 0, sizeof(double) * lb.pairs.n, st));
+    for (auto& e : lb.ev) CUADMM_HIP_TRY(hipEventCreate(&e));
+    lb.R_dirty = true;
+    if ((rc = lb.out_d.alloc(4))) return rc;          // last: marks the set as complete
+  }
+  if (lb.R_dirty && (rc = staged_h2d(lb.R_d.p, lb.R.data(), sizeof(double) * (size_t)nb, st))) return rc;
+  lb.R_dirty = false;
+  if (lb.bcopy.p && m > 0 && (rc = staged_h2d(lb.bcopy.p, b_p.data(), sizeof(double) * (size_t)m, st))) return rc;
+  return CUADMM_OK;
+}
+
+// The bound at y (device, the engine's scaled space and the factor's order).  Reads y, A, C and b; writes only the bound's own vectors.
+// out6 = [LB, b'y, sum R_k nubar_k, worst block, its term] in the caller's units, [5] unused.
+int cuadmm_solver::lb_eval(const double* y, double out6[6], float* ms) {
+  int rc;
+  const double* bw = b_d.p ? b_d.p : lb.bcopy.p;
+  if (!lb.plan2) {       // at the first evaluation: the solver's psd_* options, the full projection
+    const int nb = (int)blk_local.size();
+    size_t free0 = 0, free1 = 0, total = 0;
+    if (hipMemGetInfo(&free0, &total) != hipSuccess) { free0 = 0; (void)hipGetLastError(); }
+    lb.plan2 = new PsdPlan();
+    lb.plan2->opt = plan.opt;
+    lb.plan2->eig_rank = 0;
+    if ((rc = lb.plan2->build(blk_local.data(), nb))) { delete lb.plan2; lb.plan2 = nullptr; return rc; }
+    if (hipMemGetInfo(&free1, &total) != hipSuccess) { free1 = free0; (void)hipGetLastError(); }
+    lb.plan2_bytes = free0 > free1 ? (double)(free0 - free1) : 0.0;
+  }
+  CUADMM_HIP_TRY(hipEventRecord(lb.ev[0], st));
+  // M = A'y - C (S^ = -Cscale M), P = P+(M) with the unconstrained slices copied through
+  if ((rc = launch_aty_xb(false, L, At_rp.p, At_ci.p, At_v.p, y, C.p, X.p, 1.0, lb.mbuf.p, nullptr, st, &At_long))) return rc;
+  if ((rc = lb.plan2->project(lb.mbuf.p, lb.pbuf.p, st))) return rc;
+  LbNormArgs a{lb.mbuf.p, lb.pbuf.p, lb.off_d.p, lb.len_d.p, lb.wave_d.p, lb.chunk_d.p, lb.large_d.p, lb.nwave, lb.nchunk, lb.nlarge, lb.cpart.p, lb.pairs.p};
+  if ((rc = launch_lb_block_norms(a, st))) return rc;
+  if ((rc = launch_lb_dot(m, bw, y, lb.dpart.p, st))) return rc;
+  if ((rc = launch_lb_combine((int)blk_local.size(), lb.pairs.p, lb.R_d.p, lb.len_d.p, lb.blk_d.p, lb.dpart.p, lb.out_d.p, st))) return rc;
+  CUADMM_HIP_TRY(hipMemcpyAsync(lb.h_out.p, lb.out_d.p, sizeof(double) * 4, hipMemcpyDeviceToHost, st));
+  CUADMM_HIP_TRY(hipEventRecord(lb.ev[1], st));
+  CUADMM_HIP_TRY(hipStreamSynchronize(st));
+  *ms = 0;
+  if (hipEventElapsedTime(ms, lb.ev[0], lb.ev[1]) != hipSuccess) { *ms = 0; (void)hipGetLastError(); }
+  if (lb.plan2->fail_count(st) > 0) { set_error("lower bound: a block projection hit the QL sweep cap"); return CUADMM_ERR_EIG; }
+  const double* h = lb.h_out.p;
+  out6[1] = h[3] * objscale;
+  out6[2] = h[0] * Cscale;
+  out6[0] = out6[1] - out6[2];
+  out6[3] = h[1];
+  out6[4] = h[2] * Cscale;
+  out6[5] = 0;
+  return CUADMM_OK;
+}
+
+// End of iteration `iter`, a multiple of the period: y_d holds this iteration's y (infeas_step), pobj and errRp are this iteration's.
+int cuadmm_solver::lb_step(int iter, double stop_tol) {
+  int rc;
+  double o[6];
+  float ms = 0;
+  if ((rc = lb_eval(y_d.p, o, &ms))) return rc;
+  lb.checks++;
+  lb.ms += ms;
+  const double LB = o[0], g = std::fabs(pobj - LB) / (1 + std::fabs(pobj) + std::fabs(LB));
+  lb.last_lb = LB; lb.last_g = g;
+  if (std::isfinite(LB) && (lb.best_iter == 0 || LB > lb.best_lb)) { lb.best_lb = LB; lb.best_iter = iter; }
+  const double tol = lb.tol > 0 ? lb.tol : stop_tol;
+  if (g <= tol && errRp <= tol) {          // (false for a NaN)
+    inf.status = 5; inf.verdict_iter = iter;
+    lb.verdict_iter = iter;
+  }
+  return CUADMM_OK;
+}
+
 // SDPDuoSolver front (duo_solver.h:236-276): exactly two block sizes, then the generic engine.
 int cuadmm_duo_init(cuadmm_solver* s, int if_gpu_eig_mom, int device_num_requested, int eig_stream_num_per_gpu,
                     int cpu_eig_thread_num, int vec_len, int con_num, const int* At_cp, const int* At_ri, const double* At_vx,
@@ -2377,6 +2538,10 @@ int cuadmm_duo_init(cuadmm_solver* s, int if_gpu_eig_mom, int device_num_request
   }
   if (device_num_requested > 1 && s->inf.period > 0) {
     set_error("duo_init: option infeas_check works on one engine (device_num_requested = %d): its sums are not all-reduced", device_num_requested);
+    return CUADMM_ERR_INVALID;
+  }
+  if (device_num_requested > 1 && s->lb.period > 0) {
+    set_error("duo_init: option gap_check works on one engine (device_num_requested = %d): its sums are not all-reduced", device_num_requested);
     return CUADMM_ERR_INVALID;
   }
   if (device_num_requested > 1 && s->world == 1 && !s->in_group_call) {
@@ -2502,6 +2667,7 @@ int cuadmm_set_XyS(cuadmm_solver* s, const double* X, const double* y, const dou
   if (y) for (int i = 0; i < s->m; ++i) s->y_p[i] = s->local_mode ? y[s->cons_local[s->perm[i]]] : y[s->perm[i]];
   if (sig > 0) s->sig = sig;
   s->infeas_reset();                            // snapshots and status describe another iterate
+  s->lb_reset();
   return CUADMM_OK;
 }
 
@@ -2651,6 +2817,7 @@ int cuadmm_update_bC(cuadmm_solver* s, const int* b_idx, const double* b_vals, i
   s->bt.len = s->bt.pos = 0; s->bt.have_ck = false;
   s->closed.iters_done = 0; s->closed.out_dirty = true;
   s->infeas_reset();
+  s->lb_reset();
   s->plan.n_project = 0;
   if (s->hint_d.p) CUADMM_HIP_TRY(hipMemsetAsync(s->hint_d.p, 0, sizeof(int) * s->hint_d.n, s->st));     // the sign schedule's warm start
   if (s->closed.cl_out.p) CUADMM_HIP_TRY(hipMemsetAsync(s->closed.cl_out.p, 0, sizeof(double) * s->closed.cl_out.n, s->st));
@@ -2898,6 +3065,7 @@ int cuadmm_update_A(cuadmm_solver* s, const double* At_vals, int At_nnz, int kee
   s->bt.len = s->bt.pos = 0; s->bt.have_ck = false;
   s->closed.iters_done = 0; s->closed.out_dirty = true;
   s->infeas_reset();
+  s->lb_reset();
   s->plan.n_project = 0;
   if (s->hint_d.p) CUADMM_HIP_TRY(hipMemsetAsync(s->hint_d.p, 0, sizeof(int) * s->hint_d.n, s->st));
   if (s->closed.cl_out.p) CUADMM_HIP_TRY(hipMemsetAsync(s->closed.cl_out.p, 0, sizeof(double) * s->closed.cl_out.n, s->st));
@@ -3036,6 +3204,75 @@ int cuadmm_infeas_decide(const double stats[8], double tol, int* verdict, double
   int rc = infeas_decide(stats, tol, verdict, o3);
   if (!rc && radius) *radius = o3[2];
   return rc;
+}
+int cuadmm_set_trace_bounds(cuadmm_solver* s, const double* R, int mat_num) {
+  if (!s) { set_error("set_trace_bounds: null"); return CUADMM_ERR_INVALID; }
+  if (!R) {
+    if (s->initialised && s->lb.period > 0) { set_error("set_trace_bounds: option gap_check is on: the bounds cannot be cleared"); return CUADMM_ERR_INVALID; }
+    s->lb.R.clear();
+    return CUADMM_OK;
+  }
+  if (mat_num < 1) { set_error("set_trace_bounds: mat_num = %d", mat_num); return CUADMM_ERR_INVALID; }
+  if (s->initialised) {
+    int mn = 0;
+    cuadmm_get_dims(s, nullptr, nullptr, &mn);
+    if (mn != mat_num) { set_error("set_trace_bounds: %d bounds for a problem of %d blocks", mat_num, mn); return CUADMM_ERR_INVALID; }
+  }
+  for (int k = 0; k < mat_num; ++k)
+    if (!(R[k] >= 0) || !std::isfinite(R[k])) { set_error("set_trace_bounds: bound %d is %g: every bound must be finite and not negative", k, R[k]); return CUADMM_ERR_INVALID; }
+  s->lb.R.assign(R, R + mat_num);
+  s->lb.R_dirty = true;
+  return CUADMM_OK;
+}
+int cuadmm_lower_bound(cuadmm_solver* s, double o[8], double* per_block) {
+  if (!s || !s->initialised || !o) { set_error("lower_bound: solver not initialised or null argument"); return CUADMM_ERR_INVALID; }
+  if (s->world > 1 || s->comm_world > 1 || s->local_mode || s->group || s->in_group_call) {
+    set_error("lower_bound: works on one rank (world = %d%s): its sums are not all-reduced", std::max(s->world, s->comm_world), s->group ? ", in-process group" : "");
+    return CUADMM_ERR_INVALID;
+  }
+  if (s->lb.R.empty()) { set_error("lower_bound: no trace bounds are set (cuadmm_set_trace_bounds)"); return CUADMM_ERR_INVALID; }
+  if (s->L <= 0) { set_error("lower_bound: the problem has no svec slots"); return CUADMM_ERR_INVALID; }
+  int rc = check_device(s->device);
+  if (rc) return rc;
+  if ((rc = s->lb_prepare())) return rc;
+  // the y cuadmm_get_y would return, in the engine's scaled space and order, in a vector of the bound's own: behind a solve the
+  // iterate is held scaled (the deferred unscaling is not triggered: a following solve(if_first = false) continues from it bit
+  // for bit); otherwise the host's y (or the device's, where cuadmm_update_bC left the current one there) is in the caller's units
+  const int m = s->m;
+  if (m > 0) {
+    if (s->pending_unscale && s->dev_solve) CUADMM_HIP_TRY(hipMemcpyAsync(s->lb.ybuf.p, s->y_d.p, sizeof(double) * (size_t)m, hipMemcpyDeviceToDevice, s->st));
+    else {
+      std::vector<double> ys(s->y_p);
+      if (!s->pending_unscale) {
+        if (s->y_host_stale && (rc = staged_d2h(ys.data(), s->y_d.p, sizeof(double) * (size_t)m, s->st))) return rc;
+        for (int i = 0; i < m; ++i) ys[i] = (ys[i] * s->normA_p[i]) * (1 / s->Cscale);
+      }
+      if ((rc = staged_h2d(s->lb.ybuf.p, ys.data(), sizeof(double) * (size_t)m, s->st))) return rc;
+    }
+  } else CUADMM_HIP_TRY(hipMemsetAsync(s->lb.ybuf.p, 0, sizeof(double), s->st));
+  double r[6];
+  float ms = 0;
+  if ((rc = s->lb_eval(s->lb.ybuf.p, r, &ms))) return rc;
+  o[0] = r[0]; o[1] = r[1]; o[2] = r[2];
+  o[3] = std::fabs(s->pobj - r[0]) / (1 + std::fabs(s->pobj) + std::fabs(r[0]));
+  o[4] = r[3]; o[5] = r[4]; o[6] = ms; o[7] = s->lb.bytes();
+  if (per_block) {
+    const size_t nb = s->blk_local.size();
+    std::vector<double> pr(2 * nb);
+    if ((rc = staged_d2h(pr.data(), s->lb.pairs.p, sizeof(double) * 2 * nb, s->st))) return rc;
+    for (size_t k = 0; k < nb; ++k) { per_block[2 * k] = std::sqrt(pr[2 * k + 1]) * s->Cscale; per_block[2 * k + 1] = std::sqrt(pr[2 * k]) * s->Cscale; }
+  }
+  return CUADMM_OK;
+}
+int cuadmm_get_gap_info(const cuadmm_solver* s, double o[8]) {
+  if (!s || !o) { set_error("get_gap_info: null"); return CUADMM_ERR_INVALID; }
+  o[0] = (double)s->lb.checks; o[1] = s->lb.best_lb; o[2] = (double)s->lb.best_iter; o[3] = s->lb.last_lb; o[4] = s->lb.last_g;
+  o[5] = s->lb.ms; o[6] = s->lb.bytes(); o[7] = (double)s->lb.verdict_iter;
+  return CUADMM_OK;
+}
+int cuadmm_trace_bounds_detect(int vec_len, int con_num, const int* At_csc_col_ptrs, const int* At_csc_row_ids, const double* At_csc_vals,
+                               const int* b_indices, const double* b_vals, int b_nnz, const int* blk_vals, int mat_num, double* R_out) {
+  return lb_trace_bounds_detect(vec_len, con_num, At_csc_col_ptrs, At_csc_row_ids, At_csc_vals, b_indices, b_vals, b_nnz, blk_vals, mat_num, R_out);
 }
 int cuadmm_get_tail_info(const cuadmm_solver* s, double o[6]) {
   if (!s || !o) { set_error("get_tail_info: null"); return CUADMM_ERR_INVALID; }
@@ -3408,6 +3645,52 @@ int cuadmm_op_infeas_roll(int64_t n, const double* cur, double* prev_inout, cons
   if ((rc = staged_d2h(prev_inout, q.p + offset, sizeof(double) * (size_t)n)) || (rc = staged_d2h(d_out, out.p + offset, sizeof(double) * (size_t)n)) ||
       (rc = staged_d2h(sums2_out, sums.p, sizeof(double) * 2)))
     return rc;
+  return CUADMM_OK;
+}
+
+// the per-block norm kernels of the lower bound on host arrays (csrc/lower_bound.hip).  offs: first slot of every block (null: the
+// blocks follow one another from slot 0); offset = 1 places both vectors one double behind a 16-byte boundary.  M and P are copied
+// back as the kernels left them.
+int cuadmm_op_lb_block_norms(int64_t n, double* M_inout, double* P_inout, int nblk, const int* blk, const int64_t* offs, const double* R, int offset,
+                             double* pairs_out, double* comb3_out) {
+  if (n < 1 || !M_inout || !P_inout || nblk < 1 || !blk || !R || !pairs_out || !comb3_out || offset < 0 || offset > 1) {
+    set_error("op_lb_block_norms: invalid argument");
+    return CUADMM_ERR_INVALID;
+  }
+  std::vector<long long> off((size_t)nblk), len((size_t)nblk);
+  long long o = 0;
+  for (int k = 0; k < nblk; ++k) {
+    if (blk[k] == 0 || blk[k] > kMaxBlockSize) { set_error("op_lb_block_norms: block %d has size %d", k, blk[k]); return CUADMM_ERR_INVALID; }
+    len[k] = blk_svec_len(blk[k]);
+    off[k] = offs ? (long long)offs[k] : o;
+    o += len[k];
+    if (off[k] < 0 || off[k] + len[k] > n) { set_error("op_lb_block_norms: block %d outside the vectors", k); return CUADMM_ERR_INVALID; }
+  }
+  int rc = check_device(0);
+  if (rc) return rc;
+  LbTasks t;
+  if ((rc = lb_build_tasks(nblk, len.data(), &t))) return rc;
+  const size_t N = (size_t)n + 2;
+  DevBuf<double> Md, Pd, Rd, pairs, cpart, out;
+  DevBuf<long long> off_d, len_d;
+  DevBuf<int> blk_d, wave_d, chunk_d, large_d;
+  if ((rc = Md.alloc(N)) || (rc = Pd.alloc(N)) || (rc = Rd.alloc((size_t)nblk)) || (rc = pairs.alloc(2 * (size_t)nblk)) || (rc = cpart.alloc(2 * (size_t)t.nchunk())) ||
+      (rc = out.alloc(4)) || (rc = off_d.from(off)) || (rc = len_d.from(len)) || (rc = blk_d.from(std::vector<int>(blk, blk + nblk))) ||
+      (rc = wave_d.from(t.wave)) || (rc = chunk_d.from(t.chunk)) || (rc = large_d.from(t.large)))
+    return rc;
+  if ((rc = staged_h2d(Md.p + offset, M_inout, sizeof(double) * (size_t)n)) || (rc = staged_h2d(Pd.p + offset, P_inout, sizeof(double) * (size_t)n)) ||
+      (rc = staged_h2d(Rd.p, R, sizeof(double) * (size_t)nblk)))
+    return rc;
+  CUADMM_HIP_TRY(hipMemset(pairs.p, 0xff, sizeof(double) * pairs.n));
+  LbNormArgs a{Md.p + offset, Pd.p + offset, off_d.p, len_d.p, wave_d.p, chunk_d.p, large_d.p, t.nwave(), t.nchunk(), t.nlarge(), cpart.p, pairs.p};
+  if ((rc = launch_lb_block_norms(a, nullptr))) return rc;
+  if ((rc = launch_lb_combine(nblk, pairs.p, Rd.p, len_d.p, blk_d.p, nullptr, out.p, nullptr))) return rc;
+  CUADMM_HIP_TRY(hipDeviceSynchronize());
+  double o4[4];
+  if ((rc = staged_d2h(M_inout, Md.p + offset, sizeof(double) * (size_t)n)) || (rc = staged_d2h(P_inout, Pd.p + offset, sizeof(double) * (size_t)n)) ||
+      (rc = staged_d2h(pairs_out, pairs.p, sizeof(double) * 2 * (size_t)nblk)) || (rc = staged_d2h(o4, out.p, sizeof(double) * 4)))
+    return rc;
+  comb3_out[0] = o4[0]; comb3_out[1] = o4[1]; comb3_out[2] = o4[2];
   return CUADMM_OK;
 }
 

@@ -71,6 +71,14 @@ class Problem:
         check(lib.cuadmm_coo_to_csc(_p(cp), _p(cols), _p(rows), _p(vals), int(vals.size), int(con_num)))
         return cls(vec_len, con_num, blk, cp, rows, vals, b_idx, b_val, C_idx, C_val)
 
+    def trace_bounds(self):
+        """Trace bounds read off the constraints (cuadmm_trace_bounds_detect): one number per block, -1 where nothing was found."""
+        R = np.full(self.mat_num, -1.0)
+        check(_lib.load().cuadmm_trace_bounds_detect(self.vec_len, self.con_num, _p(self.At_csc_col_ptrs), _p(self.At_csc_row_ids),
+                                                     _p(self.At_csc_vals), _p(self.b_indices), _p(self.b_vals), self.b_nnz,
+                                                     _p(self.blk_vals), self.mat_num, _p(R)))
+        return R
+
 
 class SDPSolver:
     """Mirror of class SDPSolver (include/cuadmm/solver.h:30-248)."""
@@ -126,10 +134,10 @@ class SDPSolver:
         return {"memory": int(o[0]), "taken": int(o[1]), "accepted": int(o[2]), "rejected": int(o[3]), "restarts": int(o[4]),
                 "columns": int(o[5]), "ms": float(o[6]), "ring_bytes": float(o[7])}
 
-    STATUS_NAMES = ("none", "converged", "iteration_limit", "primal_infeasible", "dual_infeasible")
+    STATUS_NAMES = ("none", "converged", "iteration_limit", "primal_infeasible", "dual_infeasible", "certified_gap")
 
     def status(self):
-        """How the last solve ended (cuadmm_get_status); option "infeas_check" adds the two infeasible statuses."""
+        """How the last solve ended (cuadmm_get_status); option "infeas_check" adds the two infeasible statuses, "gap_check" certified_gap."""
         o = np.zeros(8)
         check(self._lib.cuadmm_get_status(self._h, _p(o)))
         return {"status": int(o[0]), "name": self.STATUS_NAMES[int(o[0])], "iteration": int(o[1]), "checks": int(o[2]), "scalar": float(o[3]),
@@ -145,6 +153,32 @@ class SDPSolver:
         y = np.zeros(self.con_num)
         check(self._lib.cuadmm_get_certificate(self._h, _p(y), None))      # any status but 3: the library's error
         return "primal", y
+
+    def set_trace_bounds(self, R):
+        """One R_k >= 0 per block (PSD: tr X_k <= R_k, unconstrained: ||x_k|| <= R_k) for lower_bound() / option "gap_check"; None clears."""
+        if R is None:
+            check(self._lib.cuadmm_set_trace_bounds(self._h, None, 0))
+            return
+        Ra = _f64(R)
+        check(self._lib.cuadmm_set_trace_bounds(self._h, _p(Ra), int(Ra.size)))
+
+    def lower_bound(self, per_block=False):
+        """The certified lower bound at the current y (cuadmm_lower_bound); per_block adds nu_k and ||S^_k||_F per block."""
+        o = np.zeros(8)
+        pb = np.zeros(2 * self.mat_num) if per_block else None
+        check(self._lib.cuadmm_lower_bound(self._h, _p(o), _p(pb)))
+        r = {"lower_bound": float(o[0]), "bty": float(o[1]), "penalty": float(o[2]), "gap": float(o[3]), "worst_block": int(o[4]),
+             "worst_term": float(o[5]), "ms": float(o[6]), "bytes": float(o[7])}
+        if per_block:
+            r["nu"], r["norm_S"] = pb[0::2].copy(), pb[1::2].copy()
+        return r
+
+    def gap_info(self):
+        """Option "gap_check" in the last solve (cuadmm_get_gap_info)."""
+        o = np.zeros(8)
+        check(self._lib.cuadmm_get_gap_info(self._h, _p(o)))
+        return {"checks": int(o[0]), "best_lower_bound": float(o[1]), "best_iteration": int(o[2]), "last_lower_bound": float(o[3]),
+                "last_gap": float(o[4]), "ms": float(o[5]), "bytes": float(o[6]), "verdict_iteration": int(o[7])}
 
     def set_allreduce(self, fn):
         """fn(dev_ptr:int, count:int, hip_stream:int) -> None : in-place sum over ranks on that stream."""

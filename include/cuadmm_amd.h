@@ -88,6 +88,15 @@ void cuadmm_destroy(cuadmm_solver* s);
  *                   a projection plan of its own.  Runs one iteration per launch (no batches, no early y-solve); refused at init together
  *                   with world > 1, an in-process group, eig_rank > 0 or accel > 0.  Weak infeasibility is not detected.  Set before cuadmm_init.
  *   "infeas_tol"    default 1e-6: a ray is a certificate when its violation eta is at most infeas_tol times its scalar (b'dy or -C'dx, per unit norm)
+ *   "gap_check"     period p of the certified-gap check ("Certified lower bound"): 0 (default) = off, an integer from 2 to
+ *                   1 000 000 = every p iterations the lower bound of cuadmm_lower_bound is formed at the iteration's y; the solve keeps the
+ *                   best one (cuadmm_get_gap_info) and ends with status 5 when g = |pobj - LB| / (1 + |pobj| + |LB|) <= gap_tol and
+ *                   errRp <= gap_tol.  Anything else is CUADMM_ERR_INVALID.  Needs trace bounds (cuadmm_set_trace_bounds before
+ *                   cuadmm_init).  Costs 2 L + m doubles, the per-block lists and, from the first check, a projection plan of its own.
+ *                   Runs one iteration per launch (no batches, no early y-solve); refused at init together with world > 1, an in-process
+ *                   group, eig_rank > 0, accel > 0 or infeas_check > 0.  Without a verdict the run is the run with the option off, bit for
+ *                   bit.  Set before cuadmm_init.
+ *   "gap_tol"       default 0 = the solve's stop_tol: the tolerance of the certified-gap verdict
  *   (every other switch: INTEGRATION.md section 6)
  */
 int cuadmm_set_option(cuadmm_solver* s, const char* key, double value);
@@ -253,7 +262,8 @@ int cuadmm_get_accel_info(const cuadmm_solver* s, double out8[8]);
  * 1 <= cols <= 16, by Cholesky in long double.  Host only (no device needed).  CUADMM_ERR_FACTOR when a pivot is not positive. */
 int cuadmm_accel_solve_ls(const double* gram, const double* rhs, int cols, double reg, double* gamma_out);
 /* How the last cuadmm_solve ended.  [0] status: 0 = no solve yet (or the problem / iterate was replaced since: cuadmm_update_bC,
- * cuadmm_update_A, cuadmm_set_XyS), 1 = converged, 2 = iteration limit, 3 = primal infeasible, 4 = dual infeasible (primal unbounded);
+ * cuadmm_update_A, cuadmm_set_XyS), 1 = converged, 2 = iteration limit, 3 = primal infeasible, 4 = dual infeasible (primal unbounded),
+ * 5 = certified gap (option "gap_check": cuadmm_get_gap_info has the bound);
  * [1] iteration of the verdict; then, of option "infeas_check" (zeros while it is off): [2] checks run in that solve, [3] beta = b'dy / ||dy||
  * (status 3) or gamma = -C'dX / ||dX|| (status 4) in the engine's scaled space, [4] eta = ||P+(A'dy)|| / ||dy|| (status 3) or
  * max(||A dX||, ||P+(-dX)||) / ||dX|| (status 4), [5] the certified radius in the caller's units: status 3: no X >= 0 with A X = b has
@@ -271,6 +281,33 @@ int cuadmm_get_certificate(cuadmm_solver* s, double* y_out, double* X_out);
  * -tol C'dX, else 0 (a NaN in a test's numbers: no verdict from it); radius (may be null): scalar / eta in the scaled space, infinite when
  * eta = 0.  Host only (no device needed). */
 int cuadmm_infeas_decide(const double stats[8], double tol, int* verdict, double* radius);
+/* Trace bounds for the certified lower bound ("Certified lower bound"): one number R_k >= 0 per block of blk_vals, in the
+ * caller's units -- PSD block: every feasible X has tr X_k <= R_k; unconstrained block: ||x_k||_2 <= R_k.  They are a property of the
+ * feasible set the caller asserts: the values are copied and survive cuadmm_update_bC / cuadmm_update_A.  R = NULL clears them (refused
+ * on an initialised solver with option "gap_check" on).  A value that is negative or not finite, or a mat_num that is not the problem's
+ * (checked here on an initialised solver, else at cuadmm_init): CUADMM_ERR_INVALID, and the solver keeps what it had.  Before or after
+ * cuadmm_init. */
+int cuadmm_set_trace_bounds(cuadmm_solver* s, const double* R, int mat_num);
+/* A lower bound on the optimal value that holds for EVERY y: with S^ = C - A'y,
+ *   LB(y) = b'y - sum_k R_k nubar_k,  nubar_k = ||P+(-S^_k)||_F + 2e-12 sqrt(2 len_k) ||S^_k||_F (PSD block), ||S^_k||_2 (unconstrained),
+ * evaluated at the y cuadmm_get_y would return, on any initialised solver with trace bounds set (before a solve, after one, between
+ * solve(..., if_first = 0) calls, after solves with any option); refused for world > 1 and in-process groups.  It changes nothing the
+ * iteration reads: a following cuadmm_solve continues bit for bit as without the call.  The second term of nubar_k is the projection
+ * kernels' accuracy; the rounding of A'y - C itself is not covered.  out8 (caller's units): [0] LB, [1] b'y, [2] sum R_k nubar_k,
+ * [3] g = |pobj - LB| / (1 + |pobj| + |LB|) against the pobj of the current state, [4] the block with the largest term, [5] its term
+ * R_k nubar_k, [6] milliseconds of device time (HIP events), [7] bytes of device memory the bound holds (its vectors exactly, plus an
+ * estimate of its projection plan).  per_block (may be NULL): 2 mat_num doubles, [2k] nu_k = ||P+(-S^_k)||_F or ||S^_k||_2, [2k + 1] ||S^_k||_F. */
+int cuadmm_lower_bound(cuadmm_solver* s, double out8[8], double* per_block);
+/* Option "gap_check" in the last cuadmm_solve: [0] checks run, [1] the best (largest) lower bound of that solve -- every one of them is
+ * valid --, [2] its iteration, [3] the last bound, [4] the last g, [5] milliseconds of device time in the checks, [6] bytes held (as [7]
+ * of cuadmm_lower_bound), [7] iteration of the status-5 verdict or 0.  Zeros while the option is off; cleared where the status is. */
+int cuadmm_get_gap_info(const cuadmm_solver* s, double out8[8]);
+/* Trace bounds read off the constraints (the arrays of cuadmm_init).  R_out[k] = -1: nothing found (always for unconstrained blocks).
+ * Rule 1: a constraint whose entries are exactly the diagonal slots of ONE PSD block, all with the same value c (c svec(I_k)), gives
+ * tr X_k = b_j / c.  Rule 2: a block whose every diagonal entry is fixed by a constraint with that single entry has the sum of those
+ * values as its trace.  The smaller one where both fire; a negative right-hand side: that rule finds nothing.  Host only (no device needed). */
+int cuadmm_trace_bounds_detect(int vec_len, int con_num, const int* At_csc_col_ptrs, const int* At_csc_row_ids, const double* At_csc_vals,
+                               const int* b_indices, const double* b_vals, int b_nnz, const int* blk_vals, int mat_num, double* R_out);
 /* The in-process group a handle leads after cuadmm_duo_init(device_num_requested = N) from one process (reference
  * src/duo_solver.cu:487-577): [0] engines in the group (1: no group), [1] exchange of its all-reduce -- 1 = device side (each
  * rank's kernel adds the N staging buffers out of its peers' memory: one shared device, or peer access over xGMI as
@@ -502,6 +539,13 @@ int cuadmm_op_accel_combine(int64_t L, int cols, const double* ring_dF, const do
  * behind a 16-byte boundary (the kernel's one-double path), 0 on one (two doubles per access). */
 int cuadmm_op_infeas_roll(int64_t n, const double* cur, double* prev_inout, const double* w, int negate, int nz, const int64_t* zoff, const int64_t* zlen,
                           int offset, double* d_out, double* sums2_out);
+/* The per-block norm kernels of the lower bound on host arrays (csrc/lower_bound.hip): pairs_out[2k] = sum of M^2, [2k + 1] = sum of P^2
+ * over the slots of block k (blk: sizes as in cuadmm_init; offs: first slot of every block in the n-vectors, NULL: one behind the other
+ * from slot 0); comb3_out = [sum_k R_k nubar_k, the block with the largest term, that term] with nubar_k as in cuadmm_lower_bound on
+ * sqrt(pairs).  offset = 1 places both vectors one double behind a 16-byte boundary, so that the one-double heads and tails run.  M and P
+ * are copied back as the kernels left them. */
+int cuadmm_op_lb_block_norms(int64_t n, double* M_inout, double* P_inout, int nblk, const int* blk, const int64_t* offs, const double* R, int offset,
+                             double* pairs_out, double* comb3_out);
 int cuadmm_op_spmv_rows(int rows, int ncols, const int* row_ptrs, const int* col_ids, const double* vals, const double* X, const double* S, const double* C,
                         int want_x, int want_s, const int* rowmap, int out_len, double* outX, double* outS, int* info4);
 int cuadmm_op_rp_stats(int m, const double* ax, const double* b, const double* normA, const double* y, double bscale, const double* sums2, double* out4);

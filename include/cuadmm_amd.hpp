@@ -103,7 +103,7 @@ class SDPSolver {
   }
 
   // how the last solve ended (cuadmm_get_status); option "infeas_check" adds the two infeasible statuses; not in the reference
-  enum Status { kNoSolve = 0, kConverged = 1, kIterationLimit = 2, kPrimalInfeasible = 3, kDualInfeasible = 4 };
+  enum Status { kNoSolve = 0, kConverged = 1, kIterationLimit = 2, kPrimalInfeasible = 3, kDualInfeasible = 4, kCertifiedGap = 5 };
   struct StatusInfo { Status status; int iteration; long long checks; double scalar, eta, radius, ms, bytes; };
   StatusInfo status() const {
     double o[8] = {0};
@@ -118,6 +118,29 @@ class SDPSolver {
     std::vector<double> ray((size_t)(st.status == kDualInfeasible ? vl : cn));
     check(cuadmm_get_certificate(h_, st.status == kDualInfeasible ? nullptr : ray.data(), st.status == kDualInfeasible ? ray.data() : nullptr));
     return ray;
+  }
+
+  // trace bounds (one per block; PSD: tr X_k <= R_k, unconstrained: ||x_k|| <= R_k) for lower_bound() and option "gap_check";
+  // an empty vector clears them; not in the reference
+  void set_trace_bounds(const std::vector<double>& R) { check(cuadmm_set_trace_bounds(h_, R.empty() ? nullptr : R.data(), (int)R.size())); }
+  // cuadmm_lower_bound at the current y; per_block (may be null): resized to 2 mat_num, [2k] nu_k, [2k + 1] ||S^_k||_F
+  struct LowerBound { double lower_bound, bty, penalty, gap; int worst_block; double worst_term, ms, bytes; };
+  LowerBound lower_bound(std::vector<double>* per_block = nullptr) {
+    double o[8] = {0};
+    if (per_block) {
+      int vl = 0, cn = 0, mn = 0;
+      check(cuadmm_get_dims(h_, &vl, &cn, &mn));
+      per_block->assign(2 * (size_t)mn, 0.0);
+    }
+    check(cuadmm_lower_bound(h_, o, per_block ? per_block->data() : nullptr));
+    return LowerBound{o[0], o[1], o[2], o[3], (int)o[4], o[5], o[6], o[7]};
+  }
+  // option "gap_check" in the last solve (cuadmm_get_gap_info)
+  struct GapInfo { long long checks; double best_lower_bound; int best_iteration; double last_lower_bound, last_gap, ms, bytes; int verdict_iteration; };
+  GapInfo gap_info() const {
+    double o[8] = {0};
+    check(cuadmm_get_gap_info(h_, o));
+    return GapInfo{(long long)o[0], o[1], (int)o[2], o[3], o[4], o[5], o[6], (int)o[7]};
   }
 
   // cuadmm_update_bC: new b and / or C on the factored solver (nnz < 0: unchanged); not in the reference
