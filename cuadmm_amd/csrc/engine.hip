@@ -102,6 +102,13 @@ static void host_ranges(int m, F&& body) {   // body(chunk, lo, hi)
   }, &ctx);
 }
 
+// milliseconds between two recorded events; 0, with the runtime's error cleared, where it cannot tell
+static float event_ms(hipEvent_t a, hipEvent_t b) {
+  float t = 0;
+  if (hipEventElapsedTime(&t, a, b) != hipSuccess) { t = 0; (void)hipGetLastError(); }
+  return t;
+}
+
 enum KClass { K_ATY = 0, K_PSD = 1, K_POST = 2, K_SPMV = 3, K_COPY = 4, K_HOST = 5, K_COMM = 6, K_TAIL = 7, K_NUM = CUADMM_NUM_KCLASS };
 
 // direct RCCL binding (symbols resolved at run time so that a process that already loaded an RCCL,
@@ -164,7 +171,7 @@ struct cuadmm_solver {
   int comm_world = 1, comm_rank = 0, m_full = 0, blk_off = 0;
   int L_caller = 0, nblk_caller = 0;   // the caller's vec_len / mat_num (cuadmm_get_dims reports the caller's numbering)
   long long sv_off = 0;
-  std::vector<int> cons_local;
+  std::vector<int> cons_local, cons_g2l;   // this rank's constraints in the caller's numbering, and the way back (-1: another rank's)
   double ov_nb = 0, ov_nc = 0, ov_nb2 = 0;
   DevBuf<double> scal_d, yfull_d, b_d, normA_d;
   PinnedBuf<double> h_scal;
@@ -384,64 +391,70 @@ struct cuadmm_solver {
 
   // Infeasibility detection behind the iteration (option "infeas_check" = period p; infeas.h, DESIGN.md "Infeasibility certificates").
   // Every p iterations the differences of y and X against the snapshot taken p iterations earlier are tested for the two certificates.
-  // The projections go through a plan of the check's own (plan2): the iteration's plan carries the sign schedule's warm start and the
-  // longest-block-first order from one iteration to the next, and a foreign matrix projected through it would change the trajectory.
+  // The projections, their two svec work vectors and b on the device are the auxiliary projector's (aux).
   struct Infeas {
     int period = 0;
     double tol = 1e-6;
-    DevBuf<double> xprev, yprev, dbuf, pbuf, dy, adx, bcopy, partials, stats_d;
+    DevBuf<double> xprev, yprev, dy, adx, partials, stats_d;
     PinnedBuf<double> h_stats;
-    PsdPlan* plan2 = nullptr;
     std::vector<std::pair<long long, long long>> free_rng;   // svec ranges of the unconstrained blocks
     bool have_snap = false;
     // of the last solve
-    int status = 0, verdict_iter = 0;
     long long checks = 0;
     double scalar = 0, eta = 0, radius = 0, ms = 0;
     std::vector<double> cert;         // the ray of a verdict, scaled space and internal order (y: m, X: L)
-    double plan2_bytes = 0;           // device memory the second plan took when it was built (estimate: free memory before - after)
-    hipEvent_t ev[2] = {};
-    double bytes() const {
-      return 8.0 * (double)(xprev.n + yprev.n + dbuf.n + pbuf.n + dy.n + adx.n + bcopy.n + partials.n + stats_d.n) + plan2_bytes;
-    }
-    ~Infeas() { for (auto& e : ev) if (e) { hipError_t r = hipEventDestroy(e); (void)r; } delete plan2; }
+    double bytes() const { return 8.0 * (double)(xprev.n + yprev.n + dy.n + adx.n + partials.n + stats_d.n); }
   } inf;
   bool infeas_on() const { return inf.period > 0 && L > 0; }
-  void infeas_reset() { inf.have_snap = false; inf.status = 0; inf.verdict_iter = 0; inf.checks = 0; inf.scalar = inf.eta = inf.radius = 0; inf.cert.clear(); }
+  // how the last solve ended and behind which iteration (cuadmm_get_status; 3, 4: infeas_step, 5: lb_step)
+  int solve_status = 0, solve_status_iter = 0;
+  void infeas_reset() { inf.have_snap = false; solve_status = 0; solve_status_iter = 0; inf.checks = 0; inf.scalar = inf.eta = inf.radius = 0; inf.cert.clear(); }
   int infeas_begin_solve();
   int infeas_step(int iter, double stop_tol);
 
   // Certified lower bound from trace bounds (cuadmm_set_trace_bounds, cuadmm_lower_bound, option "gap_check" = period p; lower_bound.h,
-  // DESIGN.md "Certified lower bound").  M = A'y - C (the iteration's kernel, into a vector of the bound's own), P = P+(M) through a plan
-  // of the bound's own as the infeasibility check has one, then one pass of per-block norms and a combine kernel: four doubles cross.
+  // DESIGN.md "Certified lower bound").  M = A'y - C (the iteration's kernel, into the auxiliary projector's input vector), P = P+(M) through
+  // its plan, then one pass of per-block norms and a combine kernel: four doubles cross.
   struct Lb {
     int period = 0;
     double tol = 0;                    // 0: the solve's stop_tol
     std::vector<double> R;             // the caller's bounds, one per block (empty: none set)
     bool R_dirty = false;
-    DevBuf<double> mbuf, pbuf, ybuf, bcopy, R_d, pairs, cpart, dpart, out_d;
+    DevBuf<double> ybuf, R_d, pairs, cpart, dpart, out_d;
     DevBuf<long long> off_d, len_d;
     DevBuf<int> blk_d, wave_d, chunk_d, large_d;
     int nwave = 0, nchunk = 0, nlarge = 0;
     PinnedBuf<double> h_out;
-    PsdPlan* plan2 = nullptr;
-    double plan2_bytes = 0;
-    hipEvent_t ev[2] = {};
     // of the last solve with the option on
     long long checks = 0;
     int best_iter = 0, verdict_iter = 0;
     double best_lb = 0, last_lb = 0, last_g = 0, ms = 0;
     double bytes() const {
-      return 8.0 * (double)(mbuf.n + pbuf.n + ybuf.n + bcopy.n + R_d.n + pairs.n + cpart.n + dpart.n + out_d.n + off_d.n + len_d.n) +
-             4.0 * (double)(blk_d.n + wave_d.n + chunk_d.n + large_d.n) + plan2_bytes;
+      return 8.0 * (double)(ybuf.n + R_d.n + pairs.n + cpart.n + dpart.n + out_d.n + off_d.n + len_d.n) +
+             4.0 * (double)(blk_d.n + wave_d.n + chunk_d.n + large_d.n);
     }
-    ~Lb() { for (auto& e : ev) if (e) { hipError_t r = hipEventDestroy(e); (void)r; } delete plan2; }
   } lb;
   bool gap_on() const { return lb.period > 0 && L > 0; }
   void lb_reset() { lb.checks = 0; lb.best_iter = lb.verdict_iter = 0; lb.best_lb = lb.last_lb = lb.last_g = 0; }
   int lb_prepare();
   int lb_eval(const double* y_scaled_d, double out6[6], float* ms);
   int lb_step(int iter, double stop_tol);
+
+  // The auxiliary projector of the infeasibility check and the lower bound ("Infeasibility certificates"): a plan beside the
+  // iteration's, an svec-length input and output vector, b on the device where the engine keeps none there, a pair of events.  The two
+  // users never run inside one another and the plan carries no result from one projection to the next, so one object serves both.
+  struct AuxProj {
+    PsdPlan* plan = nullptr;           // built at the first projection: the solver's psd_* options, the full projection
+    DevBuf<double> in, out, bcopy;
+    double plan_bytes = 0;
+    hipEvent_t ev[2] = {};
+    int ensure(cuadmm_solver& s);      // vectors and events on first use; b, which may have changed, on every call
+    const double* b_dev(const cuadmm_solver& s) const { return s.b_d.p ? s.b_d.p : bcopy.p; }
+    int project(cuadmm_solver& s, const double* from, double* to);
+    bool failed(hipStream_t st) const { return plan && plan->fail_count(st) > 0; }
+    double bytes() const { return 8.0 * (double)(in.n + out.n + bcopy.n) + plan_bytes; }
+    ~AuxProj() { for (auto& e : ev) if (e) { hipError_t r = hipEventDestroy(e); (void)r; } delete plan; }
+  } aux;
 
   // profiling
   hipEvent_t ev0[K_NUM][2] = {}, ev1[K_NUM][2] = {};
@@ -477,7 +490,7 @@ struct cuadmm_solver {
     for (int k = 0; k < K_NUM; ++k) {
       for (int j = 0; j < ev_used[k]; ++j) {
         float ms = 0;
-        if (hipEventElapsedTime(&ms, ev0[k][j], ev1[k][j]) == hipSuccess) { prof_ms[k] += ms; prof_count[k] += 1; }
+        if (hipEventElapsedTime(&ms, ev0[k][j], ev1[k][j]) == hipSuccess) { prof_ms[k] += ms; prof_count[k] += 1; }   // (a sample only where the read succeeds)
       }
       ev_used[k] = 0;
     }
@@ -791,6 +804,27 @@ struct cuadmm_solver {
   // X, S, y back in the caller's units (solver.cu:814-816); a no-op unless a solve left them scaled
   int materialise();
   int sync_y_host();
+  int reset_solve_state(double t_begin);
+
+  // bscale from nb2 = sum (b_i / normA_i)^2 and b_p from bfull = b / normA (this rank's constraints, the caller's order): solver.cu:169-191
+  void set_scaled_b(const std::vector<double>& bfull, double nb2) {
+    bscale = 1 + std::sqrt(nb2);
+    const double ibs = 1 / bscale;             // *_div_scalar multiply by 1/s (dense_scalar.cu:77-81)
+    for (int pidx = 0; pidx < m; ++pidx) b_p[pidx] = bfull[perm[pidx]] * ibs;
+  }
+  // Rp = b - A X from the fetched A X (host y-solve; with the solve on the device Rp never exists on the host)
+  void refresh_Rp() {
+    for (int i = 0; i < m && !dev_solve; ++i) Rp_p[i] = -h_out.p[i] + b_p[i];
+  }
+  // the scalars of the stopping test (solver.cu:195-228, 764-799) from nr = ||normA Rp bscale||^2, b'y and the two sums behind A X in h_out
+  void set_residual_scalars(double nr, double bty) {
+    errRp = std::sqrt(nr) / norm_borg;
+    errRd = std::sqrt(h_out.p[(size_t)m]) * Cscale / norm_Corg;
+    maxfeas = std::max(errRp, errRd);
+    pobj = h_out.p[(size_t)m + 1] * objscale;
+    dobj = bty * objscale;
+    relgap = std::fabs(pobj - dobj) / (1 + std::fabs(pobj) + std::fabs(dobj));
+  }
 
   int launch_post_mode(int mode, double tau) {
     prof_begin(K_POST);
@@ -811,6 +845,21 @@ struct DeviceGuard {
   DeviceGuard(const DeviceGuard&) = delete;
   DeviceGuard& operator=(const DeviceGuard&) = delete;
 };
+
+// `in_group_call` marks the calls an in-process group (duo_group.hip) makes on its own ranks, rank 0 -- the leader itself -- included
+template <class F>
+static int as_group_rank(cuadmm_solver* q, F&& call) {
+  q->in_group_call = true;
+  const int rc = call(q);
+  q->in_group_call = false;
+  return rc;
+}
+// the leader forwards an entry point: every rank runs `call`, ranks >= 1 on their own host threads
+template <class F>
+static int group_forward(cuadmm_solver* s, F&& call) {
+  DeviceGuard keep_device;                  // the ranks' devices are made current on this thread: leave the caller's as it was
+  return duo_group_run(s->group, [&](cuadmm_solver* q, int) { return as_group_rank(q, call); });
+}
 
 static int check_device(int device) {
   int n = 0;
@@ -839,6 +888,49 @@ struct InitCtx {
   std::vector<int> rp, rci;      // A^T in CSR over the svec rows: row pointers, constraint of every entry
   std::vector<double> rv;
 };
+
+// max(1, ||v[lo, hi)||): what a constraint's column is divided by (get_normA, sparse_matrix_norm.cu:11-31)
+static double cons_norm(const double* v, int lo, int hi) {
+  double nrm = 0.0;
+  for (int p = lo; p < hi; ++p) nrm += v[p] * v[p];
+  return std::max(1.0, std::sqrt(nrm));
+}
+
+static double sum_sq(const double* v, int n) {
+  double t = 0;
+  for (int i = 0; i < n; ++i) t += v[i] * v[i];
+  return t;
+}
+// the indices of a sparse vector (`what` of entry point `who`): inside [0, n), none twice (the norms would count both entries, the vector one)
+static int check_sparse_idx(const char* who, const char* what, const int* idx, int nnz, long long n) {
+  std::vector<char> seen((size_t)n, 0);
+  for (int i = 0; i < nnz; ++i) {
+    if (idx[i] < 0 || idx[i] >= n) { set_error("%s: %s index %d out of range", who, what, idx[i]); return CUADMM_ERR_INVALID; }
+    if (seen[idx[i]]) { set_error("%s: %s index %d appears twice", who, what, idx[i]); return CUADMM_ERR_INVALID; }
+    seen[idx[i]] = 1;
+  }
+  return CUADMM_OK;
+}
+// sum (val_i / norm[idx_i])^2 over the entries, in their order (sparse_dense.cu:11-20)
+static double sum_scaled_sq(const int* idx, const double* val, int nnz, const double* norm) {
+  double t = 0;
+  for (int i = 0; i < nnz; ++i) { const double v = val[i] / norm[idx[i]]; t += v * v; }
+  return t;
+}
+// full[j] = val_i / normA[j] for the entries of this rank (j = g2l[idx_i], -1: another rank's; g2l null: j = idx_i); returns their sum of squares
+static double scaled_b(const int* idx, const double* val, int nnz, const int* g2l, const std::vector<double>& normA, std::vector<double>& full) {
+  double t = 0;
+  full.assign(normA.size(), 0.0);
+  for (int i = 0; i < nnz; ++i) {
+    const int j = g2l ? g2l[idx[i]] : idx[i];
+    if (j < 0) continue;
+    const double v = val[i] / normA[j];
+    full[j] = v;
+    t += v * v;
+  }
+  return t;
+}
+
 #define CUADMM_INIT_STAGE_PROLOGUE \
   const int vec_len = in.vec_len, con_num = in.con_num, At_nnz = in.At_nnz, b_nnz = in.b_nnz, C_nnz = in.C_nnz, mat_num = in.mat_num; \
   const int *At_cp = in.At_cp, *At_ri = in.At_ri, *b_idx = in.b_idx, *C_idx = in.C_idx, *blk = in.blk; \
@@ -876,9 +968,7 @@ static int init_normalise(Solver* s, const InitIn& in, InitCtx& c) {
   if (!s->upa.in_update) { s->upa.cp.assign(At_cp, At_cp + m + 1); s->upa.ri.assign(At_ri, At_ri + At_nnz); }
   s->normA.assign(m, 1.0);
   for (int j = 0; j < m; ++j) {
-    double nrm = 0.0;
-    for (int p = At_cp[j]; p < At_cp[j + 1]; ++p) nrm += vals[p] * vals[p];
-    nrm = std::max(1.0, std::sqrt(nrm));
+    const double nrm = cons_norm(vals.data(), At_cp[j], At_cp[j + 1]);
     s->normA[j] = nrm;
     for (int p = At_cp[j]; p < At_cp[j + 1]; ++p) vals[p] /= nrm;
   }
@@ -1192,30 +1282,13 @@ static int init_matrices(Solver* s, const InitIn& in, InitCtx& c) {
 static int init_vectors(Solver* s, const InitIn& in, InitCtx& c) {
   CUADMM_INIT_STAGE_PROLOGUE
   // --- scaling (solver.cu:169-191)
-  double nb = 0, nc = 0;
-  for (int i = 0; i < b_nnz; ++i) nb += b_vals[i] * b_vals[i];
-  for (int i = 0; i < C_nnz; ++i) nc += C_vals[i] * C_vals[i];
-  if (s->local_mode) { nb = s->ov_nb; nc = s->ov_nc; }      // norms over ALL constraints / the whole C
+  if ((rc = check_sparse_idx("init", "b", b_idx, b_nnz, m))) return rc;
+  std::vector<double> bfull;
+  double nb = sum_sq(b_vals, b_nnz), nc = sum_sq(C_vals, C_nnz), nb2 = scaled_b(b_idx, b_vals, b_nnz, nullptr, s->normA, bfull);
+  if (s->local_mode) { nb = s->ov_nb; nb2 = s->ov_nb2; nc = s->ov_nc; }      // norms over ALL constraints / the whole C
   s->norm_borg = 1 + std::sqrt(nb);
   s->norm_Corg = 1 + std::sqrt(nc);
   s->upa.b_idx.assign(b_idx, b_idx + b_nnz); s->upa.b_val.assign(b_vals, b_vals + b_nnz);
-  std::vector<double> bfull(m, 0.0);
-  std::vector<char> seen_b((size_t)m, 0);
-  double nb2 = 0;
-  for (int i = 0; i < b_nnz; ++i) {
-    if (b_idx[i] < 0 || b_idx[i] >= m) { set_error("init: b index %d out of range", b_idx[i]); return CUADMM_ERR_INVALID; }
-    // a sparse vector with a repeated index has no defined value (the norms would count both entries, the vector one)
-    if (seen_b[b_idx[i]]) { set_error("init: b index %d appears twice", b_idx[i]); return CUADMM_ERR_INVALID; }
-    seen_b[b_idx[i]] = 1;
-    double v = b_vals[i] / s->normA[b_idx[i]];             // sparse_dense.cu:11-20
-    bfull[b_idx[i]] = v;
-    nb2 += v * v;
-  }
-  if (s->local_mode) nb2 = s->ov_nb2;
-  s->bscale = 1 + std::sqrt(nb2);
-  s->Cscale = 1 + std::sqrt(nc);
-  s->objscale = s->bscale * s->Cscale;
-  const double ibs = 1 / s->bscale, ics = 1 / s->Cscale;   // *_div_scalar multiply by 1/s (dense_scalar.cu:77-81)
   if (s->y_registered) {   // a second init on the same handle: the registration must not outlive the storage it names
     hipError_t e = hipHostUnregister(s->y_p.data()); (void)e;
     s->y_registered = false;
@@ -1224,10 +1297,13 @@ static int init_vectors(Solver* s, const InitIn& in, InitCtx& c) {
   s->y_best_p.assign(m, 0.0);
   if (m > 0 && hipHostRegister(s->y_p.data(), sizeof(double) * (size_t)m, hipHostRegisterDefault) == hipSuccess) s->y_registered = true;
   else { hipError_t e = hipGetLastError(); (void)e; }   // not fatal: upload_y then stages through the pinned buffer
+  s->set_scaled_b(bfull, nb2);
+  s->Cscale = 1 + std::sqrt(nc);
+  s->objscale = s->bscale * s->Cscale;
+  const double ibs = 1 / s->bscale, ics = 1 / s->Cscale;   // *_div_scalar multiply by 1/s (dense_scalar.cu:77-81)
   for (int pidx = 0; pidx < m; ++pidx) {
     const int j = s->perm[pidx];
     s->normA_p[pidx] = s->normA[j];
-    s->b_p[pidx] = bfull[j] * ibs;
     if (y0) s->y_p[pidx] = (y0[j] * s->normA[j]) * ics;     // solver.cu:182,191
   }
   {
@@ -1462,8 +1538,8 @@ static int init_residuals(Solver* s, bool y_resident) {
   if ((rc = s->fetch_out(0, 2 * (size_t)m + 2))) return rc;
   {
     double nr = 0, bty = 0;
+    s->refresh_Rp();
     for (int i = 0; i < m && !s->dev_solve; ++i) {
-      s->Rp_p[i] = -s->h_out.p[i] + s->b_p[i];
       double ro = s->normA_p[i] * s->Rp_p[i] * s->bscale;
       nr += ro * ro;
       bty += s->b_p[i] * s->y_p[i];
@@ -1474,12 +1550,7 @@ static int init_residuals(Solver* s, bool y_resident) {
       else if ((rc = s->allreduce_scalars(v, 4))) return rc;
       nr = v[0]; bty = v[1]; s->h_out.p[(size_t)m] = v[2]; s->h_out.p[(size_t)m + 1] = v[3];
     }
-    s->errRp = std::sqrt(nr) / s->norm_borg;
-    s->errRd = std::sqrt(s->h_out.p[(size_t)m]) * s->Cscale / s->norm_Corg;
-    s->maxfeas = std::max(s->errRp, s->errRd);
-    s->pobj = s->h_out.p[(size_t)m + 1] * s->objscale;
-    s->dobj = bty * s->objscale;
-    s->relgap = std::fabs(s->pobj - s->dobj) / (1 + std::fabs(s->pobj) + std::fabs(s->dobj));
+    s->set_residual_scalars(nr, bty);
   }
   return rc;
 }
@@ -1698,16 +1769,10 @@ int cuadmm_init(cuadmm_solver* s, int eig_stream_num_per_gpu, int cpu_eig_thread
     if (all_owned) {
       const int me = s->rank;
       // global norms (solver.cu:169-191) from the full inputs every rank holds
-      double nb = 0, nc = 0, nb2 = 0;
-      for (int i = 0; i < b_nnz; ++i) {
-        if (b_idx[i] < 0 || b_idx[i] >= con_num) { set_error("init: b index %d out of range", b_idx[i]); return CUADMM_ERR_INVALID; }
-        nb += b_vals[i] * b_vals[i];
-        double cn = 0;
-        for (int p = At_cp[b_idx[i]]; p < At_cp[b_idx[i] + 1]; ++p) cn += At_vx[p] * At_vx[p];
-        const double v = b_vals[i] / std::max(1.0, std::sqrt(cn));
-        nb2 += v * v;
-      }
-      for (int i = 0; i < C_nnz; ++i) nc += C_vals[i] * C_vals[i];
+      { int rc = check_sparse_idx("init", "b", b_idx, b_nnz, con_num); if (rc) return rc; }
+      std::vector<double> norm_all((size_t)con_num);         // what a later cuadmm_update_bC divides the whole new b by
+      for (int j = 0; j < con_num; ++j) norm_all[j] = cons_norm(At_vx, At_cp[j], At_cp[j + 1]);
+      const double nb = sum_sq(b_vals, b_nnz), nc = sum_sq(C_vals, C_nnz), nb2 = sum_scaled_sq(b_idx, b_vals, b_nnz, norm_all.data());
       std::vector<int> cons, g2l(con_num, -1);
       for (int j = 0; j < con_num; ++j) if (owner[j] == me) { g2l[j] = (int)cons.size(); cons.push_back(j); }
       const long long lo = svb[me], hi = svb[me + 1];
@@ -1725,15 +1790,9 @@ int cuadmm_init(cuadmm_solver* s, int eig_stream_num_per_gpu, int cpu_eig_thread
       if (y0) { ly0.resize(cons.size()); for (size_t q = 0; q < cons.size(); ++q) ly0[q] = y0[cons[q]]; }
       s->local_mode = true;
       s->comm_world = s->world; s->comm_rank = s->rank;
-      s->m_full = con_num; s->cons_local = cons; s->sv_off = lo; s->blk_off = first[me];
+      s->m_full = con_num; s->cons_local = cons; s->cons_g2l = g2l; s->sv_off = lo; s->blk_off = first[me];
       s->L_caller = vec_len; s->nblk_caller = mat_num;
-      s->ov_nb = nb; s->ov_nc = nc; s->ov_nb2 = nb2;
-      s->normA_all.assign((size_t)con_num, 1.0);            // what a later cuadmm_update_bC divides the whole new b by
-      for (int j = 0; j < con_num; ++j) {
-        double cn = 0;
-        for (int p = At_cp[j]; p < At_cp[j + 1]; ++p) cn += At_vx[p] * At_vx[p];
-        s->normA_all[j] = std::max(1.0, std::sqrt(cn));
-      }
+      s->ov_nb = nb; s->ov_nc = nc; s->ov_nb2 = nb2; s->normA_all = norm_all;
       s->upa.g_cp.assign(At_cp, At_cp + con_num + 1);
       s->upa.g_from.clear();
       for (size_t q = 0; q < cons.size(); ++q)
@@ -1756,9 +1815,9 @@ int cuadmm_init(cuadmm_solver* s, int eig_stream_num_per_gpu, int cpu_eig_thread
   int rc;
   if ((rc = init_device(s, in, ctx)) || (rc = init_normalise(s, in, ctx)) || (rc = init_factor(s, in, ctx)) || (rc = init_plan(s, in, ctx)) ||
       (rc = init_matrices(s, in, ctx)) || (rc = init_vectors(s, in, ctx)) || (rc = init_solve_plan(s, in, ctx)) || (rc = init_closed(s, in, ctx)) ||
+      (rc = s->reset_solve_state(s->t_init0)) ||       // (in front of the residual stage, as in the updates: it clears Rp)
       (rc = init_finish(s, in, ctx)))
     return rc;
-  s->prim_win = 0; s->dual_win = 0; s->ratioconst = 1e0; s->sigmax = 1e3; s->sigmin = 1e-3;
   s->initialised = true;
   return CUADMM_OK;
 }
@@ -1771,15 +1830,10 @@ int cuadmm_solve(cuadmm_solver* s, int max_iter, double stop_tol, int sig_update
   if (!s || !s->initialised) { set_error("solve: solver not initialised"); return CUADMM_ERR_INVALID; }
   if (s->factor_bad) { set_error("solve: the last cuadmm_update_A could not factor the new A A^T; the solver needs a successful cuadmm_update_A first"); return CUADMM_ERR_FACTOR; }
   if (sig_update_stage_1 <= 0 || sig_update_stage_2 <= 0) { set_error("solve: sig_update stages must be positive"); return CUADMM_ERR_INVALID; }
-  if (s->group && !s->in_group_call) {    // the leader of an in-process group (duo_group.hip): every rank solves, on its own host thread
-    DeviceGuard keep_device;
-    return duo_group_run(s->group, [&](cuadmm_solver* q, int) {
-      q->in_group_call = true;
-      int r2 = cuadmm_solve(q, max_iter, stop_tol, sig_update_threshold, sig_update_stage_1, sig_update_stage_2, switch_admm, sigscale, if_first);
-      q->in_group_call = false;
-      return r2;
+  if (s->group && !s->in_group_call)      // the leader of an in-process group (duo_group.hip): every rank solves, on its own host thread
+    return group_forward(s, [&](cuadmm_solver* q) {
+      return cuadmm_solve(q, max_iter, stop_tol, sig_update_threshold, sig_update_stage_1, sig_update_stage_2, switch_admm, sigscale, if_first);
     });
-  }
   int rc = check_device(s->device);
   if (rc) return rc;
   s->y_early = false;                       // (a solve that ended in an error may have left it set)
@@ -1817,7 +1871,7 @@ int cuadmm_solve(cuadmm_solver* s, int max_iter, double stop_tol, int sig_update
     if ((rc = launch_scale(s->S.p, L, 1 / s->Cscale, s->st))) return rc;
     if ((rc = s->launch_spmv(true, true))) return rc;
     if ((rc = s->fetch_out(0, 2 * (size_t)m + 2))) return rc;
-    for (int i = 0; i < m && !s->dev_solve; ++i) s->Rp_p[i] = -s->h_out.p[i] + s->b_p[i];
+    s->refresh_Rp();
   }
 
   if (verbose) {
@@ -1827,7 +1881,7 @@ int cuadmm_solve(cuadmm_solver* s, int max_iter, double stop_tol, int sig_update
 
   if ((rc = s->batch_agree())) return rc;
   if (s->accel_on() && (rc = s->accel_begin_solve())) return rc;
-  s->inf.status = 0;
+  s->solve_status = 0;
   if (s->infeas_on() && (rc = s->infeas_begin_solve())) return rc;
   s->lb_reset();
   s->lb.ms = 0;
@@ -1835,23 +1889,27 @@ int cuadmm_solve(cuadmm_solver* s, int max_iter, double stop_tol, int sig_update
   const bool lpt_enabled = s->sw.lpt != 0;
   long long& lpt_ev = s->lpt_next;             // counts iterations over all solve calls of this solver
   if (!lpt_enabled) lpt_ev = 0;
+  // iteration i may change sigma in its step 5 (by reference: the switch to ADMM halves sig_update_stage_2 mid-solve)
+  const auto sig_may_change_at = [&](int i) {
+    return (i <= sig_update_threshold && i % sig_update_stage_1 == 1) || (i > sig_update_threshold && i % sig_update_stage_2 == 1);
+  };
   for (int iter = 1; iter <= max_iter + 1; ++iter) {
     // ---- Step 0 (solver.cu:419-467)
     if (std::max(s->maxfeas, s->relgap) < stop_tol) { breakyes = true; final_msg = "Solver ended: converged."; }
     if (iter > max_iter) { breakyes = true; final_msg = "Solver ended: maximum iteration reached"; }
-    if (s->inf.status == 5) {             // the certified gap behind the previous iteration (lb_step)
+    if (s->solve_status == 5) {           // the certified gap behind the previous iteration (lb_step)
       breakyes = true;
       char msg[160];
-      snprintf(msg, sizeof msg, "Solver ended: certified gap %.3e (lower bound %.10e at iteration %d)", s->lb.last_g, s->lb.last_lb, s->inf.verdict_iter);
+      snprintf(msg, sizeof msg, "Solver ended: certified gap %.3e (lower bound %.10e at iteration %d)", s->lb.last_g, s->lb.last_lb, s->solve_status_iter);
       final_msg = msg;
-    } else if (s->inf.status >= 3) {      // a certificate behind the previous iteration (infeas_step)
+    } else if (s->solve_status >= 3) {    // a certificate behind the previous iteration (infeas_step)
       breakyes = true;
       char msg[128];
-      snprintf(msg, sizeof msg, "Solver ended: %s infeasible (certificate at iteration %d)", s->inf.status == 3 ? "primal" : "dual", s->inf.verdict_iter);
+      snprintf(msg, sizeof msg, "Solver ended: %s infeasible (certificate at iteration %d)", s->solve_status == 3 ? "primal" : "dual", s->solve_status_iter);
       final_msg = msg;
     } else if (breakyes) {
-      s->inf.status = iter > max_iter ? 2 : 1;
-      s->inf.verdict_iter = iter - 1;
+      s->solve_status = iter > max_iter ? 2 : 1;
+      s->solve_status_iter = iter - 1;
     }
     const double seconds = wall_s() - s->t_init0;
     if (verbose && (breakyes || (iter <= 200 && iter % 50 == 1) || (iter > 200 && iter % 100 == 1))) {
@@ -1878,11 +1936,11 @@ int cuadmm_solve(cuadmm_solver* s, int max_iter, double stop_tol, int sig_update
     // ---- Step 1 (solver.cu:478-500): y = (AA^T)^-1 (Rp/sig - A(S-C)); with closed blocks the fused projection of this
     // iteration solves it (not on the last pass through the loop, which stops before the projection)
     if (s->y_early) s->y_early = false;       // enqueued at the end of the previous iteration (fetch_out, solve_next)
-    else if (s->inf.status == 5) {}           // the bound was formed at the y the solve returns: no further y-solve behind the verdict
+    else if (s->solve_status == 5) {}         // the bound was formed at the y the solve returns: no further y-solve behind the verdict
     else if (s->bt.len == 0 && (rc = s->host_solve(s->fuse && !breakyes))) return rc;
 
     if (breakyes) {   // solver.cu:567-576
-      if (iter > switch_admm && s->have_best && s->inf.status < 3) {   // (a certificate describes the last iterate: no restore)
+      if (iter > switch_admm && s->have_best && s->solve_status < 3) {   // (a certificate describes the last iterate: no restore)
         CUADMM_HIP_TRY(hipMemcpyAsync(s->X.p, s->X_best.p, sizeof(double) * (size_t)L, hipMemcpyDeviceToDevice, s->st));
         CUADMM_HIP_TRY(hipMemcpyAsync(s->S.p, s->S_best.p, sizeof(double) * (size_t)L, hipMemcpyDeviceToDevice, s->st));
         CUADMM_HIP_TRY(hipStreamSynchronize(s->st));
@@ -1926,8 +1984,7 @@ int cuadmm_solve(cuadmm_solver* s, int max_iter, double stop_tol, int sig_update
       if ((rc = s->batch_alloc())) return rc;
       int K = std::min(std::min(s->bt.max_iters, s->bt.cap), max_iter - iter + 1);
       for (int j = 0; j < K; ++j) {          // the batch may END on a sigma-update iteration, not contain one
-        const int i = iter + j;
-        if ((i <= sig_update_threshold && i % sig_update_stage_1 == 1) || (i > sig_update_threshold && i % sig_update_stage_2 == 1)) { K = j + 1; break; }
+        if (sig_may_change_at(iter + j)) { K = j + 1; break; }
       }
       if (K >= 2) {
         // a batch can only be invalidated by the stopping test or the errRd < stop_tol rule for tau: no checkpoint without a tolerance
@@ -1959,7 +2016,7 @@ int cuadmm_solve(cuadmm_solver* s, int max_iter, double stop_tol, int sig_update
     // the next iteration's y-solve may follow this iteration's last kernel at once (fetch_out, solve_next): the whole solve is on the
     // device and belongs to the engine (not to a closed block's kernel), sigma does not change in this iteration's step 5, nothing of a
     // batch is pending, and the per-class event timers (profile = 1) are off -- they are collected at the wait, before that solve ends
-    const bool sig_may_change = (iter <= sig_update_threshold && iter % sig_update_stage_1 == 1) || (iter > sig_update_threshold && iter % sig_update_stage_2 == 1);
+    const bool sig_may_change = sig_may_change_at(iter);
     const bool solve_next_ok = s->sw.solve_next != 0 && !s->accel_on() && !s->infeas_on() && !s->gap_on() && s->dev_solve && !from_batch && !sig_may_change && !(s->fuse && s->closed.active) && s->profile != 1;
     if (from_batch) {
       // consumed below (Step 5) from bt.h
@@ -2068,16 +2125,10 @@ int cuadmm_solve(cuadmm_solver* s, int max_iter, double stop_tol, int sig_update
           }
         }
       }
-      s->errRp = std::sqrt(nr) / s->norm_borg;
-      s->pobj = s->h_out.p[(size_t)m + 1] * s->objscale;
-      s->errRd = std::sqrt(s->h_out.p[(size_t)m]) * s->Cscale / s->norm_Corg;
-      s->dobj = bty * s->objscale;
-      s->maxfeas = std::max(s->errRp, s->errRd);
-      s->relgap = std::fabs(s->pobj - s->dobj) / (1 + std::fabs(s->pobj) + std::fabs(s->dobj));
+      s->set_residual_scalars(nr, bty);
       s->feasratio = s->ratioconst * s->errRp / s->errRd;
       if (s->feasratio < 1) s->prim_win += 1; else s->dual_win += 1;
-      if ((iter <= sig_update_threshold && iter % sig_update_stage_1 == 1) ||
-          (iter > sig_update_threshold && iter % sig_update_stage_2 == 1)) {
+      if (sig_may_change) {
         if (s->prim_win > 1.2 * s->dual_win) { s->prim_win = 0; s->sig = std::min(s->sigmax, s->sig * sigscale); }
         else if (s->dual_win > 1.2 * s->prim_win) { s->dual_win = 0; s->sig = std::max(s->sigmin, s->sig / sigscale); }
       }
@@ -2098,9 +2149,7 @@ int cuadmm_solve(cuadmm_solver* s, int max_iter, double stop_tol, int sig_update
     }
     // ---- acceleration: behind the iteration, on every path (the scalars above are those of the plain iterate f_k)
     if (s->accel_on()) {
-      const int nx = iter + 1;
-      const bool next_sig_may_change = (nx <= sig_update_threshold && nx % sig_update_stage_1 == 1) || (nx > sig_update_threshold && nx % sig_update_stage_2 == 1);
-      if ((rc = s->accel_step(iter, max_iter, stop_tol, switch_admm, tau, s->sig != sig_of_iter, next_sig_may_change))) return rc;
+      if ((rc = s->accel_step(iter, max_iter, stop_tol, switch_admm, tau, s->sig != sig_of_iter, sig_may_change_at(iter + 1)))) return rc;
     }
     // ---- infeasibility check: on the state at the end of the iteration, after the sigma update
     if (s->infeas_on() && iter % s->inf.period == 0 && (rc = s->infeas_step(iter, stop_tol))) return rc;
@@ -2122,6 +2171,26 @@ int cuadmm_solve(cuadmm_solver* s, int max_iter, double stop_tol, int sig_update
     set_error("solve: %d block projections hit the QL sweep cap", s->eig_fail_total);
     return CUADMM_ERR_EIG;
   }
+  return CUADMM_OK;
+}
+
+// per-solve bookkeeping as init leaves it, in front of the residual stage (profile counters, plans, the blocks' launch order stay)
+int cuadmm_solver::reset_solve_state(double t_begin) {
+  for (auto& a : info) a.clear();
+  info_iter_num = 0;
+  t_init0 = t_begin; total_time = 0;
+  best_KKT = 0; sgs_KKT = 0; have_best = false; eig_fail_total = 0;
+  prim_win = 0; dual_win = 0; feasratio = 0; ratioconst = 1e0; sigmax = 1e3; sigmin = 1e-3;
+  y_early = false; stats_fused = false;
+  bt.len = bt.pos = 0; bt.have_ck = false;
+  closed.iters_done = 0; closed.out_dirty = true;
+  infeas_reset();
+  lb_reset();
+  plan.n_project = 0;
+  if (hint_d.p) CUADMM_HIP_TRY(hipMemsetAsync(hint_d.p, 0, sizeof(int) * hint_d.n, st));     // the sign schedule's warm start
+  if (closed.cl_out.p) CUADMM_HIP_TRY(hipMemsetAsync(closed.cl_out.p, 0, sizeof(double) * closed.cl_out.n, st));
+  if (!dev_solve) std::fill(Rp_p.begin(), Rp_p.end(), 0.0);
+  y_full.clear();
   return CUADMM_OK;
 }
 
@@ -2200,10 +2269,7 @@ int cuadmm_solver::accel_step(int iter, int max_iter, double stop_tol, int switc
   int rc;
   const size_t n2 = 2 * (size_t)aa.hs;
   const bool timed = profile != 0 && aa.ev[0];
-  auto elapsed = [&](int a) {   // after a synchronisation behind ev[a + 1]
-    float t = 0;
-    if (timed && hipEventElapsedTime(&t, aa.ev[a], aa.ev[a + 1]) == hipSuccess) aa.ms += t;
-  };
+  auto elapsed = [&](int a) { if (timed) aa.ms += event_ms(aa.ev[a], aa.ev[a + 1]); };   // after a synchronisation behind ev[a + 1]
   // the map changed under this iteration's feet (sigma in step 5): nothing held describes the new map.  (No candidate is ever
   // pending here: none is taken in front of an iteration that may change sigma.)
   if (sig_changed) {
@@ -2307,7 +2373,7 @@ int cuadmm_solver::accel_step(int iter, int max_iter, double stop_tol, int switc
   // X and S were overwritten: [A X | sums | A (S - C)] and Rp again, as a continued solve forms them
   if ((rc = launch_spmv(true, true))) return rc;
   if ((rc = fetch_out(0, 2 * (size_t)m + 2))) return rc;
-  for (int i = 0; i < m && !dev_solve; ++i) Rp_p[i] = -h_out.p[i] + b_p[i];
+  refresh_Rp();
   elapsed(2);
   aa.pending = true;
   aa.taken++;
@@ -2317,20 +2383,43 @@ int cuadmm_solver::accel_step(int iter, int max_iter, double stop_tol, int switc
 // ------------------------------------------------------------------------------------------
 // Infeasibility detection (option "infeas_check"): DESIGN.md, "Infeasibility certificates"
 // ------------------------------------------------------------------------------------------
-// start of every solve: buffers on first use, no snapshot, b on the device where the engine keeps none there
+// Auxiliary projector (infeasibility check, lower bound)
+int cuadmm_solver::AuxProj::ensure(cuadmm_solver& s) {
+  int rc;
+  if (!ev[1]) {
+    if ((rc = in.alloc((size_t)s.L)) || (rc = out.alloc((size_t)s.L)) || (!s.b_d.p && (rc = bcopy.alloc((size_t)std::max(s.m, 1))))) return rc;
+    for (auto& e : ev) CUADMM_HIP_TRY(hipEventCreate(&e));
+  }
+  if (bcopy.p && s.m > 0 && (rc = staged_h2d(bcopy.p, s.b_p.data(), sizeof(double) * (size_t)s.m, s.st))) return rc;
+  return CUADMM_OK;
+}
+int cuadmm_solver::AuxProj::project(cuadmm_solver& s, const double* from, double* to) {
+  if (!plan) {
+    int rc;
+    size_t free0 = 0, free1 = 0, total = 0;
+    if (hipMemGetInfo(&free0, &total) != hipSuccess) { free0 = 0; (void)hipGetLastError(); }
+    plan = new PsdPlan();
+    plan->opt = s.plan.opt;
+    plan->eig_rank = 0;
+    if ((rc = plan->build(s.blk_local.data(), (int)s.blk_local.size()))) { delete plan; plan = nullptr; return rc; }
+    if (hipMemGetInfo(&free1, &total) != hipSuccess) { free1 = free0; (void)hipGetLastError(); }
+    plan_bytes = free0 > free1 ? (double)(free0 - free1) : 0.0;
+  }
+  return plan->project(from, to, s.st);
+}
+
+// start of every solve: buffers on first use, no snapshot
 int cuadmm_solver::infeas_begin_solve() {
   int rc;
   if (!inf.xprev.p) {
     const size_t mm = (size_t)std::max(m, 1);
-    if ((rc = inf.xprev.alloc(L)) || (rc = inf.dbuf.alloc(L)) || (rc = inf.pbuf.alloc(L)) || (rc = inf.yprev.alloc(mm)) || (rc = inf.dy.alloc(mm)) ||
+    if ((rc = inf.xprev.alloc(L)) || (rc = inf.yprev.alloc(mm)) || (rc = inf.dy.alloc(mm)) ||
         (rc = inf.adx.alloc(mm)) || (rc = inf.partials.alloc(kInfeasPartials)) || (rc = inf.stats_d.alloc(INF_NSTATS)) || (rc = inf.h_stats.alloc(INF_NSTATS)))
       return rc;
-    if (!b_d.p && (rc = inf.bcopy.alloc(mm))) return rc;
-    for (auto& e : inf.ev) CUADMM_HIP_TRY(hipEventCreate(&e));
     long long off = 0;
     for (int n : blk_local) { if (n < 0) inf.free_rng.emplace_back(off, blk_svec_len(n)); off += blk_svec_len(n); }
   }
-  if (inf.bcopy.p && m > 0 && (rc = staged_h2d(inf.bcopy.p, b_p.data(), sizeof(double) * (size_t)m, st))) return rc;
+  if ((rc = aux.ensure(*this))) return rc;
   infeas_reset();
   inf.ms = 0;
   return CUADMM_OK;
@@ -2347,12 +2436,13 @@ int cuadmm_solver::infeas_step(int iter, double stop_tol) {
     inf.have_snap = true;
     return CUADMM_OK;
   }
-  const double* bw = b_d.p ? b_d.p : inf.bcopy.p;
-  CUADMM_HIP_TRY(hipEventRecord(inf.ev[0], st));
+  double* const dbuf = aux.in.p;      // a difference, the input of a projection
+  double* const pbuf = aux.out.p;     // its PSD part
+  CUADMM_HIP_TRY(hipEventRecord(aux.ev[0], st));
   // d = cur - prev and prev <- cur in one pass each; the X difference is written negated: it is the input of P+(-dX), and the norm
   // of A dX does not see the sign
-  if ((rc = launch_infeas_roll(m, y_d.p, inf.yprev.p, bw, inf.dy.p, 0, 0, nullptr, nullptr, inf.partials.p, inf.stats_d.p + INF_DY2, st))) return rc;
-  if ((rc = launch_infeas_roll(L, X.p, inf.xprev.p, C.p, inf.dbuf.p, 1, 0, nullptr, nullptr, inf.partials.p, inf.stats_d.p + INF_DX2, st))) return rc;
+  if ((rc = launch_infeas_roll(m, y_d.p, inf.yprev.p, aux.b_dev(*this), inf.dy.p, 0, 0, nullptr, nullptr, inf.partials.p, inf.stats_d.p + INF_DY2, st))) return rc;
+  if ((rc = launch_infeas_roll(L, X.p, inf.xprev.p, C.p, dbuf, 1, 0, nullptr, nullptr, inf.partials.p, inf.stats_d.p + INF_DX2, st))) return rc;
   inf.checks++;
   double* hs = inf.h_stats.p;
   CUADMM_HIP_TRY(hipMemcpyAsync(hs, inf.stats_d.p, sizeof(double) * 4, hipMemcpyDeviceToHost, st));
@@ -2362,24 +2452,13 @@ int cuadmm_solver::infeas_step(int iter, double stop_tol) {
   int verdict = 0;
   double o3[3] = {0, 0, 0}, stats[INF_NSTATS];
   const double nan = std::nan("");
-  if ((try_dual || try_primal) && !inf.plan2) {
-    size_t free0 = 0, free1 = 0, total = 0;
-    if (hipMemGetInfo(&free0, &total) != hipSuccess) { free0 = 0; (void)hipGetLastError(); }
-    inf.plan2 = new PsdPlan();
-    inf.plan2->opt = plan.opt;
-    inf.plan2->eig_rank = 0;
-    if ((rc = inf.plan2->build(blk_local.data(), (int)blk_local.size()))) { delete inf.plan2; inf.plan2 = nullptr; return rc; }
-    // what the build took from the device's free memory: an estimate (other users of the device and the allocator's caching move it)
-    if (hipMemGetInfo(&free1, &total) != hipSuccess) { free1 = free0; (void)hipGetLastError(); }
-    inf.plan2_bytes = free0 > free1 ? (double)(free0 - free1) : 0.0;
-  }
   // The dual test first: its input -dX sits in dbuf, which the primal test overwrites.
   if (try_dual) {      // A (-dX) over the whole svec; P+(-dX) with the unconstrained blocks' slices (copied through by the plan) left out
-    if ((rc = launch_spmv_rows(m, A_avg_nnz, A_rp.p, A_ci.p, A_v.p, inf.dbuf.p, S.p, C.p, inf.adx.p, nullptr, st, &A_long))) return rc;
+    if ((rc = launch_spmv_rows(m, A_avg_nnz, A_rp.p, A_ci.p, A_v.p, dbuf, S.p, C.p, inf.adx.p, nullptr, st, &A_long))) return rc;
     if ((rc = launch_infeas_norm2(m, inf.adx.p, inf.partials.p, inf.stats_d.p + INF_ADX2, st))) return rc;
-    if ((rc = inf.plan2->project(inf.dbuf.p, inf.pbuf.p, st))) return rc;
-    for (auto& r : inf.free_rng) CUADMM_HIP_TRY(hipMemsetAsync(inf.pbuf.p + r.first, 0, sizeof(double) * (size_t)r.second, st));
-    if ((rc = launch_infeas_norm2(L, inf.pbuf.p, inf.partials.p, inf.stats_d.p + INF_PNEGDX2, st))) return rc;
+    if ((rc = aux.project(*this, dbuf, pbuf))) return rc;
+    for (auto& r : inf.free_rng) CUADMM_HIP_TRY(hipMemsetAsync(pbuf + r.first, 0, sizeof(double) * (size_t)r.second, st));
+    if ((rc = launch_infeas_norm2(L, pbuf, inf.partials.p, inf.stats_d.p + INF_PNEGDX2, st))) return rc;
     CUADMM_HIP_TRY(hipMemcpyAsync(hs + INF_ADX2, inf.stats_d.p + INF_ADX2, sizeof(double) * 2, hipMemcpyDeviceToHost, st));
     CUADMM_HIP_TRY(hipStreamSynchronize(st));
     for (int q = 0; q < INF_NSTATS; ++q) stats[q] = hs[q];
@@ -2387,21 +2466,21 @@ int cuadmm_solver::infeas_step(int iter, double stop_tol) {
     if ((rc = infeas_decide(stats, inf.tol, &verdict, o3))) return rc;
   }
   if (verdict == 0 && try_primal) {   // A^T dy (the kernel forms A^T y - C: pbuf, zeroed, stands in for C), its PSD part, its norm
-    CUADMM_HIP_TRY(hipMemsetAsync(inf.pbuf.p, 0, sizeof(double) * (size_t)L, st));
-    if ((rc = launch_aty_xb(false, L, At_rp.p, At_ci.p, At_v.p, inf.dy.p, inf.pbuf.p, X.p, 1.0, inf.dbuf.p, nullptr, st, &At_long))) return rc;
-    if ((rc = launch_infeas_norm2(L, inf.dbuf.p, inf.partials.p, inf.stats_d.p + INF_ATY2, st))) return rc;      // ||A^T dy||^2: the radius' rounding term
-    if ((rc = inf.plan2->project(inf.dbuf.p, inf.pbuf.p, st))) return rc;
-    if ((rc = launch_infeas_norm2(L, inf.pbuf.p, inf.partials.p, inf.stats_d.p + INF_PATY2, st))) return rc;
+    CUADMM_HIP_TRY(hipMemsetAsync(pbuf, 0, sizeof(double) * (size_t)L, st));
+    if ((rc = launch_aty_xb(false, L, At_rp.p, At_ci.p, At_v.p, inf.dy.p, pbuf, X.p, 1.0, dbuf, nullptr, st, &At_long))) return rc;
+    if ((rc = launch_infeas_norm2(L, dbuf, inf.partials.p, inf.stats_d.p + INF_ATY2, st))) return rc;      // ||A^T dy||^2: the radius' rounding term
+    if ((rc = aux.project(*this, dbuf, pbuf))) return rc;
+    if ((rc = launch_infeas_norm2(L, pbuf, inf.partials.p, inf.stats_d.p + INF_PATY2, st))) return rc;
     CUADMM_HIP_TRY(hipMemcpyAsync(hs + INF_PATY2, inf.stats_d.p + INF_PATY2, sizeof(double) * 4, hipMemcpyDeviceToHost, st));
     CUADMM_HIP_TRY(hipStreamSynchronize(st));
     for (int q = 0; q < INF_NSTATS; ++q) stats[q] = hs[q];
     stats[INF_DX2] = stats[INF_CDX] = stats[INF_ADX2] = stats[INF_PNEGDX2] = nan;
     if ((rc = infeas_decide(stats, inf.tol, &verdict, o3))) return rc;
   }
-  CUADMM_HIP_TRY(hipEventRecord(inf.ev[1], st));
-  CUADMM_HIP_TRY(hipEventSynchronize(inf.ev[1]));
-  { float t = 0; if (hipEventElapsedTime(&t, inf.ev[0], inf.ev[1]) == hipSuccess) inf.ms += t; else (void)hipGetLastError(); }
-  if ((try_dual || try_primal) && inf.plan2->fail_count(st) > 0) {
+  CUADMM_HIP_TRY(hipEventRecord(aux.ev[1], st));
+  CUADMM_HIP_TRY(hipEventSynchronize(aux.ev[1]));
+  inf.ms += event_ms(aux.ev[0], aux.ev[1]);
+  if ((try_dual || try_primal) && aux.failed(st)) {
     set_error("solve: a block projection of the infeasibility check hit the QL sweep cap");
     return CUADMM_ERR_EIG;
   }
@@ -2409,9 +2488,9 @@ int cuadmm_solver::infeas_step(int iter, double stop_tol) {
   // the ray, as the check left it on the device (scaled space, the factor's order / the svec): dy, or -dX in dbuf
   const size_t n = verdict == 3 ? (size_t)m : (size_t)L;
   inf.cert.assign(n, 0.0);
-  if ((rc = staged_d2h(inf.cert.data(), verdict == 3 ? inf.dy.p : inf.dbuf.p, sizeof(double) * n, st))) return rc;
+  if ((rc = staged_d2h(inf.cert.data(), verdict == 3 ? inf.dy.p : dbuf, sizeof(double) * n, st))) return rc;
   if (verdict == 4) for (double& v : inf.cert) v = -v;
-  inf.status = verdict; inf.verdict_iter = iter;
+  solve_status = verdict; solve_status_iter = iter;
   inf.scalar = o3[0]; inf.eta = o3[1];
   // The reported radius is scalar / (eta + eta_fl): eta is the norm of a projection the kernels evaluate to 1e-12 ||M||_F per entry
   // (M = A^T dy or -dX: the projection's contract), so the true violation may exceed eta by eta_fl = 1e-12 sqrt(L) ||M||_F / ||d||, and
@@ -2425,7 +2504,7 @@ int cuadmm_solver::infeas_step(int iter, double stop_tol) {
 // ------------------------------------------------------------------------------------------
 // Certified lower bound from trace bounds (cuadmm_lower_bound, option "gap_check"): DESIGN.md, "Certified lower bound"
 // ------------------------------------------------------------------------------------------
-// vectors, task lists and events on first use; R and (where the engine keeps none on the device) b on every call: both may have changed
+// vectors and task lists on first use; R and (the auxiliary projector's, where the engine keeps none on the device) b on every call: both may have changed
 int cuadmm_solver::lb_prepare() {
   int rc;
   const int nb = (int)blk_local.size();
@@ -2437,54 +2516,40 @@ int cuadmm_solver::lb_prepare() {
     for (int k = 0; k < nb; ++k) { off[k] = o; len[k] = blk_svec_len(blk_local[k]); o += len[k]; }
     LbTasks t;
     if ((rc = lb_build_tasks(nb, len.data(), &t))) return rc;
-    if ((rc = lb.mbuf.alloc((size_t)L)) || (rc = lb.pbuf.alloc((size_t)L)) || (rc = lb.ybuf.alloc(mm)) || (rc = lb.R_d.alloc((size_t)nb)) ||
+    if ((rc = lb.ybuf.alloc(mm)) || (rc = lb.R_d.alloc((size_t)nb)) ||
         (rc = lb.pairs.alloc(2 * (size_t)nb)) || (rc = lb.dpart.alloc(kLbDotSlots)) || (rc = lb.h_out.alloc(4)) || (rc = lb.off_d.from(off)) ||
         (rc = lb.len_d.from(len)) || (rc = lb.blk_d.from(blk_local)) || (rc = lb.wave_d.from(t.wave)) || (rc = lb.chunk_d.from(t.chunk)) ||
         (rc = lb.large_d.from(t.large)) || (rc = lb.cpart.alloc(2 * (size_t)t.nchunk())))
       return rc;
-    if (!b_d.p && (rc = lb.bcopy.alloc(mm))) return rc;
     lb.nwave = t.nwave(); lb.nchunk = t.nchunk(); lb.nlarge = t.nlarge();
     CUADMM_HIP_TRY(hipMemsetAsync(lb.pairs.p, 0, sizeof(double) * lb.pairs.n, st));
-    for (auto& e : lb.ev) CUADMM_HIP_TRY(hipEventCreate(&e));
     lb.R_dirty = true;
     if ((rc = lb.out_d.alloc(4))) return rc;          // last: marks the set as complete
   }
   if (lb.R_dirty && (rc = staged_h2d(lb.R_d.p, lb.R.data(), sizeof(double) * (size_t)nb, st))) return rc;
   lb.R_dirty = false;
-  if (lb.bcopy.p && m > 0 && (rc = staged_h2d(lb.bcopy.p, b_p.data(), sizeof(double) * (size_t)m, st))) return rc;
-  return CUADMM_OK;
+  return aux.ensure(*this);
 }
 
 // The bound at y (device, the engine's scaled space and the factor's order).  Reads y, A, C and b; writes only the bound's own vectors.
 // out6 = [LB, b'y, sum R_k nubar_k, worst block, its term] in the caller's units, [5] unused.
 int cuadmm_solver::lb_eval(const double* y, double out6[6], float* ms) {
   int rc;
-  const double* bw = b_d.p ? b_d.p : lb.bcopy.p;
-  if (!lb.plan2) {       // at the first evaluation: the solver's psd_* options, the full projection
-    const int nb = (int)blk_local.size();
-    size_t free0 = 0, free1 = 0, total = 0;
-    if (hipMemGetInfo(&free0, &total) != hipSuccess) { free0 = 0; (void)hipGetLastError(); }
-    lb.plan2 = new PsdPlan();
-    lb.plan2->opt = plan.opt;
-    lb.plan2->eig_rank = 0;
-    if ((rc = lb.plan2->build(blk_local.data(), nb))) { delete lb.plan2; lb.plan2 = nullptr; return rc; }
-    if (hipMemGetInfo(&free1, &total) != hipSuccess) { free1 = free0; (void)hipGetLastError(); }
-    lb.plan2_bytes = free0 > free1 ? (double)(free0 - free1) : 0.0;
-  }
-  CUADMM_HIP_TRY(hipEventRecord(lb.ev[0], st));
+  double* const mbuf = aux.in.p;
+  double* const pbuf = aux.out.p;
+  CUADMM_HIP_TRY(hipEventRecord(aux.ev[0], st));
   // M = A'y - C (S^ = -Cscale M), P = P+(M) with the unconstrained slices copied through
-  if ((rc = launch_aty_xb(false, L, At_rp.p, At_ci.p, At_v.p, y, C.p, X.p, 1.0, lb.mbuf.p, nullptr, st, &At_long))) return rc;
-  if ((rc = lb.plan2->project(lb.mbuf.p, lb.pbuf.p, st))) return rc;
-  LbNormArgs a{lb.mbuf.p, lb.pbuf.p, lb.off_d.p, lb.len_d.p, lb.wave_d.p, lb.chunk_d.p, lb.large_d.p, lb.nwave, lb.nchunk, lb.nlarge, lb.cpart.p, lb.pairs.p};
+  if ((rc = launch_aty_xb(false, L, At_rp.p, At_ci.p, At_v.p, y, C.p, X.p, 1.0, mbuf, nullptr, st, &At_long))) return rc;
+  if ((rc = aux.project(*this, mbuf, pbuf))) return rc;
+  LbNormArgs a{mbuf, pbuf, lb.off_d.p, lb.len_d.p, lb.wave_d.p, lb.chunk_d.p, lb.large_d.p, lb.nwave, lb.nchunk, lb.nlarge, lb.cpart.p, lb.pairs.p};
   if ((rc = launch_lb_block_norms(a, st))) return rc;
-  if ((rc = launch_lb_dot(m, bw, y, lb.dpart.p, st))) return rc;
+  if ((rc = launch_lb_dot(m, aux.b_dev(*this), y, lb.dpart.p, st))) return rc;
   if ((rc = launch_lb_combine((int)blk_local.size(), lb.pairs.p, lb.R_d.p, lb.len_d.p, lb.blk_d.p, lb.dpart.p, lb.out_d.p, st))) return rc;
   CUADMM_HIP_TRY(hipMemcpyAsync(lb.h_out.p, lb.out_d.p, sizeof(double) * 4, hipMemcpyDeviceToHost, st));
-  CUADMM_HIP_TRY(hipEventRecord(lb.ev[1], st));
+  CUADMM_HIP_TRY(hipEventRecord(aux.ev[1], st));
   CUADMM_HIP_TRY(hipStreamSynchronize(st));
-  *ms = 0;
-  if (hipEventElapsedTime(ms, lb.ev[0], lb.ev[1]) != hipSuccess) { *ms = 0; (void)hipGetLastError(); }
-  if (lb.plan2->fail_count(st) > 0) { set_error("lower bound: a block projection hit the QL sweep cap"); return CUADMM_ERR_EIG; }
+  *ms = event_ms(aux.ev[0], aux.ev[1]);
+  if (aux.failed(st)) { set_error("lower bound: a block projection hit the QL sweep cap"); return CUADMM_ERR_EIG; }
   const double* h = lb.h_out.p;
   out6[1] = h[3] * objscale;
   out6[2] = h[0] * Cscale;
@@ -2508,7 +2573,7 @@ int cuadmm_solver::lb_step(int iter, double stop_tol) {
   if (std::isfinite(LB) && (lb.best_iter == 0 || LB > lb.best_lb)) { lb.best_lb = LB; lb.best_iter = iter; }
   const double tol = lb.tol > 0 ? lb.tol : stop_tol;
   if (g <= tol && errRp <= tol) {          // (false for a NaN)
-    inf.status = 5; inf.verdict_iter = iter;
+    solve_status = 5; solve_status_iter = iter;
     lb.verdict_iter = iter;
   }
   return CUADMM_OK;
@@ -2552,12 +2617,9 @@ int cuadmm_duo_init(cuadmm_solver* s, int if_gpu_eig_mom, int device_num_request
     if (rc) return rc;
     duo_group_inject(s->group, s->duo_inject);
     s->world = device_num_requested; s->rank = 0;
-    rc = duo_group_run(s->group, [&](cuadmm_solver* q, int) {
-      q->in_group_call = true;
-      int r2 = cuadmm_duo_init(q, if_gpu_eig_mom, device_num_requested, eig_stream_num_per_gpu, cpu_eig_thread_num, vec_len, con_num, At_cp, At_ri,
-                               At_vx, At_nnz, b_idx, b_vals, b_nnz, C_idx, C_vals, C_nnz, blk, mat_num, X0, y0, S0, sig);
-      q->in_group_call = false;
-      return r2;
+    rc = group_forward(s, [&](cuadmm_solver* q) {
+      return cuadmm_duo_init(q, if_gpu_eig_mom, device_num_requested, eig_stream_num_per_gpu, cpu_eig_thread_num, vec_len, con_num, At_cp, At_ri,
+                             At_vx, At_nnz, b_idx, b_vals, b_nnz, C_idx, C_vals, C_nnz, blk, mat_num, X0, y0, S0, sig);
     });
     if (rc) { duo_group_destroy(s->group); s->group = nullptr; s->world = 1; s->allreduce = nullptr; s->allreduce_user = nullptr; }
     return rc;
@@ -2616,12 +2678,12 @@ static int get_vec(cuadmm_solver* s, const DevBuf<double>& v, double* out) {
 static int group_gather(cuadmm_solver* s, double* out, int (*get)(cuadmm_solver*, double*)) {
   DeviceGuard keep_device;                  // every rank's getter makes its device current on this thread
   for (int r = 0; r < duo_group_world(s->group); ++r) {
-    cuadmm_solver* q = duo_group_rank(s->group, r);
-    int64_t b = 0, e = 0;
-    q->in_group_call = true;                // rank 0 IS the leader: without the mark get_shard would answer for the whole group
-    int rc = cuadmm_get_shard(q, &b, &e, nullptr, nullptr);
-    if (!rc) rc = e > b ? get(q, out + b) : CUADMM_OK;
-    q->in_group_call = false;
+    // (rank 0 IS the leader: without the mark get_shard would answer for the whole group)
+    int rc = as_group_rank(duo_group_rank(s->group, r), [&](cuadmm_solver* q) {
+      int64_t b = 0, e = 0;
+      const int rs = cuadmm_get_shard(q, &b, &e, nullptr, nullptr);
+      return rs ? rs : (e > b ? get(q, out + b) : CUADMM_OK);
+    });
     if (rc) return rc;
   }
   return CUADMM_OK;
@@ -2651,10 +2713,7 @@ int cuadmm_set_XyS(cuadmm_solver* s, const double* X, const double* y, const dou
   if (s->group && !s->in_group_call) {      // every rank of the group takes its range of the caller's vectors
     DeviceGuard keep_device;
     for (int r = 0; r < duo_group_world(s->group); ++r) {
-      cuadmm_solver* q = duo_group_rank(s->group, r);
-      q->in_group_call = true;
-      int rc = cuadmm_set_XyS(q, X, y, S, sig);
-      q->in_group_call = false;
+      int rc = as_group_rank(duo_group_rank(s->group, r), [&](cuadmm_solver* q) { return cuadmm_set_XyS(q, X, y, S, sig); });
       if (rc) return rc;
     }
     return CUADMM_OK;
@@ -2682,58 +2741,29 @@ int cuadmm_update_bC(cuadmm_solver* s, const int* b_idx, const double* b_vals, i
   const bool new_b = b_nnz >= 0, new_C = C_nnz >= 0;
   if ((b_nnz > 0 && (!b_idx || !b_vals)) || (C_nnz > 0 && (!C_idx || !C_vals))) { set_error("update_bC: entries without their index / value arrays"); return CUADMM_ERR_INVALID; }
   // --- every check before anything changes (the caller's numbering; the rules of init_vectors, over the whole of b and C on every rank)
-  const int m_call = s->local_mode ? s->m_full : s->m;
-  const long long L_call = s->local_mode ? s->L_caller : s->L_full;
-  if (new_b) {
-    std::vector<char> seen((size_t)m_call, 0);
-    for (int i = 0; i < b_nnz; ++i) {
-      if (b_idx[i] < 0 || b_idx[i] >= m_call) { set_error("update_bC: b index %d out of range", b_idx[i]); return CUADMM_ERR_INVALID; }
-      if (seen[b_idx[i]]) { set_error("update_bC: b index %d appears twice", b_idx[i]); return CUADMM_ERR_INVALID; }
-      seen[b_idx[i]] = 1;
-    }
-  }
-  if (new_C) {
-    std::vector<char> seen((size_t)L_call, 0);
-    for (int i = 0; i < C_nnz; ++i) {
-      if (C_idx[i] < 0 || C_idx[i] >= L_call) { set_error("update_bC: C index %d out of range", C_idx[i]); return CUADMM_ERR_INVALID; }
-      if (seen[C_idx[i]]) { set_error("update_bC: C index %d appears twice", C_idx[i]); return CUADMM_ERR_INVALID; }
-      seen[C_idx[i]] = 1;
-    }
-  }
-  if (s->group && !s->in_group_call) {      // every rank takes the full b and C, as with init; their residual stage meets in the group's all-reduce
-    DeviceGuard keep_device;
-    return duo_group_run(s->group, [&](cuadmm_solver* q, int) {
-      q->in_group_call = true;
-      int r2 = cuadmm_update_bC(q, b_idx, b_vals, b_nnz, C_idx, C_vals, C_nnz, keep_iterate, sig);
-      q->in_group_call = false;
-      return r2;
-    });
-  }
-  int rc = check_device(s->device);
-  if (rc) return rc;
+  int rc;
+  if (new_b && (rc = check_sparse_idx("update_bC", "b", b_idx, b_nnz, s->local_mode ? s->m_full : s->m))) return rc;
+  if (new_C && (rc = check_sparse_idx("update_bC", "C", C_idx, C_nnz, s->local_mode ? s->L_caller : s->L_full))) return rc;
+  if (s->group && !s->in_group_call)        // every rank takes the full b and C, as with init; their residual stage meets in the group's all-reduce
+    return group_forward(s, [&](cuadmm_solver* q) { return cuadmm_update_bC(q, b_idx, b_vals, b_nnz, C_idx, C_vals, C_nnz, keep_iterate, sig); });
+  if ((rc = check_device(s->device))) return rc;
   const double t_begin = wall_s();
   const int m = s->m;
   const long long L = s->L;
 
-  // --- this rank's entries, in the engine's numbering: b by position in the factor's order and divided by normA (sparse_dense.cu:11-20),
-  // C by local svec slot; the norms over the WHOLE of b and C (owned constraints: from the full inputs every rank holds)
+  // --- this rank's entries, in the engine's numbering: b by position in the factor's order and divided by normA, C by local svec slot; the
+  // norms over the WHOLE of b and C (owned constraints: from the full inputs every rank holds)
+  const int* const g2l = s->local_mode ? s->cons_g2l.data() : nullptr;
   double nb = 0, nb2 = 0, nc = 0;
   std::vector<int> bi, ci;
-  std::vector<double> bv, cv;
-  std::vector<double> bfull;
+  std::vector<double> bv, cv, bfull;
   if (new_b) {
-    bfull.assign((size_t)m, 0.0);
-    std::vector<int> g2l;
-    if (s->local_mode) { g2l.assign((size_t)s->m_full, -1); for (int q = 0; q < m; ++q) g2l[s->cons_local[q]] = q; }
+    nb = sum_sq(b_vals, b_nnz);
+    nb2 = scaled_b(b_idx, b_vals, b_nnz, g2l, s->normA, bfull);
+    if (s->local_mode) nb2 = sum_scaled_sq(b_idx, b_vals, b_nnz, s->normA_all.data());
     for (int i = 0; i < b_nnz; ++i) {
-      nb += b_vals[i] * b_vals[i];
-      if (s->local_mode) { const double v = b_vals[i] / s->normA_all[b_idx[i]]; nb2 += v * v; }
-      const int j = s->local_mode ? g2l[b_idx[i]] : b_idx[i];
-      if (j < 0) continue;
-      const double v = b_vals[i] / s->normA[j];
-      bfull[j] = v;
-      if (!s->local_mode) nb2 += v * v;
-      bi.push_back(s->perm_inv[j]); bv.push_back(v);
+      const int j = g2l ? g2l[b_idx[i]] : b_idx[i];
+      if (j >= 0) { bi.push_back(s->perm_inv[j]); bv.push_back(bfull[j]); }
     }
   }
   if (new_C) {
@@ -2762,12 +2792,10 @@ int cuadmm_update_bC(cuadmm_solver* s, const int* b_idx, const double* b_vals, i
     else {
       s->upa.bg_idx.assign(b_idx, b_idx + b_nnz); s->upa.bg_val.assign(b_vals, b_vals + b_nnz);
       s->upa.b_idx.clear(); s->upa.b_val.clear();
-      std::vector<int> g2l2((size_t)s->m_full, -1);
-      for (int q = 0; q < m; ++q) g2l2[s->cons_local[q]] = q;
-      for (int i = 0; i < b_nnz; ++i) if (g2l2[b_idx[i]] >= 0) { s->upa.b_idx.push_back(g2l2[b_idx[i]]); s->upa.b_val.push_back(b_vals[i]); }
+      for (int i = 0; i < b_nnz; ++i) if (g2l[b_idx[i]] >= 0) { s->upa.b_idx.push_back(g2l[b_idx[i]]); s->upa.b_val.push_back(b_vals[i]); }
     }
     s->norm_borg = 1 + std::sqrt(nb);
-    s->bscale = 1 + std::sqrt(nb2);
+    s->set_scaled_b(bfull, nb2);
     if (s->local_mode) { s->ov_nb = nb; s->ov_nb2 = nb2; }
   }
   if (new_C) {
@@ -2777,8 +2805,6 @@ int cuadmm_update_bC(cuadmm_solver* s, const int* b_idx, const double* b_vals, i
   }
   s->objscale = s->bscale * s->Cscale;
   const double ibs = 1 / s->bscale, ics = 1 / s->Cscale;
-  if (new_b)
-    for (int pidx = 0; pidx < m; ++pidx) s->b_p[pidx] = bfull[s->perm[pidx]] * ibs;
 
   // svec pass: X, S (and C <- 0), then C's entries
   const bool keep = keep_iterate != 0;
@@ -2804,25 +2830,9 @@ int cuadmm_update_bC(cuadmm_solver* s, const int* b_idx, const double* b_vals, i
     if ((rc = launch_scatter_scaled(s->b_d.p, bi_d.p, bv_d.p, (int)bi.size(), ibs, s->st))) return rc;
     if (s->closed.active && (rc = launch_closed_patch_b(s->closed.rec.p, s->plan.fused_blocks(), s->b_d.p, s->st))) return rc;
   }
-  s->pending_unscale = false;
+  s->pending_unscale = false;           // (y_host_stale: set above, by where y lives)
   if (sig > 0) s->sig = sig;
-
-  // --- per-solve bookkeeping as init leaves it (profile counters, plans, the blocks' launch order stay)
-  for (auto& a : s->info) a.clear();
-  s->info_iter_num = 0;
-  s->t_init0 = t_begin; s->total_time = 0;
-  s->best_KKT = 0; s->sgs_KKT = 0; s->have_best = false; s->eig_fail_total = 0;
-  s->prim_win = 0; s->dual_win = 0; s->feasratio = 0; s->ratioconst = 1e0; s->sigmax = 1e3; s->sigmin = 1e-3;
-  s->y_early = false; s->stats_fused = false;
-  s->bt.len = s->bt.pos = 0; s->bt.have_ck = false;
-  s->closed.iters_done = 0; s->closed.out_dirty = true;
-  s->infeas_reset();
-  s->lb_reset();
-  s->plan.n_project = 0;
-  if (s->hint_d.p) CUADMM_HIP_TRY(hipMemsetAsync(s->hint_d.p, 0, sizeof(int) * s->hint_d.n, s->st));     // the sign schedule's warm start
-  if (s->closed.cl_out.p) CUADMM_HIP_TRY(hipMemsetAsync(s->closed.cl_out.p, 0, sizeof(double) * s->closed.cl_out.n, s->st));
-  if (!s->dev_solve) std::fill(s->Rp_p.begin(), s->Rp_p.end(), 0.0);
-  s->y_full.clear();
+  if ((rc = s->reset_solve_state(t_begin))) return rc;
 
   // --- initial A X, A (S - C), residual scalars: init's own last stage (it ends with a stream synchronisation)
   return init_residuals(s, y_on_device);
@@ -2846,15 +2856,8 @@ int cuadmm_update_A(cuadmm_solver* s, const double* At_vals, int At_nnz, int kee
   for (int p = 0; p < At_nnz; ++p)
     if (!std::isfinite(At_vals[p])) { set_error("update_A: value %d is not finite", p); return CUADMM_ERR_INVALID; }
   // (init keeps explicit zeros in the pattern -- of A, of A A^T and of the factor --, so a value of exactly 0 is as good as any other)
-  if (s->group && !s->in_group_call) {      // every rank takes the full value array, as with init
-    DeviceGuard keep_device;
-    return duo_group_run(s->group, [&](cuadmm_solver* q, int) {
-      q->in_group_call = true;
-      int r2 = cuadmm_update_A(q, At_vals, At_nnz, keep_iterate, sig);
-      q->in_group_call = false;
-      return r2;
-    });
-  }
+  if (s->group && !s->in_group_call)        // every rank takes the full value array, as with init
+    return group_forward(s, [&](cuadmm_solver* q) { return cuadmm_update_A(q, At_vals, At_nnz, keep_iterate, sig); });
   if (s->upa.tail_fellback) {
     set_error("update_A: init fell back from the GPU tail to the host-only factor on the values it was given; whether new values would take the tail is a decision only an init can take");
     return CUADMM_ERR_INVALID;
@@ -2874,14 +2877,8 @@ int cuadmm_update_A(cuadmm_solver* s, const double* At_vals, int At_nnz, int kee
   std::vector<double> local_vals;
   if (s->local_mode) {
     const int* gcp = s->upa.g_cp.data();
-    for (int j = 0; j < s->m_full; ++j) {
-      double cn = 0;
-      for (int p = gcp[j]; p < gcp[j + 1]; ++p) cn += At_vals[p] * At_vals[p];
-      s->normA_all[j] = std::max(1.0, std::sqrt(cn));
-    }
-    double nb2 = 0;
-    for (size_t i = 0; i < s->upa.bg_idx.size(); ++i) { const double v = s->upa.bg_val[i] / s->normA_all[s->upa.bg_idx[i]]; nb2 += v * v; }
-    s->ov_nb2 = nb2;
+    for (int j = 0; j < s->m_full; ++j) s->normA_all[j] = cons_norm(At_vals, gcp[j], gcp[j + 1]);
+    s->ov_nb2 = sum_scaled_sq(s->upa.bg_idx.data(), s->upa.bg_val.data(), (int)s->upa.bg_idx.size(), s->normA_all.data());
     local_vals.resize(s->upa.g_from.size());
     for (size_t p = 0; p < local_vals.size(); ++p) local_vals[p] = At_vals[s->upa.g_from[p]];
     At_vals = local_vals.data();
@@ -3020,22 +3017,12 @@ int cuadmm_update_A(cuadmm_solver* s, const double* At_vals, int At_nnz, int kee
   // --- scaling constants, b, and the iterate in the new units (init_vectors; b and C themselves are the caller's of before)
   double ibs = 1, ics = 1;
   {
-    double nb2 = 0;
-    std::vector<double> bfull((size_t)m, 0.0);
-    for (size_t i = 0; i < s->upa.b_idx.size(); ++i) {
-      const double v = s->upa.b_val[i] / s->normA[s->upa.b_idx[i]];
-      bfull[s->upa.b_idx[i]] = v;
-      nb2 += v * v;
-    }
-    if (s->local_mode) nb2 = s->ov_nb2;
-    s->bscale = 1 + std::sqrt(nb2);
+    std::vector<double> bfull;
+    const double nb2 = scaled_b(s->upa.b_idx.data(), s->upa.b_val.data(), (int)s->upa.b_idx.size(), nullptr, s->normA, bfull);
+    s->set_scaled_b(bfull, s->local_mode ? s->ov_nb2 : nb2);
     s->objscale = s->bscale * s->Cscale;
     ibs = 1 / s->bscale; ics = 1 / s->Cscale;
-    for (int pidx = 0; pidx < m; ++pidx) {
-      const int j = s->perm[pidx];
-      s->normA_p[pidx] = s->normA[j];
-      s->b_p[pidx] = bfull[j] * ibs;
-    }
+    for (int pidx = 0; pidx < m; ++pidx) s->normA_p[pidx] = s->normA[s->perm[pidx]];
     if (s->b_d.p) {
       if ((rc = s->b_d.upload(s->b_p.data(), (size_t)m)) || (rc = s->normA_d.upload(s->normA_p.data(), (size_t)m))) return fail(rc);
       s->upa.bytes += 16.0 * (double)m;
@@ -3054,31 +3041,15 @@ int cuadmm_update_A(cuadmm_solver* s, const double* At_vals, int At_nnz, int kee
   s->upa.pass_bytes[1] = (keep ? 32.0 : 16.0) * (double)L;
   if (sig > 0) s->sig = sig;
   s->factor_bad = false;
-
-  // --- per-solve bookkeeping as init leaves it (profile counters, plans, the blocks' launch order stay)
-  for (auto& a : s->info) a.clear();
-  s->info_iter_num = 0;
-  s->t_init0 = t_begin; s->total_time = 0;
-  s->best_KKT = 0; s->sgs_KKT = 0; s->have_best = false; s->eig_fail_total = 0;
-  s->prim_win = 0; s->dual_win = 0; s->feasratio = 0; s->ratioconst = 1e0; s->sigmax = 1e3; s->sigmin = 1e-3;
-  s->y_early = false; s->stats_fused = false;
-  s->bt.len = s->bt.pos = 0; s->bt.have_ck = false;
-  s->closed.iters_done = 0; s->closed.out_dirty = true;
-  s->infeas_reset();
-  s->lb_reset();
-  s->plan.n_project = 0;
-  if (s->hint_d.p) CUADMM_HIP_TRY(hipMemsetAsync(s->hint_d.p, 0, sizeof(int) * s->hint_d.n, s->st));
-  if (s->closed.cl_out.p) CUADMM_HIP_TRY(hipMemsetAsync(s->closed.cl_out.p, 0, sizeof(double) * s->closed.cl_out.n, s->st));
-  if (!s->dev_solve) std::fill(s->Rp_p.begin(), s->Rp_p.end(), 0.0);
-  s->y_full.clear();
-  s->y_host_stale = false;
+  if ((rc = s->reset_solve_state(t_begin))) return rc;
+  s->y_host_stale = false;              // (materialise above left both as they are set here)
   s->pending_unscale = false;
   s->upa.bytes += 8.0 * (double)m;                             // y, uploaded by the residual stage
 
   rc = init_residuals(s, false);                               // (ends with a stream synchronisation)
   s->upa.pass_ms[0] = s->upa.pass_ms[1] = 0;
   if (timed && !rc)
-    for (int q = 0; q < 2; ++q) { float ms = 0; if (hipEventElapsedTime(&ms, s->upa.ev[2 * q], s->upa.ev[2 * q + 1]) == hipSuccess) s->upa.pass_ms[q] = ms; else (void)hipGetLastError(); }
+    for (int q = 0; q < 2; ++q) s->upa.pass_ms[q] = event_ms(s->upa.ev[2 * q], s->upa.ev[2 * q + 1]);
   s->upa.count++;
   s->upa.host_ms = (t_f1 - t_f0) * 1e3;
   s->upa.dev_ms = (t_f2 - t_f1) * 1e3;
@@ -3172,15 +3143,15 @@ int cuadmm_accel_solve_ls(const double* gram, const double* rhs, int cols, doubl
 }
 int cuadmm_get_status(const cuadmm_solver* s, double o[8]) {
   if (!s || !o) { set_error("get_status: null"); return CUADMM_ERR_INVALID; }
-  o[0] = (double)s->inf.status; o[1] = (double)s->inf.verdict_iter; o[2] = (double)s->inf.checks; o[3] = s->inf.scalar; o[4] = s->inf.eta;
-  o[5] = s->inf.radius; o[6] = s->inf.ms; o[7] = s->inf.bytes();
+  o[0] = (double)s->solve_status; o[1] = (double)s->solve_status_iter; o[2] = (double)s->inf.checks; o[3] = s->inf.scalar; o[4] = s->inf.eta;
+  o[5] = s->inf.radius; o[6] = s->inf.ms; o[7] = s->inf.bytes() + (s->inf.xprev.p ? s->aux.bytes() : 0.0);
   return CUADMM_OK;
 }
 int cuadmm_get_certificate(cuadmm_solver* s, double* y_out, double* X_out) {
   if (!s || !s->initialised) { set_error("get_certificate: solver not initialised"); return CUADMM_ERR_INVALID; }
-  if (s->inf.status != 3 && s->inf.status != 4) { set_error("get_certificate: the last solve found no certificate of infeasibility (status %d)", s->inf.status); return CUADMM_ERR_INVALID; }
+  if (s->solve_status != 3 && s->solve_status != 4) { set_error("get_certificate: the last solve found no certificate of infeasibility (status %d)", s->solve_status); return CUADMM_ERR_INVALID; }
   const std::vector<double>& c = s->inf.cert;
-  if (s->inf.status == 3) {
+  if (s->solve_status == 3) {
     if (!y_out) { set_error("get_certificate: status 3 returns a y ray: y_out is null"); return CUADMM_ERR_INVALID; }
     // back to the caller's units and order as materialise / cuadmm_get_y map y, then b' y = 1 on the caller's b
     for (int i = 0; i < s->m; ++i) y_out[s->perm[i]] = c[i] / s->normA_p[i];
@@ -3255,7 +3226,7 @@ int cuadmm_lower_bound(cuadmm_solver* s, double o[8], double* per_block) {
   if ((rc = s->lb_eval(s->lb.ybuf.p, r, &ms))) return rc;
   o[0] = r[0]; o[1] = r[1]; o[2] = r[2];
   o[3] = std::fabs(s->pobj - r[0]) / (1 + std::fabs(s->pobj) + std::fabs(r[0]));
-  o[4] = r[3]; o[5] = r[4]; o[6] = ms; o[7] = s->lb.bytes();
+  o[4] = r[3]; o[5] = r[4]; o[6] = ms; o[7] = s->lb.bytes() + s->aux.bytes();
   if (per_block) {
     const size_t nb = s->blk_local.size();
     std::vector<double> pr(2 * nb);
@@ -3267,7 +3238,7 @@ int cuadmm_lower_bound(cuadmm_solver* s, double o[8], double* per_block) {
 int cuadmm_get_gap_info(const cuadmm_solver* s, double o[8]) {
   if (!s || !o) { set_error("get_gap_info: null"); return CUADMM_ERR_INVALID; }
   o[0] = (double)s->lb.checks; o[1] = s->lb.best_lb; o[2] = (double)s->lb.best_iter; o[3] = s->lb.last_lb; o[4] = s->lb.last_g;
-  o[5] = s->lb.ms; o[6] = s->lb.bytes(); o[7] = (double)s->lb.verdict_iter;
+  o[5] = s->lb.ms; o[6] = s->lb.bytes() + (s->lb.out_d.p ? s->aux.bytes() : 0.0); o[7] = (double)s->lb.verdict_iter;
   return CUADMM_OK;
 }
 int cuadmm_trace_bounds_detect(int vec_len, int con_num, const int* At_csc_col_ptrs, const int* At_csc_row_ids, const double* At_csc_vals,

@@ -242,6 +242,43 @@ def test_gap_check_without_a_verdict_is_the_run_with_the_option_off(name):
         assert abs(got - want) <= tol
 
 
+def test_the_bound_and_the_infeasibility_check_share_one_projector():
+    """Fixture A (a free block, PSD blocks of the register, one-wavefront, LDS and cluster classes) with trace bounds and infeas_check = 10:
+    the check and cuadmm_lower_bound project through the same auxiliary plan and work vectors (csrc/engine.hip: AuxProj).  Neither
+    sees the other: the trajectory is that of a handle with neither feature, both bounds are those of a handle without the check.
+    stop_tol = 0: in each solve every multiple of the period behind the first (the snapshot) is a check, 5 of them.  That one of the
+    first five passed a sign test and projected shows in the bytes: the plan is built at the first projection, and without it the check holds
+    3 L + 4 m doubles of vectors (its own two snapshots, dy, A dX; the projector's two work vectors and, at most, its copy of b), the
+    2 048 + 8 doubles of its reduction and nothing else."""
+    fx = fixture("A")
+    L, m = int(blk_lens(fx.blk).sum()), fx.m
+    plain, bound, both = solver(fx, bounds=False), solver(fx), solver(fx, {"infeas_check": 10})
+    lbs = {}
+    for s in (plain, bound, both):
+        s.solve(60, 0.0)
+        if s is both:
+            st = s.status()
+            print("after the first solve:", st, "vectors alone %d bytes" % (8 * (3 * L + 4 * m + 2056)))
+            assert st["status"] == 2 and st["checks"] == 5 and st["ms"] > 0
+            assert st["bytes"] > 8 * (3 * L + 4 * m + 2056)
+        if s is not plain:
+            lbs[s] = [s.lower_bound(per_block=True)]
+        s.solve(60, 0.0, if_first=False)
+        if s is not plain:
+            lbs[s].append(s.lower_bound(per_block=True))
+    for a, b in zip(_traj(plain), _traj(both)):
+        assert np.array_equal(a, b)
+    for want, got in zip(lbs[bound], lbs[both]):
+        print("LB %.15g | %.15g" % (want["lower_bound"], got["lower_bound"]))
+        for k in want:
+            if k not in ("ms", "bytes"):
+                assert np.array_equal(want[k], got[k]), k
+        assert got["bytes"] > 0 and got["ms"] > 0
+    assert both.status()["checks"] == 5 and both.status()["status"] == 2
+    for s in (plain, bound, both):                                 # no projection of either plan hit the QL sweep cap (a call would have failed)
+        assert s.state()["eig_not_converged"] == 0
+
+
 # ---- 6. the verdict -------------------------------------------------------------------------------------------------------
 GAP_TOL = 1e-3
 
