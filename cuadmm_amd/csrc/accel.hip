@@ -23,16 +23,6 @@ constexpr int kQ = 2 * kAccelMaxMem;     // partial sums per slot
 
 __device__ __forceinline__ long long aa_tid() { return (long long)blockIdx.x * kAccelThreads + threadIdx.x; }
 
-// sum over the workgroup in a fixed order; the result is valid in thread 0
-__device__ __forceinline__ double block_sum(double v, double* lds /* 4 doubles */) {
-  v = wave_sum(v);
-  const int w = threadIdx.x >> 6;
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) lds[w] = v;
-  __syncthreads();
-  return (lds[0] + lds[1]) + (lds[2] + lds[3]);
-}
-
 // ---- push ------------------------------------------------------------------------------------------------------------------
 struct PushHalf {
   const double *u, *x, *fp, *gp;

@@ -14,6 +14,10 @@
 //   read off the constraints (cuadmm_trace_bounds_detect; an error when a block has none).  With them the sidecar carries "lower_bound"
 //   (cuadmm_lower_bound at the returned y) and "certified_gap"; without the flag it is what it was
 //   --gap=P --gap_tol=T: certified-gap check every P iterations (options "gap_check", "gap_tol"; needs --trace-bounds); status "certified_gap"
+//   --kkt: the KKT and DIMACS report of the returned point behind every solve (cuadmm_evaluate at the current X, y, S), printed and added to
+//   the sidecar as "kkt"
+//   --kkt-point=<dir2/>: no solve; the report of the point in <dir2/>{X,y,S}.txt (one number per line, as this program writes X_opt.txt; a
+//   missing file: that vector is zero) is printed and, with --json, written as the sidecar's "kkt"
 //   --json=<file>: a sidecar with the run's figures (iterations, residuals, iters/s, per-phase milliseconds, the projection's
 //   nominal TFLOP/s = 10.67 sum n^3 per projection and the vector kernels' algorithmic GB/s: SURVEY.md 8d); switches the
 //   engine's per-phase HIP-event timers on (option "profile").  Nothing is written unless asked for: the reference writes X_opt.txt only.
@@ -42,8 +46,48 @@ static bool opt(const char* arg, const char* key, double& out) {
   return false;
 }
 
+static const char* const kkt_names[16] = {"pobj", "dobj", "norm_Rp", "norm_Rd", "vX", "vS", "XS", "norm_b", "norm_C", "err1", "err2", "err3", "err4", "err5", "err6", "ms"};
+// "kkt": {...} with the sixteen numbers of cuadmm_evaluate and "per_block": mat_num rows of six
+static void write_kkt(FILE* f, const double* k, const std::vector<double>& pb) {
+  fprintf(f, " \"kkt\": {");
+  for (int q = 0; q < 16; ++q) fprintf(f, "\"%s\": %.17g, ", kkt_names[q], k[q]);
+  fprintf(f, "\"per_block\": [");
+  for (size_t b = 0; b < pb.size() / 6; ++b)
+    fprintf(f, "%s[%.17g, %.17g, %.17g, %.17g, %.17g, %.17g]", b ? ", " : "", pb[6 * b], pb[6 * b + 1], pb[6 * b + 2], pb[6 * b + 3], pb[6 * b + 4], pb[6 * b + 5]);
+  fprintf(f, "]}");
+}
+static void print_kkt(const double* k, const std::vector<double>& pb) {
+  printf("\n KKT report (cuadmm_evaluate):\n");
+  printf("  pobj = %.10e, dobj = %.10e, <X,S> = %.3e\n", k[0], k[1], k[6]);
+  printf("  ||AX - b|| = %.3e, ||A'y + S - C|| = %.3e, ||P+(-X)|| = %.3e, ||P+(-S)|| = %.3e (||b|| = %.3e, ||C|| = %.3e)\n", k[2], k[3], k[4], k[5], k[7], k[8]);
+  printf("  DIMACS: err1 = %.3e, err2 = %.3e, err3 = %.3e, err4 = %.3e, err5 = %.3e, err6 = %.3e (err2, err4: Frobenius norm of the negative parts)\n",
+         k[9], k[10], k[11], k[12], k[13], k[14]);
+  size_t wx = 0, ws = 0, wr = 0;
+  for (size_t b = 0; b < pb.size() / 6; ++b) {
+    if (pb[6 * b + 1] > pb[6 * wx + 1]) wx = b;
+    if (pb[6 * b + 3] > pb[6 * ws + 3]) ws = b;
+    if (pb[6 * b + 5] > pb[6 * wr + 5]) wr = b;
+  }
+  if (!pb.empty())
+    printf("  worst blocks: vX %.3e (block %zu), vS %.3e (block %zu), ||Rd_k|| %.3e (block %zu); %.3f ms\n", pb[6 * wx + 1], wx, pb[6 * ws + 3], ws, pb[6 * wr + 5], wr, k[15]);
+}
+// <dir/>name.txt, one number per line (cuadmm_write_dense_txt); a missing file: zeros
+static bool read_point_vec(const std::string& fn, std::vector<double>& out, size_t n) {
+  out.assign(n, 0.0);
+  FILE* f = fopen(fn.c_str(), "r");
+  if (!f) return true;
+  size_t got = 0;
+  double x = 0;
+  while (got < n && fscanf(f, "%lf", &x) == 1) out[got++] = x;
+  const bool more = fscanf(f, "%lf", &x) == 1;
+  fclose(f);
+  if (got != n || more) { std::cerr << "--kkt-point: '" << fn << "' must hold " << n << " numbers" << std::endl; return false; }
+  return true;
+}
+
 // --json=<file>: one object; every number printed with %.17g
-static bool write_sidecar(const std::string& path, const std::string& prefix, cuadmm_solver* solver, const cuadmm_problem_view& v, bool have_bounds) {
+static bool write_sidecar(const std::string& path, const std::string& prefix, cuadmm_solver* solver, const cuadmm_problem_view& v, bool have_bounds,
+                          const double* kkt = nullptr, const std::vector<double>& kkt_blocks = std::vector<double>()) {
   FILE* f = fopen(path.c_str(), "w");
   if (!f) return false;
   const int iters = cuadmm_get_info_iter_num(solver);
@@ -81,6 +125,7 @@ static bool write_sidecar(const std::string& path, const std::string& prefix, cu
                 gi[0], gi[1], gi[2], gi[4], gi[5], gi[6], gi[7]);
     } else std::cerr << cuadmm_last_error() << std::endl;
   }
+  if (kkt) { write_kkt(f, kkt, kkt_blocks); fprintf(f, ",\n"); }
   double acc[8] = {0};
   cuadmm_get_accel_info(solver, acc);
   if (acc[0] > 0)
@@ -119,8 +164,8 @@ int main(int argc, char* argv[]) {
   int eig_stream_num_per_gpu = 15, cpu_eig_thread_num = 30;
   double max_iter = 1e6, stop_tol = 1e-3, threshold = 0, stage1 = 50, stage2 = 100, switch_admm = 5000, sigscale = 1.05,
          sig = 1e0, device = 0, accel = 0, infeas = 0, infeas_tol = -1, gap = 0, gap_tol = -1;
-  bool quiet = false;
-  std::string json_path, bounds_arg;
+  bool quiet = false, kkt = false;
+  std::string json_path, bounds_arg, kkt_point;
   std::vector<std::string> then_dirs;
   std::vector<char> then_is_A;
   for (int i = 2; i < argc; ++i) {
@@ -134,6 +179,8 @@ int main(int argc, char* argv[]) {
         opt(argv[i], "--infeas_tol", infeas_tol) || opt(argv[i], "--infeas", infeas) || opt(argv[i], "--gap_tol", gap_tol) || opt(argv[i], "--gap", gap))
       continue;
     if (strcmp(argv[i], "--quiet") == 0) { quiet = true; continue; }
+    if (strcmp(argv[i], "--kkt") == 0) { kkt = true; continue; }
+    if (strncmp(argv[i], "--kkt-point=", 12) == 0) { kkt_point = argv[i] + 12; continue; }
     std::cerr << "unknown option " << argv[i] << std::endl;
     return 1;
   }
@@ -199,8 +246,35 @@ int main(int argc, char* argv[]) {
     std::cerr << cuadmm_last_error() << std::endl;
     return 1;
   }
+  double kk[16] = {0};
+  std::vector<double> kkb(6 * (size_t)v.mat_num);
+  if (!kkt_point.empty()) {       // the report of a point from files, no solve
+    std::vector<double> pX, py, pS;
+    rc = (read_point_vec(kkt_point + "X.txt", pX, (size_t)v.vec_len) && read_point_vec(kkt_point + "y.txt", py, (size_t)v.con_num) &&
+          read_point_vec(kkt_point + "S.txt", pS, (size_t)v.vec_len)) ? CUADMM_OK : CUADMM_ERR_IO;
+    if (rc == CUADMM_OK && (rc = cuadmm_evaluate(solver, pX.data(), py.data(), pS.data(), kk, kkb.data())) != CUADMM_OK) std::cerr << cuadmm_last_error() << std::endl;
+    if (rc == CUADMM_OK) {
+      print_kkt(kk, kkb);
+      if (!json_path.empty()) {
+        FILE* f = fopen(json_path.c_str(), "w");
+        if (f) { fprintf(f, "{\n \"problem\": \"%s\", \"point\": \"%s\",\n", prefix.c_str(), kkt_point.c_str()); write_kkt(f, kk, kkb); fprintf(f, "\n}\n"); }
+        if (!f || fclose(f) != 0) std::cerr << "cannot write " << json_path << std::endl;
+      }
+    }
+    cuadmm_destroy(solver);
+    cuadmm_problem_free(prob);
+    return rc == CUADMM_OK ? 0 : 1;
+  }
+  // --kkt: the report of the point a solve returns, taken before anything reads the iterate
+  auto kkt_report = [&]() {
+    if (!kkt) return false;
+    if (cuadmm_evaluate(solver, nullptr, nullptr, nullptr, kk, kkb.data()) != CUADMM_OK) { std::cerr << cuadmm_last_error() << std::endl; return false; }
+    print_kkt(kk, kkb);
+    return true;
+  };
   rc = cuadmm_solve(solver, (int)max_iter, stop_tol, (int)threshold, (int)stage1, (int)stage2, (int)switch_admm, sigscale, 1);
   if (rc != CUADMM_OK) std::cerr << cuadmm_last_error() << std::endl;
+  bool have_kkt = kkt_report();
 
   if (accel != 0) {
     double acc[8] = {0};
@@ -209,7 +283,7 @@ int main(int argc, char* argv[]) {
   }
   std::vector<double> X((size_t)v.vec_len);
   if (cuadmm_get_X(solver, X.data()) == CUADMM_OK) cuadmm_write_dense_txt((prefix + "X_opt.txt").c_str(), X.data(), v.vec_len);
-  if (!json_path.empty() && !write_sidecar(json_path, prefix, solver, v, !bounds_arg.empty())) std::cerr << "cannot write " << json_path << std::endl;
+  if (!json_path.empty() && !write_sidecar(json_path, prefix, solver, v, !bounds_arg.empty(), have_kkt ? kk : nullptr, kkb)) std::cerr << "cannot write " << json_path << std::endl;
   for (size_t k = 0; k < then_dirs.size() && rc == CUADMM_OK; ++k) {
     const std::string& d = then_dirs[k];
     std::vector<int> bi, ci;
@@ -233,9 +307,10 @@ int main(int argc, char* argv[]) {
     rc = cuadmm_update_bC(solver, bi.data(), bv.data(), bn, ci.data(), cv.data(), cn, 1, 0.0);
     if (rc == CUADMM_OK) rc = cuadmm_solve(solver, (int)max_iter, stop_tol, (int)threshold, (int)stage1, (int)stage2, (int)switch_admm, sigscale, 1);
     if (rc != CUADMM_OK) { std::cerr << cuadmm_last_error() << std::endl; break; }
+    have_kkt = kkt_report();
     if (cuadmm_get_X(solver, X.data()) == CUADMM_OK) cuadmm_write_dense_txt((d + "X_opt.txt").c_str(), X.data(), v.vec_len);
     const std::string side = json_path + "." + std::to_string(k + 1);
-    if (!json_path.empty() && !write_sidecar(side, d, solver, v, !bounds_arg.empty())) std::cerr << "cannot write " << side << std::endl;
+    if (!json_path.empty() && !write_sidecar(side, d, solver, v, !bounds_arg.empty(), have_kkt ? kk : nullptr, kkb)) std::cerr << "cannot write " << side << std::endl;
   }
   cuadmm_destroy(solver);
   cuadmm_problem_free(prob);

@@ -33,6 +33,7 @@
 #include "accel.h"
 #include "infeas.h"
 #include "lower_bound.h"
+#include "evaluate.h"
 
 using namespace cuadmm;
 
@@ -455,6 +456,27 @@ struct cuadmm_solver {
     double bytes() const { return 8.0 * (double)(in.n + out.n + bcopy.n) + plan_bytes; }
     ~AuxProj() { for (auto& e : ev) if (e) { hipError_t r = hipEventDestroy(e); (void)r; } delete plan; }
   } aux;
+
+  // Evaluation of a point (cuadmm_evaluate; evaluate.h, DESIGN.md "Evaluation of a point").  The point in the engine's scaled space: xs, ss
+  // (allocated when a vector is passed, or the resident one is in the caller's units; behind a solve the scaled iterate is read where it
+  // lies) and cons, which holds y and then A X.  px = P+(X); P+(S) and A'y - C go to the auxiliary projector's two vectors.  normA: the
+  // column norms where the engine keeps them on the host only (as AuxProj::bcopy for b).  Nothing here is read by the iteration.
+  struct Ev {
+    DevBuf<double> xs, ss, px, cons, normA, sums, cpart, part, out_d;
+    DevBuf<long long> off_d, len_d;
+    DevBuf<int> blk_d, wave_d, chunk_d, large_d;
+    int nwave = 0, nchunk = 0, nlarge = 0;
+    PinnedBuf<double> h_out;
+    long long calls = 0;
+    double ms = 0;
+    double bytes() const {
+      return 8.0 * (double)(xs.n + ss.n + px.n + cons.n + normA.n + sums.n + cpart.n + part.n + out_d.n + off_d.n + len_d.n) +
+             4.0 * (double)(blk_d.n + wave_d.n + chunk_d.n + large_d.n);
+    }
+  } ev;
+  int ev_prepare();
+  int ev_point(const double* host, const DevBuf<double>& resident, double inv_scale, DevBuf<double>& own, const double** out);
+  int ev_run(const double* xs, const double* ss, double out16[16], double* per_block);
 
   // profiling
   hipEvent_t ev0[K_NUM][2] = {}, ev1[K_NUM][2] = {};
@@ -2579,6 +2601,110 @@ int cuadmm_solver::lb_step(int iter, double stop_tol) {
   return CUADMM_OK;
 }
 
+// ------------------------------------------------------------------------------------------
+// Evaluation of a point (cuadmm_evaluate): DESIGN.md, "Evaluation of a point"
+// ------------------------------------------------------------------------------------------
+// vectors and task lists on first use; the column norms (where the engine keeps none on the device) and the auxiliary projector's b on
+// every call: cuadmm_update_A / cuadmm_update_bC may have changed them
+int cuadmm_solver::ev_prepare() {
+  int rc;
+  const int nb = (int)blk_local.size();
+  const size_t mm = (size_t)std::max(m, 1);
+  if (!ev.out_d.p) {
+    std::vector<long long> off((size_t)nb), len((size_t)nb);
+    long long o = 0;
+    for (int k = 0; k < nb; ++k) { off[k] = o; len[k] = blk_svec_len(blk_local[k]); o += len[k]; }
+    LbTasks t;
+    if ((rc = lb_build_tasks(nb, len.data(), &t))) return rc;
+    if ((rc = ev.px.alloc((size_t)L)) || (rc = ev.cons.alloc(mm)) || (!normA_d.p && (rc = ev.normA.alloc(mm))) || (rc = ev.sums.alloc(kEvSums * (size_t)nb)) ||
+        (rc = ev.cpart.alloc(kEvSums * (size_t)t.nchunk())) || (rc = ev.part.alloc(3 * (size_t)kLbDotSlots)) || (rc = ev.h_out.alloc(kEvGlobals)) ||
+        (rc = ev.off_d.from(off)) || (rc = ev.len_d.from(len)) || (rc = ev.blk_d.from(blk_local)) || (rc = ev.wave_d.from(t.wave)) ||
+        (rc = ev.chunk_d.from(t.chunk)) || (rc = ev.large_d.from(t.large)))
+      return rc;
+    ev.nwave = t.nwave(); ev.nchunk = t.nchunk(); ev.nlarge = t.nlarge();
+    CUADMM_HIP_TRY(hipMemsetAsync(ev.sums.p, 0, sizeof(double) * ev.sums.n, st));      // (a block without slots keeps zeros)
+    if ((rc = ev.out_d.alloc(kEvGlobals))) return rc;      // last: marks the set as complete
+  }
+  if (ev.normA.p && m > 0 && (rc = staged_h2d(ev.normA.p, normA_p.data(), sizeof(double) * (size_t)m, st))) return rc;
+  return aux.ensure(*this);
+}
+
+// One svec vector of the point in the engine's scaled space.  host: the caller's (this rank's L entries), scaled as init scales X0 / S0,
+// into `own`; null: the resident one -- read where it lies when a solve left it scaled, else a scaled copy in `own`.
+int cuadmm_solver::ev_point(const double* host, const DevBuf<double>& resident, double inv_scale, DevBuf<double>& own, const double** out) {
+  int rc;
+  if (!host && pending_unscale) { *out = resident.p; return CUADMM_OK; }
+  if (!own.p && (rc = own.alloc((size_t)L))) return rc;
+  if (host) {
+    std::vector<double> tmp((size_t)L);
+    for (long long i = 0; i < L; ++i) tmp[i] = host[i] * inv_scale;
+    if ((rc = staged_h2d(own.p, tmp.data(), sizeof(double) * (size_t)L, st))) return rc;
+  } else {
+    CUADMM_HIP_TRY(hipMemcpyAsync(own.p, resident.p, sizeof(double) * (size_t)L, hipMemcpyDeviceToDevice, st));
+    if ((rc = launch_scale(own.p, L, inv_scale, st))) return rc;
+  }
+  *out = own.p;
+  return CUADMM_OK;
+}
+
+// The report at (xs, y in ev.cons, ss), all scaled and in the engine's order.  Reads A, A', b, C; writes only the evaluation's and the
+// auxiliary projector's vectors.  The scalars go back to the caller's units as set_residual_scalars and lb_eval convert theirs:
+// X = bscale X_s, S = Cscale S_s, Rd = Cscale Rd_s, objectives and <X, S> times objscale; ev_rp forms ||A X - b|| in them itself.
+int cuadmm_solver::ev_run(const double* xs, const double* ss, double o[16], double* per_block) {
+  int rc;
+  const int nb = (int)blk_local.size();
+  double* const cons = ev.cons.p;
+  double* const rd1 = aux.in.p;      // A'y - C
+  double* const ps = aux.out.p;      // P+(S)
+  double *const cx_part = ev.part.p, *const by_part = ev.part.p + kLbDotSlots, *const rp_part = ev.part.p + 2 * kLbDotSlots;
+  const double* const normA_dev = normA_d.p ? normA_d.p : ev.normA.p;
+  CUADMM_HIP_TRY(hipEventRecord(aux.ev[0], st));
+  if ((rc = launch_aty_xb(false, L, At_rp.p, At_ci.p, At_v.p, cons, C.p, xs, 1.0, rd1, nullptr, st, &At_long))) return rc;
+  if ((rc = launch_lb_dot(m, aux.b_dev(*this), cons, by_part, st))) return rc;
+  if ((rc = launch_lb_dot(L, C.p, xs, cx_part, st))) return rc;
+  // A X from the engine's whole A (kept in every mode: the fused and closed iterations evaluate rows of it elsewhere), over y in cons
+  if (m > 0 && (rc = launch_spmv_rows(m, A_avg_nnz, A_rp.p, A_ci.p, A_v.p, xs, ss, C.p, cons, nullptr, st, &A_long))) return rc;
+  if ((rc = launch_ev_rp(m, cons, aux.b_dev(*this), normA_dev, bscale, rp_part, st))) return rc;
+  if ((rc = aux.project(*this, xs, ev.px.p))) return rc;
+  if ((rc = aux.project(*this, ss, ps))) return rc;
+  EvStatArgs a{xs, ss, ev.px.p, ps, rd1, ev.off_d.p, ev.len_d.p, ev.blk_d.p, ev.wave_d.p, ev.chunk_d.p, ev.large_d.p, ev.nwave, ev.nchunk, ev.nlarge,
+               ev.cpart.p, ev.sums.p};
+  if ((rc = launch_ev_block_stats(a, st))) return rc;
+  if ((rc = launch_ev_combine(nb, ev.sums.p, cx_part, by_part, rp_part, ev.out_d.p, st))) return rc;
+  CUADMM_HIP_TRY(hipMemcpyAsync(ev.h_out.p, ev.out_d.p, sizeof(double) * kEvGlobals, hipMemcpyDeviceToHost, st));
+  CUADMM_HIP_TRY(hipEventRecord(aux.ev[1], st));
+  CUADMM_HIP_TRY(hipStreamSynchronize(st));
+  ev.ms = event_ms(aux.ev[0], aux.ev[1]);
+  ev.calls++;
+  if (aux.failed(st)) { set_error("evaluate: a block projection hit the QL sweep cap"); return CUADMM_ERR_EIG; }
+  const double* h = ev.h_out.p;
+  const double nb1 = norm_borg, nc1 = norm_Corg;      // 1 + ||b||, 1 + ||C||
+  o[0] = h[4] * objscale;
+  o[1] = h[5] * objscale;
+  o[2] = std::sqrt(h[6]);
+  o[3] = std::sqrt(h[3]) * Cscale;
+  o[4] = std::sqrt(h[0]) * bscale;
+  o[5] = std::sqrt(h[1]) * Cscale;
+  o[6] = h[2] * objscale;
+  o[7] = nb1 - 1;
+  o[8] = nc1 - 1;
+  const double den = 1 + std::fabs(o[0]) + std::fabs(o[1]);
+  o[9] = o[2] / nb1; o[10] = o[4] / nb1; o[11] = o[3] / nc1; o[12] = o[5] / nc1;
+  o[13] = (o[0] - o[1]) / den; o[14] = o[6] / den;
+  o[15] = ev.ms;
+  if (per_block) {
+    std::vector<double> q(kEvSums * (size_t)nb);
+    if (nb > 0 && (rc = staged_d2h(q.data(), ev.sums.p, sizeof(double) * q.size(), st))) return rc;
+    for (size_t k = 0; k < (size_t)nb; ++k) {
+      const double* v = q.data() + kEvSums * k;
+      double* w = per_block + kEvSums * k;
+      w[0] = std::sqrt(v[0]) * bscale; w[1] = std::sqrt(v[1]) * bscale; w[2] = std::sqrt(v[2]) * Cscale; w[3] = std::sqrt(v[3]) * Cscale;
+      w[4] = v[4] * objscale; w[5] = std::sqrt(v[5]) * Cscale;
+    }
+  }
+  return CUADMM_OK;
+}
+
 // SDPDuoSolver front (duo_solver.h:236-276): exactly two block sizes, then the generic engine.
 int cuadmm_duo_init(cuadmm_solver* s, int if_gpu_eig_mom, int device_num_requested, int eig_stream_num_per_gpu,
                     int cpu_eig_thread_num, int vec_len, int con_num, const int* At_cp, const int* At_ri, const double* At_vx,
@@ -3241,6 +3367,51 @@ int cuadmm_get_gap_info(const cuadmm_solver* s, double o[8]) {
   o[5] = s->lb.ms; o[6] = s->lb.bytes() + (s->lb.out_d.p ? s->aux.bytes() : 0.0); o[7] = (double)s->lb.verdict_iter;
   return CUADMM_OK;
 }
+int cuadmm_evaluate(cuadmm_solver* s, const double* X, const double* y, const double* S, double o[16], double* per_block) {
+  if (!s || !s->initialised || !o) { set_error("evaluate: solver not initialised or null argument"); return CUADMM_ERR_INVALID; }
+  if (s->world > 1 || s->comm_world > 1 || s->local_mode || s->group || s->in_group_call) {
+    set_error("evaluate: works on one rank (world = %d%s): its sums are not all-reduced", std::max(s->world, s->comm_world), s->group ? ", in-process group" : "");
+    return CUADMM_ERR_INVALID;
+  }
+  if (s->L <= 0) { set_error("evaluate: the problem has no svec slots"); return CUADMM_ERR_INVALID; }
+  if (s->factor_bad) { set_error("evaluate: the last cuadmm_update_A could not factor the new A A^T; the solver needs a successful cuadmm_update_A first"); return CUADMM_ERR_FACTOR; }
+  const int m = s->m;
+  const long long L = s->L;
+  // before anything is uploaded: a passed vector with an entry that is not finite
+  const struct { const char* name; const double* v; long long n; } in[3] = {{"X", X, L}, {"y", y, m}, {"S", S, L}};
+  for (const auto& q : in)
+    for (long long i = 0; q.v && i < q.n; ++i)
+      if (!std::isfinite(q.v[i])) { set_error("evaluate: %s[%lld] is not finite", q.name, i); return CUADMM_ERR_INVALID; }
+  int rc = check_device(s->device);
+  if (rc) return rc;
+  if ((rc = s->ev_prepare())) return rc;
+  // The point in the engine's scaled space and order, in vectors of the evaluation's own (the constants of materialise(), inverted, as
+  // cuadmm_init and cuadmm_solve(if_first = 0) apply them).  A null vector is the one its getter would return: behind a solve the
+  // iterate is held scaled and is read as it lies -- the deferred unscaling is not triggered, a following solve(if_first = 0)
+  // continues from it bit for bit --, otherwise it is in the caller's units (y on the host, or on the device where cuadmm_update_bC
+  // left the current one there).
+  const double ibs = 1 / s->bscale, ics = 1 / s->Cscale;
+  const double *xs = nullptr, *ss = nullptr;
+  if ((rc = s->ev_point(X, s->X, ibs, s->ev.xs, &xs)) || (rc = s->ev_point(S, s->S, ics, s->ev.ss, &ss))) return rc;
+  if (m > 0) {
+    if (!y && s->pending_unscale && s->dev_solve) CUADMM_HIP_TRY(hipMemcpyAsync(s->ev.cons.p, s->y_d.p, sizeof(double) * (size_t)m, hipMemcpyDeviceToDevice, s->st));
+    else {
+      std::vector<double> ys(s->y_p);
+      if (y) for (int i = 0; i < m; ++i) ys[i] = (y[s->perm[i]] * s->normA_p[i]) * ics;
+      else if (!s->pending_unscale) {
+        if (s->y_host_stale && (rc = staged_d2h(ys.data(), s->y_d.p, sizeof(double) * (size_t)m, s->st))) return rc;
+        for (int i = 0; i < m; ++i) ys[i] = (ys[i] * s->normA_p[i]) * ics;
+      }
+      if ((rc = staged_h2d(s->ev.cons.p, ys.data(), sizeof(double) * (size_t)m, s->st))) return rc;
+    }
+  }
+  return s->ev_run(xs, ss, o, per_block);
+}
+int cuadmm_get_evaluate_info(const cuadmm_solver* s, double o[4]) {
+  if (!s || !o) { set_error("get_evaluate_info: null"); return CUADMM_ERR_INVALID; }
+  o[0] = (double)s->ev.calls; o[1] = s->ev.bytes(); o[2] = s->ev.out_d.p ? s->aux.bytes() : 0.0; o[3] = s->ev.ms;
+  return CUADMM_OK;
+}
 int cuadmm_trace_bounds_detect(int vec_len, int con_num, const int* At_csc_col_ptrs, const int* At_csc_row_ids, const double* At_csc_vals,
                                const int* b_indices, const double* b_vals, int b_nnz, const int* blk_vals, int mat_num, double* R_out) {
   return lb_trace_bounds_detect(vec_len, con_num, At_csc_col_ptrs, At_csc_row_ids, At_csc_vals, b_indices, b_vals, b_nnz, blk_vals, mat_num, R_out);
@@ -3663,6 +3834,47 @@ int cuadmm_op_lb_block_norms(int64_t n, double* M_inout, double* P_inout, int nb
     return rc;
   comb3_out[0] = o4[0]; comb3_out[1] = o4[1]; comb3_out[2] = o4[2];
   return CUADMM_OK;
+}
+
+// the per-block statistics kernels of cuadmm_evaluate on host arrays (csrc/evaluate.hip).  offs and offset as in cuadmm_op_lb_block_norms;
+// every block's size and range is validated before anything is launched.  The five vectors are copied back as the kernels left them.
+int cuadmm_op_ev_block_stats(int64_t n, double* X, double* S, double* PX, double* PS, double* Rd1, int nblk, const int* blk, const int64_t* offs, int offset,
+                             double* sums6_out) {
+  if (n < 1 || !X || !S || !PX || !PS || !Rd1 || nblk < 1 || !blk || !sums6_out || offset < 0 || offset > 1) {
+    set_error("op_ev_block_stats: invalid argument");
+    return CUADMM_ERR_INVALID;
+  }
+  std::vector<long long> off((size_t)nblk), len((size_t)nblk);
+  long long o = 0;
+  for (int k = 0; k < nblk; ++k) {
+    if (blk[k] == 0 || blk[k] > kMaxBlockSize) { set_error("op_ev_block_stats: block %d has size %d", k, blk[k]); return CUADMM_ERR_INVALID; }
+    len[k] = blk_svec_len(blk[k]);
+    off[k] = offs ? (long long)offs[k] : o;
+    o += len[k];
+    if (off[k] < 0 || off[k] + len[k] > n) { set_error("op_ev_block_stats: block %d outside the vectors", k); return CUADMM_ERR_INVALID; }
+  }
+  int rc = check_device(0);
+  if (rc) return rc;
+  LbTasks t;
+  if ((rc = lb_build_tasks(nblk, len.data(), &t))) return rc;
+  const size_t N = (size_t)n + 2;
+  double* const host[5] = {X, S, PX, PS, Rd1};
+  DevBuf<double> v[5], sums, cpart;
+  DevBuf<long long> off_d, len_d;
+  DevBuf<int> blk_d, wave_d, chunk_d, large_d;
+  for (int q = 0; q < 5; ++q)
+    if ((rc = v[q].alloc(N)) || (rc = staged_h2d(v[q].p + offset, host[q], sizeof(double) * (size_t)n))) return rc;
+  if ((rc = sums.alloc(kEvSums * (size_t)nblk)) || (rc = cpart.alloc(kEvSums * (size_t)t.nchunk())) || (rc = off_d.from(off)) || (rc = len_d.from(len)) ||
+      (rc = blk_d.from(std::vector<int>(blk, blk + nblk))) || (rc = wave_d.from(t.wave)) || (rc = chunk_d.from(t.chunk)) || (rc = large_d.from(t.large)))
+    return rc;
+  CUADMM_HIP_TRY(hipMemset(sums.p, 0xff, sizeof(double) * sums.n));
+  EvStatArgs a{v[0].p + offset, v[1].p + offset, v[2].p + offset, v[3].p + offset, v[4].p + offset, off_d.p, len_d.p, blk_d.p, wave_d.p, chunk_d.p, large_d.p,
+               t.nwave(), t.nchunk(), t.nlarge(), cpart.p, sums.p};
+  if ((rc = launch_ev_block_stats(a, nullptr))) return rc;
+  CUADMM_HIP_TRY(hipDeviceSynchronize());
+  for (int q = 0; q < 5; ++q)
+    if ((rc = staged_d2h(host[q], v[q].p + offset, sizeof(double) * (size_t)n))) return rc;
+  return staged_d2h(sums6_out, sums.p, sizeof(double) * kEvSums * (size_t)nblk);
 }
 
 int cuadmm_dev_malloc(void** ptr, size_t bytes) { CUADMM_HIP_TRY(hipMalloc(ptr, bytes ? bytes : 8)); return CUADMM_OK; }

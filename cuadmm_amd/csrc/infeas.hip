@@ -24,16 +24,6 @@ constexpr long long kStride = (long long)kInfeasSlots * kInfeasThreads;
 
 __device__ __forceinline__ long long inf_tid() { return (long long)blockIdx.x * kInfeasThreads + threadIdx.x; }
 
-// sum over the workgroup in a fixed order; the result is valid in thread 0
-__device__ __forceinline__ double block_sum(double v, double* lds /* 4 doubles */) {
-  v = wave_sum(v);
-  const int w = threadIdx.x >> 6;
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) lds[w] = v;
-  __syncthreads();
-  return (lds[0] + lds[1]) + (lds[2] + lds[3]);
-}
-
 struct RollArgs {
   const double *cur, *w;
   double *prev, *out;

@@ -24,28 +24,6 @@
 namespace cuadmm {
 namespace {
 
-// the sum over each row of 16 lanes, in every lane of the row (the first four steps of wave_sum)
-__device__ __forceinline__ double row_sum(double v) {
-  v += sw_dpp<0xB1>(v);
-  v += sw_dpp<0x4E>(v);
-  v += sw_dpp<0x141>(v);
-  v += sw_dpp<0x140>(v);
-  return v;
-}
-__device__ __forceinline__ double rows_to_wave(double v) {
-  return (sw_readlane(v, 0) + sw_readlane(v, 16)) + (sw_readlane(v, 32) + sw_readlane(v, 48));
-}
-
-// sum over the workgroup in a fixed order; valid in every thread
-__device__ __forceinline__ double block_sum(double v, double* lds /* 4 doubles */) {
-  v = wave_sum(v);
-  const int w = threadIdx.x >> 6;
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) lds[w] = v;
-  __syncthreads();
-  return (lds[0] + lds[1]) + (lds[2] + lds[3]);
-}
-
 // partial sums of lane j of a group of W lanes over slots [0, len) of m and p
 __device__ __forceinline__ void range_acc(const double* __restrict__ m, const double* __restrict__ p, long long len, int j, int W, int vec,
                                           double& sm, double& sp) {

@@ -29,5 +29,29 @@ __device__ __forceinline__ double wave_sum(double v) {
   return (sw_readlane(v, 0) + sw_readlane(v, 16)) + (sw_readlane(v, 32) + sw_readlane(v, 48));
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// The pieces of wave_sum for the per-block reductions (lower_bound.hip, evaluate.hip): a row of 16 lanes or the
+// wavefront owns a block, a workgroup of 256 threads a chunk of a long one.
+// ---------------------------------------------------------------------------------------------------------------
+// the sum over each row of 16 lanes, in every lane of the row (the first four steps of wave_sum)
+__device__ __forceinline__ double row_sum(double v) {
+  v += sw_dpp<0xB1>(v);
+  v += sw_dpp<0x4E>(v);
+  v += sw_dpp<0x141>(v);
+  v += sw_dpp<0x140>(v);
+  return v;
+}
+__device__ __forceinline__ double rows_to_wave(double v) {
+  return (sw_readlane(v, 0) + sw_readlane(v, 16)) + (sw_readlane(v, 32) + sw_readlane(v, 48));
+}
+// sum over a workgroup of 256 threads in a fixed order; valid in every thread
+__device__ __forceinline__ double block_sum(double v, double* lds /* 4 doubles */) {
+  v = wave_sum(v);
+  const int w = threadIdx.x >> 6;
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) lds[w] = v;
+  __syncthreads();
+  return (lds[0] + lds[1]) + (lds[2] + lds[3]);
+}
 
 }  // namespace cuadmm

@@ -180,6 +180,30 @@ class SDPSolver:
         return {"checks": int(o[0]), "best_lower_bound": float(o[1]), "best_iteration": int(o[2]), "last_lower_bound": float(o[3]),
                 "last_gap": float(o[4]), "ms": float(o[5]), "bytes": float(o[6]), "verdict_iteration": int(o[7])}
 
+    EVALUATE_KEYS = ("pobj", "dobj", "norm_Rp", "norm_Rd", "vX", "vS", "XS", "norm_b", "norm_C", "err1", "err2", "err3", "err4", "err5", "err6", "ms")
+
+    def evaluate(self, X=None, y=None, S=None):
+        """KKT and DIMACS report of a point in the caller's units (cuadmm_evaluate); None: the vector .X / .y / .S would return now.
+        The named scalars of EVALUATE_KEYS and "per_block": (mat_num, 6) = ||X_k||, vX_k, ||S_k||, vS_k, <X_k, S_k>, ||Rd_k||."""
+        Xa = None if X is None else _f64(X)
+        ya = None if y is None else _f64(y)
+        Sa = None if S is None else _f64(S)
+        for a, n, what in ((Xa, self.vec_len, "X"), (ya, self.con_num, "y"), (Sa, self.vec_len, "S")):
+            if a is not None and a.size != n:
+                raise ValueError("evaluate: %s has %d entries, the problem %d" % (what, a.size, n))
+        o = np.zeros(16)
+        pb = np.zeros(6 * self.mat_num)
+        check(self._lib.cuadmm_evaluate(self._h, _p(Xa), _p(ya), _p(Sa), _p(o), _p(pb)))
+        r = dict(zip(self.EVALUATE_KEYS, o.tolist()))
+        r["per_block"] = pb.reshape(self.mat_num, 6)
+        return r
+
+    def evaluate_info(self):
+        """cuadmm_get_evaluate_info: calls so far, bytes the evaluation holds, bytes of the auxiliary projector, ms of the last call."""
+        o = np.zeros(4)
+        check(self._lib.cuadmm_get_evaluate_info(self._h, _p(o)))
+        return {"calls": int(o[0]), "bytes": float(o[1]), "aux_bytes": float(o[2]), "ms": float(o[3])}
+
     def set_allreduce(self, fn):
         """fn(dev_ptr:int, count:int, hip_stream:int) -> None : in-place sum over ranks on that stream."""
         def tramp(_user, buf, count, stream):

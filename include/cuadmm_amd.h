@@ -302,6 +302,34 @@ int cuadmm_lower_bound(cuadmm_solver* s, double out8[8], double* per_block);
  * valid --, [2] its iteration, [3] the last bound, [4] the last g, [5] milliseconds of device time in the checks, [6] bytes held (as [7]
  * of cuadmm_lower_bound), [7] iteration of the status-5 verdict or 0.  Zeros while the option is off; cleared where the status is. */
 int cuadmm_get_gap_info(const cuadmm_solver* s, double out8[8]);
+/* KKT and DIMACS report of any point (X, y, S) ("Evaluation of a point").  X, y, S: host pointers in the caller's units and
+ * order, vec_len, con_num and vec_len doubles as cuadmm_set_XyS takes them; NULL: the vector cuadmm_get_X / _y / _S would return now
+ * (behind a solve the scaled iterate is read where it lies: the deferred unscaling is not triggered).  With P+ the projection onto the
+ * PSD cone of a block, Rd = A'y + S - C and ||.|| the 2-norm of the svec (the Frobenius norm of the block), all in the caller's units:
+ *   per_block (may be NULL; 6 mat_num doubles), [6k + ...]: [0] ||X_k||, [1] vX_k = ||P+(-X_k)||, [2] ||S_k||, [3] vS_k = ||P+(-S_k)||,
+ *     [4] <X_k, S_k>, [5] ||Rd_k||.  An unconstrained block has the whole space as its primal cone and {0} as its dual cone:
+ *     vX_k = 0, vS_k = ||S_k||.
+ *   out16: [0] pobj = <C, X>, [1] dobj = b'y, [2] ||A X - b||, [3] ||Rd||, [4] vX = sqrt(sum vX_k^2), [5] vS = sqrt(sum vS_k^2),
+ *     [6] <X, S>, [7] ||b||, [8] ||C||, and the six DIMACS error measures [9] err1 = [2] / (1 + ||b||), [10] err2 = vX / (1 + ||b||),
+ *     [11] err3 = [3] / (1 + ||C||), [12] err4 = vS / (1 + ||C||), [13] err5 = (pobj - dobj) / (1 + |pobj| + |dobj|),
+ *     [14] err6 = <X, S> / (1 + |pobj| + |dobj|) (both signed), [15] milliseconds of device time (HIP events on the engine's stream).
+ * Where DIMACS has max(0, -lambda_min(.)) in err2 and err4, this report has ||P+(-.)||_F, the 2-norm of ALL negative eigenvalues of all
+ * blocks: the projection path has no eigenvalues.  That value lies between DIMACS's and sqrt(n) times it (n: the sum of the block
+ * sizes) and is zero exactly when DIMACS's is.  The projections are the iteration's kernels, accurate to 2e-12 sqrt(2) ||M_k|| per
+ * entry: vX_k, vS_k below that times sqrt(len_k) are rounding.
+ * The call changes nothing the iteration reads: a following cuadmm_solve(..., if_first = 0) continues bit for bit as without it, also
+ * behind a foreign point.  It works on any initialised solver (before, after and between solves, after cuadmm_update_bC / _update_A,
+ * with any option) and on every plan of the engine: A X is formed from the engine's whole A by the iteration's kernel.  Device memory
+ * beyond the auxiliary projector of cuadmm_lower_bound: at most 3 vec_len + con_num doubles (con_num more where the y-solve runs on the
+ * host) and the per-block lists, allocated on first use and kept (cuadmm_get_evaluate_info).
+ * CUADMM_ERR_INVALID, with the solver as it was: not initialised, out16 NULL, world > 1 or an in-process group (its sums are not
+ * all-reduced), a passed vector with an entry that is not finite (checked on the host before anything is uploaded), no svec slots.
+ * CUADMM_ERR_EIG: a block projection reported failure.  CUADMM_ERR_FACTOR: behind a failed cuadmm_update_A. */
+int cuadmm_evaluate(cuadmm_solver* s, const double* X, const double* y, const double* S, double out16[16], double* per_block);
+/* [0] calls of cuadmm_evaluate so far, [1] bytes of device memory the evaluation holds beyond the auxiliary projector (exact), [2] the
+ * auxiliary projector's bytes (its vectors exactly, plus an estimate of its plan; shared with the lower bound and the infeasibility
+ * check), [3] milliseconds of device time of the last call. */
+int cuadmm_get_evaluate_info(const cuadmm_solver* s, double out4[4]);
 /* Trace bounds read off the constraints (the arrays of cuadmm_init).  R_out[k] = -1: nothing found (always for unconstrained blocks).
  * Rule 1: a constraint whose entries are exactly the diagonal slots of ONE PSD block, all with the same value c (c svec(I_k)), gives
  * tr X_k = b_j / c.  Rule 2: a block whose every diagonal entry is fixed by a constraint with that single entry has the sum of those
@@ -546,6 +574,12 @@ int cuadmm_op_infeas_roll(int64_t n, const double* cur, double* prev_inout, cons
  * are copied back as the kernels left them. */
 int cuadmm_op_lb_block_norms(int64_t n, double* M_inout, double* P_inout, int nblk, const int* blk, const int64_t* offs, const double* R, int offset,
                              double* pairs_out, double* comb3_out);
+/* The per-block statistics kernels of cuadmm_evaluate on host arrays (csrc/evaluate.hip): sums6_out[6k + ...] = sum X^2, sum (PX - X)^2,
+ * sum S^2, sum (PS - S)^2, sum X S, sum (Rd1 + S)^2 over the slots of block k; an unconstrained block (negative size) has 0 and sum S^2
+ * as its second and fourth.  blk, offs, offset as in cuadmm_op_lb_block_norms; every block's size and range is checked before anything
+ * is launched.  The five vectors are copied back as the kernels left them (they write none of them). */
+int cuadmm_op_ev_block_stats(int64_t n, double* X_inout, double* S_inout, double* PX_inout, double* PS_inout, double* Rd1_inout, int nblk, const int* blk,
+                             const int64_t* offs, int offset, double* sums6_out /* 6 nblk */);
 int cuadmm_op_spmv_rows(int rows, int ncols, const int* row_ptrs, const int* col_ids, const double* vals, const double* X, const double* S, const double* C,
                         int want_x, int want_s, const int* rowmap, int out_len, double* outX, double* outS, int* info4);
 int cuadmm_op_rp_stats(int m, const double* ax, const double* b, const double* normA, const double* y, double bscale, const double* sums2, double* out4);

@@ -143,6 +143,20 @@ class SDPSolver {
     return GapInfo{(long long)o[0], o[1], (int)o[2], o[3], o[4], o[5], o[6], (int)o[7]};
   }
 
+  // cuadmm_evaluate: KKT and DIMACS report of a point (host pointers in the caller's units, null: the current vector); per_block (may be
+  // null): resized to 6 mat_num, [6k ..] = ||X_k||, vX_k, ||S_k||, vS_k, <X_k, S_k>, ||Rd_k||; not in the reference
+  struct Evaluation { double pobj, dobj, norm_Rp, norm_Rd, vX, vS, XS, norm_b, norm_C, err[6], ms; };
+  Evaluation evaluate(const double* X = nullptr, const double* y = nullptr, const double* S = nullptr, std::vector<double>* per_block = nullptr) {
+    double o[16] = {0};
+    if (per_block) {
+      int vl = 0, cn = 0, mn = 0;
+      check(cuadmm_get_dims(h_, &vl, &cn, &mn));
+      per_block->assign(6 * (size_t)mn, 0.0);
+    }
+    check(cuadmm_evaluate(h_, X, y, S, o, per_block ? per_block->data() : nullptr));
+    return Evaluation{o[0], o[1], o[2], o[3], o[4], o[5], o[6], o[7], o[8], {o[9], o[10], o[11], o[12], o[13], o[14]}, o[15]};
+  }
+
   // cuadmm_update_bC: new b and / or C on the factored solver (nnz < 0: unchanged); not in the reference
   void update_bC(const int* cpu_b_indices, const double* cpu_b_vals, int b_nnz, const int* cpu_C_indices, const double* cpu_C_vals,
                  int C_nnz, bool keep_iterate = true, double sig = 0.0) {
