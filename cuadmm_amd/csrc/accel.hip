@@ -79,15 +79,6 @@ __global__ __launch_bounds__(kAccelThreads) void aa_push_kernel(long long L, Pus
   if (threadIdx.x == 0) partials[(size_t)blockIdx.x * kQ] = acc;
 }
 
-// ---- second stage of the reductions: workgroup q adds partials[slot * kQ + q] over the slots ----------------------------------
-__global__ __launch_bounds__(64) void aa_final_kernel(const double* partials, int nslots, double* out) {
-  const int q = blockIdx.x;
-  double v = 0;
-  for (int s = threadIdx.x; s < nslots; s += 64) v += partials[(size_t)s * kQ + q];
-  v = wave_sum(v);
-  if (threadIdx.x == 0) out[q] = v;
-}
-
 // ---- gram ------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kAccelThreads) void aa_gram_kernel(long long L, long long hs, long long col_stride, int cols, int newest, const double* ring,
                                                                  const double* g, int vec_x, int vec_s, double* partials) {
@@ -229,7 +220,7 @@ int launch_aa_push(long long L, long long hs, const double* u, const double* X, 
              (!have_prev || (aligned16(h->fp) && aligned16(h->gp) && aligned16(h->dF) && aligned16(h->dG)));
   const int nb = grid_for(L);
   hipLaunchKernelGGL(aa_push_kernel, dim3(nb), dim3(kAccelThreads), 0, st, L, hx, hh, have_prev, partials);
-  hipLaunchKernelGGL(aa_final_kernel, dim3(1), dim3(64), 0, st, partials, nb, gnorm2_out);
+  hipLaunchKernelGGL(slots_final_kernel<kQ>, dim3(1), dim3(64), 0, st, partials, nb, gnorm2_out);
   CUADMM_HIP_TRY(hipGetLastError());
   return CUADMM_OK;
 }
@@ -245,7 +236,7 @@ int launch_aa_gram(long long L, long long hs, long long col_stride, int cols, in
   const int vec_s = stride_ok && aligned16(ring_dG + hs) && aligned16(g + hs);
   const int nb = grid_for(L);
   hipLaunchKernelGGL(aa_gram_kernel, dim3(nb), dim3(kAccelThreads), 0, st, L, hs, col_stride, cols, newest, ring_dG, g, vec_x, vec_s, partials);
-  hipLaunchKernelGGL(aa_final_kernel, dim3(2 * cols), dim3(64), 0, st, partials, nb, dots);
+  hipLaunchKernelGGL(slots_final_kernel<kQ>, dim3(2 * cols), dim3(64), 0, st, partials, nb, dots);
   CUADMM_HIP_TRY(hipGetLastError());
   return CUADMM_OK;
 }

@@ -422,18 +422,12 @@ struct cuadmm_solver {
     std::vector<double> R;             // the caller's bounds, one per block (empty: none set)
     bool R_dirty = false;
     DevBuf<double> ybuf, R_d, pairs, cpart, dpart, out_d;
-    DevBuf<long long> off_d, len_d;
-    DevBuf<int> blk_d, wave_d, chunk_d, large_d;
-    int nwave = 0, nchunk = 0, nlarge = 0;
     PinnedBuf<double> h_out;
     // of the last solve with the option on
     long long checks = 0;
     int best_iter = 0, verdict_iter = 0;
     double best_lb = 0, last_lb = 0, last_g = 0, ms = 0;
-    double bytes() const {
-      return 8.0 * (double)(ybuf.n + R_d.n + pairs.n + cpart.n + dpart.n + out_d.n + off_d.n + len_d.n) +
-             4.0 * (double)(blk_d.n + wave_d.n + chunk_d.n + large_d.n);
-    }
+    double bytes() const { return 8.0 * (double)(ybuf.n + R_d.n + pairs.n + cpart.n + dpart.n + out_d.n); }      // its own; the reports add btasks and aux
   } lb;
   bool gap_on() const { return lb.period > 0 && L > 0; }
   void lb_reset() { lb.checks = 0; lb.best_iter = lb.verdict_iter = 0; lb.best_lb = lb.last_lb = lb.last_g = 0; }
@@ -457,22 +451,41 @@ struct cuadmm_solver {
     ~AuxProj() { for (auto& e : ev) if (e) { hipError_t r = hipEventDestroy(e); (void)r; } delete plan; }
   } aux;
 
+  // The per-block task lists of block_reduce.h on the device, for the lower bound and the evaluation: built from blk_local by whichever
+  // of lb_prepare / ev_prepare runs first.  blk_local never changes after init, so cuadmm_update_A / cuadmm_update_bC leave them alone.
+  // Each of the two reports these bytes with its own, as it does the auxiliary projector's.
+  struct BlockTasksDev {
+    DevBuf<long long> off, len;
+    DevBuf<int> blk, wave, chunk, large;
+    int nwave = 0, nchunk = 0, nlarge = 0;
+    bool built = false;
+    int build(const int* blk_h, int nb, const int64_t* off_h /* null: consecutive */) {
+      std::vector<long long> o((size_t)nb), l((size_t)nb);
+      long long next = 0;
+      for (int k = 0; k < nb; ++k) { l[k] = blk_svec_len(blk_h[k]); o[k] = off_h ? (long long)off_h[k] : next; next += l[k]; }
+      BlockTasks t;
+      int rc;
+      if ((rc = build_block_tasks(nb, l.data(), &t)) || (rc = off.from(o)) || (rc = len.from(l)) || (rc = blk.from(std::vector<int>(blk_h, blk_h + nb))) ||
+          (rc = wave.from(t.wave)) || (rc = chunk.from(t.chunk)) || (rc = large.from(t.large)))
+        return rc;
+      nwave = t.nwave(); nchunk = t.nchunk(); nlarge = t.nlarge();
+      built = true;
+      return CUADMM_OK;
+    }
+    BlockTasksView view() const { return {off.p, len.p, blk.p, wave.p, chunk.p, large.p, nwave, nchunk, nlarge}; }
+    double bytes() const { return 8.0 * (double)(off.n + len.n) + 4.0 * (double)(blk.n + wave.n + chunk.n + large.n); }
+  } btasks;
+
   // Evaluation of a point (cuadmm_evaluate; evaluate.h, DESIGN.md "Evaluation of a point").  The point in the engine's scaled space: xs, ss
   // (allocated when a vector is passed, or the resident one is in the caller's units; behind a solve the scaled iterate is read where it
   // lies) and cons, which holds y and then A X.  px = P+(X); P+(S) and A'y - C go to the auxiliary projector's two vectors.  normA: the
   // column norms where the engine keeps them on the host only (as AuxProj::bcopy for b).  Nothing here is read by the iteration.
   struct Ev {
     DevBuf<double> xs, ss, px, cons, normA, sums, cpart, part, out_d;
-    DevBuf<long long> off_d, len_d;
-    DevBuf<int> blk_d, wave_d, chunk_d, large_d;
-    int nwave = 0, nchunk = 0, nlarge = 0;
     PinnedBuf<double> h_out;
     long long calls = 0;
     double ms = 0;
-    double bytes() const {
-      return 8.0 * (double)(xs.n + ss.n + px.n + cons.n + normA.n + sums.n + cpart.n + part.n + out_d.n + off_d.n + len_d.n) +
-             4.0 * (double)(blk_d.n + wave_d.n + chunk_d.n + large_d.n);
-    }
+    double bytes() const { return 8.0 * (double)(xs.n + ss.n + px.n + cons.n + normA.n + sums.n + cpart.n + part.n + out_d.n); }      // its own
   } ev;
   int ev_prepare();
   int ev_point(const double* host, const DevBuf<double>& resident, double inv_scale, DevBuf<double>& own, const double** out);
@@ -2533,17 +2546,10 @@ int cuadmm_solver::lb_prepare() {
   if ((int)lb.R.size() != nb) { set_error("lower bound: %d trace bounds are set, the solver has %d blocks", (int)lb.R.size(), nb); return CUADMM_ERR_INVALID; }
   if (!lb.out_d.p) {
     const size_t mm = (size_t)std::max(m, 1);
-    std::vector<long long> off((size_t)nb), len((size_t)nb);
-    long long o = 0;
-    for (int k = 0; k < nb; ++k) { off[k] = o; len[k] = blk_svec_len(blk_local[k]); o += len[k]; }
-    LbTasks t;
-    if ((rc = lb_build_tasks(nb, len.data(), &t))) return rc;
-    if ((rc = lb.ybuf.alloc(mm)) || (rc = lb.R_d.alloc((size_t)nb)) ||
-        (rc = lb.pairs.alloc(2 * (size_t)nb)) || (rc = lb.dpart.alloc(kLbDotSlots)) || (rc = lb.h_out.alloc(4)) || (rc = lb.off_d.from(off)) ||
-        (rc = lb.len_d.from(len)) || (rc = lb.blk_d.from(blk_local)) || (rc = lb.wave_d.from(t.wave)) || (rc = lb.chunk_d.from(t.chunk)) ||
-        (rc = lb.large_d.from(t.large)) || (rc = lb.cpart.alloc(2 * (size_t)t.nchunk())))
+    if (!btasks.built && (rc = btasks.build(blk_local.data(), nb, nullptr))) return rc;
+    if ((rc = lb.ybuf.alloc(mm)) || (rc = lb.R_d.alloc((size_t)nb)) || (rc = lb.pairs.alloc(2 * (size_t)nb)) || (rc = lb.dpart.alloc(kBrSlots)) ||
+        (rc = lb.h_out.alloc(4)) || (rc = lb.cpart.alloc(2 * (size_t)btasks.nchunk)))
       return rc;
-    lb.nwave = t.nwave(); lb.nchunk = t.nchunk(); lb.nlarge = t.nlarge();
     CUADMM_HIP_TRY(hipMemsetAsync(lb.pairs.p, 0, sizeof(double) * lb.pairs.n, st));
     lb.R_dirty = true;
     if ((rc = lb.out_d.alloc(4))) return rc;          // last: marks the set as complete
@@ -2563,10 +2569,9 @@ int cuadmm_solver::lb_eval(const double* y, double out6[6], float* ms) {
   // M = A'y - C (S^ = -Cscale M), P = P+(M) with the unconstrained slices copied through
   if ((rc = launch_aty_xb(false, L, At_rp.p, At_ci.p, At_v.p, y, C.p, X.p, 1.0, mbuf, nullptr, st, &At_long))) return rc;
   if ((rc = aux.project(*this, mbuf, pbuf))) return rc;
-  LbNormArgs a{mbuf, pbuf, lb.off_d.p, lb.len_d.p, lb.wave_d.p, lb.chunk_d.p, lb.large_d.p, lb.nwave, lb.nchunk, lb.nlarge, lb.cpart.p, lb.pairs.p};
-  if ((rc = launch_lb_block_norms(a, st))) return rc;
+  if ((rc = launch_lb_block_norms(mbuf, pbuf, btasks.view(), lb.cpart.p, lb.pairs.p, st))) return rc;
   if ((rc = launch_lb_dot(m, aux.b_dev(*this), y, lb.dpart.p, st))) return rc;
-  if ((rc = launch_lb_combine((int)blk_local.size(), lb.pairs.p, lb.R_d.p, lb.len_d.p, lb.blk_d.p, lb.dpart.p, lb.out_d.p, st))) return rc;
+  if ((rc = launch_lb_combine((int)blk_local.size(), lb.pairs.p, lb.R_d.p, btasks.len.p, btasks.blk.p, lb.dpart.p, lb.out_d.p, st))) return rc;
   CUADMM_HIP_TRY(hipMemcpyAsync(lb.h_out.p, lb.out_d.p, sizeof(double) * 4, hipMemcpyDeviceToHost, st));
   CUADMM_HIP_TRY(hipEventRecord(aux.ev[1], st));
   CUADMM_HIP_TRY(hipStreamSynchronize(st));
@@ -2611,17 +2616,10 @@ int cuadmm_solver::ev_prepare() {
   const int nb = (int)blk_local.size();
   const size_t mm = (size_t)std::max(m, 1);
   if (!ev.out_d.p) {
-    std::vector<long long> off((size_t)nb), len((size_t)nb);
-    long long o = 0;
-    for (int k = 0; k < nb; ++k) { off[k] = o; len[k] = blk_svec_len(blk_local[k]); o += len[k]; }
-    LbTasks t;
-    if ((rc = lb_build_tasks(nb, len.data(), &t))) return rc;
+    if (!btasks.built && (rc = btasks.build(blk_local.data(), nb, nullptr))) return rc;
     if ((rc = ev.px.alloc((size_t)L)) || (rc = ev.cons.alloc(mm)) || (!normA_d.p && (rc = ev.normA.alloc(mm))) || (rc = ev.sums.alloc(kEvSums * (size_t)nb)) ||
-        (rc = ev.cpart.alloc(kEvSums * (size_t)t.nchunk())) || (rc = ev.part.alloc(3 * (size_t)kLbDotSlots)) || (rc = ev.h_out.alloc(kEvGlobals)) ||
-        (rc = ev.off_d.from(off)) || (rc = ev.len_d.from(len)) || (rc = ev.blk_d.from(blk_local)) || (rc = ev.wave_d.from(t.wave)) ||
-        (rc = ev.chunk_d.from(t.chunk)) || (rc = ev.large_d.from(t.large)))
+        (rc = ev.cpart.alloc(kEvSums * (size_t)btasks.nchunk)) || (rc = ev.part.alloc(3 * (size_t)kBrSlots)) || (rc = ev.h_out.alloc(kEvGlobals)))
       return rc;
-    ev.nwave = t.nwave(); ev.nchunk = t.nchunk(); ev.nlarge = t.nlarge();
     CUADMM_HIP_TRY(hipMemsetAsync(ev.sums.p, 0, sizeof(double) * ev.sums.n, st));      // (a block without slots keeps zeros)
     if ((rc = ev.out_d.alloc(kEvGlobals))) return rc;      // last: marks the set as complete
   }
@@ -2656,7 +2654,7 @@ int cuadmm_solver::ev_run(const double* xs, const double* ss, double o[16], doub
   double* const cons = ev.cons.p;
   double* const rd1 = aux.in.p;      // A'y - C
   double* const ps = aux.out.p;      // P+(S)
-  double *const cx_part = ev.part.p, *const by_part = ev.part.p + kLbDotSlots, *const rp_part = ev.part.p + 2 * kLbDotSlots;
+  double *const cx_part = ev.part.p, *const by_part = ev.part.p + kBrSlots, *const rp_part = ev.part.p + 2 * kBrSlots;
   const double* const normA_dev = normA_d.p ? normA_d.p : ev.normA.p;
   CUADMM_HIP_TRY(hipEventRecord(aux.ev[0], st));
   if ((rc = launch_aty_xb(false, L, At_rp.p, At_ci.p, At_v.p, cons, C.p, xs, 1.0, rd1, nullptr, st, &At_long))) return rc;
@@ -2667,9 +2665,7 @@ int cuadmm_solver::ev_run(const double* xs, const double* ss, double o[16], doub
   if ((rc = launch_ev_rp(m, cons, aux.b_dev(*this), normA_dev, bscale, rp_part, st))) return rc;
   if ((rc = aux.project(*this, xs, ev.px.p))) return rc;
   if ((rc = aux.project(*this, ss, ps))) return rc;
-  EvStatArgs a{xs, ss, ev.px.p, ps, rd1, ev.off_d.p, ev.len_d.p, ev.blk_d.p, ev.wave_d.p, ev.chunk_d.p, ev.large_d.p, ev.nwave, ev.nchunk, ev.nlarge,
-               ev.cpart.p, ev.sums.p};
-  if ((rc = launch_ev_block_stats(a, st))) return rc;
+  if ((rc = launch_ev_block_stats(xs, ss, ev.px.p, ps, rd1, btasks.view(), ev.cpart.p, ev.sums.p, st))) return rc;
   if ((rc = launch_ev_combine(nb, ev.sums.p, cx_part, by_part, rp_part, ev.out_d.p, st))) return rc;
   CUADMM_HIP_TRY(hipMemcpyAsync(ev.h_out.p, ev.out_d.p, sizeof(double) * kEvGlobals, hipMemcpyDeviceToHost, st));
   CUADMM_HIP_TRY(hipEventRecord(aux.ev[1], st));
@@ -3352,7 +3348,7 @@ int cuadmm_lower_bound(cuadmm_solver* s, double o[8], double* per_block) {
   if ((rc = s->lb_eval(s->lb.ybuf.p, r, &ms))) return rc;
   o[0] = r[0]; o[1] = r[1]; o[2] = r[2];
   o[3] = std::fabs(s->pobj - r[0]) / (1 + std::fabs(s->pobj) + std::fabs(r[0]));
-  o[4] = r[3]; o[5] = r[4]; o[6] = ms; o[7] = s->lb.bytes() + s->aux.bytes();
+  o[4] = r[3]; o[5] = r[4]; o[6] = ms; o[7] = s->lb.bytes() + s->btasks.bytes() + s->aux.bytes();
   if (per_block) {
     const size_t nb = s->blk_local.size();
     std::vector<double> pr(2 * nb);
@@ -3364,7 +3360,7 @@ int cuadmm_lower_bound(cuadmm_solver* s, double o[8], double* per_block) {
 int cuadmm_get_gap_info(const cuadmm_solver* s, double o[8]) {
   if (!s || !o) { set_error("get_gap_info: null"); return CUADMM_ERR_INVALID; }
   o[0] = (double)s->lb.checks; o[1] = s->lb.best_lb; o[2] = (double)s->lb.best_iter; o[3] = s->lb.last_lb; o[4] = s->lb.last_g;
-  o[5] = s->lb.ms; o[6] = s->lb.bytes() + (s->lb.out_d.p ? s->aux.bytes() : 0.0); o[7] = (double)s->lb.verdict_iter;
+  o[5] = s->lb.ms; o[6] = s->lb.bytes() + (s->lb.out_d.p ? s->btasks.bytes() + s->aux.bytes() : 0.0); o[7] = (double)s->lb.verdict_iter;
   return CUADMM_OK;
 }
 int cuadmm_evaluate(cuadmm_solver* s, const double* X, const double* y, const double* S, double o[16], double* per_block) {
@@ -3409,7 +3405,7 @@ int cuadmm_evaluate(cuadmm_solver* s, const double* X, const double* y, const do
 }
 int cuadmm_get_evaluate_info(const cuadmm_solver* s, double o[4]) {
   if (!s || !o) { set_error("get_evaluate_info: null"); return CUADMM_ERR_INVALID; }
-  o[0] = (double)s->ev.calls; o[1] = s->ev.bytes(); o[2] = s->ev.out_d.p ? s->aux.bytes() : 0.0; o[3] = s->ev.ms;
+  o[0] = (double)s->ev.calls; o[1] = s->ev.bytes() + (s->ev.out_d.p ? s->btasks.bytes() : 0.0); o[2] = s->ev.out_d.p ? s->aux.bytes() : 0.0; o[3] = s->ev.ms;
   return CUADMM_OK;
 }
 int cuadmm_trace_bounds_detect(int vec_len, int con_num, const int* At_csc_col_ptrs, const int* At_csc_row_ids, const double* At_csc_vals,
@@ -3790,6 +3786,18 @@ int cuadmm_op_infeas_roll(int64_t n, const double* cur, double* prev_inout, cons
   return CUADMM_OK;
 }
 
+// every block's size and range, before the op hooks of the per-block reductions allocate or launch anything
+static int op_check_blocks(const char* who, int64_t n, int nblk, const int* blk, const int64_t* offs) {
+  long long o = 0;
+  for (int k = 0; k < nblk; ++k) {
+    if (blk[k] == 0 || blk[k] > kMaxBlockSize) { set_error("%s: block %d has size %d", who, k, blk[k]); return CUADMM_ERR_INVALID; }
+    const long long len = blk_svec_len(blk[k]), off = offs ? (long long)offs[k] : o;
+    o += len;
+    if (off < 0 || off + len > n) { set_error("%s: block %d outside the vectors", who, k); return CUADMM_ERR_INVALID; }
+  }
+  return CUADMM_OK;
+}
+
 // the per-block norm kernels of the lower bound on host arrays (csrc/lower_bound.hip).  offs: first slot of every block (null: the
 // blocks follow one another from slot 0); offset = 1 places both vectors one double behind a 16-byte boundary.  M and P are copied
 // back as the kernels left them.
@@ -3799,34 +3807,20 @@ int cuadmm_op_lb_block_norms(int64_t n, double* M_inout, double* P_inout, int nb
     set_error("op_lb_block_norms: invalid argument");
     return CUADMM_ERR_INVALID;
   }
-  std::vector<long long> off((size_t)nblk), len((size_t)nblk);
-  long long o = 0;
-  for (int k = 0; k < nblk; ++k) {
-    if (blk[k] == 0 || blk[k] > kMaxBlockSize) { set_error("op_lb_block_norms: block %d has size %d", k, blk[k]); return CUADMM_ERR_INVALID; }
-    len[k] = blk_svec_len(blk[k]);
-    off[k] = offs ? (long long)offs[k] : o;
-    o += len[k];
-    if (off[k] < 0 || off[k] + len[k] > n) { set_error("op_lb_block_norms: block %d outside the vectors", k); return CUADMM_ERR_INVALID; }
-  }
-  int rc = check_device(0);
-  if (rc) return rc;
-  LbTasks t;
-  if ((rc = lb_build_tasks(nblk, len.data(), &t))) return rc;
+  int rc = op_check_blocks("op_lb_block_norms", n, nblk, blk, offs);
+  if (rc || (rc = check_device(0))) return rc;
+  cuadmm_solver::BlockTasksDev t;
   const size_t N = (size_t)n + 2;
   DevBuf<double> Md, Pd, Rd, pairs, cpart, out;
-  DevBuf<long long> off_d, len_d;
-  DevBuf<int> blk_d, wave_d, chunk_d, large_d;
-  if ((rc = Md.alloc(N)) || (rc = Pd.alloc(N)) || (rc = Rd.alloc((size_t)nblk)) || (rc = pairs.alloc(2 * (size_t)nblk)) || (rc = cpart.alloc(2 * (size_t)t.nchunk())) ||
-      (rc = out.alloc(4)) || (rc = off_d.from(off)) || (rc = len_d.from(len)) || (rc = blk_d.from(std::vector<int>(blk, blk + nblk))) ||
-      (rc = wave_d.from(t.wave)) || (rc = chunk_d.from(t.chunk)) || (rc = large_d.from(t.large)))
+  if ((rc = t.build(blk, nblk, offs)) || (rc = Md.alloc(N)) || (rc = Pd.alloc(N)) || (rc = Rd.alloc((size_t)nblk)) || (rc = pairs.alloc(2 * (size_t)nblk)) ||
+      (rc = cpart.alloc(2 * (size_t)t.nchunk)) || (rc = out.alloc(4)))
     return rc;
   if ((rc = staged_h2d(Md.p + offset, M_inout, sizeof(double) * (size_t)n)) || (rc = staged_h2d(Pd.p + offset, P_inout, sizeof(double) * (size_t)n)) ||
       (rc = staged_h2d(Rd.p, R, sizeof(double) * (size_t)nblk)))
     return rc;
   CUADMM_HIP_TRY(hipMemset(pairs.p, 0xff, sizeof(double) * pairs.n));
-  LbNormArgs a{Md.p + offset, Pd.p + offset, off_d.p, len_d.p, wave_d.p, chunk_d.p, large_d.p, t.nwave(), t.nchunk(), t.nlarge(), cpart.p, pairs.p};
-  if ((rc = launch_lb_block_norms(a, nullptr))) return rc;
-  if ((rc = launch_lb_combine(nblk, pairs.p, Rd.p, len_d.p, blk_d.p, nullptr, out.p, nullptr))) return rc;
+  if ((rc = launch_lb_block_norms(Md.p + offset, Pd.p + offset, t.view(), cpart.p, pairs.p, nullptr))) return rc;
+  if ((rc = launch_lb_combine(nblk, pairs.p, Rd.p, t.len.p, t.blk.p, nullptr, out.p, nullptr))) return rc;
   CUADMM_HIP_TRY(hipDeviceSynchronize());
   double o4[4];
   if ((rc = staged_d2h(M_inout, Md.p + offset, sizeof(double) * (size_t)n)) || (rc = staged_d2h(P_inout, Pd.p + offset, sizeof(double) * (size_t)n)) ||
@@ -3844,33 +3838,17 @@ int cuadmm_op_ev_block_stats(int64_t n, double* X, double* S, double* PX, double
     set_error("op_ev_block_stats: invalid argument");
     return CUADMM_ERR_INVALID;
   }
-  std::vector<long long> off((size_t)nblk), len((size_t)nblk);
-  long long o = 0;
-  for (int k = 0; k < nblk; ++k) {
-    if (blk[k] == 0 || blk[k] > kMaxBlockSize) { set_error("op_ev_block_stats: block %d has size %d", k, blk[k]); return CUADMM_ERR_INVALID; }
-    len[k] = blk_svec_len(blk[k]);
-    off[k] = offs ? (long long)offs[k] : o;
-    o += len[k];
-    if (off[k] < 0 || off[k] + len[k] > n) { set_error("op_ev_block_stats: block %d outside the vectors", k); return CUADMM_ERR_INVALID; }
-  }
-  int rc = check_device(0);
-  if (rc) return rc;
-  LbTasks t;
-  if ((rc = lb_build_tasks(nblk, len.data(), &t))) return rc;
+  int rc = op_check_blocks("op_ev_block_stats", n, nblk, blk, offs);
+  if (rc || (rc = check_device(0))) return rc;
+  cuadmm_solver::BlockTasksDev t;
   const size_t N = (size_t)n + 2;
   double* const host[5] = {X, S, PX, PS, Rd1};
   DevBuf<double> v[5], sums, cpart;
-  DevBuf<long long> off_d, len_d;
-  DevBuf<int> blk_d, wave_d, chunk_d, large_d;
   for (int q = 0; q < 5; ++q)
     if ((rc = v[q].alloc(N)) || (rc = staged_h2d(v[q].p + offset, host[q], sizeof(double) * (size_t)n))) return rc;
-  if ((rc = sums.alloc(kEvSums * (size_t)nblk)) || (rc = cpart.alloc(kEvSums * (size_t)t.nchunk())) || (rc = off_d.from(off)) || (rc = len_d.from(len)) ||
-      (rc = blk_d.from(std::vector<int>(blk, blk + nblk))) || (rc = wave_d.from(t.wave)) || (rc = chunk_d.from(t.chunk)) || (rc = large_d.from(t.large)))
-    return rc;
+  if ((rc = t.build(blk, nblk, offs)) || (rc = sums.alloc(kEvSums * (size_t)nblk)) || (rc = cpart.alloc(kEvSums * (size_t)t.nchunk))) return rc;
   CUADMM_HIP_TRY(hipMemset(sums.p, 0xff, sizeof(double) * sums.n));
-  EvStatArgs a{v[0].p + offset, v[1].p + offset, v[2].p + offset, v[3].p + offset, v[4].p + offset, off_d.p, len_d.p, blk_d.p, wave_d.p, chunk_d.p, large_d.p,
-               t.nwave(), t.nchunk(), t.nlarge(), cpart.p, sums.p};
-  if ((rc = launch_ev_block_stats(a, nullptr))) return rc;
+  if ((rc = launch_ev_block_stats(v[0].p + offset, v[1].p + offset, v[2].p + offset, v[3].p + offset, v[4].p + offset, t.view(), cpart.p, sums.p, nullptr))) return rc;
   CUADMM_HIP_TRY(hipDeviceSynchronize());
   for (int q = 0; q < 5; ++q)
     if ((rc = staged_d2h(host[q], v[q].p + offset, sizeof(double) * (size_t)n))) return rc;

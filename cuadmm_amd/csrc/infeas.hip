@@ -84,15 +84,6 @@ __global__ __launch_bounds__(kInfeasThreads) void infeas_norm2_kernel(long long 
   if (threadIdx.x == 0) partials[2 * (size_t)blockIdx.x] = s;
 }
 
-// second stage: workgroup q adds partials[2 slot + q] over the slots
-__global__ __launch_bounds__(64) void infeas_final_kernel(const double* partials, int nslots, double* out) {
-  const int q = blockIdx.x;
-  double v = 0;
-  for (int s = threadIdx.x; s < nslots; s += 64) v += partials[2 * (size_t)s + q];
-  v = wave_sum(v);
-  if (threadIdx.x == 0) out[q] = v;
-}
-
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 // workgroups with work: one item per thread, an item = 2 doubles on the 16-byte path
 int grid_for(long long n, bool vec) {
@@ -113,7 +104,7 @@ int launch_infeas_roll(long long n, const double* cur, double* prev, const doubl
   a.vec = aligned16(cur) && aligned16(prev) && aligned16(w) && aligned16(out);
   const int nb = grid_for(n, a.vec != 0);
   hipLaunchKernelGGL(infeas_roll_kernel, dim3(nb), dim3(kInfeasThreads), 0, st, n, a, partials);
-  hipLaunchKernelGGL(infeas_final_kernel, dim3(2), dim3(64), 0, st, partials, nb, sums2);
+  hipLaunchKernelGGL(slots_final_kernel<2>, dim3(2), dim3(64), 0, st, partials, nb, sums2);
   CUADMM_HIP_TRY(hipGetLastError());
   return CUADMM_OK;
 }
@@ -123,7 +114,7 @@ int launch_infeas_norm2(long long n, const double* v, double* partials, double* 
   const int vec = aligned16(v);
   const int nb = grid_for(n, vec != 0);
   hipLaunchKernelGGL(infeas_norm2_kernel, dim3(nb), dim3(kInfeasThreads), 0, st, n, v, vec, partials);
-  hipLaunchKernelGGL(infeas_final_kernel, dim3(1), dim3(64), 0, st, partials, nb, sum_out);
+  hipLaunchKernelGGL(slots_final_kernel<2>, dim3(1), dim3(64), 0, st, partials, nb, sum_out);
   CUADMM_HIP_TRY(hipGetLastError());
   return CUADMM_OK;
 }

@@ -30,7 +30,7 @@ __device__ __forceinline__ double wave_sum(double v) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// The pieces of wave_sum for the per-block reductions (lower_bound.hip, evaluate.hip): a row of 16 lanes or the
+// The pieces of wave_sum for the per-block reductions (block_reduce.h): a row of 16 lanes or the
 // wavefront owns a block, a workgroup of 256 threads a chunk of a long one.
 // ---------------------------------------------------------------------------------------------------------------
 // the sum over each row of 16 lanes, in every lane of the row (the first four steps of wave_sum)
@@ -52,6 +52,17 @@ __device__ __forceinline__ double block_sum(double v, double* lds /* 4 doubles *
   if ((threadIdx.x & 63) == 0) lds[w] = v;
   __syncthreads();
   return (lds[0] + lds[1]) + (lds[2] + lds[3]);
+}
+
+// second stage of the stream kernels' reductions (accel.hip, infeas.hip): with STRIDE partial sums per slot, workgroup q (one
+// wavefront) adds partials[slot * STRIDE + q] over the slots, lane l the slots l, l + 64, ...
+template <int STRIDE>
+__global__ __launch_bounds__(64) void slots_final_kernel(const double* partials, int nslots, double* out) {
+  const int q = blockIdx.x;
+  double v = 0;
+  for (int s = threadIdx.x; s < nslots; s += 64) v += partials[(size_t)s * STRIDE + q];
+  v = wave_sum(v);
+  if (threadIdx.x == 0) out[q] = v;
 }
 
 }  // namespace cuadmm

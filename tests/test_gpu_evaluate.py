@@ -370,6 +370,50 @@ def test_report_after_updates_and_with_gap_check():
     assert g.gap_info()["checks"] == 3
 
 
+def test_the_report_and_the_bound_share_one_task_list():
+    """Fixture B (odd offsets, a free block, a wavefront-owned block) at one random point, set with set_XyS: a handle that runs lower_bound()
+    and then evaluate(), one that runs them the other way round, and two fresh handles with one call each.  The per-block task lists
+    on the device are built once per handle by whichever call comes first (csrc/engine.hip: BlockTasksDev): every number but ms is the
+    same to the bit in all three, and each call reports the bytes it would report alone, the lists' included.  The bound's figure
+    contains the auxiliary projector's, whose plan is sized from the device's free memory around its build and is no function of the
+    handle alone: it is compared without them (evaluate_info's aux_bytes; the lone bound's handle evaluates afterwards to learn them)."""
+    fx = fixture("B")
+    rng = np.random.default_rng(23)
+    X, y, S = rng.standard_normal(fx.L), rng.standard_normal(fx.m), rng.standard_normal(fx.L)
+
+    def handle():
+        s = solver(fx)
+        s.set_trace_bounds(fx.R)
+        s.set_XyS(X, y, S)
+        return s
+
+    def own_bytes(s, lb):
+        return lb["bytes"] - s.evaluate_info()["aux_bytes"]
+
+    s1, s2, s3b, s3e = handle(), handle(), handle(), handle()
+    lb1 = s1.lower_bound(per_block=True)
+    ev1 = s1.evaluate()
+    ev2 = s2.evaluate()
+    lb2 = s2.lower_bound(per_block=True)
+    lb3 = s3b.lower_bound(per_block=True)
+    ev3 = s3e.evaluate()
+    evb = [s.evaluate_info()["bytes"] for s in (s1, s2, s3e)]
+    s3b.evaluate()
+    lbb = [own_bytes(s, lb) for s, lb in ((s1, lb1), (s2, lb2), (s3b, lb3))]
+    print("bytes: evaluate %s, lower_bound without the projector %s (with it %s)" % (evb, lbb, [lb["bytes"] for lb in (lb1, lb2, lb3)]))
+    for lb in (lb2, lb3):
+        for k in lb1:
+            if k not in ("ms", "bytes"):
+                assert np.array_equal(lb1[k], lb[k]), k
+    for ev in (ev2, ev3):
+        for k in ev1:
+            if k != "ms":
+                assert np.array_equal(ev1[k], ev[k]), k
+    assert np.isfinite(lb1["lower_bound"]) and np.isfinite([ev1[k] for k in KEYS]).all()
+    assert evb[0] == evb[1] == evb[2] and lbb[0] == lbb[1] == lbb[2] and min(evb + lbb) > 0
+    assert s3b.evaluate_info()["bytes"] == evb[0] and s3e.gap_info()["bytes"] == 0.0
+
+
 # ---- 7. refusals ----------------------------------------------------------------------------------------------------------
 def test_refusals_leave_the_solver_as_it_was():
     fx = fixture("B")
