@@ -18,6 +18,8 @@
 //   the sidecar as "kkt"
 //   --kkt-point=<dir2/>: no solve; the report of the point in <dir2/>{X,y,S}.txt (one number per line, as this program writes X_opt.txt; a
 //   missing file: that vector is zero) is printed and, with --json, written as the sidecar's "kkt"
+//   --lambda-min[=T]: behind every solve, certified lower bounds on lambda_min of the blocks of X, S and C - A'y (cuadmm_lambda_min with T
+//   bisection steps, default 12), one line each, and "lambda_min" in the sidecar
 //   --json=<file>: a sidecar with the run's figures (iterations, residuals, iters/s, per-phase milliseconds, the projection's
 //   nominal TFLOP/s = 10.67 sum n^3 per projection and the vector kernels' algorithmic GB/s: SURVEY.md 8d); switches the
 //   engine's per-phase HIP-event timers on (option "profile").  Nothing is written unless asked for: the reference writes X_opt.txt only.
@@ -71,6 +73,18 @@ static void print_kkt(const double* k, const std::vector<double>& pb) {
   if (!pb.empty())
     printf("  worst blocks: vX %.3e (block %zu), vS %.3e (block %zu), ||Rd_k|| %.3e (block %zu); %.3f ms\n", pb[6 * wx + 1], wx, pb[6 * ws + 3], ws, pb[6 * wr + 5], wr, k[15]);
 }
+static const char* const lm_names[3] = {"X", "S", "dual"};
+// "lambda_min": {"steps": T, "X": {...}, "S": {...}, "dual": {...}} with the eight numbers of cuadmm_lambda_min each (NaN: null)
+static void write_lambda_min(FILE* f, int steps, const double (*lm)[8]) {
+  fprintf(f, " \"lambda_min\": {\"steps\": %d", steps);
+  for (int w = 0; w < 3; ++w) {
+    const double* o = lm[w];
+    fprintf(f, ", \"%s\": {\"lambda_min\": %.17g, \"block\": %.0f, \"dimacs\": %.17g, \"lower_bound\": ", lm_names[w], o[0], o[1], o[2]);
+    if (std::isfinite(o[3])) fprintf(f, "%.17g", o[3]); else fprintf(f, "null");
+    fprintf(f, ", \"unrefined\": %.0f, \"psd_at_floor\": %.0f, \"ms\": %.17g, \"bytes\": %.0f}", o[4], o[5], o[6], o[7]);
+  }
+  fprintf(f, "}");
+}
 // <dir/>name.txt, one number per line (cuadmm_write_dense_txt); a missing file: zeros
 static bool read_point_vec(const std::string& fn, std::vector<double>& out, size_t n) {
   out.assign(n, 0.0);
@@ -87,7 +101,8 @@ static bool read_point_vec(const std::string& fn, std::vector<double>& out, size
 
 // --json=<file>: one object; every number printed with %.17g
 static bool write_sidecar(const std::string& path, const std::string& prefix, cuadmm_solver* solver, const cuadmm_problem_view& v, bool have_bounds,
-                          const double* kkt = nullptr, const std::vector<double>& kkt_blocks = std::vector<double>()) {
+                          const double* kkt = nullptr, const std::vector<double>& kkt_blocks = std::vector<double>(), int lm_steps = 0,
+                          const double (*lm)[8] = nullptr) {
   FILE* f = fopen(path.c_str(), "w");
   if (!f) return false;
   const int iters = cuadmm_get_info_iter_num(solver);
@@ -126,6 +141,7 @@ static bool write_sidecar(const std::string& path, const std::string& prefix, cu
     } else std::cerr << cuadmm_last_error() << std::endl;
   }
   if (kkt) { write_kkt(f, kkt, kkt_blocks); fprintf(f, ",\n"); }
+  if (lm) { write_lambda_min(f, lm_steps, lm); fprintf(f, ",\n"); }
   double acc[8] = {0};
   cuadmm_get_accel_info(solver, acc);
   if (acc[0] > 0)
@@ -165,6 +181,7 @@ int main(int argc, char* argv[]) {
   double max_iter = 1e6, stop_tol = 1e-3, threshold = 0, stage1 = 50, stage2 = 100, switch_admm = 5000, sigscale = 1.05,
          sig = 1e0, device = 0, accel = 0, infeas = 0, infeas_tol = -1, gap = 0, gap_tol = -1;
   bool quiet = false, kkt = false;
+  int lm_steps = 0;      // --lambda-min: 0 = off
   std::string json_path, bounds_arg, kkt_point;
   std::vector<std::string> then_dirs;
   std::vector<char> then_is_A;
@@ -181,6 +198,12 @@ int main(int argc, char* argv[]) {
     if (strcmp(argv[i], "--quiet") == 0) { quiet = true; continue; }
     if (strcmp(argv[i], "--kkt") == 0) { kkt = true; continue; }
     if (strncmp(argv[i], "--kkt-point=", 12) == 0) { kkt_point = argv[i] + 12; continue; }
+    if (strcmp(argv[i], "--lambda-min") == 0) { lm_steps = 12; continue; }
+    if (strncmp(argv[i], "--lambda-min=", 13) == 0) {
+      lm_steps = atoi(argv[i] + 13);
+      if (lm_steps < 1 || lm_steps > 40) { std::cerr << "--lambda-min: 1 to 40 bisection steps" << std::endl; return 1; }
+      continue;
+    }
     std::cerr << "unknown option " << argv[i] << std::endl;
     return 1;
   }
@@ -272,9 +295,23 @@ int main(int argc, char* argv[]) {
     print_kkt(kk, kkb);
     return true;
   };
+  // --lambda-min: the certified bounds at the point a solve returns, taken before anything reads the iterate
+  double lm[3][8] = {{0}};
+  auto lm_report = [&]() {
+    if (lm_steps == 0) return false;
+    for (int w = 0; w < 3; ++w) {
+      if (cuadmm_lambda_min(solver, w, lm_steps, lm[w], nullptr) != CUADMM_OK) { std::cerr << cuadmm_last_error() << std::endl; return false; }
+      printf(" lambda_min(%s) >= %.10e (block %.0f), DIMACS measure <= %.3e, %.0f unrefined, %.0f PSD at the floor, %.3f ms", lm_names[w], lm[w][0], lm[w][1],
+             lm[w][2], lm[w][4], lm[w][5], lm[w][6]);
+      if (std::isfinite(lm[w][3])) printf(", LB_lambda = %.10e", lm[w][3]);
+      printf("\n");
+    }
+    return true;
+  };
   rc = cuadmm_solve(solver, (int)max_iter, stop_tol, (int)threshold, (int)stage1, (int)stage2, (int)switch_admm, sigscale, 1);
   if (rc != CUADMM_OK) std::cerr << cuadmm_last_error() << std::endl;
   bool have_kkt = kkt_report();
+  bool have_lm = lm_report();
 
   if (accel != 0) {
     double acc[8] = {0};
@@ -283,7 +320,7 @@ int main(int argc, char* argv[]) {
   }
   std::vector<double> X((size_t)v.vec_len);
   if (cuadmm_get_X(solver, X.data()) == CUADMM_OK) cuadmm_write_dense_txt((prefix + "X_opt.txt").c_str(), X.data(), v.vec_len);
-  if (!json_path.empty() && !write_sidecar(json_path, prefix, solver, v, !bounds_arg.empty(), have_kkt ? kk : nullptr, kkb)) std::cerr << "cannot write " << json_path << std::endl;
+  if (!json_path.empty() && !write_sidecar(json_path, prefix, solver, v, !bounds_arg.empty(), have_kkt ? kk : nullptr, kkb, lm_steps, have_lm ? lm : nullptr)) std::cerr << "cannot write " << json_path << std::endl;
   for (size_t k = 0; k < then_dirs.size() && rc == CUADMM_OK; ++k) {
     const std::string& d = then_dirs[k];
     std::vector<int> bi, ci;
@@ -308,9 +345,10 @@ int main(int argc, char* argv[]) {
     if (rc == CUADMM_OK) rc = cuadmm_solve(solver, (int)max_iter, stop_tol, (int)threshold, (int)stage1, (int)stage2, (int)switch_admm, sigscale, 1);
     if (rc != CUADMM_OK) { std::cerr << cuadmm_last_error() << std::endl; break; }
     have_kkt = kkt_report();
+    have_lm = lm_report();
     if (cuadmm_get_X(solver, X.data()) == CUADMM_OK) cuadmm_write_dense_txt((d + "X_opt.txt").c_str(), X.data(), v.vec_len);
     const std::string side = json_path + "." + std::to_string(k + 1);
-    if (!json_path.empty() && !write_sidecar(side, d, solver, v, !bounds_arg.empty(), have_kkt ? kk : nullptr, kkb)) std::cerr << "cannot write " << side << std::endl;
+    if (!json_path.empty() && !write_sidecar(side, d, solver, v, !bounds_arg.empty(), have_kkt ? kk : nullptr, kkb, lm_steps, have_lm ? lm : nullptr)) std::cerr << "cannot write " << side << std::endl;
   }
   cuadmm_destroy(solver);
   cuadmm_problem_free(prob);

@@ -34,6 +34,7 @@
 #include "infeas.h"
 #include "lower_bound.h"
 #include "evaluate.h"
+#include "lambda_min.h"
 
 using namespace cuadmm;
 
@@ -490,6 +491,43 @@ struct cuadmm_solver {
   int ev_prepare();
   int ev_point(const double* host, const DevBuf<double>& resident, double inv_scale, DevBuf<double>& own, const double** out);
   int ev_run(const double* xs, const double* ss, double out16[16], double* per_block);
+
+  // Certified lambda_min per block (cuadmm_lambda_min, cuadmm_op_block_lambda_min; lambda_min.h, DESIGN.md "Certified lambda_min"): the
+  // size classes' block lists on the device, the global scratch of the blocks beyond the LDS (only where there are such), the results.
+  // The offsets and sizes per block are the task lists' (btasks).  Nothing here is read by the iteration.
+  struct LmPlan {
+    LmClass cls[kLmClasses];
+    DevBuf<int> list[kLmClasses];
+    DevBuf<long long> work_off;
+    DevBuf<double> work, out, ybuf, dpart;
+    PinnedBuf<double> h_out;
+    int nb = 0;
+    long long calls = 0;
+    int build(const int* blk_h, int nblk) {
+      long long w = 0;
+      int rc = lm_build_classes(nblk, blk_h, cls, &w);
+      if (rc) return rc;
+      for (int q = 0; q < kLmClasses; ++q)
+        if ((rc = list[q].from(cls[q].blocks))) return rc;
+      if ((rc = work_off.from(cls[kLmClasses - 2].work)) || (rc = work.alloc((size_t)w)) || (rc = h_out.alloc(kLmOut * (size_t)nblk + kBrSlots))) return rc;
+      nb = nblk;
+      return out.alloc(kLmOut * (size_t)nblk);      // last: marks the set as complete
+    }
+    // out (device) <- the four numbers per block of sign * v; one launch per class that has blocks
+    int run(const double* v, double sign, const long long* off_d, const int* blk_d, int steps, hipStream_t st) {
+      int rc;
+      for (int q = 0; q < kLmClasses; ++q)
+        if ((rc = launch_lambda_min(q, (int)cls[q].blocks.size(), cls[q].nmax, list[q].p, v, sign, off_d, blk_d, steps, work.p, work_off.p, out.p, st))) return rc;
+      return CUADMM_OK;
+    }
+    double bytes() const {
+      double b = 8.0 * (double)(work_off.n + work.n + out.n + ybuf.n + dpart.n);
+      for (const auto& l : list) b += 4.0 * (double)l.n;
+      return b;
+    }
+  } lm;
+  int lm_prepare(int which);
+  int lm_run(int which, int steps, double out8[8], double* per_block);
 
   // profiling
   hipEvent_t ev0[K_NUM][2] = {}, ev1[K_NUM][2] = {};
@@ -2701,6 +2739,68 @@ int cuadmm_solver::ev_run(const double* xs, const double* ss, double o[16], doub
   return CUADMM_OK;
 }
 
+// ------------------------------------------------------------------------------------------
+// Certified lambda_min per block (cuadmm_lambda_min): DESIGN.md, "Certified lambda_min"
+// ------------------------------------------------------------------------------------------
+// lists and vectors on first use; the auxiliary projector's events, vectors and b (which may have changed) on every call
+int cuadmm_solver::lm_prepare(int which) {
+  int rc;
+  const int nb = (int)blk_local.size();
+  if (!btasks.built && (rc = btasks.build(blk_local.data(), nb, nullptr))) return rc;
+  if (!lm.out.p && (rc = lm.build(blk_local.data(), nb))) return rc;
+  if (which == 2 && !lm.dpart.p && ((rc = lm.ybuf.alloc((size_t)std::max(m, 1))) || (rc = lm.dpart.alloc(kBrSlots)))) return rc;
+  return aux.ensure(*this);
+}
+
+// which = 0: X, 1: S, read where they lie (scaled behind a solve, else in the caller's units); 2: S^ = C - A'y at the scaled y in lm.ybuf,
+// formed as -(A'y - C) by the iteration's kernel into the auxiliary projector's input vector.  The kernel's numbers are in the units of
+// the vector it read; lo goes to the caller's units rounded down.  Writes only the plan's own vectors and that input vector.
+int cuadmm_solver::lm_run(int which, int steps, double o[8], double* per_block) {
+  int rc;
+  const int nb = (int)blk_local.size();
+  const double* v = which == 0 ? X.p : S.p;
+  double sign = 1.0, unit = pending_unscale ? (which == 0 ? bscale : Cscale) : 1.0;
+  CUADMM_HIP_TRY(hipEventRecord(aux.ev[0], st));
+  if (which == 2) {
+    if ((rc = launch_aty_xb(false, L, At_rp.p, At_ci.p, At_v.p, lm.ybuf.p, C.p, X.p, 1.0, aux.in.p, nullptr, st, &At_long))) return rc;
+    if ((rc = launch_lb_dot(m, aux.b_dev(*this), lm.ybuf.p, lm.dpart.p, st))) return rc;
+    v = aux.in.p; sign = -1.0; unit = Cscale;
+  }
+  if ((rc = lm.run(v, sign, btasks.off.p, btasks.blk.p, steps, st))) return rc;
+  double* const h = lm.h_out.p;
+  CUADMM_HIP_TRY(hipMemcpyAsync(h, lm.out.p, sizeof(double) * kLmOut * (size_t)nb, hipMemcpyDeviceToHost, st));
+  if (which == 2) CUADMM_HIP_TRY(hipMemcpyAsync(h + kLmOut * (size_t)nb, lm.dpart.p, sizeof(double) * kBrSlots, hipMemcpyDeviceToHost, st));
+  CUADMM_HIP_TRY(hipEventRecord(aux.ev[1], st));
+  CUADMM_HIP_TRY(hipStreamSynchronize(st));
+  lm.calls++;
+  const bool bound = which == 2 && !lb.R.empty();
+  double worst = INFINITY, pen = 0;
+  int arg = -1, unrefined = 0, at_floor = 0;
+  for (int k = 0; k < nb; ++k) {
+    const double* q = h + kLmOut * (size_t)k;
+    const int flag = (int)q[2];
+    double lo = q[0] * unit, hi = q[1] * unit;
+    if (unit != 1.0 && flag != kLmFree) lo = std::nextafter(lo, -INFINITY);
+    if (flag != kLmFree && lo < worst) { worst = lo; arg = k; }
+    unrefined += flag == kLmUnrefined; at_floor += flag == kLmPsdAtFloor;
+    if (bound) pen += lb.R[k] * (flag == kLmFree ? q[3] * unit : std::max(0.0, -lo));
+    if (per_block) { per_block[3 * k] = lo; per_block[3 * k + 1] = hi; per_block[3 * k + 2] = (double)flag; }
+  }
+  o[0] = arg >= 0 ? worst : 0.0;
+  o[1] = (double)arg;
+  o[2] = std::max(0.0, -o[0]) / (which == 0 ? norm_borg : norm_Corg);
+  o[3] = NAN;
+  if (bound) {
+    double by = 0;
+    for (int j = 0; j < kBrSlots; ++j) by += h[kLmOut * (size_t)nb + j];
+    o[3] = by * objscale - pen;
+  }
+  o[4] = (double)unrefined; o[5] = (double)at_floor;
+  o[6] = event_ms(aux.ev[0], aux.ev[1]);
+  o[7] = lm.bytes() + btasks.bytes() + aux.bytes();
+  return CUADMM_OK;
+}
+
 // SDPDuoSolver front (duo_solver.h:236-276): exactly two block sizes, then the generic engine.
 int cuadmm_duo_init(cuadmm_solver* s, int if_gpu_eig_mom, int device_num_requested, int eig_stream_num_per_gpu,
                     int cpu_eig_thread_num, int vec_len, int con_num, const int* At_cp, const int* At_ri, const double* At_vx,
@@ -3403,6 +3503,39 @@ int cuadmm_evaluate(cuadmm_solver* s, const double* X, const double* y, const do
   }
   return s->ev_run(xs, ss, o, per_block);
 }
+int cuadmm_lambda_min(cuadmm_solver* s, int which, int steps, double o[8], double* per_block) {
+  if (!s || !s->initialised || !o) { set_error("lambda_min: solver not initialised or null argument"); return CUADMM_ERR_INVALID; }
+  if (s->world > 1 || s->comm_world > 1 || s->local_mode || s->group || s->in_group_call) {
+    set_error("lambda_min: works on one rank (world = %d%s): its results are not all-reduced", std::max(s->world, s->comm_world), s->group ? ", in-process group" : "");
+    return CUADMM_ERR_INVALID;
+  }
+  if (which < 0 || which > 2) { set_error("lambda_min: which = %d (0: X, 1: S, 2: C - A'y)", which); return CUADMM_ERR_INVALID; }
+  if (steps < 1 || steps > kLmStepsMax) { set_error("lambda_min: steps = %d, allowed are 1 to %d", steps, kLmStepsMax); return CUADMM_ERR_INVALID; }
+  if (s->L <= 0) { set_error("lambda_min: the problem has no svec slots"); return CUADMM_ERR_INVALID; }
+  if (which == 2 && !s->lb.R.empty() && s->lb.R.size() != s->blk_local.size()) {
+    set_error("lambda_min: %d trace bounds are set, the solver has %d blocks", (int)s->lb.R.size(), (int)s->blk_local.size());
+    return CUADMM_ERR_INVALID;
+  }
+  if (which == 2 && s->factor_bad) { set_error("lambda_min: the last cuadmm_update_A could not factor the new A A^T; the solver needs a successful cuadmm_update_A first"); return CUADMM_ERR_FACTOR; }
+  int rc = check_device(s->device);
+  if (rc) return rc;
+  if ((rc = s->lm_prepare(which))) return rc;
+  if (which == 2) {      // the y cuadmm_get_y would return, scaled and in the engine's order, as cuadmm_lower_bound stages it
+    const int m = s->m;
+    if (m > 0) {
+      if (s->pending_unscale && s->dev_solve) CUADMM_HIP_TRY(hipMemcpyAsync(s->lm.ybuf.p, s->y_d.p, sizeof(double) * (size_t)m, hipMemcpyDeviceToDevice, s->st));
+      else {
+        std::vector<double> ys(s->y_p);
+        if (!s->pending_unscale) {
+          if (s->y_host_stale && (rc = staged_d2h(ys.data(), s->y_d.p, sizeof(double) * (size_t)m, s->st))) return rc;
+          for (int i = 0; i < m; ++i) ys[i] = (ys[i] * s->normA_p[i]) * (1 / s->Cscale);
+        }
+        if ((rc = staged_h2d(s->lm.ybuf.p, ys.data(), sizeof(double) * (size_t)m, s->st))) return rc;
+      }
+    } else CUADMM_HIP_TRY(hipMemsetAsync(s->lm.ybuf.p, 0, sizeof(double), s->st));
+  }
+  return s->lm_run(which, steps, o, per_block);
+}
 int cuadmm_get_evaluate_info(const cuadmm_solver* s, double o[4]) {
   if (!s || !o) { set_error("get_evaluate_info: null"); return CUADMM_ERR_INVALID; }
   o[0] = (double)s->ev.calls; o[1] = s->ev.bytes() + (s->ev.out_d.p ? s->btasks.bytes() : 0.0); o[2] = s->ev.out_d.p ? s->aux.bytes() : 0.0; o[3] = s->ev.ms;
@@ -3853,6 +3986,26 @@ int cuadmm_op_ev_block_stats(int64_t n, double* X, double* S, double* PX, double
   for (int q = 0; q < 5; ++q)
     if ((rc = staged_d2h(host[q], v[q].p + offset, sizeof(double) * (size_t)n))) return rc;
   return staged_d2h(sums6_out, sums.p, sizeof(double) * kEvSums * (size_t)nblk);
+}
+
+// the lambda_min kernel on a device vector whose blocks follow one another from slot 0 (csrc/lambda_min.hip); blk_vals on the host
+int cuadmm_op_block_lambda_min(const double* svec_dev, const int* blk_vals, int mat_num, int steps, double* per_block3_host, void* stream) {
+  if (!svec_dev || !blk_vals || mat_num < 1 || !per_block3_host || steps < 1 || steps > kLmStepsMax) { set_error("op_block_lambda_min: invalid argument"); return CUADMM_ERR_INVALID; }
+  for (int k = 0; k < mat_num; ++k)
+    if (blk_vals[k] == 0 || blk_vals[k] > kMaxBlockSize) { set_error("op_block_lambda_min: block %d has size %d", k, blk_vals[k]); return CUADMM_ERR_INVALID; }
+  int rc, ndev = 0;      // the current device is the vector's: it is not changed
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_error("no HIP device available; this engine has no CPU fallback"); return CUADMM_ERR_NO_DEVICE; }
+  hipStream_t st = (hipStream_t)stream;
+  cuadmm_solver::BlockTasksDev t;
+  cuadmm_solver::LmPlan plan;
+  if ((rc = t.build(blk_vals, mat_num, nullptr)) || (rc = plan.build(blk_vals, mat_num))) return rc;
+  if ((rc = plan.run(svec_dev, 1.0, t.off.p, t.blk.p, steps, st))) return rc;
+  CUADMM_HIP_TRY(hipStreamSynchronize(st));
+  std::vector<double> h(kLmOut * (size_t)mat_num);
+  if ((rc = staged_d2h(h.data(), plan.out.p, sizeof(double) * h.size()))) return rc;
+  for (int k = 0; k < mat_num; ++k)
+    for (int q = 0; q < 3; ++q) per_block3_host[3 * k + q] = h[kLmOut * (size_t)k + q];
+  return CUADMM_OK;
 }
 
 int cuadmm_dev_malloc(void** ptr, size_t bytes) { CUADMM_HIP_TRY(hipMalloc(ptr, bytes ? bytes : 8)); return CUADMM_OK; }

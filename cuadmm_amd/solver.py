@@ -204,6 +204,21 @@ class SDPSolver:
         check(self._lib.cuadmm_get_evaluate_info(self._h, _p(o)))
         return {"calls": int(o[0]), "bytes": float(o[1]), "aux_bytes": float(o[2]), "ms": float(o[3])}
 
+    LAMBDA_MIN_WHICH = {"X": 0, "S": 1, "dual": 2}
+
+    def lambda_min(self, which="X", steps=12):
+        """Certified lower bounds on lambda_min of every PSD block of X, S or ("dual") C - A'y at the current y (cuadmm_lambda_min).
+        "lo" is certified, "hi" an estimate; "flag": 0 refined, 1 PSD at the floor, 2 unconstrained, 3 unrefined.  "lower_bound" is NaN
+        unless which = "dual" and trace bounds are set."""
+        if which not in self.LAMBDA_MIN_WHICH:
+            raise ValueError("lambda_min: which must be 'X', 'S' or 'dual'")
+        o = np.zeros(8)
+        pb = np.zeros(3 * self.mat_num)
+        check(self._lib.cuadmm_lambda_min(self._h, self.LAMBDA_MIN_WHICH[which], int(steps), _p(o), _p(pb)))
+        return {"lambda_min": float(o[0]), "block": int(o[1]), "dimacs": float(o[2]), "lower_bound": float(o[3]), "unrefined": int(o[4]),
+                "psd_at_floor": int(o[5]), "ms": float(o[6]), "bytes": float(o[7]), "lo": pb[0::3].copy(), "hi": pb[1::3].copy(),
+                "flag": pb[2::3].astype(int)}
+
     def set_allreduce(self, fn):
         """fn(dev_ptr:int, count:int, hip_stream:int) -> None : in-place sum over ranks on that stream."""
         def tramp(_user, buf, count, stream):

@@ -330,6 +330,28 @@ int cuadmm_evaluate(cuadmm_solver* s, const double* X, const double* y, const do
  * auxiliary projector's bytes (its vectors exactly, plus an estimate of its plan; shared with the lower bound and the infeasibility
  * check), [3] milliseconds of device time of the last call. */
 int cuadmm_get_evaluate_info(const cuadmm_solver* s, double out4[4]);
+/* Certified lower bounds on the smallest eigenvalue of every PSD block of X (which = 0), S (1) or S^ = C - A'y at the y cuadmm_get_y
+ * would return (2; formed as cuadmm_lower_bound forms it), by bisection on the shift mu of a floating-point Cholesky factorisation of
+ * M_k + mu I ("Certified lambda_min").  A factorisation that runs to completion proves lambda_min(M_k) >= -mu - margin (Higham,
+ * Accuracy and Stability of Numerical Algorithms, Thm 10.3; margin: cuadmm_lambda_min_margin), so lo_k is CERTIFIED; hi_k = -(the largest
+ * shift that failed) is an estimate and is NOT certified.  steps (1 .. 40): bisection steps; with T steps lo_k lies within the factor
+ * (nu_max / nu_floor)^(2^-T) of the smallest shift that can succeed, 12 gives about 1 %.  Results in the caller's units: behind a solve the
+ * scaled iterate is read where it lies and the numbers are rescaled (lo rounded down); the deferred unscaling is not triggered and nothing
+ * the iteration reads changes: a following cuadmm_solve(..., if_first = 0) continues bit for bit.
+ * out8: [0] min_k lo_k over the PSD blocks, [1] its block (-1: there is none), [2] max(0, -[0]) / (1 + ||b||) for which = 0,
+ * / (1 + ||C||) for which = 1, 2: DIMACS err2 / err4 as DIMACS defines them, bounded from above, [3] which = 2 with trace bounds set
+ * (cuadmm_set_trace_bounds): LB_lambda = b'y - sum_k R_k nubar_k with nubar_k = max(0, -lo_k) on PSD blocks and ||s^_k||_2 on
+ * unconstrained ones, never below cuadmm_lower_bound's value up to rounding; otherwise NaN, [4] blocks with flag 3, [5] blocks with flag 1,
+ * [6] milliseconds of device time (HIP events), [7] bytes of device memory held (allocated on first use and kept; the auxiliary
+ * projector's vectors included).  per_block (may be NULL): 3 mat_num doubles, [3k] lo_k, [3k + 1] hi_k, [3k + 2] flag: 0 refined,
+ * 1 PSD at the floor (the factorisation succeeded at the smallest shift tried, nu_floor = (n + 2) 2^-52 ||M_k||_F; hi_k = min_i m_ii),
+ * 2 unconstrained block (lo = hi = 0), 3 unrefined: n > 1024 or max |m_ij| outside [2^-500, 2^500]: no factorisation, lo_k = -nu_max
+ * from Gershgorin's discs, hi_k = min_i m_ii.
+ * CUADMM_ERR_INVALID, with the solver as it was: not initialised, out8 NULL, world > 1 or an in-process group, which outside 0 .. 2,
+ * steps outside 1 .. 40.  CUADMM_ERR_FACTOR: which = 2 behind a failed cuadmm_update_A. */
+int cuadmm_lambda_min(cuadmm_solver* s, int which, int steps, double out8[8], double* per_block);
+/* (n + 2) 2^-52 (trace + n mu): the margin of a factorisation of M + mu I that succeeded, trace = tr M.  Host only. */
+double cuadmm_lambda_min_margin(int n, double trace, double mu);
 /* Trace bounds read off the constraints (the arrays of cuadmm_init).  R_out[k] = -1: nothing found (always for unconstrained blocks).
  * Rule 1: a constraint whose entries are exactly the diagonal slots of ONE PSD block, all with the same value c (c svec(I_k)), gives
  * tr X_k = b_j / c.  Rule 2: a block whose every diagonal entry is fixed by a constraint with that single entry has the sum of those
@@ -580,6 +602,10 @@ int cuadmm_op_lb_block_norms(int64_t n, double* M_inout, double* P_inout, int nb
  * is launched.  The five vectors are copied back as the kernels left them (they write none of them). */
 int cuadmm_op_ev_block_stats(int64_t n, double* X_inout, double* S_inout, double* PX_inout, double* PS_inout, double* Rd1_inout, int nblk, const int* blk,
                              const int64_t* offs, int offset, double* sums6_out /* 6 nblk */);
+/* The kernel of cuadmm_lambda_min on a DEVICE svec vector whose blocks follow one another from slot 0 (csrc/lambda_min.hip); blk_vals on
+ * the host (negative: unconstrained).  per_block3_host: 3 mat_num doubles, lo, hi, flag per block as in cuadmm_lambda_min.  Synchronises
+ * the stream. */
+int cuadmm_op_block_lambda_min(const double* svec_dev, const int* blk_vals, int mat_num, int steps, double* per_block3_host, void* stream);
 int cuadmm_op_spmv_rows(int rows, int ncols, const int* row_ptrs, const int* col_ids, const double* vals, const double* X, const double* S, const double* C,
                         int want_x, int want_s, const int* rowmap, int out_len, double* outX, double* outS, int* info4);
 int cuadmm_op_rp_stats(int m, const double* ax, const double* b, const double* normA, const double* y, double bscale, const double* sums2, double* out4);

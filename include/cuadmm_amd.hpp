@@ -157,6 +157,20 @@ class SDPSolver {
     return Evaluation{o[0], o[1], o[2], o[3], o[4], o[5], o[6], o[7], o[8], {o[9], o[10], o[11], o[12], o[13], o[14]}, o[15]};
   }
 
+  // cuadmm_lambda_min: certified lower bounds on lambda_min of the blocks of X (which = 0), S (1) or C - A'y (2); per_block (may be
+  // null): resized to 3 mat_num, [3k ..] = lo_k (certified), hi_k (an estimate), flag; not in the reference
+  struct LambdaMin { double lambda_min; int block; double dimacs, lower_bound; int unrefined, psd_at_floor; double ms, bytes; };
+  LambdaMin lambda_min(int which, int steps = 12, std::vector<double>* per_block = nullptr) {
+    double o[8] = {0};
+    if (per_block) {
+      int vl = 0, cn = 0, mn = 0;
+      check(cuadmm_get_dims(h_, &vl, &cn, &mn));
+      per_block->assign(3 * (size_t)mn, 0.0);
+    }
+    check(cuadmm_lambda_min(h_, which, steps, o, per_block ? per_block->data() : nullptr));
+    return LambdaMin{o[0], (int)o[1], o[2], o[3], (int)o[4], (int)o[5], o[6], o[7]};
+  }
+
   // cuadmm_update_bC: new b and / or C on the factored solver (nnz < 0: unchanged); not in the reference
   void update_bC(const int* cpu_b_indices, const double* cpu_b_vals, int b_nnz, const int* cpu_C_indices, const double* cpu_C_vals,
                  int C_nnz, bool keep_iterate = true, double sig = 0.0) {
