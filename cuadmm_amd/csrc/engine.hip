@@ -434,6 +434,7 @@ struct cuadmm_solver {
   void lb_reset() { lb.checks = 0; lb.best_iter = lb.verdict_iter = 0; lb.best_lb = lb.last_lb = lb.last_g = 0; }
   int lb_prepare();
   int lb_eval(const double* y_scaled_d, double out6[6], float* ms);
+  int lb_report(double out8[8], double* per_block);
   int lb_step(int iter, double stop_tol);
 
   // The auxiliary projector of the infeasibility check and the lower bound ("Infeasibility certificates"): a plan beside the
@@ -444,13 +445,29 @@ struct cuadmm_solver {
     DevBuf<double> in, out, bcopy;
     double plan_bytes = 0;
     hipEvent_t ev[2] = {};
+    bool projected = false;            // inside the open bracket
     int ensure(cuadmm_solver& s);      // vectors and events on first use; b, which may have changed, on every call
     const double* b_dev(const cuadmm_solver& s) const { return s.b_d.p ? s.b_d.p : bcopy.p; }
     int project(cuadmm_solver& s, const double* from, double* to);
     bool failed(hipStream_t st) const { return plan && plan->fail_count(st) > 0; }
+    // The bracket around one user's work on the stream.  end: the stream is drained; *ms between the two events; *bad: a projection
+    // inside the bracket was made and the plan's (cumulative) failure count is not zero -- the user words its own CUADMM_ERR_EIG
+    // (null for a user that projects nothing).
+    int begin(hipStream_t st) { projected = false; CUADMM_HIP_TRY(hipEventRecord(ev[0], st)); return CUADMM_OK; }
+    int end(hipStream_t st, float* ms, bool* bad) {
+      CUADMM_HIP_TRY(hipEventRecord(ev[1], st));
+      CUADMM_HIP_TRY(hipStreamSynchronize(st));
+      *ms = event_ms(ev[0], ev[1]);
+      if (bad) *bad = projected && failed(st);
+      return CUADMM_OK;
+    }
     double bytes() const { return 8.0 * (double)(in.n + out.n + bcopy.n) + plan_bytes; }
     ~AuxProj() { for (auto& e : ev) if (e) { hipError_t r = hipEventDestroy(e); (void)r; } delete plan; }
   } aux;
+  // What the reports on a point share besides it ("The front of the point reports"): y scaled and in the engine's order
+  // (y_caller null: the resident one) into dst, max(m, 1) doubles; A'y - C into aux.in and the 256 slot sums of b'y.
+  int stage_scaled_y(double* dst, const double* y_caller);
+  int dual_slack(const double* y_scaled_d, double* by_part);
 
   // The per-block task lists of block_reduce.h on the device, for the lower bound and the evaluation: built from blk_local by whichever
   // of lb_prepare / ev_prepare runs first.  blk_local never changes after init, so cuadmm_update_A / cuadmm_update_bC leave them alone.
@@ -2478,7 +2495,37 @@ int cuadmm_solver::AuxProj::project(cuadmm_solver& s, const double* from, double
     if (hipMemGetInfo(&free1, &total) != hipSuccess) { free1 = free0; (void)hipGetLastError(); }
     plan_bytes = free0 > free1 ? (double)(free0 - free1) : 0.0;
   }
+  projected = true;
   return plan->project(from, to, s.st);
+}
+
+// The y a report reads, in the engine's scaled space and the factor's order, in a vector of the report's own.  y_caller: the caller's,
+// with the constants of materialise() inverted as cuadmm_init applies them.  Null: the y cuadmm_get_y would return -- behind a solve the
+// iterate is held scaled and is copied as it lies (the deferred unscaling is not triggered: a following solve(if_first = false)
+// continues from it bit for bit); otherwise y is in the caller's units, on the host, or on the device only where cuadmm_update_bC left
+// the current one there.
+int cuadmm_solver::stage_scaled_y(double* dst, const double* y_caller) {
+  int rc;
+  if (m <= 0) { CUADMM_HIP_TRY(hipMemsetAsync(dst, 0, sizeof(double), st)); return CUADMM_OK; }
+  if (!y_caller && pending_unscale && dev_solve) {
+    CUADMM_HIP_TRY(hipMemcpyAsync(dst, y_d.p, sizeof(double) * (size_t)m, hipMemcpyDeviceToDevice, st));
+    return CUADMM_OK;
+  }
+  std::vector<double> ys(y_p);
+  const double ics = 1 / Cscale;
+  if (y_caller) for (int i = 0; i < m; ++i) ys[i] = (y_caller[perm[i]] * normA_p[i]) * ics;
+  else if (!pending_unscale) {
+    if (y_host_stale && (rc = staged_d2h(ys.data(), y_d.p, sizeof(double) * (size_t)m, st))) return rc;
+    for (int i = 0; i < m; ++i) ys[i] = (ys[i] * normA_p[i]) * ics;
+  }
+  return staged_h2d(dst, ys.data(), sizeof(double) * (size_t)m, st);
+}
+
+// M = A'y - C by the iteration's kernel into the auxiliary projector's input vector (S^ = -Cscale M), and the slot sums of b'y
+int cuadmm_solver::dual_slack(const double* y, double* by_part) {
+  int rc;
+  if ((rc = launch_aty_xb(false, L, At_rp.p, At_ci.p, At_v.p, y, C.p, X.p, 1.0, aux.in.p, nullptr, st, &At_long))) return rc;
+  return launch_lb_dot(m, aux.b_dev(*this), y, by_part, st);
 }
 
 // start of every solve: buffers on first use, no snapshot
@@ -2511,7 +2558,7 @@ int cuadmm_solver::infeas_step(int iter, double stop_tol) {
   }
   double* const dbuf = aux.in.p;      // a difference, the input of a projection
   double* const pbuf = aux.out.p;     // its PSD part
-  CUADMM_HIP_TRY(hipEventRecord(aux.ev[0], st));
+  if ((rc = aux.begin(st))) return rc;
   // d = cur - prev and prev <- cur in one pass each; the X difference is written negated: it is the input of P+(-dX), and the norm
   // of A dX does not see the sign
   if ((rc = launch_infeas_roll(m, y_d.p, inf.yprev.p, aux.b_dev(*this), inf.dy.p, 0, 0, nullptr, nullptr, inf.partials.p, inf.stats_d.p + INF_DY2, st))) return rc;
@@ -2550,13 +2597,11 @@ int cuadmm_solver::infeas_step(int iter, double stop_tol) {
     stats[INF_DX2] = stats[INF_CDX] = stats[INF_ADX2] = stats[INF_PNEGDX2] = nan;
     if ((rc = infeas_decide(stats, inf.tol, &verdict, o3))) return rc;
   }
-  CUADMM_HIP_TRY(hipEventRecord(aux.ev[1], st));
-  CUADMM_HIP_TRY(hipEventSynchronize(aux.ev[1]));
-  inf.ms += event_ms(aux.ev[0], aux.ev[1]);
-  if ((try_dual || try_primal) && aux.failed(st)) {
-    set_error("solve: a block projection of the infeasibility check hit the QL sweep cap");
-    return CUADMM_ERR_EIG;
-  }
+  float ms = 0;
+  bool bad = false;
+  if ((rc = aux.end(st, &ms, &bad))) return rc;
+  inf.ms += ms;
+  if (bad) { set_error("solve: a block projection of the infeasibility check hit the QL sweep cap"); return CUADMM_ERR_EIG; }
   if (verdict == 0) return CUADMM_OK;
   // the ray, as the check left it on the device (scaled space, the factor's order / the svec): dy, or -dX in dbuf
   const size_t n = verdict == 3 ? (size_t)m : (size_t)L;
@@ -2603,18 +2648,15 @@ int cuadmm_solver::lb_eval(const double* y, double out6[6], float* ms) {
   int rc;
   double* const mbuf = aux.in.p;
   double* const pbuf = aux.out.p;
-  CUADMM_HIP_TRY(hipEventRecord(aux.ev[0], st));
+  bool bad = false;
+  if ((rc = aux.begin(st))) return rc;
   // M = A'y - C (S^ = -Cscale M), P = P+(M) with the unconstrained slices copied through
-  if ((rc = launch_aty_xb(false, L, At_rp.p, At_ci.p, At_v.p, y, C.p, X.p, 1.0, mbuf, nullptr, st, &At_long))) return rc;
-  if ((rc = aux.project(*this, mbuf, pbuf))) return rc;
+  if ((rc = dual_slack(y, lb.dpart.p)) || (rc = aux.project(*this, mbuf, pbuf))) return rc;
   if ((rc = launch_lb_block_norms(mbuf, pbuf, btasks.view(), lb.cpart.p, lb.pairs.p, st))) return rc;
-  if ((rc = launch_lb_dot(m, aux.b_dev(*this), y, lb.dpart.p, st))) return rc;
   if ((rc = launch_lb_combine((int)blk_local.size(), lb.pairs.p, lb.R_d.p, btasks.len.p, btasks.blk.p, lb.dpart.p, lb.out_d.p, st))) return rc;
   CUADMM_HIP_TRY(hipMemcpyAsync(lb.h_out.p, lb.out_d.p, sizeof(double) * 4, hipMemcpyDeviceToHost, st));
-  CUADMM_HIP_TRY(hipEventRecord(aux.ev[1], st));
-  CUADMM_HIP_TRY(hipStreamSynchronize(st));
-  *ms = event_ms(aux.ev[0], aux.ev[1]);
-  if (aux.failed(st)) { set_error("lower bound: a block projection hit the QL sweep cap"); return CUADMM_ERR_EIG; }
+  if ((rc = aux.end(st, ms, &bad))) return rc;
+  if (bad) { set_error("lower bound: a block projection hit the QL sweep cap"); return CUADMM_ERR_EIG; }
   const double* h = lb.h_out.p;
   out6[1] = h[3] * objscale;
   out6[2] = h[0] * Cscale;
@@ -2622,6 +2664,24 @@ int cuadmm_solver::lb_eval(const double* y, double out6[6], float* ms) {
   out6[3] = h[1];
   out6[4] = h[2] * Cscale;
   out6[5] = 0;
+  return CUADMM_OK;
+}
+
+// cuadmm_lower_bound's numbers at the scaled y in lb.ybuf; per_block: [nu_k, ||S^_k||_F] in the caller's units
+int cuadmm_solver::lb_report(double o[8], double* per_block) {
+  int rc;
+  double r[6];
+  float ms = 0;
+  if ((rc = lb_eval(lb.ybuf.p, r, &ms))) return rc;
+  o[0] = r[0]; o[1] = r[1]; o[2] = r[2];
+  o[3] = std::fabs(pobj - r[0]) / (1 + std::fabs(pobj) + std::fabs(r[0]));
+  o[4] = r[3]; o[5] = r[4]; o[6] = ms; o[7] = lb.bytes() + btasks.bytes() + aux.bytes();
+  if (per_block) {
+    const size_t nb = blk_local.size();
+    std::vector<double> pr(2 * nb);
+    if ((rc = staged_d2h(pr.data(), lb.pairs.p, sizeof(double) * 2 * nb, st))) return rc;
+    for (size_t k = 0; k < nb; ++k) { per_block[2 * k] = std::sqrt(pr[2 * k + 1]) * Cscale; per_block[2 * k + 1] = std::sqrt(pr[2 * k]) * Cscale; }
+  }
   return CUADMM_OK;
 }
 
@@ -2694,9 +2754,9 @@ int cuadmm_solver::ev_run(const double* xs, const double* ss, double o[16], doub
   double* const ps = aux.out.p;      // P+(S)
   double *const cx_part = ev.part.p, *const by_part = ev.part.p + kBrSlots, *const rp_part = ev.part.p + 2 * kBrSlots;
   const double* const normA_dev = normA_d.p ? normA_d.p : ev.normA.p;
-  CUADMM_HIP_TRY(hipEventRecord(aux.ev[0], st));
-  if ((rc = launch_aty_xb(false, L, At_rp.p, At_ci.p, At_v.p, cons, C.p, xs, 1.0, rd1, nullptr, st, &At_long))) return rc;
-  if ((rc = launch_lb_dot(m, aux.b_dev(*this), cons, by_part, st))) return rc;
+  float ms = 0;
+  bool bad = false;
+  if ((rc = aux.begin(st)) || (rc = dual_slack(cons, by_part))) return rc;
   if ((rc = launch_lb_dot(L, C.p, xs, cx_part, st))) return rc;
   // A X from the engine's whole A (kept in every mode: the fused and closed iterations evaluate rows of it elsewhere), over y in cons
   if (m > 0 && (rc = launch_spmv_rows(m, A_avg_nnz, A_rp.p, A_ci.p, A_v.p, xs, ss, C.p, cons, nullptr, st, &A_long))) return rc;
@@ -2706,11 +2766,10 @@ int cuadmm_solver::ev_run(const double* xs, const double* ss, double o[16], doub
   if ((rc = launch_ev_block_stats(xs, ss, ev.px.p, ps, rd1, btasks.view(), ev.cpart.p, ev.sums.p, st))) return rc;
   if ((rc = launch_ev_combine(nb, ev.sums.p, cx_part, by_part, rp_part, ev.out_d.p, st))) return rc;
   CUADMM_HIP_TRY(hipMemcpyAsync(ev.h_out.p, ev.out_d.p, sizeof(double) * kEvGlobals, hipMemcpyDeviceToHost, st));
-  CUADMM_HIP_TRY(hipEventRecord(aux.ev[1], st));
-  CUADMM_HIP_TRY(hipStreamSynchronize(st));
-  ev.ms = event_ms(aux.ev[0], aux.ev[1]);
+  if ((rc = aux.end(st, &ms, &bad))) return rc;
+  ev.ms = ms;
   ev.calls++;
-  if (aux.failed(st)) { set_error("evaluate: a block projection hit the QL sweep cap"); return CUADMM_ERR_EIG; }
+  if (bad) { set_error("evaluate: a block projection hit the QL sweep cap"); return CUADMM_ERR_EIG; }
   const double* h = ev.h_out.p;
   const double nb1 = norm_borg, nc1 = norm_Corg;      // 1 + ||b||, 1 + ||C||
   o[0] = h[4] * objscale;
@@ -2760,18 +2819,17 @@ int cuadmm_solver::lm_run(int which, int steps, double o[8], double* per_block) 
   const int nb = (int)blk_local.size();
   const double* v = which == 0 ? X.p : S.p;
   double sign = 1.0, unit = pending_unscale ? (which == 0 ? bscale : Cscale) : 1.0;
-  CUADMM_HIP_TRY(hipEventRecord(aux.ev[0], st));
+  float ms = 0;
+  if ((rc = aux.begin(st))) return rc;
   if (which == 2) {
-    if ((rc = launch_aty_xb(false, L, At_rp.p, At_ci.p, At_v.p, lm.ybuf.p, C.p, X.p, 1.0, aux.in.p, nullptr, st, &At_long))) return rc;
-    if ((rc = launch_lb_dot(m, aux.b_dev(*this), lm.ybuf.p, lm.dpart.p, st))) return rc;
+    if ((rc = dual_slack(lm.ybuf.p, lm.dpart.p))) return rc;
     v = aux.in.p; sign = -1.0; unit = Cscale;
   }
   if ((rc = lm.run(v, sign, btasks.off.p, btasks.blk.p, steps, st))) return rc;
   double* const h = lm.h_out.p;
   CUADMM_HIP_TRY(hipMemcpyAsync(h, lm.out.p, sizeof(double) * kLmOut * (size_t)nb, hipMemcpyDeviceToHost, st));
   if (which == 2) CUADMM_HIP_TRY(hipMemcpyAsync(h + kLmOut * (size_t)nb, lm.dpart.p, sizeof(double) * kBrSlots, hipMemcpyDeviceToHost, st));
-  CUADMM_HIP_TRY(hipEventRecord(aux.ev[1], st));
-  CUADMM_HIP_TRY(hipStreamSynchronize(st));
+  if ((rc = aux.end(st, &ms, nullptr))) return rc;
   lm.calls++;
   const bool bound = which == 2 && !lb.R.empty();
   double worst = INFINITY, pen = 0;
@@ -2796,7 +2854,7 @@ int cuadmm_solver::lm_run(int which, int steps, double o[8], double* per_block) 
     o[3] = by * objscale - pen;
   }
   o[4] = (double)unrefined; o[5] = (double)at_floor;
-  o[6] = event_ms(aux.ev[0], aux.ev[1]);
+  o[6] = ms;
   o[7] = lm.bytes() + btasks.bytes() + aux.bytes();
   return CUADMM_OK;
 }
@@ -3417,45 +3475,25 @@ int cuadmm_set_trace_bounds(cuadmm_solver* s, const double* R, int mat_num) {
   s->lb.R_dirty = true;
   return CUADMM_OK;
 }
-int cuadmm_lower_bound(cuadmm_solver* s, double o[8], double* per_block) {
-  if (!s || !s->initialised || !o) { set_error("lower_bound: solver not initialised or null argument"); return CUADMM_ERR_INVALID; }
+// What every report on a point refuses before it touches the device ("The front of the point reports").  what: the results that
+// are not all-reduced; reads_A: the report reads A', C, b and the scaling constants, which a failed cuadmm_update_A leaves half updated.
+static int report_guard(const cuadmm_solver* s, const void* out, const char* who, const char* what, bool reads_A) {
+  if (!s || !s->initialised || !out) { set_error("%s: solver not initialised or null argument", who); return CUADMM_ERR_INVALID; }
   if (s->world > 1 || s->comm_world > 1 || s->local_mode || s->group || s->in_group_call) {
-    set_error("lower_bound: works on one rank (world = %d%s): its sums are not all-reduced", std::max(s->world, s->comm_world), s->group ? ", in-process group" : "");
+    set_error("%s: works on one rank (world = %d%s): its %s are not all-reduced", who, std::max(s->world, s->comm_world), s->group ? ", in-process group" : "", what);
     return CUADMM_ERR_INVALID;
   }
-  if (s->lb.R.empty()) { set_error("lower_bound: no trace bounds are set (cuadmm_set_trace_bounds)"); return CUADMM_ERR_INVALID; }
-  if (s->L <= 0) { set_error("lower_bound: the problem has no svec slots"); return CUADMM_ERR_INVALID; }
-  int rc = check_device(s->device);
+  if (s->L <= 0) { set_error("%s: the problem has no svec slots", who); return CUADMM_ERR_INVALID; }
+  if (reads_A && s->factor_bad) { set_error("%s: the last cuadmm_update_A could not factor the new A A^T; the solver needs a successful cuadmm_update_A first", who); return CUADMM_ERR_FACTOR; }
+  return check_device(s->device);
+}
+// Each report: the guard, its own checks, its vectors (*_prepare), the point staged in them, the run.
+int cuadmm_lower_bound(cuadmm_solver* s, double o[8], double* per_block) {
+  int rc = report_guard(s, o, "lower_bound", "sums", true);
   if (rc) return rc;
-  if ((rc = s->lb_prepare())) return rc;
-  // the y cuadmm_get_y would return, in the engine's scaled space and order, in a vector of the bound's own: behind a solve the
-  // iterate is held scaled (the deferred unscaling is not triggered: a following solve(if_first = false) continues from it bit
-  // for bit); otherwise the host's y (or the device's, where cuadmm_update_bC left the current one there) is in the caller's units
-  const int m = s->m;
-  if (m > 0) {
-    if (s->pending_unscale && s->dev_solve) CUADMM_HIP_TRY(hipMemcpyAsync(s->lb.ybuf.p, s->y_d.p, sizeof(double) * (size_t)m, hipMemcpyDeviceToDevice, s->st));
-    else {
-      std::vector<double> ys(s->y_p);
-      if (!s->pending_unscale) {
-        if (s->y_host_stale && (rc = staged_d2h(ys.data(), s->y_d.p, sizeof(double) * (size_t)m, s->st))) return rc;
-        for (int i = 0; i < m; ++i) ys[i] = (ys[i] * s->normA_p[i]) * (1 / s->Cscale);
-      }
-      if ((rc = staged_h2d(s->lb.ybuf.p, ys.data(), sizeof(double) * (size_t)m, s->st))) return rc;
-    }
-  } else CUADMM_HIP_TRY(hipMemsetAsync(s->lb.ybuf.p, 0, sizeof(double), s->st));
-  double r[6];
-  float ms = 0;
-  if ((rc = s->lb_eval(s->lb.ybuf.p, r, &ms))) return rc;
-  o[0] = r[0]; o[1] = r[1]; o[2] = r[2];
-  o[3] = std::fabs(s->pobj - r[0]) / (1 + std::fabs(s->pobj) + std::fabs(r[0]));
-  o[4] = r[3]; o[5] = r[4]; o[6] = ms; o[7] = s->lb.bytes() + s->btasks.bytes() + s->aux.bytes();
-  if (per_block) {
-    const size_t nb = s->blk_local.size();
-    std::vector<double> pr(2 * nb);
-    if ((rc = staged_d2h(pr.data(), s->lb.pairs.p, sizeof(double) * 2 * nb, s->st))) return rc;
-    for (size_t k = 0; k < nb; ++k) { per_block[2 * k] = std::sqrt(pr[2 * k + 1]) * s->Cscale; per_block[2 * k + 1] = std::sqrt(pr[2 * k]) * s->Cscale; }
-  }
-  return CUADMM_OK;
+  if (s->lb.R.empty()) { set_error("lower_bound: no trace bounds are set (cuadmm_set_trace_bounds)"); return CUADMM_ERR_INVALID; }
+  if ((rc = s->lb_prepare()) || (rc = s->stage_scaled_y(s->lb.ybuf.p, nullptr))) return rc;
+  return s->lb_report(o, per_block);
 }
 int cuadmm_get_gap_info(const cuadmm_solver* s, double o[8]) {
   if (!s || !o) { set_error("get_gap_info: null"); return CUADMM_ERR_INVALID; }
@@ -3464,76 +3502,33 @@ int cuadmm_get_gap_info(const cuadmm_solver* s, double o[8]) {
   return CUADMM_OK;
 }
 int cuadmm_evaluate(cuadmm_solver* s, const double* X, const double* y, const double* S, double o[16], double* per_block) {
-  if (!s || !s->initialised || !o) { set_error("evaluate: solver not initialised or null argument"); return CUADMM_ERR_INVALID; }
-  if (s->world > 1 || s->comm_world > 1 || s->local_mode || s->group || s->in_group_call) {
-    set_error("evaluate: works on one rank (world = %d%s): its sums are not all-reduced", std::max(s->world, s->comm_world), s->group ? ", in-process group" : "");
-    return CUADMM_ERR_INVALID;
-  }
-  if (s->L <= 0) { set_error("evaluate: the problem has no svec slots"); return CUADMM_ERR_INVALID; }
-  if (s->factor_bad) { set_error("evaluate: the last cuadmm_update_A could not factor the new A A^T; the solver needs a successful cuadmm_update_A first"); return CUADMM_ERR_FACTOR; }
-  const int m = s->m;
-  const long long L = s->L;
+  int rc = report_guard(s, o, "evaluate", "sums", true);
+  if (rc) return rc;
   // before anything is uploaded: a passed vector with an entry that is not finite
-  const struct { const char* name; const double* v; long long n; } in[3] = {{"X", X, L}, {"y", y, m}, {"S", S, L}};
+  const struct { const char* name; const double* v; long long n; } in[3] = {{"X", X, s->L}, {"y", y, s->m}, {"S", S, s->L}};
   for (const auto& q : in)
     for (long long i = 0; q.v && i < q.n; ++i)
       if (!std::isfinite(q.v[i])) { set_error("evaluate: %s[%lld] is not finite", q.name, i); return CUADMM_ERR_INVALID; }
-  int rc = check_device(s->device);
-  if (rc) return rc;
   if ((rc = s->ev_prepare())) return rc;
   // The point in the engine's scaled space and order, in vectors of the evaluation's own (the constants of materialise(), inverted, as
   // cuadmm_init and cuadmm_solve(if_first = 0) apply them).  A null vector is the one its getter would return: behind a solve the
-  // iterate is held scaled and is read as it lies -- the deferred unscaling is not triggered, a following solve(if_first = 0)
-  // continues from it bit for bit --, otherwise it is in the caller's units (y on the host, or on the device where cuadmm_update_bC
-  // left the current one there).
-  const double ibs = 1 / s->bscale, ics = 1 / s->Cscale;
+  // iterate is held scaled and is read as it lies, otherwise it is in the caller's units (stage_scaled_y has the cases of y).
   const double *xs = nullptr, *ss = nullptr;
-  if ((rc = s->ev_point(X, s->X, ibs, s->ev.xs, &xs)) || (rc = s->ev_point(S, s->S, ics, s->ev.ss, &ss))) return rc;
-  if (m > 0) {
-    if (!y && s->pending_unscale && s->dev_solve) CUADMM_HIP_TRY(hipMemcpyAsync(s->ev.cons.p, s->y_d.p, sizeof(double) * (size_t)m, hipMemcpyDeviceToDevice, s->st));
-    else {
-      std::vector<double> ys(s->y_p);
-      if (y) for (int i = 0; i < m; ++i) ys[i] = (y[s->perm[i]] * s->normA_p[i]) * ics;
-      else if (!s->pending_unscale) {
-        if (s->y_host_stale && (rc = staged_d2h(ys.data(), s->y_d.p, sizeof(double) * (size_t)m, s->st))) return rc;
-        for (int i = 0; i < m; ++i) ys[i] = (ys[i] * s->normA_p[i]) * ics;
-      }
-      if ((rc = staged_h2d(s->ev.cons.p, ys.data(), sizeof(double) * (size_t)m, s->st))) return rc;
-    }
-  }
+  if ((rc = s->ev_point(X, s->X, 1 / s->bscale, s->ev.xs, &xs)) || (rc = s->ev_point(S, s->S, 1 / s->Cscale, s->ev.ss, &ss)) ||
+      (rc = s->stage_scaled_y(s->ev.cons.p, y)))
+    return rc;
   return s->ev_run(xs, ss, o, per_block);
 }
 int cuadmm_lambda_min(cuadmm_solver* s, int which, int steps, double o[8], double* per_block) {
-  if (!s || !s->initialised || !o) { set_error("lambda_min: solver not initialised or null argument"); return CUADMM_ERR_INVALID; }
-  if (s->world > 1 || s->comm_world > 1 || s->local_mode || s->group || s->in_group_call) {
-    set_error("lambda_min: works on one rank (world = %d%s): its results are not all-reduced", std::max(s->world, s->comm_world), s->group ? ", in-process group" : "");
-    return CUADMM_ERR_INVALID;
-  }
+  int rc = report_guard(s, o, "lambda_min", "results", which == 2);
+  if (rc) return rc;
   if (which < 0 || which > 2) { set_error("lambda_min: which = %d (0: X, 1: S, 2: C - A'y)", which); return CUADMM_ERR_INVALID; }
   if (steps < 1 || steps > kLmStepsMax) { set_error("lambda_min: steps = %d, allowed are 1 to %d", steps, kLmStepsMax); return CUADMM_ERR_INVALID; }
-  if (s->L <= 0) { set_error("lambda_min: the problem has no svec slots"); return CUADMM_ERR_INVALID; }
   if (which == 2 && !s->lb.R.empty() && s->lb.R.size() != s->blk_local.size()) {
     set_error("lambda_min: %d trace bounds are set, the solver has %d blocks", (int)s->lb.R.size(), (int)s->blk_local.size());
     return CUADMM_ERR_INVALID;
   }
-  if (which == 2 && s->factor_bad) { set_error("lambda_min: the last cuadmm_update_A could not factor the new A A^T; the solver needs a successful cuadmm_update_A first"); return CUADMM_ERR_FACTOR; }
-  int rc = check_device(s->device);
-  if (rc) return rc;
-  if ((rc = s->lm_prepare(which))) return rc;
-  if (which == 2) {      // the y cuadmm_get_y would return, scaled and in the engine's order, as cuadmm_lower_bound stages it
-    const int m = s->m;
-    if (m > 0) {
-      if (s->pending_unscale && s->dev_solve) CUADMM_HIP_TRY(hipMemcpyAsync(s->lm.ybuf.p, s->y_d.p, sizeof(double) * (size_t)m, hipMemcpyDeviceToDevice, s->st));
-      else {
-        std::vector<double> ys(s->y_p);
-        if (!s->pending_unscale) {
-          if (s->y_host_stale && (rc = staged_d2h(ys.data(), s->y_d.p, sizeof(double) * (size_t)m, s->st))) return rc;
-          for (int i = 0; i < m; ++i) ys[i] = (ys[i] * s->normA_p[i]) * (1 / s->Cscale);
-        }
-        if ((rc = staged_h2d(s->lm.ybuf.p, ys.data(), sizeof(double) * (size_t)m, s->st))) return rc;
-      }
-    } else CUADMM_HIP_TRY(hipMemsetAsync(s->lm.ybuf.p, 0, sizeof(double), s->st));
-  }
+  if ((rc = s->lm_prepare(which)) || (which == 2 && (rc = s->stage_scaled_y(s->lm.ybuf.p, nullptr)))) return rc;
   return s->lm_run(which, steps, o, per_block);
 }
 int cuadmm_get_evaluate_info(const cuadmm_solver* s, double o[4]) {

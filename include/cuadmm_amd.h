@@ -291,7 +291,8 @@ int cuadmm_set_trace_bounds(cuadmm_solver* s, const double* R, int mat_num);
 /* A lower bound on the optimal value that holds for EVERY y: with S^ = C - A'y,
  *   LB(y) = b'y - sum_k R_k nubar_k,  nubar_k = ||P+(-S^_k)||_F + 2e-12 sqrt(2 len_k) ||S^_k||_F (PSD block), ||S^_k||_2 (unconstrained),
  * evaluated at the y cuadmm_get_y would return, on any initialised solver with trace bounds set (before a solve, after one, between
- * solve(..., if_first = 0) calls, after solves with any option); refused for world > 1 and in-process groups.  It changes nothing the
+ * solve(..., if_first = 0) calls, after solves with any option); refused for world > 1 and in-process groups (CUADMM_ERR_INVALID) and,
+ * as cuadmm_evaluate, behind a failed cuadmm_update_A (CUADMM_ERR_FACTOR: A', C, b and the scaling are half updated).  It changes nothing the
  * iteration reads: a following cuadmm_solve continues bit for bit as without the call.  The second term of nubar_k is the projection
  * kernels' accuracy; the rounding of A'y - C itself is not covered.  out8 (caller's units): [0] LB, [1] b'y, [2] sum R_k nubar_k,
  * [3] g = |pobj - LB| / (1 + |pobj| + |LB|) against the pobj of the current state, [4] the block with the largest term, [5] its term

@@ -414,6 +414,78 @@ def test_the_report_and_the_bound_share_one_task_list():
     assert s3b.evaluate_info()["bytes"] == evb[0] and s3e.gap_info()["bytes"] == 0.0
 
 
+def _one_y(fx, a, b, what):
+    """a reports on its resident point without handing it out; b, in the same state, hands it out and numpy forms the numbers (the
+    inner product and C - A'y in longdouble, so that the bounds below are spent on the engine alone)"""
+    lb, ev, lm = a.lower_bound(per_block=True), a.evaluate(), a.lambda_min("dual")
+    X, y, S = b.X, b.y, b.S
+    off = offsets(fx.blk)
+    by = float(np.sum(fx.b.astype(LD) * y.astype(LD)))
+    sc_by = float(np.abs(fx.b) @ np.abs(y))
+    Sh = np.asarray(fx.C.astype(LD) - fx.A.T.astype(LD) @ y.astype(LD), np.float64)
+    e = np.abs(fx.C) + np.abs(fx.A).T @ np.abs(y)
+    sc = np.array([np.linalg.norm(e[off[k]:off[k + 1]]) for k in range(len(fx.blk))])
+    for name, got in (("evaluate dobj", ev["dobj"]), ("lower_bound bty", lb["bty"]), ("lower_bound", lb["lower_bound"]), ("lambda_min lower_bound", lm["lower_bound"])):
+        print("%s, %-22s %.17g | numpy %.17g  difference / |b|'|y| %.3g" % (what, name, got, by, abs(got - by) / sc_by))
+        assert abs(got - by) <= 1e-13 * sc_by, (what, name)
+    nS = np.array([np.linalg.norm(Sh[off[k]:off[k + 1]]) for k in range(len(fx.blk))])
+    lam = np.array([np.linalg.eigvalsh(smat(Sh[off[k]:off[k + 1]], int(n)))[0] if n > 0 else np.inf for k, n in enumerate(fx.blk)])
+    psd = np.asarray(fx.blk) > 0
+    print("%s: worst | ||S^_k|| - numpy | / scale %.3g, worst (lo_k - lambda_min_k) / scale %.3g"
+          % (what, float(np.max(np.abs(lb["norm_S"] - nS) / sc)), float(np.max((lm["lo"][psd] - lam[psd]) / sc[psd]))))
+    assert np.all(np.abs(lb["norm_S"] - nS) <= 1e-13 * sc), what
+    assert np.all(lm["lo"][psd] <= lam[psd] + 1e-13 * sc[psd]), what
+    against_twin(fx, ev, X, y, S, what)
+
+
+@pytest.mark.parametrize("name", ["A", "closed"])
+def test_the_three_reports_read_one_y_in_every_resident_state(name):
+    """lower_bound(), evaluate() and lambda_min("dual") stage the resident y through one routine (csrc/engine.hip: stage_scaled_y), whose
+    branches are the states y can be in: in the caller's units on the host (1: behind set_XyS), scaled behind a solve (2; on the host
+    with the y-solve there: fixture A, on the device with it there: 256 blocks of 8, test_report_on_closed_blocks), in the caller's
+    units on the device only (3: behind update_bC(keep_iterate) on the device y-solve, before any getter) and on the host again (4: a
+    getter has run).  Trace bounds of zero: the penalty vanishes and all three expose b'y.  Bounds: the rule of
+    test_report_of_the_current_iterate -- every entry of y moved by at most two roundings, so a number moves by a few U times the
+    absolute sum it is formed from, 1e-13 (900 U) relative to |b|'|y| for b'y and to ||(|C| + |A|'|y|)_k|| for block k of C - A'y, its
+    norm and (Weyl) its smallest eigenvalue."""
+    if name == "A":
+        fx = fixture("A")
+        prob, where = amd(fx), (0, 2)                              # cuadmm_get_counters: the y-solve on the host (2: hybrid)
+    else:
+        p = synthetic.make_synthetic([8] * 256, cons_per_block=2, seed=5)
+        fx = _dense_fixture(p)
+        prob, where = cuadmm_amd.Problem(p.vec_len, p.con_num, p.blk, p.At_col_ptrs, p.At_row_ids, p.At_vals, p.b_idx, p.b_vals, p.C_idx, p.C_vals), (1, 3)
+    rng = np.random.default_rng(31)
+    X0, y0, S0 = rng.standard_normal(fx.L), rng.standard_normal(fx.m), rng.standard_normal(fx.L)
+    fb = Fixture(fx.blk, fx.A, fx.b * (1 + 0.3 * rng.standard_normal(fx.m)), fx.C + 0.2 * rng.standard_normal(fx.L))
+    bi, ci = np.nonzero(fb.b)[0], np.nonzero(fb.C)[0]
+
+    def pair():
+        hs = []
+        for _ in range(2):
+            s = cuadmm_amd.SDPSolver(verbose=False)
+            s.set_trace_bounds(np.zeros(len(fx.blk)))
+            s.init_problem(prob)
+            assert int(s.counters()["dev_solve"]) in where
+            hs.append(s)
+        return hs
+
+    a, b = pair()
+    for s in (a, b):
+        s.set_XyS(X0, y0, S0)
+    _one_y(fx, a, b, name + " state 1 (set_XyS)")
+    for s in (a, b):
+        s.solve(30, 0.0)
+    _one_y(fx, a, b, name + " state 2 (behind a solve)")
+    a, b = pair()
+    for s in (a, b):
+        s.solve(30, 0.0)
+        s.update_bC(bi, fb.b[bi], ci, fb.C[ci], keep_iterate=True)
+    _one_y(fb, a, b, name + " state 3 (behind update_bC, no getter)")
+    assert a.y.size == fx.m                                        # one getter: y is on the host again
+    _one_y(fb, a, b, name + " state 4 (behind update_bC and a getter)")
+
+
 # ---- 7. refusals ----------------------------------------------------------------------------------------------------------
 def test_refusals_leave_the_solver_as_it_was():
     fx = fixture("B")

@@ -333,6 +333,20 @@ def test_refusals():
         s.set_option("gap_check", 50)
     s.set_trace_bounds(fx.R)                                       # after init: allowed
     assert np.isfinite(s.lower_bound()["lower_bound"])
+    # behind a failed cuadmm_update_A the bound would come from half-updated matrices: refused, as evaluate() and lambda_min("dual") are
+    s.set_XyS(y=np.random.default_rng(6).standard_normal(fx.m))
+    s.set_option("update_A_inject_fail", 1)                        # the test hook of tests/test_gpu_update_a.py
+    with pytest.raises(cuadmm_amd.CuadmmError) as e:
+        s.update_A(p.At_csc_vals * 1.5)
+    assert e.value.code == -4
+    with pytest.raises(cuadmm_amd.CuadmmError, match=r"lower_bound: the last cuadmm_update_A could not factor the new A A\^T; "
+                                                     "the solver needs a successful cuadmm_update_A first") as e:
+        s.lower_bound()
+    assert e.value.code == -4
+    s.update_A(p.At_csc_vals)                                      # a good update on the same handle: the bound is back
+    got = s.lower_bound(per_block=True)
+    y = s.y
+    _against_twin(fx, got, dict(lower_bound(fx, y, fx.R), y=y), fx.R, "B behind a failed and a good update_A")
 
 
 # ---- 8. command line ------------------------------------------------------------------------------------------------------
