@@ -168,6 +168,7 @@ PROTOTYPES = {
     "cuadmm_psd_plan_set_hint": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
     "cuadmm_psd_plan_reorder": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
     "cuadmm_psd_plan_project_ordered": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, c_int_p]),
+    "cuadmm_psd_plan_ranges": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_char_p), C.c_void_p, C.c_int] + [C.c_void_p] * 5),
     "cuadmm_op_psd_project": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "cuadmm_op_permute": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "cuadmm_op_get_normA": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),

@@ -3796,6 +3796,31 @@ int cuadmm_psd_plan_project(cuadmm_psd_plan* p, const double* Xb, double* Xproj,
   return p->plan.project(Xb, Xproj, (hipStream_t)stream);
 }
 void cuadmm_psd_plan_destroy(cuadmm_psd_plan* p) { delete p; }
+int cuadmm_psd_plan_ranges(const int* blk_host, int mat_num, int eig_rank, int tiny_sign, const char* const* opt_keys, const double* opt_vals,
+                           int n_opts, int* ranges_out, int* ids_out, int* slot_out, int* rest_out, int* summary_out) {
+  if (!blk_host || mat_num < 0 || eig_rank < 0 || n_opts < 0 || !ranges_out || !ids_out || !slot_out || !rest_out || !summary_out) {
+    set_error("psd_plan_ranges: bad arguments"); return CUADMM_ERR_INVALID;
+  }
+  PsdPlan plan;
+  plan.opt = PsdOptions();
+  for (int i = 0; i < n_opts; ++i)
+    if (!plan.opt.set(opt_keys[i], opt_vals[i])) { set_error("psd_plan_ranges: unknown option %s", opt_keys[i]); return CUADMM_ERR_INVALID; }
+  plan.eig_rank = eig_rank;
+  plan.tiny_sign = tiny_sign != 0;
+  int rc = plan.build_host(blk_host, mat_num);
+  if (rc) return rc;
+  for (const PsdRange& r : plan.ranges)
+    for (int v : {r.cls, r.first, r.count, (int)r.kind, r.nt, r.occ, r.occ_batch, (int)r.full, (int)r.triple, r.maxn}) *ranges_out++ = v;
+  std::vector<int> slot_of, rest;
+  plan.fused_slots(slot_of);
+  plan.rest_elements(rest);
+  std::copy(plan.h_ids.begin(), plan.h_ids.end(), ids_out);
+  std::copy(slot_of.begin(), slot_of.end(), slot_out);
+  std::copy(rest.begin(), rest.end(), rest_out);
+  const int summary[6] = {plan.ranges.n, (int)plan.h_ids.size(), (int)rest.size(), plan.fusable() ? 1 : 0, plan.fused_blocks(), plan.ranges.sign_min};
+  std::copy(summary, summary + 6, summary_out);
+  return CUADMM_OK;
+}
 
 // ---- the plan in the state the engine keeps it in (tests): schedule hints, re-sorted descriptors, a non-blocking caller's stream
 static int psd_plan_stream(cuadmm_psd_plan* p, int own_stream, hipStream_t* st) {

@@ -328,14 +328,6 @@ static int launch_sign_wave(const PsdArgs& a, int first, int count, hipStream_t 
   return CUADMM_OK;
 }
 
-// 17 <= n <= 32: three or four wavefronts per SIMD (PsdOptions::w32_occ; the launches of several iterations: cu_occ)
-static int launch_sign_wave32(const PsdArgs& a, int first, int count, hipStream_t st, const PsdOptions& opt, const SignFuse* fz = nullptr) {
-  if (count <= 0) return CUADMM_OK;
-  const int occ = (fz && fz->iters > 1) ? opt.cu_occ : opt.w32_occ;
-  if (occ == 3) return launch_sign_wave<2, 3>(a, first, count, st, fz);
-  return launch_sign_wave<2, 4>(a, first, count, st, fz);
-}
-
 template <int NP, bool TRIPLE>
 static int launch_sign_lds_t(const PsdArgs& a, int first, int count, hipStream_t st) {
   const size_t lds = sizeof(double) * (TRIPLE ? 3 : 2) * NP * SignLdsCfg<NP>::LD;
@@ -373,51 +365,78 @@ int psd_class_of(int n) {
   return 6;
 }
 
-int PsdPlan::build(const int* blk, int mat_num) {
-  release();
+// The launch table (psd_plan.h): size classes in ascending order, members of a class largest first.  With a rank mask
+// (eig_rank > 0) every block needs eigenvalues and goes through the eigensolver kernels.
+PsdRanges psd_build_ranges(const int* blk, int nblk, const PsdOptions& opt, int eig_rank, bool tiny_sign, std::vector<int>& ids) {
+  PsdRanges t;
+  const bool sign_ok = eig_rank == 0, sign16 = opt.n16_sign != 0;
+  t.sign_min = sign_ok ? std::max(65, opt.sign_min) : 0x7fffffff;
+  ids.clear();
+  int n_wave = 0;
+  for (int c = 0; c < kNumPsdClasses; ++c) {
+    const int begin = (int)ids.size();
+    for (int k = 0; k < nblk; ++k)   // tiny_sign: n <= 8 joins the one-wavefront range of 9 <= n <= 16
+      if (blk[k] > 0 && blk[k] < t.sign_min && ((tiny_sign && sign16 && blk[k] <= 16) ? 2 : psd_class_of(blk[k])) == c) ids.push_back(k);
+    std::stable_sort(ids.begin() + begin, ids.end(), [&](int x, int y) { return blk[x] > blk[y]; });
+    const int count = (int)ids.size() - begin;
+    auto add = [&](int first, int cnt, PsdKind kind, int nt = 0, int occ = 0, int occ_batch = 0, bool triple = false) {
+      if (cnt <= 0) return;
+      PsdRange& r = t.r[t.n++];
+      r = PsdRange{c, first, cnt, kind, nt, occ, occ_batch, kind == PsdKind::SignWave, triple, blk[ids[(size_t)first]]};
+      // FULL: every member fills its tile exactly, so the closed-block kernels know every slot of the svec walks at compile time
+      for (int q = first; q < first + cnt; ++q) r.full = r.full && blk[ids[(size_t)q]] == 16 * nt;
+      if (r.wave()) n_wave += cnt;
+    };
+    if (c == 2 && sign16 && sign_ok) {
+      // 9 <= n <= 16: the sign iteration on ONE 16 x 16 sub-tile, eight wavefronts per SIMD (the register eigensolver needs
+      // ~20 us of dependent rotations per block; here a block is 8 MFMAs per step); psd_n16 = 0: register eigensolver
+      add(begin, count, PsdKind::SignWave, 1, 8, 8);
+    } else if (c == 3 && opt.n32_sign != 0 && sign_ok) {
+      // 16 < n <= 32: psd_n32 = 0 -> register eigensolver, default the one-wavefront sign kernel (0.256 vs 0.92 ms per 10 000 x 32
+      // blocks on MI355X, 0.05 vs 0.35 ms latency for a single block); three or four wavefronts per SIMD (psd_w32_occ, psd_cu_occ)
+      add(begin, count, PsdKind::SignWave, 2, opt.w32_occ, opt.cu_occ);
+    } else if (c == 4 && opt.mid != 1 && sign_ok) {
+      // 32 < n <= 64, the n > 48 members first.  One wavefront per block (throughput: 1.3x the one-workgroup kernels in bulk) only
+      // when there are enough blocks to fill the chip; a handful of blocks (moment relaxations) is a LATENCY problem, and there six /
+      // ten wavefronts per block win (measured crossover: ~1000 blocks at n = 45 and at n = 64; psd_wave4_min moves it, psd_mid = 2
+      // forces one workgroup per block, 1 the register eigensolver).  triple: psd_sign_lds.h, launch_sign_lds
+      int big = 0;
+      while (big < count && blk[ids[(size_t)(begin + big)]] > 48) ++big;
+      const bool wave4 = opt.mid == 0 && count >= opt.wave4_min, triple = opt.lds_triple != 0 && count <= 256;
+      add(begin, big, wave4 ? PsdKind::SignWave : PsdKind::SignLds, 4, 1, 1, triple);
+      add(begin + big, count - big, wave4 ? PsdKind::SignWave : PsdKind::SignLds, 3, 2, 2, triple);
+    } else {
+      add(begin, count, c == 5 ? PsdKind::WgEig : (c == 6 ? PsdKind::ChipEig : PsdKind::RegEig));
+    }
+  }
+  t.can_fuse = sign_ok && opt.n32_sign != 0 && opt.mid != 1 && n_wave > 0;
+  return t;
+}
+
+int PsdPlan::build_host(const int* blk, int mat_num) {
   nblk = mat_num;
   h_blk.assign(blk, blk + mat_num);
-  sign16 = opt.n16_sign != 0;
-  sign.opt = opt;
-  std::vector<long long> off((size_t)mat_num + 1, 0);
-  std::vector<long long> free_off, free_len;   // unconstrained blocks (negative size): identity "projection"
+  h_off.assign((size_t)mat_num + 1, 0);
   for (int k = 0; k < mat_num; ++k) {
     if (blk[k] == 0) { set_error("block %d has size 0", k); return CUADMM_ERR_INVALID; }
     if (blk[k] > kMaxBlockSize) { set_error("block %d has size %d > %d (largest supported this build)", k, blk[k], kMaxBlockSize); return CUADMM_ERR_INVALID; }
-    off[k + 1] = off[k] + blk_svec_len(blk[k]);
-    if (blk[k] < 0) { free_off.push_back(off[k]); free_len.push_back(-(long long)blk[k]); }
+    h_off[k + 1] = h_off[k] + blk_svec_len(blk[k]);
   }
-  vec_len = off[mat_num];
-  sign_min = std::max(65, opt.sign_min);
-  // a rank mask needs eigenvalues: with eig_rank set every block goes through the eigensolver kernels
-  if (eig_rank > 0) sign_min = 0x7fffffff;
+  vec_len = h_off[mat_num];
+  ranges = psd_build_ranges(blk, mat_num, opt, eig_rank, tiny_sign, h_ids);
+  return CUADMM_OK;
+}
+
+int PsdPlan::build(const int* blk, int mat_num) {
+  release();
+  sign.opt = opt;
+  { int rc = build_host(blk, mat_num); if (rc) return rc; }
+  const auto& off = h_off; const auto& ids = h_ids;
+  std::vector<long long> free_off, free_len;   // unconstrained blocks (negative size): identity "projection"
   std::vector<int> sign_members;
-  for (int k = 0; k < mat_num; ++k)
-    if (blk[k] >= sign_min) sign_members.push_back(k);
-  std::vector<int> ids;
-  cls4_big = 0;
-  for (int c = 0; c < kNumPsdClasses; ++c) {
-    cls_begin[c] = (int)ids.size();
-    std::vector<int> members;
-    for (int k = 0; k < mat_num; ++k)
-      if (blk[k] > 0 && class_of(blk[k]) == c && blk[k] < sign_min) members.push_back(k);
-    std::stable_sort(members.begin(), members.end(), [&](int x, int y) { return blk[x] > blk[y]; });
-    for (int k : members) {
-      ids.push_back(k);
-      if (c >= 4) cls_maxn[c] = std::max(cls_maxn[c], blk[k]);
-      if (c == 4 && blk[k] > 48) ++cls4_big;
-    }
-    cls_count[c] = (int)ids.size() - cls_begin[c];
-  }
-  wave4 = opt.mid == 0 && cls_count[4] >= opt.wave4_min;
-  // ranges whose members all fill their tile exactly (n = 16 NT): the closed-block kernels then know every slot of the svec walks
-  // at compile time (psd_sign_closed.h, FULL)
-  {
-    auto all_eq = [&](int begin, int count, int n) { for (int q = begin; q < begin + count; ++q) if (blk[ids[(size_t)q]] != n) return false; return count > 0; };
-    range_full[0] = all_eq(cls_begin[2], cls_count[2], 16);
-    range_full[1] = all_eq(cls_begin[3], cls_count[3], 32);
-    range_full[2] = all_eq(cls_begin[4] + cls4_big, cls_count[4] - cls4_big, 48);
-    range_full[3] = all_eq(cls_begin[4], cls4_big, 64);
+  for (int k = 0; k < mat_num; ++k) {
+    if (blk[k] < 0) { free_off.push_back(off[k]); free_len.push_back(-(long long)blk[k]); }
+    if (blk[k] >= ranges.sign_min) sign_members.push_back(k);
   }
   n_free = (int)free_off.size();
   if (n_free > 0) {
@@ -433,23 +452,17 @@ int PsdPlan::build(const int* blk, int mat_num) {
   { int rc_ = staged_h2d(d_off, off.data(), sizeof(long long) * ((size_t)mat_num + 1)); if (rc_) return rc_; }
   { int rc_ = staged_h2d(d_n, blk, sizeof(int) * (size_t)mat_num); if (rc_) return rc_; }
   if (!ids.empty()) { int rc_ = staged_h2d(d_ids, ids.data(), sizeof(int) * ids.size()); if (rc_) return rc_; }
-  h_ids = ids;
   {
-    std::vector<PsdDesc> desc(std::max<size_t>(ids.size(), 1));
+    h_desc.assign(std::max<size_t>(ids.size(), 1), PsdDesc{});
     std::vector<int> slot_of;
     fused_slots(slot_of);
-    for (size_t q = 0; q < ids.size(); ++q) desc[q] = PsdDesc{off[ids[q]], blk[ids[q]], ids[q], slot_of[ids[q]], {0, 0, 0}};
-    CUADMM_HIP_TRY(hipMalloc(&d_desc, sizeof(PsdDesc) * desc.size()));
-    CUADMM_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h_desc_pin), sizeof(PsdDesc) * desc.size(), hipHostMallocDefault));   // reorder_by_steps_async
-    { int rc_ = staged_h2d(d_desc, desc.data(), sizeof(PsdDesc) * desc.size()); if (rc_) return rc_; }
-    h_desc = desc;
+    for (size_t q = 0; q < ids.size(); ++q) h_desc[q] = PsdDesc{off[ids[q]], blk[ids[q]], ids[q], slot_of[ids[q]], {0, 0, 0}};
+    CUADMM_HIP_TRY(hipMalloc(&d_desc, sizeof(PsdDesc) * h_desc.size()));
+    CUADMM_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h_desc_pin), sizeof(PsdDesc) * h_desc.size(), hipHostMallocDefault));   // reorder_by_steps_async
+    { int rc_ = staged_h2d(d_desc, h_desc.data(), sizeof(PsdDesc) * h_desc.size()); if (rc_) return rc_; }
   }
-  {
-    int rc = sign.build(blk, sign_members);
-    if (rc) return rc;
-  }
+  { int rc = sign.build(blk, sign_members); if (rc) return rc; }
   CUADMM_HIP_TRY(hipMemset(d_fail, 0, sizeof(int)));
-  h_off = off;
   dominant_geometry = compute_dominant_geometry();
   // nominal flops 10.67 n^3 per block, GEMM-shaped part 2 n^3
   sum_n3 = 0;
@@ -471,7 +484,7 @@ void PsdPlan::release() {
     for (int i = 0; i < kNumPsdClasses; ++i) { e = hipEventDestroy(ev_done[i]); (void)e; e = hipStreamDestroy(aux[i]); (void)e; }
     ev_fork = nullptr;
   }
-  for (int c = 0; c < kNumPsdClasses; ++c) { cls_begin[c] = cls_count[c] = 0; cls_maxn[c] = 0; }
+  ranges = PsdRanges{};
 }
 
 template <int NT, int MODE>
@@ -506,100 +519,77 @@ static int launch_class(int c, PsdArgs a, int maxn, hipStream_t st) {
   return CUADMM_OK;
 }
 
-// Xproj = Pi_+(Xb) over all blocks of the plan (device pointers, svec layout)
-// Size classes are independent: with `overlap` (engine-owned plans) every class and the sign path run on their own
-// stream between a fork and a join event on `st`, so small classes (a moment relaxation has a handful of blocks per
-// size) overlap instead of queueing behind each other.
 // schedule hints age: one lift step fewer every 16th projection, so that a block whose spectrum got easier finds out
 __global__ void hint_decay_kernel(int* hint, int n) {
   const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
   if (i < n && hint[i] > 1) hint[i] -= 1;
 }
 
-// Blocks of the one-wavefront-per-block sign kernels (classes 3 and 4) can take the iteration's vector work with them
-bool PsdPlan::fusable() const {
-  return eig_rank == 0 && opt.debug != 1 && opt.n32_sign && opt.mid != 1 && fused_blocks() > 0 && vec_len < 0x7fffffffLL;
-}
-
-bool PsdPlan::sort_by_steps_host(const int* steps_host, std::vector<std::pair<int, int>>& ranges) {
-  // ranges served by the one-wavefront kernels: class 2 (sign16), class 3, class 4 (wave4: the n > 48 members and the others)
-  ranges.clear();
-  if (sign16 && cls_count[2] > 0) ranges.push_back({cls_begin[2], cls_count[2]});
-  if (cls_count[3] > 0) ranges.push_back({cls_begin[3], cls_count[3]});
-  if (wave4 && cls_count[4] > 0) {
-    if (cls4_big > 0) ranges.push_back({cls_begin[4], cls4_big});
-    if (cls_count[4] > cls4_big) ranges.push_back({cls_begin[4] + cls4_big, cls_count[4] - cls4_big});
-  }
+bool PsdPlan::sort_by_steps_host(const int* steps_host) {
+  bool any = false;
   std::vector<PsdDesc> tmp;
-  for (auto& rg : ranges) {   // counting sort by steps (<= SignSched::kCap), descending, stable
+  for (const PsdRange& rg : ranges) {   // counting sort by steps (<= SignSched::kCap), descending, stable
+    if (!rg.wave()) continue;
+    any = true;
     constexpr int K = SignSched::kCap + 2;
     int cnt[K + 1] = {0};
     auto key = [&](const PsdDesc& d) { const int st = steps_host[d.id]; return K - 1 - (st < 0 ? 0 : (st > K - 1 ? K - 1 : st)); };
-    for (int q = 0; q < rg.second; ++q) cnt[key(h_desc[rg.first + q]) + 1]++;
+    for (int q = 0; q < rg.count; ++q) cnt[key(h_desc[rg.first + q]) + 1]++;
     for (int k = 0; k < K; ++k) cnt[k + 1] += cnt[k];
-    tmp.resize((size_t)rg.second);
-    for (int q = 0; q < rg.second; ++q) tmp[(size_t)cnt[key(h_desc[rg.first + q])]++] = h_desc[rg.first + q];
+    tmp.resize((size_t)rg.count);
+    for (int q = 0; q < rg.count; ++q) tmp[(size_t)cnt[key(h_desc[rg.first + q])]++] = h_desc[rg.first + q];
     std::copy(tmp.begin(), tmp.end(), h_desc.begin() + rg.first);
   }
-  return !ranges.empty();
+  return any;
 }
 
 bool PsdPlan::compute_dominant_geometry() const {
   double w[4] = {0, 0, 0, 0}, tot = 0;                     // NT = 1 .. 4
-  for (int c = 2; c <= 4; ++c) {
-    if ((c == 2 && !sign16) || (c == 4 && !wave4)) continue;
-    for (int q = 0; q < cls_count[c]; ++q) {
-      const int n = h_blk[h_ids[cls_begin[c] + q]];
-      const int nt = n <= 16 ? 1 : (n <= 32 ? 2 : (n <= 48 ? 3 : 4));
-      const double x = (double)nt * nt * nt;               // the tile is what is paid for
-      w[nt - 1] += x; tot += x;
-    }
-  }
+  for (const PsdRange& r : ranges)
+    if (r.wave()) { const double x = (double)r.nt * r.nt * r.nt * r.count; w[r.nt - 1] += x; tot += x; }   // the tile is what is paid for
   for (double x : w) if (x >= 0.9 * tot && tot > 0) return true;
   return false;
 }
 
 int PsdPlan::reorder_by_steps(const int* steps_host, hipStream_t st) {
-  std::vector<std::pair<int, int>> ranges;
-  sort_by_steps_host(steps_host, ranges);
-  for (auto& rg : ranges) {
-    int rc = staged_h2d(d_desc + rg.first, &h_desc[rg.first], sizeof(PsdDesc) * (size_t)rg.second, st);
+  sort_by_steps_host(steps_host);
+  for (const PsdRange& rg : ranges) {
+    if (!rg.wave()) continue;
+    int rc = staged_h2d(d_desc + rg.first, &h_desc[rg.first], sizeof(PsdDesc) * (size_t)rg.count, st);
     if (rc) return rc;
   }
   return CUADMM_OK;
 }
 
 int PsdPlan::reorder_by_steps_async(const int* steps_host, hipStream_t st) {
-  std::vector<std::pair<int, int>> ranges;
-  if (!sort_by_steps_host(steps_host, ranges)) return CUADMM_OK;
+  if (!sort_by_steps_host(steps_host)) return CUADMM_OK;
   std::copy(h_desc.begin(), h_desc.end(), h_desc_pin);
-  for (auto& rg : ranges)
-    CUADMM_HIP_TRY(hipMemcpyAsync(d_desc + rg.first, h_desc_pin + rg.first, sizeof(PsdDesc) * (size_t)rg.second, hipMemcpyHostToDevice, st));
+  for (const PsdRange& rg : ranges)
+    if (rg.wave()) CUADMM_HIP_TRY(hipMemcpyAsync(d_desc + rg.first, h_desc_pin + rg.first, sizeof(PsdDesc) * (size_t)rg.count, hipMemcpyHostToDevice, st));
   return CUADMM_OK;
 }
 
-// partial-sum slots in launch order: class 2 (when it runs the sign kernel), 3, 4 -- as PsdPlan::project hands them out
+// partial-sum slots: the members of the one-wavefront ranges, in launch order
 void PsdPlan::fused_slots(std::vector<int>& slot_of) const {
   slot_of.assign((size_t)nblk, -1);
   int slot = 0;
-  for (int c = 2; c <= 4; ++c) {
-    if ((c == 2 && !sign16) || (c == 4 && !wave4)) continue;
-    for (int q = 0; q < cls_count[c]; ++q) slot_of[h_ids[cls_begin[c] + q]] = slot++;
-  }
+  for (const PsdRange& r : ranges)
+    if (r.wave()) for (int q = 0; q < r.count; ++q) slot_of[h_ids[r.first + q]] = slot++;
 }
 
-// svec elements outside the fused blocks, ascending (the stand-alone vector kernels run over this list)
+void PsdPlan::rest_elements(std::vector<int>& rest) const {
+  std::vector<int> slot_of;
+  fused_slots(slot_of);
+  rest.clear();
+  for (int k = 0; k < nblk; ++k)
+    if (slot_of[k] < 0) for (long long i = h_off[k]; i < h_off[k + 1]; ++i) rest.push_back((int)i);
+}
+
+// the stand-alone vector kernels run over this list
 int PsdPlan::build_rest_index() {
   if (d_rest) { hipError_t e = hipFree(d_rest); (void)e; d_rest = nullptr; }
   std::vector<int> rest;
-  long long off = 0;
-  for (int k = 0; k < nblk; ++k) {
-    const long long len = blk_svec_len(h_blk[k]);
-    const int c = h_blk[k] > 0 && h_blk[k] < sign_min ? class_of(h_blk[k]) : -1;
-    if (!(c == 3 || (c == 4 && wave4) || (c == 2 && sign16)))
-      for (long long i = off; i < off + len; ++i) rest.push_back((int)i);
-    off += len;
-  }
+  rest_elements(rest);
   n_rest = (long long)rest.size();
   if (n_rest > 0) {
     CUADMM_HIP_TRY(hipMalloc(&d_rest, sizeof(int) * rest.size()));
@@ -608,17 +598,116 @@ int PsdPlan::build_rest_index() {
   return CUADMM_OK;
 }
 
+// one range of the table on `st`; a.ids / a.desc start at the range's first member
+static int launch_range(const PsdPlan& p, const PsdRange& r, const PsdArgs& a, hipStream_t st, const SignFuse* fz) {
+  switch (r.kind) {
+    case PsdKind::SignWave: {
+      SignFuse f;
+      if (fz) { f = *fz; f.full = r.full; fz = &f; }
+      const int occ = (fz && fz->iters > 1) ? r.occ_batch : r.occ;
+      switch (r.nt) {
+        case 1: return launch_sign_wave<1, 8>(a, 0, r.count, st, fz);
+        case 2: return occ == 3 ? launch_sign_wave<2, 3>(a, 0, r.count, st, fz) : launch_sign_wave<2, 4>(a, 0, r.count, st, fz);
+        case 3: return launch_sign_wave<3, 2>(a, 0, r.count, st, fz);
+        default: return launch_sign_wave<4, 1>(a, 0, r.count, st, fz);
+      }
+    }
+    case PsdKind::SignLds:
+      return r.nt == 4 ? launch_sign_lds<64>(a, 0, r.count, st, r.triple) : launch_sign_lds<48>(a, 0, r.count, st, r.triple);
+    case PsdKind::ChipEig: {
+      // blocks beyond one workgroup's LDS that need EIGENVALUES (the rank-limited projection; everything else of this size takes
+      // the matrix-sign path): one block at a time on the whole chip (eig_large.hip)
+      int rc = CUADMM_OK;
+      for (int q = 0; q < r.count && !rc; ++q) {
+        const int k = p.h_ids[r.first + q];
+        rc = eig_large_project(a.in + p.h_off[k], a.out + p.h_off[k], p.h_blk[k], a.eig_rank, p.d_fail, st, &p.big_ws);
+      }
+      return rc;
+    }
+    default: return launch_class<0>(r.cls, a, r.maxn, st);   // RegEig, WgEig
+  }
+}
+
+// Developer aids (psd_debug): a range launched with h.size() zeroed tick stamps behind a.dbg, waited for (the dumps serialise the
+// ranges) and the stamps downloaded
+static int launch_with_ticks(const PsdPlan& p, const PsdRange& r, PsdArgs a, hipStream_t st, const SignFuse* fz, std::vector<long long>& h) {
+  long long* d = nullptr;
+  CUADMM_HIP_TRY(hipMalloc(&d, sizeof(long long) * h.size()));
+  CUADMM_HIP_TRY(hipMemset(d, 0, sizeof(long long) * h.size()));
+  a.dbg = d;
+  int rc = launch_range(p, r, a, st, fz);
+  if (rc) return rc;
+  CUADMM_HIP_TRY(hipStreamSynchronize(st));
+  rc = staged_d2h(h.data(), d, sizeof(long long) * h.size(), st);
+  { hipError_t e = hipFree(d); (void)e; }
+  return rc;
+}
+
+// psd_debug = 1: phase ticks of the one-wavefront kernels, unfused
+static int dump_wave_ticks(const PsdPlan& p, const PsdRange& r, const PsdArgs& a, hipStream_t st) {
+  std::vector<long long> h((size_t)r.count * 10, 0);
+  int rc = launch_with_ticks(p, r, a, st, nullptr, h);
+  if (rc) return rc;
+  double ph[7] = {0, 0, 0, 0, 0, 0, 0};
+  for (int w = 0; w < r.count; ++w) for (int q = 0; q < 7; ++q) ph[q] += (double)h[(size_t)w * 10 + q];
+  const double nw = r.count;
+  fprintf(stderr, "[psd debug] class %d: %d blocks: ticks/block prologue %.0f (zero fill done at %.0f, first batch of loads back at %.0f, tile written at %.0f) "
+                  "iteration %.0f (%.1f steps, %.0f per step) epilogue %.0f\n",
+          r.cls, r.count, ph[0] / nw, ph[4] / nw, ph[5] / nw, ph[6] / nw, ph[1] / nw, ph[3] / nw, ph[1] / std::max(ph[3], 1.0), ph[2] / nw);
+  return CUADMM_OK;
+}
+
+// psd_debug = 2: phase ticks of the batched launches of 16 < n <= 32 at full occupancy
+static int dump_batch_ticks(const PsdPlan& p, const PsdRange& r, const PsdArgs& a, hipStream_t st, const SignFuse* fz) {
+  std::vector<long long> h((size_t)r.count * 16, 0);
+  int rc = launch_with_ticks(p, r, a, st, fz, h);
+  if (rc) return rc;
+  double ph[16] = {0};
+  for (int w = 0; w < r.count; ++w) for (int q = 0; q < 16; ++q) ph[q] += (double)h[(size_t)w * 16 + q];
+  for (double& x : ph) x /= (double)r.count;
+  const double ep0 = ph[0] + ph[1];   // stamps 4..9 are offsets from the start of the task; ph[0..2] are the phase lengths
+  fprintf(stderr, "[cu debug] %d blocks x %d iterations: ticks/task prologue %.0f [solve done %.0f, loads back %.0f, gather done %.0f] iteration %.0f (%.2f steps, %.0f per step) "
+                  "epilogue %.0f [Xb rebuilt +%.0f, P stored +%.0f, walk done +%.0f] total %.0f | outside the body: claim + flag wait %.0f, arguments + descriptor %.0f, "
+                  "body call %.0f, release + flag %.0f\n",
+          r.count, fz->iters, ph[0], ph[4], ph[5], ph[6], ph[1], ph[3], ph[1] / std::max(ph[3], 1.0), ph[2], ph[7] - ep0, ph[8] - ep0, ph[9] - ep0,
+          ph[0] + ph[1] + ph[2], ph[10], ph[11], ph[12], ph[13]);
+  double ck = 0, rt = 0;
+  const int ng = std::min(r.count, 256);
+  for (int w = 0; w < ng; ++w) { ck += (double)h[(size_t)w * 16 + 14]; rt += (double)h[(size_t)w * 16 + 15]; }
+  fprintf(stderr, "[cu debug] launch: %.3f ms, s_memtime runs at %.3f GHz\n", rt / ng * 1e-5, ck / std::max(rt, 1.0) * 0.1);
+  return CUADMM_OK;
+}
+
+// psd_debug = 1: phase cycles of the register eigensolver on 16 < n <= 32
+static int dump_reg_ticks(const PsdPlan& p, const PsdRange& r, const PsdArgs& a, hipStream_t st) {
+  const int nwg = (r.count + 1) / 2 + 4;
+  std::vector<long long> h((size_t)nwg * 8, 0);
+  int rc = launch_with_ticks(p, r, a, st, nullptr, h);
+  if (rc) return rc;
+  double ph[5] = {0, 0, 0, 0, 0}, its = 0;
+  for (int w = 0; w < nwg; ++w) {
+    for (int i = 0; i < 5; ++i) ph[i] += (double)(h[w * 8 + i + 1] - h[w * 8 + i]);
+    its += (double)h[w * 8 + 6];
+  }
+  // MFMA utilisation of the rebuild: 2 blocks x 3 upper tiles x 8 k-steps x 64 cycles per v_mfma_f64_16x16x4
+  fprintf(stderr, "[psd debug] %d waves: cycles/wave load %.0f tridiag %.0f ql %.0f handoff %.0f tail %.0f | mfma rebuild %.0f cycles/wave -> MFMA busy %.1f%%\n",
+          nwg, ph[0] / nwg, ph[1] / nwg, ph[2] / nwg, ph[3] / nwg, ph[4] / nwg, its / nwg, 100.0 * (2 * 3 * 8 * 64.0) / (its / nwg));
+  return CUADMM_OK;
+}
+
+// Xproj = Pi_+(Xb) over all blocks of the plan (device pointers, svec layout)
+// Size classes are independent: with `overlap` (engine-owned plans) every class and the sign path run on their own
+// stream between a fork and a join event on `st`, so small classes (a moment relaxation has a handful of blocks per
+// size) overlap instead of queueing behind each other.
 int PsdPlan::project(const double* Xb, double* Xproj, hipStream_t st, const SignFuse* fz) const {
   if (d_hint && !(fz && fz->rec) && (++n_project & 15) == 0) {   // closed blocks age their hints themselves (psd_sign_closed.h)
     hipLaunchKernelGGL(hint_decay_kernel, dim3((nblk + 255) / 256), dim3(256), 0, st, d_hint, nblk);
     CUADMM_HIP_TRY(hipGetLastError());
   }
-  const bool psd_debug = opt.debug != 0;
-  const bool no_overlap = !opt.overlap || psd_debug;
   if (fz && !fusable()) { set_error("psd: fused projection requested on a plan that cannot fuse"); return CUADMM_ERR_INVALID; }
-  int lanes = sign.empty() ? 0 : 1;
-  for (int c = 0; c < kNumPsdClasses; ++c) lanes += cls_count[c] > 0;
-  const bool fork = overlap && !no_overlap && st != nullptr && lanes > 1;
+  int lanes = sign.empty() ? 0 : 1, last_class = -1;
+  for (const PsdRange& r : ranges) { lanes += r.cls != last_class; last_class = r.cls; }
+  const bool fork = overlap && opt.overlap && opt.debug == 0 && st != nullptr && lanes > 1;
   if (fork && !ev_fork) {
     CUADMM_HIP_TRY(hipEventCreateWithFlags(&ev_fork, hipEventDisableTiming));
     for (int i = 0; i < kNumPsdClasses; ++i) {
@@ -628,160 +717,45 @@ int PsdPlan::project(const double* Xb, double* Xproj, hipStream_t st, const Sign
   }
   if (fork) CUADMM_HIP_TRY(hipEventRecord(ev_fork, st));
   hipStream_t main_st = st;
-  // 16 < n <= 32: option psd_n32 = 0 -> register eigensolver (psd_small_reg.h), default the one-wavefront sign kernel
-  // (0.256 vs 0.92 ms per 10 000 x 32 blocks on MI355X, 0.05 vs 0.35 ms latency for a single block)
-  const bool sign32 = opt.n32_sign != 0;
+  // beside a sign path (hundreds of microseconds; it keeps the main stream, it is the longest chain) the small classes (tens each)
+  // share ONE side stream, one after the other: one fork and one join instead of one per class (each costs ~10 us of idle queue),
+  // and none of them can land on the hardware queue of the main stream (streams are multiplexed onto four queues: the n = 28
+  // class of PlanarHand_N=1 ran in FRONT of the sign path)
   const bool one_side = fork && !sign.empty();
   bool side_forked = false;
-  int last_class = -1;
-  for (int c = 0; c < kNumPsdClasses; ++c) if (cls_count[c] > 0) last_class = c;
   // without a sign path the class of the LARGEST blocks (the longest chain: pendulum N = 80's 80 blocks of n = 55) stays on the caller's
   // stream: it starts right behind the kernel before it instead of behind a fork event, and the join waits for the short classes only
   const int main_class = (fork && sign.empty()) ? last_class : -1;
-  for (int cc = 0; cc < kNumPsdClasses; ++cc) {
-    // the class that stays on the caller's stream (the longest chain) is launched FIRST, the others in ascending order
-    const int c = main_class < 0 ? cc : (cc == 0 ? main_class : (cc <= main_class ? cc - 1 : cc));
-    if (cls_count[c] == 0) continue;
-    if (fork) {   // the sign path keeps the main stream (it is the longest chain)
-      // beside a sign path (hundreds of microseconds) the small classes (tens each) share ONE side stream, one after the other: one
-      // fork and one join instead of one per class (each costs ~10 us of idle queue), and none of them can land on the hardware queue
-      // of the main stream (streams are multiplexed onto four queues: the n = 28 class of PlanarHand_N=1 ran in FRONT of the sign path)
-      if (c == main_class) st = main_st;
-      else {
-        st = one_side ? aux[0] : aux[c];
-        if (!one_side || !side_forked) CUADMM_HIP_TRY(hipStreamWaitEvent(st, ev_fork, 0));
-        side_forked = true;
+  // the last range of a class on a side stream carries the class's join event (the shared side stream: the last class only)
+  auto joins = [&](const PsdRange* r) {
+    return fork && (r + 1 == ranges.end() || r[1].cls != r->cls) && r->cls != main_class && (!one_side || r->cls == last_class);
+  };
+  for (int pass = main_class < 0 ? 1 : 0; pass < 2; ++pass)   // the class on the caller's stream is launched FIRST, the others in table order
+    for (const PsdRange* r = ranges.begin(); r != ranges.end(); ++r) {
+      const int c = r->cls;
+      if ((c == main_class) != (pass == 0)) continue;
+      if (fork) {
+        if (c == main_class) st = main_st;
+        else {
+          st = one_side ? aux[0] : aux[c];
+          const bool head = r == ranges.begin() || r[-1].cls != c;
+          if (head && (!one_side || !side_forked)) CUADMM_HIP_TRY(hipStreamWaitEvent(st, ev_fork, 0));
+          side_forked = true;
+        }
       }
+      PsdArgs a{};
+      a.in = Xb; a.out = Xproj; a.Wout = nullptr; a.info = d_fail;
+      a.ids = d_ids + r->first; a.boff = d_off; a.bn = d_n; a.desc = d_desc + r->first;
+      a.count = r->count; a.n_uniform = 0; a.steps = d_steps;
+      a.eig_rank = (eig_rank > 0 && rank_active) ? eig_rank : 0; a.hint = d_hint;
+      int rc;
+      if (opt.debug == 1 && r->wave() && !fz) rc = dump_wave_ticks(*this, *r, a, st);
+      else if (opt.debug >= 2 && r->wave() && c == 3 && fz && fz->iters > 1) rc = dump_batch_ticks(*this, *r, a, st, fz);
+      else if (opt.debug == 1 && r->kind == PsdKind::RegEig && c == 3) rc = dump_reg_ticks(*this, *r, a, st);
+      else rc = launch_range(*this, *r, a, st, fz);
+      if (rc) return rc;
+      if (joins(r)) CUADMM_HIP_TRY(hipEventRecord(ev_done[c], st));
     }
-    PsdArgs a{};
-    a.in = Xb; a.out = Xproj; a.Wout = nullptr; a.info = d_fail;
-    a.ids = d_ids + cls_begin[c]; a.boff = d_off; a.bn = d_n; a.desc = d_desc + cls_begin[c];
-    a.count = cls_count[c]; a.n_uniform = 0; a.steps = d_steps;
-    a.eig_rank = (eig_rank > 0 && rank_active) ? eig_rank : 0;
-    a.hint = d_hint;
-    long long* dbg = nullptr;
-    const int nwg = (cls_count[c] + 1) / 2 + 4;
-    if (opt.debug == 1 && eig_rank == 0 && !fz && ((c == 2 && sign16) || (c == 3 && sign32) || (c == 4 && wave4))) {
-      // phase ticks of the one-wavefront kernels (CUADMM_PSD_DEBUG=1 / option psd_debug), unfused
-      std::vector<long long> h((size_t)cls_count[c] * 10, 0);
-      long long* d = nullptr;
-      CUADMM_HIP_TRY(hipMalloc(&d, sizeof(long long) * h.size()));
-      CUADMM_HIP_TRY(hipMemset(d, 0, sizeof(long long) * h.size()));
-      a.dbg = d;
-      int rc2 = CUADMM_OK;
-      if (c == 2) rc2 = launch_sign_wave<1, 8>(a, 0, cls_count[c], st);
-      else if (c == 3) rc2 = launch_sign_wave<2, 4>(a, 0, cls_count[c], st);
-      else {
-        rc2 = launch_sign_wave<4, 1>(a, 0, cls4_big, st);
-        if (!rc2) rc2 = launch_sign_wave<3, 2>(a, cls4_big, cls_count[c] - cls4_big, st);
-      }
-      if (rc2) return rc2;
-      CUADMM_HIP_TRY(hipStreamSynchronize(st));
-      { int rc_ = staged_d2h(h.data(), d, sizeof(long long) * h.size(), st); if (rc_) return rc_; }
-      double ph[7] = {0, 0, 0, 0, 0, 0, 0};
-      for (int w = 0; w < cls_count[c]; ++w) for (int q = 0; q < 7; ++q) ph[q] += (double)h[(size_t)w * 10 + q];
-      const double nw = cls_count[c];
-      fprintf(stderr, "[psd debug] class %d: %d blocks: ticks/block prologue %.0f (zero fill done at %.0f, first batch of loads back at %.0f, tile written at %.0f) "
-                      "iteration %.0f (%.1f steps, %.0f per step) epilogue %.0f\n",
-              c, cls_count[c], ph[0] / nw, ph[4] / nw, ph[5] / nw, ph[6] / nw, ph[1] / nw, ph[3] / nw, ph[1] / std::max(ph[3], 1.0), ph[2] / nw);
-      { hipError_t e = hipFree(d); (void)e; }
-      if (fork && c != main_class && (!one_side || c == last_class)) CUADMM_HIP_TRY(hipEventRecord(ev_done[c], st));
-      continue;
-    }
-    if (c == 3 && fz && fz->iters > 1 && opt.debug >= 2) {   // developer aid (psd_debug = 2): phase ticks of the batched launches at full occupancy
-      std::vector<long long> h((size_t)cls_count[c] * 16, 0);
-      long long* d = nullptr;
-      CUADMM_HIP_TRY(hipMalloc(&d, sizeof(long long) * h.size()));
-      CUADMM_HIP_TRY(hipMemset(d, 0, sizeof(long long) * h.size()));
-      a.dbg = d;
-      SignFuse f2 = *fz;
-      f2.full = range_full[1];
-      int rc2 = launch_sign_wave32(a, 0, cls_count[c], st, opt, &f2);
-      if (rc2) return rc2;
-      CUADMM_HIP_TRY(hipStreamSynchronize(st));
-      { int rc_ = staged_d2h(h.data(), d, sizeof(long long) * h.size(), st); if (rc_) return rc_; }
-      double ph[16] = {0};
-      for (int w = 0; w < cls_count[c]; ++w) for (int q = 0; q < 16; ++q) ph[q] += (double)h[(size_t)w * 16 + q];
-      const double nw = cls_count[c];
-      for (double& x : ph) x /= nw;
-      // stamps 4..9 are offsets from the start of the task; ph[0..2] are the phase lengths
-      const double it0 = ph[0], ep0 = ph[0] + ph[1];
-      fprintf(stderr, "[cu debug] %d blocks x %d iterations: ticks/task prologue %.0f [solve done %.0f, loads back %.0f, gather done %.0f] iteration %.0f (%.2f steps, %.0f per step) "
-                      "epilogue %.0f [Xb rebuilt +%.0f, P stored +%.0f, walk done +%.0f] total %.0f | outside the body: claim + flag wait %.0f, arguments + descriptor %.0f, "
-                      "body call %.0f, release + flag %.0f\n",
-              cls_count[c], fz->iters, ph[0], ph[4], ph[5], ph[6], ph[1], ph[3], ph[1] / std::max(ph[3], 1.0), ph[2], ph[7] - ep0, ph[8] - ep0, ph[9] - ep0,
-              ph[0] + ph[1] + ph[2], ph[10], ph[11], ph[12], ph[13]);
-      {
-        double ck = 0, rt = 0;
-        const int ng = std::min(cls_count[c], 256);
-        for (int w = 0; w < ng; ++w) { ck += (double)h[(size_t)w * 16 + 14]; rt += (double)h[(size_t)w * 16 + 15]; }
-        fprintf(stderr, "[cu debug] launch: %.3f ms, s_memtime runs at %.3f GHz\n", rt / ng * 1e-5, ck / std::max(rt, 1.0) * 0.1);
-      }
-      (void)it0;
-      { hipError_t e = hipFree(d); (void)e; }
-      if (fork && c != main_class && (!one_side || c == last_class)) CUADMM_HIP_TRY(hipEventRecord(ev_done[c], st));
-      continue;
-    }
-    if (c == 3 && opt.debug == 1 && !sign32) {   // phase cycles of the register eigensolver
-      CUADMM_HIP_TRY(hipMalloc(&dbg, sizeof(long long) * 8 * (size_t)nwg));
-      CUADMM_HIP_TRY(hipMemset(dbg, 0, sizeof(long long) * 8 * (size_t)nwg));
-      a.dbg = dbg;
-    }
-    int rc;
-    if (c == 4 && opt.mid != 1 && eig_rank == 0) {   // members are sorted by size, largest first: [0, cls4_big) have n > 48
-      // one wavefront per block (psd_sign_wave.h) from psd_wave4_min blocks on, else one workgroup per block (latency); option
-      // psd_mid = 2 forces the one-workgroup kernels, 1 the register eigensolver
-      if (wave4) {
-        SignFuse f4, f3;
-        if (fz) { f4 = *fz; f3 = *fz; f4.full = range_full[3]; f3.full = range_full[2]; }
-        rc = launch_sign_wave<4, 1>(a, 0, cls4_big, st, fz ? &f4 : nullptr);
-        if (!rc) rc = launch_sign_wave<3, 2>(a, cls4_big, cls_count[c] - cls4_big, st, fz ? &f3 : nullptr);
-      } else {
-        const bool triple = opt.lds_triple != 0 && cls_count[c] <= 256;
-        rc = launch_sign_lds<64>(a, 0, cls4_big, st, triple);
-        if (!rc) rc = launch_sign_lds<48>(a, cls4_big, cls_count[c] - cls4_big, st, triple);
-      }
-    } else if (c == 3 && sign32 && eig_rank == 0) {
-      SignFuse f2;
-      if (fz) { f2 = *fz; f2.full = range_full[1]; }
-      rc = launch_sign_wave32(a, 0, cls_count[c], st, opt, fz ? &f2 : nullptr);
-    } else if (c == 2 && sign16 && eig_rank == 0 && opt.debug != 1) {
-      // 9 <= n <= 16: the same iteration on ONE 16 x 16 sub-tile, eight wavefronts per SIMD (the register eigensolver needs
-      // ~20 us of dependent rotations per block; here a block is 8 MFMAs per step)
-      SignFuse f1;
-      if (fz) { f1 = *fz; f1.full = range_full[0]; }
-      rc = launch_sign_wave<1, 8>(a, 0, cls_count[c], st, fz ? &f1 : nullptr);
-    } else if (c == 6) {
-      // blocks beyond one workgroup's LDS that need EIGENVALUES (the rank-limited projection; everything else of this size takes
-      // the matrix-sign path): one block at a time on the whole chip (eig_large.hip)
-      rc = CUADMM_OK;
-      for (int q = 0; q < cls_count[c] && !rc; ++q) {
-        const int k = h_ids[cls_begin[c] + q];
-        rc = eig_large_project(Xb + h_off[k], Xproj + h_off[k], h_blk[k], a.eig_rank, d_fail, st, &big_ws);
-      }
-    } else {
-      rc = launch_class<0>(c, a, cls_maxn[c], st);
-    }
-    if (rc) return rc;
-    if (dbg) {
-      std::vector<long long> h((size_t)nwg * 8);
-      CUADMM_HIP_TRY(hipStreamSynchronize(st));
-      { int rc_ = staged_d2h(h.data(), dbg, sizeof(long long) * h.size(), st); if (rc_) return rc_; }
-      double ph[6] = {0, 0, 0, 0, 0, 0}, its = 0, slots = 0;
-      long long tmin = h[0], tmax = 0;
-      for (int w = 0; w < nwg; ++w) {
-        for (int i = 0; i < 5; ++i) ph[i] += (double)(h[w * 8 + i + 1] - h[w * 8 + i]);
-        tmin = std::min(tmin, h[w * 8]); tmax = std::max(tmax, h[w * 8 + 5]);
-        its += (double)h[w * 8 + 6]; slots += (double)h[w * 8 + 7];
-      }
-      // MFMA utilisation of the rebuild: 2 blocks x 3 upper tiles x 8 k-steps x 64 cycles per v_mfma_f64_16x16x4
-      fprintf(stderr, "[psd debug] %d waves: cycles/wave load %.0f tridiag %.0f ql %.0f handoff %.0f tail %.0f | mfma rebuild %.0f cycles/wave -> MFMA busy %.1f%%\n",
-              nwg, ph[0] / nwg, ph[1] / nwg, ph[2] / nwg, ph[3] / nwg, ph[4] / nwg, its / nwg, 100.0 * (2 * 3 * 8 * 64.0) / (its / nwg));
-      (void)slots; (void)tmin; (void)tmax;
-      { hipError_t e = hipFree(dbg); (void)e; }
-    }
-    if (fork && c != main_class && (!one_side || c == last_class)) CUADMM_HIP_TRY(hipEventRecord(ev_done[c], st));
-  }
   st = main_st;
   if (n_free > 0 && Xb != Xproj) {   // unconstrained blocks: Xproj = Xb on their svec ranges
     hipLaunchKernelGGL(copy_ranges_kernel, dim3(n_free), dim3(256), 0, st, Xb, Xproj, d_free_off, d_free_len);
@@ -791,9 +765,8 @@ int PsdPlan::project(const double* Xb, double* Xproj, hipStream_t st, const Sign
     int rc = sign.project(Xb, Xproj, d_off, d_n, d_fail, st);
     if (rc) return rc;
   }
-  if (fork)
-    for (int c = 0; c < kNumPsdClasses; ++c)
-      if (cls_count[c] > 0 && c != main_class && (!one_side || c == last_class)) CUADMM_HIP_TRY(hipStreamWaitEvent(st, ev_done[c], 0));
+  for (const PsdRange* r = ranges.begin(); r != ranges.end(); ++r)
+    if (joins(r)) CUADMM_HIP_TRY(hipStreamWaitEvent(st, ev_done[r->cls], 0));
   return CUADMM_OK;
 }
 

@@ -1,6 +1,9 @@
 // Switches of the projection planner and its kernels.  ONE INSTANCE PER PLAN (PsdPlan::opt): two solvers in a process can
 // choose differently, and every variant is reachable by a test through cuadmm_set_option (keys "psd_*").  Nothing here is
 // cached process-wide; from_env() gives the defaults and reads the developer-aid variables.
+// PsdPlan::build() resolves every option that selects a kernel or an instantiation into the plan's launch table (psd_plan.h) and
+// into SignPsd::opt: set on a built plan, such an option is kept for the plans built afterwards and changes nothing in this one.
+// Only psd_overlap and psd_debug are read at every projection.
 #pragma once
 #include <cstdlib>
 #include <cstring>

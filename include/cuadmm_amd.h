@@ -640,6 +640,15 @@ int cuadmm_psd_plan_set_hint(cuadmm_psd_plan* plan, int* hint_dev, int hint_max_
 int cuadmm_psd_plan_reorder(cuadmm_psd_plan* plan, const int* steps_host, int async, int own_stream);
 int cuadmm_psd_plan_project_ordered(cuadmm_psd_plan* plan, const double* Xb, double* Xproj, double* snap_dev /* may be NULL */, int* steps_dev /* may be NULL */,
                                     int own_stream, int* fails_out /* may be NULL */);
+/* Test hook, host only (no device is touched): the launch ranges a plan of these blocks builds under the default options changed by
+ * opt_keys[n_opts] = opt_vals[n_opts] ("psd_*").  ranges_out: 10 ints per range, at most 8 ranges, in launch order: size class,
+ * first, count (members of ids_out), kind (0 register eigensolver, 1 workgroup eigensolver, 2 whole-chip eigensolver, 3 one-wavefront
+ * sign, 4 one-workgroup sign), tiles of 16 per side, wavefronts per SIMD of single / batched launches, full, triple, largest member.
+ * ids_out[mat_num]: the members (block ids); slot_out[mat_num]: partial-sum slot of the fused launches per block, -1: not fused;
+ * rest_out[svec length]: svec elements outside the fused blocks.  summary_out[6]: ranges, members, rest elements, fusable,
+ * fused blocks, first size on the batched-GEMM path. */
+int cuadmm_psd_plan_ranges(const int* blk_host, int mat_num, int eig_rank, int tiny_sign, const char* const* opt_keys, const double* opt_vals,
+                           int n_opts, int* ranges_out, int* ids_out, int* slot_out, int* rest_out, int* summary_out);
 /* General form: blk[k] < 0 is an UNCONSTRAINED block of -blk[k] variables (blk.txt type 'u', reference README.md:55-64),
  * copied through; eig_rank > 0 keeps only the eig_rank largest eigenvalues of every PSD block: V diag(max(W,0) * mask) V^T with
  * the mask of get_eig_rank_mask.cu:13-37 (dense_scalar.cu:51-57) -- computed through the eigensolver kernels. */

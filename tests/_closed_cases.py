@@ -3,7 +3,7 @@
 make_synthetic gives every block the same number of rows and draws every row's slots uniformly, so a block's record (ClosedRec,
 psd_fuse.h) is only ever filled one way: one scatter round (two on a rare collision), off-diagonal slots, rows of equal length.
 build(blk, structure, seed) places the rows so that the record's other shapes occur in every block, and the block lists below
-hold classes made only of 16s, 32s, 48s or 64s, which is what selects the FULL instantiations of the kernels (PsdPlan::range_full).
+hold classes made only of 16s, 32s, 48s or 64s, which is what selects the FULL instantiations of the kernels (PsdRange::full).
 
 Everything but the placement follows make_synthetic: slot t of a block is (column ii[t], row jj[t]) of np.tril_indices(n) (slot 0
 is (0,0), slot len - 1 is (n-1,n-1), the diagonal slot of index i is i (i + 3) / 2), the arrays are the CSC of A^T sorted by

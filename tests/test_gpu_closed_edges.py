@@ -1,5 +1,5 @@
 """The closed-block iteration (psd_sign_closed.h) on the hand-placed problems of tests/_closed_cases.py: the FULL instantiations
-for n = 16, 48 and 64 (a class made only of blocks that fill their tile, PsdPlan::range_full) and the shapes of a block's record
+for n = 16, 48 and 64 (a class made only of blocks that fill their tile, PsdRange::full) and the shapes of a block's record
 that make_synthetic never produces -- eight scatter rounds, nonzeros on the first and the last (diagonal) slot, blocks with
 different numbers of rows or none, rows of length 1 beside one of 57, eight rows and 64 nonzeros together.
 
