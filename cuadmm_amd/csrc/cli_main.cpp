@@ -20,6 +20,9 @@
 //   missing file: that vector is zero) is printed and, with --json, written as the sidecar's "kkt"
 //   --lambda-min[=T]: behind every solve, certified lower bounds on lambda_min of the blocks of X, S and C - A'y (cuadmm_lambda_min with T
 //   bisection steps, default 12), one line each, and "lambda_min" in the sidecar
+//   --lowrank=TOL[,RMAX]: behind every solve, the numerical rank of every block of X and of S by pivoted Cholesky (cuadmm_lowrank with the
+//   relative tolerance TOL and at most RMAX columns per block, default the largest block size), one line each, and "lowrank" in the sidecar
+//   --lowrank-out=DIR/ (with --lowrank): the factors, DIR/L_X_<k>.txt and DIR/L_S_<k>.txt per PSD block k, n_k r_k numbers column by column
 //   --json=<file>: a sidecar with the run's figures (iterations, residuals, iters/s, per-phase milliseconds, the projection's
 //   nominal TFLOP/s = 10.67 sum n^3 per projection and the vector kernels' algorithmic GB/s: SURVEY.md 8d); switches the
 //   engine's per-phase HIP-event timers on (option "profile").  Nothing is written unless asked for: the reference writes X_opt.txt only.
@@ -32,6 +35,7 @@
 //   <dir2/>X_opt.txt.
 #include <dirent.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -85,6 +89,28 @@ static void write_lambda_min(FILE* f, int steps, const double (*lm)[8]) {
   }
   fprintf(f, "}");
 }
+// --lowrank: what cuadmm_lowrank returned for X (0) and S (1)
+struct LowRankReport {
+  double tol = 0;
+  int rmax = 0;
+  double o[2][8] = {{0}};
+  std::vector<double> pb[2], L[2];
+};
+// "lowrank": {"tol": .., "rmax": .., "X": {...}, "S": {...}} with the eight numbers of cuadmm_lowrank each and "rank", "flag" per block
+static void write_lowrank(FILE* f, const LowRankReport& r) {
+  fprintf(f, " \"lowrank\": {\"tol\": %.17g, \"rmax\": %d", r.tol, r.rmax);
+  for (int w = 0; w < 2; ++w) {
+    const double* o = r.o[w];
+    fprintf(f, ", \"%s\": {\"rank_sum\": %.0f, \"rank_max\": %.0f, \"block\": %.0f, \"resid_sum\": ", lm_names[w], o[0], o[1], o[2]);
+    if (std::isfinite(o[3])) fprintf(f, "%.17g", o[3]); else fprintf(f, "null");
+    fprintf(f, ", \"dneg_min\": %.17g, \"capped\": %.0f, \"ms\": %.17g, \"bytes\": %.0f, \"rank\": [", o[4], o[5], o[6], o[7]);
+    for (size_t b = 0; b < r.pb[w].size() / 6; ++b) fprintf(f, "%s%.0f", b ? ", " : "", r.pb[w][6 * b]);
+    fprintf(f, "], \"flag\": [");
+    for (size_t b = 0; b < r.pb[w].size() / 6; ++b) fprintf(f, "%s%.0f", b ? ", " : "", r.pb[w][6 * b + 4]);
+    fprintf(f, "]}");
+  }
+  fprintf(f, "}");
+}
 // <dir/>name.txt, one number per line (cuadmm_write_dense_txt); a missing file: zeros
 static bool read_point_vec(const std::string& fn, std::vector<double>& out, size_t n) {
   out.assign(n, 0.0);
@@ -102,7 +128,7 @@ static bool read_point_vec(const std::string& fn, std::vector<double>& out, size
 // --json=<file>: one object; every number printed with %.17g
 static bool write_sidecar(const std::string& path, const std::string& prefix, cuadmm_solver* solver, const cuadmm_problem_view& v, bool have_bounds,
                           const double* kkt = nullptr, const std::vector<double>& kkt_blocks = std::vector<double>(), int lm_steps = 0,
-                          const double (*lm)[8] = nullptr) {
+                          const double (*lm)[8] = nullptr, const LowRankReport* lr = nullptr) {
   FILE* f = fopen(path.c_str(), "w");
   if (!f) return false;
   const int iters = cuadmm_get_info_iter_num(solver);
@@ -142,6 +168,7 @@ static bool write_sidecar(const std::string& path, const std::string& prefix, cu
   }
   if (kkt) { write_kkt(f, kkt, kkt_blocks); fprintf(f, ",\n"); }
   if (lm) { write_lambda_min(f, lm_steps, lm); fprintf(f, ",\n"); }
+  if (lr) { write_lowrank(f, *lr); fprintf(f, ",\n"); }
   double acc[8] = {0};
   cuadmm_get_accel_info(solver, acc);
   if (acc[0] > 0)
@@ -182,7 +209,9 @@ int main(int argc, char* argv[]) {
          sig = 1e0, device = 0, accel = 0, infeas = 0, infeas_tol = -1, gap = 0, gap_tol = -1;
   bool quiet = false, kkt = false;
   int lm_steps = 0;      // --lambda-min: 0 = off
-  std::string json_path, bounds_arg, kkt_point;
+  LowRankReport lr;      // --lowrank: rmax = 0 = off
+  bool lr_on = false;
+  std::string json_path, bounds_arg, kkt_point, lr_out;
   std::vector<std::string> then_dirs;
   std::vector<char> then_is_A;
   for (int i = 2; i < argc; ++i) {
@@ -204,10 +233,24 @@ int main(int argc, char* argv[]) {
       if (lm_steps < 1 || lm_steps > 40) { std::cerr << "--lambda-min: 1 to 40 bisection steps" << std::endl; return 1; }
       continue;
     }
+    if (strncmp(argv[i], "--lowrank=", 10) == 0) {
+      char* end = nullptr;
+      lr.tol = strtod(argv[i] + 10, &end);
+      lr.rmax = 0;      // 0: the largest block size, known once the problem is read
+      if (end && *end == ',') lr.rmax = atoi(end + 1);
+      if (end == argv[i] + 10 || !(lr.tol >= 0 && lr.tol < 1) || (*end == ',' && lr.rmax < 1) || (*end != ',' && *end != 0)) {
+        std::cerr << "--lowrank=TOL[,RMAX]: 0 <= TOL < 1, RMAX >= 1" << std::endl;
+        return 1;
+      }
+      lr_on = true;
+      continue;
+    }
+    if (strncmp(argv[i], "--lowrank-out=", 14) == 0) { lr_out = argv[i] + 14; continue; }
     std::cerr << "unknown option " << argv[i] << std::endl;
     return 1;
   }
 
+  if (!lr_out.empty() && !lr_on) { std::cerr << "--lowrank-out needs --lowrank=TOL[,RMAX]" << std::endl; return 1; }
   for (size_t k = 0; k < then_dirs.size(); ++k) {   // before any work: a stage that cannot be read must not cost the stages before it
     const std::string& d = then_dirs[k];
     DIR* dp = d.empty() ? nullptr : opendir(d.c_str());
@@ -308,10 +351,39 @@ int main(int argc, char* argv[]) {
     }
     return true;
   };
+  // --lowrank: ranks (and, with --lowrank-out, factors) at the point a solve returns, taken before anything reads the iterate
+  auto lr_report = [&]() {
+    if (!lr_on) return false;
+    if (lr.rmax == 0)
+      for (int k = 0; k < v.mat_num; ++k) lr.rmax = std::max(lr.rmax, std::max(v.blk_vals[k], 1));
+    long long count = 0;
+    if (cuadmm_lowrank_size(solver, lr.rmax, &count) != CUADMM_OK) { std::cerr << cuadmm_last_error() << std::endl; return false; }
+    for (int w = 0; w < 2; ++w) {
+      lr.pb[w].assign(6 * (size_t)v.mat_num, 0.0);
+      if (!lr_out.empty()) lr.L[w].assign((size_t)count + 1, 0.0);
+      if (cuadmm_lowrank(solver, w, lr.tol, lr.rmax, lr.o[w], lr.pb[w].data(), lr_out.empty() ? nullptr : lr.L[w].data(), nullptr) != CUADMM_OK) {
+        std::cerr << cuadmm_last_error() << std::endl;
+        return false;
+      }
+      printf(" rank(%s): sum %.0f, max %.0f (block %.0f), residual trace %.3e, min residual diagonal %.3e, %.0f stopped at %d columns, %.3f ms\n", lm_names[w],
+             lr.o[w][0], lr.o[w][1], lr.o[w][2], lr.o[w][3], lr.o[w][4], lr.o[w][5], lr.rmax, lr.o[w][6]);
+      for (int k = 0; k < v.mat_num && !lr_out.empty(); ++k) {
+        const double* q = lr.pb[w].data() + 6 * (size_t)k;
+        if (v.blk_vals[k] <= 0) continue;
+        const std::string fn = lr_out + "L_" + lm_names[w] + "_" + std::to_string(k) + ".txt";
+        if (cuadmm_write_dense_txt(fn.c_str(), lr.L[w].data() + (size_t)q[5], (int64_t)v.blk_vals[k] * (int64_t)q[0]) != CUADMM_OK) {
+          std::cerr << cuadmm_last_error() << std::endl;
+          return false;
+        }
+      }
+    }
+    return true;
+  };
   rc = cuadmm_solve(solver, (int)max_iter, stop_tol, (int)threshold, (int)stage1, (int)stage2, (int)switch_admm, sigscale, 1);
   if (rc != CUADMM_OK) std::cerr << cuadmm_last_error() << std::endl;
   bool have_kkt = kkt_report();
   bool have_lm = lm_report();
+  bool have_lr = lr_report();
 
   if (accel != 0) {
     double acc[8] = {0};
@@ -320,7 +392,7 @@ int main(int argc, char* argv[]) {
   }
   std::vector<double> X((size_t)v.vec_len);
   if (cuadmm_get_X(solver, X.data()) == CUADMM_OK) cuadmm_write_dense_txt((prefix + "X_opt.txt").c_str(), X.data(), v.vec_len);
-  if (!json_path.empty() && !write_sidecar(json_path, prefix, solver, v, !bounds_arg.empty(), have_kkt ? kk : nullptr, kkb, lm_steps, have_lm ? lm : nullptr)) std::cerr << "cannot write " << json_path << std::endl;
+  if (!json_path.empty() && !write_sidecar(json_path, prefix, solver, v, !bounds_arg.empty(), have_kkt ? kk : nullptr, kkb, lm_steps, have_lm ? lm : nullptr, have_lr ? &lr : nullptr)) std::cerr << "cannot write " << json_path << std::endl;
   for (size_t k = 0; k < then_dirs.size() && rc == CUADMM_OK; ++k) {
     const std::string& d = then_dirs[k];
     std::vector<int> bi, ci;
@@ -346,9 +418,10 @@ int main(int argc, char* argv[]) {
     if (rc != CUADMM_OK) { std::cerr << cuadmm_last_error() << std::endl; break; }
     have_kkt = kkt_report();
     have_lm = lm_report();
+    have_lr = lr_report();
     if (cuadmm_get_X(solver, X.data()) == CUADMM_OK) cuadmm_write_dense_txt((d + "X_opt.txt").c_str(), X.data(), v.vec_len);
     const std::string side = json_path + "." + std::to_string(k + 1);
-    if (!json_path.empty() && !write_sidecar(side, d, solver, v, !bounds_arg.empty(), have_kkt ? kk : nullptr, kkb, lm_steps, have_lm ? lm : nullptr)) std::cerr << "cannot write " << side << std::endl;
+    if (!json_path.empty() && !write_sidecar(side, d, solver, v, !bounds_arg.empty(), have_kkt ? kk : nullptr, kkb, lm_steps, have_lm ? lm : nullptr, have_lr ? &lr : nullptr)) std::cerr << "cannot write " << side << std::endl;
   }
   cuadmm_destroy(solver);
   cuadmm_problem_free(prob);

@@ -35,6 +35,7 @@
 #include "lower_bound.h"
 #include "evaluate.h"
 #include "lambda_min.h"
+#include "lowrank.h"
 
 using namespace cuadmm;
 
@@ -545,6 +546,78 @@ struct cuadmm_solver {
   } lm;
   int lm_prepare(int which);
   int lm_run(int which, int steps, double out8[8], double* per_block);
+
+  // Rank and low-rank factor per block (cuadmm_lowrank, cuadmm_op_block_lowrank; lowrank.h, DESIGN.md "Low-rank factors"): the size
+  // classes' block lists, the offsets of the blocks' factors and pivots for the rmax of the last call, the factor, pivot and result
+  // buffers (they grow with rmax and are kept), a pair of events.  The offsets and sizes per block are the task lists' (btasks).  Nothing
+  // here is read by the iteration.
+  struct LrPlan {
+    LrClass cls[kLrClasses];
+    DevBuf<int> list[kLrClasses], piv;
+    DevBuf<long long> loff_d, poff_d;
+    DevBuf<double> Lbuf, out;
+    std::vector<long long> loff, poff;      // of rmax_now, nb + 1 entries each
+    int nb = 0, rmax_now = 0;
+    hipEvent_t ev[2] = {};
+    long long calls = 0;
+    int prepare(const int* blk_h, int nblk, int rmax) {
+      if (out.p && rmax == rmax_now) return CUADMM_OK;
+      int rc = lr_build_classes(nblk, blk_h, rmax, cls, &loff, &poff);
+      if (rc) return rc;
+      const bool first = !out.p;
+      if (first) {
+        for (int q = 0; q < kLrClasses; ++q)
+          if ((rc = list[q].from(cls[q].blocks))) return rc;
+        if ((rc = loff_d.alloc((size_t)nblk + 1)) || (rc = poff_d.alloc((size_t)nblk + 1))) return rc;
+        for (auto& e : ev) CUADMM_HIP_TRY(hipEventCreate(&e));
+      }
+      rmax_now = 0;                           // (until the offsets on the device are this rmax's)
+      if ((rc = loff_d.upload(loff.data(), loff.size())) || (rc = poff_d.upload(poff.data(), poff.size()))) return rc;
+      if (Lbuf.n < (size_t)loff.back() + 1 && (rc = Lbuf.alloc((size_t)loff.back() + 1))) return rc;      // (+ 1: never empty)
+      if (piv.n < (size_t)poff.back() + 1 && (rc = piv.alloc((size_t)poff.back() + 1))) return rc;
+      nb = nblk;
+      rmax_now = rmax;
+      return first ? out.alloc(kLrOut * (size_t)nblk) : CUADMM_OK;      // last: marks the set as complete
+    }
+    // out, Lbuf, piv (device) <- the kernel's results on sign * v; one launch per class that has blocks
+    int run(const double* v, double sign, const long long* off_d, const int* blk_d, double tol, hipStream_t st) {
+      int rc;
+      for (int q = 0; q < kLrClasses; ++q)
+        if ((rc = launch_lowrank(q, (int)cls[q].blocks.size(), cls[q].nmax, list[q].p, v, sign, off_d, blk_d, tol, rmax_now, loff_d.p, poff_d.p, Lbuf.p, piv.p,
+                                 out.p, st)))
+          return rc;
+      return CUADMM_OK;
+    }
+    // The results behind a drained stream, on the host and in the units `unit` times the vector's: per_block (kLrOut nb, not null); L_out
+    // (may be null): loff.back() doubles; piv_out (may be null): as many ints, block k's min(n_k, rmax) pivots at loff[k], -1 elsewhere.
+    int fetch(double unit, double* per_block, double* L_out, int* piv_out) {
+      int rc;
+      if (nb > 0 && (rc = staged_d2h(per_block, out.p, sizeof(double) * kLrOut * (size_t)nb))) return rc;
+      for (int k = 0; k < nb; ++k)
+        for (int q = 1; q <= 3; ++q) per_block[kLrOut * (size_t)k + q] *= unit;
+      const size_t count = (size_t)loff.back();
+      if (L_out && count > 0) {
+        if ((rc = staged_d2h(L_out, Lbuf.p, sizeof(double) * count))) return rc;
+        const double root = std::sqrt(unit);
+        for (size_t e = 0; unit != 1.0 && e < count; ++e) L_out[e] *= root;
+      }
+      if (piv_out && count > 0) {
+        std::vector<int> h((size_t)poff.back() + 1);
+        if ((rc = staged_d2h(h.data(), piv.p, sizeof(int) * (size_t)poff.back()))) return rc;
+        std::fill(piv_out, piv_out + count, -1);
+        for (int k = 0; k < nb; ++k) std::copy(h.begin() + poff[k], h.begin() + poff[k + 1], piv_out + loff[k]);
+      }
+      return CUADMM_OK;
+    }
+    double bytes() const {
+      double b = 8.0 * (double)(loff_d.n + poff_d.n + Lbuf.n + out.n) + 4.0 * (double)piv.n;
+      for (const auto& l : list) b += 4.0 * (double)l.n;
+      return b;
+    }
+    ~LrPlan() { for (auto& e : ev) if (e) { hipError_t r = hipEventDestroy(e); (void)r; } }
+  } lr;
+  int lr_prepare(int rmax);
+  int lr_run(int which, double tol, double out8[8], double* per_block, double* L_out, int* piv_out);
 
   // profiling
   hipEvent_t ev0[K_NUM][2] = {}, ev1[K_NUM][2] = {};
@@ -2859,6 +2932,51 @@ int cuadmm_solver::lm_run(int which, int steps, double o[8], double* per_block) 
   return CUADMM_OK;
 }
 
+// ------------------------------------------------------------------------------------------
+// Rank and low-rank factor per block (cuadmm_lowrank): DESIGN.md, "Low-rank factors"
+// ------------------------------------------------------------------------------------------
+// lists, events and buffers on first use; offsets and larger buffers when rmax changes
+int cuadmm_solver::lr_prepare(int rmax) {
+  int rc;
+  const int nb = (int)blk_local.size();
+  if (!btasks.built && (rc = btasks.build(blk_local.data(), nb, nullptr))) return rc;
+  return lr.prepare(blk_local.data(), nb, rmax);
+}
+
+// which = 0: X, 1: S, read where they lie (scaled behind a solve, else in the caller's units).  The kernel's numbers are in the units of the
+// vector it read: M = unit M_s, so L = sqrt(unit) L_s and the residual diagonal, its sums and the trace take the factor unit.  Writes only
+// the plan's own buffers.
+int cuadmm_solver::lr_run(int which, double tol, double o[8], double* per_block, double* L_out, int* piv_out) {
+  int rc;
+  const int nb = (int)blk_local.size();
+  const double* v = which == 0 ? X.p : S.p;
+  const double unit = pending_unscale ? (which == 0 ? bscale : Cscale) : 1.0;
+  CUADMM_HIP_TRY(hipEventRecord(lr.ev[0], st));
+  if ((rc = lr.run(v, 1.0, btasks.off.p, btasks.blk.p, tol, st))) return rc;
+  CUADMM_HIP_TRY(hipEventRecord(lr.ev[1], st));
+  CUADMM_HIP_TRY(hipStreamSynchronize(st));
+  const float ms = event_ms(lr.ev[0], lr.ev[1]);
+  lr.calls++;
+  std::vector<double> own;
+  if (!per_block) { own.resize(kLrOut * (size_t)nb); per_block = own.data(); }
+  if ((rc = lr.fetch(unit, per_block, L_out, piv_out))) return rc;
+  double sum_r = 0, max_r = 0, resid = 0, dneg = 0;
+  int arg = -1, capped = 0;
+  for (int k = 0; k < nb; ++k) {
+    const double* q = per_block + kLrOut * (size_t)k;
+    if ((int)q[4] == kLrFree) continue;
+    sum_r += q[0];
+    if (arg < 0 || q[0] > max_r) { max_r = q[0]; arg = k; }
+    resid += q[1];
+    if (q[2] < dneg) dneg = q[2];
+    capped += (int)q[4] == kLrCapped;
+  }
+  o[0] = sum_r; o[1] = max_r; o[2] = (double)arg; o[3] = resid; o[4] = dneg; o[5] = (double)capped;
+  o[6] = ms;
+  o[7] = lr.bytes() + btasks.bytes();
+  return CUADMM_OK;
+}
+
 // SDPDuoSolver front (duo_solver.h:236-276): exactly two block sizes, then the generic engine.
 int cuadmm_duo_init(cuadmm_solver* s, int if_gpu_eig_mom, int device_num_requested, int eig_stream_num_per_gpu,
                     int cpu_eig_thread_num, int vec_len, int con_num, const int* At_cp, const int* At_ri, const double* At_vx,
@@ -3531,6 +3649,24 @@ int cuadmm_lambda_min(cuadmm_solver* s, int which, int steps, double o[8], doubl
   if ((rc = s->lm_prepare(which)) || (which == 2 && (rc = s->stage_scaled_y(s->lm.ybuf.p, nullptr)))) return rc;
   return s->lm_run(which, steps, o, per_block);
 }
+int cuadmm_lowrank_size(const cuadmm_solver* s, int rmax, long long* count_out) {
+  if (!s || !s->initialised || !count_out) { set_error("lowrank_size: solver not initialised or null argument"); return CUADMM_ERR_INVALID; }
+  if (rmax < 1 || rmax > kMaxBlockSize) { set_error("lowrank_size: rmax = %d, allowed are 1 to %d", rmax, kMaxBlockSize); return CUADMM_ERR_INVALID; }
+  long long c = 0;
+  for (int n : s->blk_local)
+    if (n > 0) c += (long long)n * std::min(n, rmax);
+  *count_out = c;
+  return CUADMM_OK;
+}
+int cuadmm_lowrank(cuadmm_solver* s, int which, double tol, int rmax, double o[8], double* per_block, double* L_out, int* piv_out) {
+  int rc = report_guard(s, o, "lowrank", "results", false);
+  if (rc) return rc;
+  if (which < 0 || which > 1) { set_error("lowrank: which = %d (0: X, 1: S)", which); return CUADMM_ERR_INVALID; }
+  if (!(tol >= 0.0 && tol < 1.0)) { set_error("lowrank: tol = %g, allowed is 0 <= tol < 1", tol); return CUADMM_ERR_INVALID; }
+  if (rmax < 1 || rmax > kMaxBlockSize) { set_error("lowrank: rmax = %d, allowed are 1 to %d", rmax, kMaxBlockSize); return CUADMM_ERR_INVALID; }
+  if ((rc = s->lr_prepare(rmax))) return rc;
+  return s->lr_run(which, tol, o, per_block, L_out, piv_out);
+}
 int cuadmm_get_evaluate_info(const cuadmm_solver* s, double o[4]) {
   if (!s || !o) { set_error("get_evaluate_info: null"); return CUADMM_ERR_INVALID; }
   o[0] = (double)s->ev.calls; o[1] = s->ev.bytes() + (s->ev.out_d.p ? s->btasks.bytes() : 0.0); o[2] = s->ev.out_d.p ? s->aux.bytes() : 0.0; o[3] = s->ev.ms;
@@ -4026,6 +4162,26 @@ int cuadmm_op_block_lambda_min(const double* svec_dev, const int* blk_vals, int 
   for (int k = 0; k < mat_num; ++k)
     for (int q = 0; q < 3; ++q) per_block3_host[3 * k + q] = h[kLmOut * (size_t)k + q];
   return CUADMM_OK;
+}
+
+// the lowrank kernel on a device vector whose blocks follow one another from slot 0 (csrc/lowrank.hip); blk_vals on the host
+int cuadmm_op_block_lowrank(const double* svec_dev, const int* blk_vals, int mat_num, double tol, int rmax, double* per_block6_host, double* L_host, int* piv_host,
+                            void* stream) {
+  if (!svec_dev || !blk_vals || mat_num < 1 || !per_block6_host || !(tol >= 0.0 && tol < 1.0) || rmax < 1 || rmax > kMaxBlockSize) {
+    set_error("op_block_lowrank: invalid argument");
+    return CUADMM_ERR_INVALID;
+  }
+  for (int k = 0; k < mat_num; ++k)
+    if (blk_vals[k] == 0 || blk_vals[k] > kMaxBlockSize) { set_error("op_block_lowrank: block %d has size %d", k, blk_vals[k]); return CUADMM_ERR_INVALID; }
+  int rc, ndev = 0;      // the current device is the vector's: it is not changed
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_error("no HIP device available; this engine has no CPU fallback"); return CUADMM_ERR_NO_DEVICE; }
+  hipStream_t st = (hipStream_t)stream;
+  cuadmm_solver::BlockTasksDev t;
+  cuadmm_solver::LrPlan plan;
+  if ((rc = t.build(blk_vals, mat_num, nullptr)) || (rc = plan.prepare(blk_vals, mat_num, rmax))) return rc;
+  if ((rc = plan.run(svec_dev, 1.0, t.off.p, t.blk.p, tol, st))) return rc;
+  CUADMM_HIP_TRY(hipStreamSynchronize(st));
+  return plan.fetch(1.0, per_block6_host, L_host, piv_host);
 }
 
 int cuadmm_dev_malloc(void** ptr, size_t bytes) { CUADMM_HIP_TRY(hipMalloc(ptr, bytes ? bytes : 8)); return CUADMM_OK; }

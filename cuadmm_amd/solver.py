@@ -219,6 +219,37 @@ class SDPSolver:
                 "psd_at_floor": int(o[5]), "ms": float(o[6]), "bytes": float(o[7]), "lo": pb[0::3].copy(), "hi": pb[1::3].copy(),
                 "flag": pb[2::3].astype(int)}
 
+    LOWRANK_WHICH = {"X": 0, "S": 1}
+
+    def lowrank(self, which="X", *, tol, rmax=None):
+        """Numerical rank and a factor M_k ~ L_k L_k' of every PSD block of X or S by Cholesky with diagonal pivoting (cuadmm_lowrank), stopped
+        where the largest residual diagonal entry is <= tol * max_i m_ii or at rmax columns (default: the largest block size).  Per block
+        "rank", "resid", "dneg", "trace", "flag" (0 complete, 1 stopped at rmax, 2 unconstrained, 3 not factored); "L": a list of (n_k, r_k)
+        arrays in the block's row order (unconstrained: (0, 0)); "piv": a list of the r_k pivot rows."""
+        if which not in self.LOWRANK_WHICH:
+            raise ValueError("lowrank: which must be 'X' or 'S'")
+        blk = [int(n) for n in self.blk_vals]
+        if rmax is None:
+            rmax = max([n for n in blk if n > 0] + [1])
+        rmax = int(rmax)
+        count = C.c_longlong(0)
+        check(self._lib.cuadmm_lowrank_size(self._h, rmax, C.byref(count)))
+        o = np.zeros(8)
+        pb = np.zeros(6 * self.mat_num)
+        Lv = np.zeros(max(count.value, 1))
+        pv = np.full(max(count.value, 1), -1, np.int32)
+        check(self._lib.cuadmm_lowrank(self._h, self.LOWRANK_WHICH[which], float(tol), rmax, _p(o), _p(pb), _p(Lv), _p(pv)))
+        pb = pb.reshape(-1, 6)
+        rank, off = pb[:, 0].astype(int), pb[:, 5].astype(np.int64)
+        L, piv = [], []
+        for k, n in enumerate(blk):
+            r = rank[k]
+            L.append(Lv[off[k]:off[k] + max(n, 0) * r].reshape(r, max(n, 0)).T.copy())
+            piv.append(pv[off[k]:off[k] + r].copy())
+        return {"rank_sum": int(o[0]), "rank_max": int(o[1]), "block": int(o[2]), "resid_sum": float(o[3]), "dneg_min": float(o[4]), "capped": int(o[5]),
+                "ms": float(o[6]), "bytes": float(o[7]), "rank": rank, "resid": pb[:, 1].copy(), "dneg": pb[:, 2].copy(), "trace": pb[:, 3].copy(),
+                "flag": pb[:, 4].astype(int), "L": L, "piv": piv}
+
     def set_allreduce(self, fn):
         """fn(dev_ptr:int, count:int, hip_stream:int) -> None : in-place sum over ranks on that stream."""
         def tramp(_user, buf, count, stream):
@@ -247,6 +278,7 @@ class SDPSolver:
                                     int(b_nnz), _p(a[5]), _p(a[6]), int(C_nnz), _p(a[7]), int(mat_num),
                                     _p(Xa), _p(ya), _p(Sa), float(sig)))
         self.vec_len, self.con_num, self.mat_num = int(vec_len), int(con_num), int(mat_num)
+        self.blk_vals = a[7].copy()
         return self
 
     def init_problem(self, p, X=None, y=None, S=None, sig=1.0, eig_stream_num_per_gpu=15, cpu_eig_thread_num=30):
@@ -276,6 +308,7 @@ class SDPSolver:
                                         _p(a[0]), _p(a[1]), _p(a[2]), int(At_nnz), _p(a[3]), _p(a[4]), int(b_nnz),
                                         _p(a[5]), _p(a[6]), int(C_nnz), _p(a[7]), int(mat_num), _p(Xa), _p(ya), _p(Sa), float(sig)))
         self.vec_len, self.con_num, self.mat_num = int(vec_len), int(con_num), int(mat_num)
+        self.blk_vals = a[7].copy()
         return self
 
     # -- results (public members of the reference class) -----------------------------------------

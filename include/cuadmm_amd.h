@@ -353,6 +353,38 @@ int cuadmm_get_evaluate_info(const cuadmm_solver* s, double out4[4]);
 int cuadmm_lambda_min(cuadmm_solver* s, int which, int steps, double out8[8], double* per_block);
 /* (n + 2) 2^-52 (trace + n mu): the margin of a factorisation of M + mu I that succeeded, trace = tr M.  Host only. */
 double cuadmm_lambda_min_margin(int n, double trace, double mu);
+/* Numerical rank and a low-rank factor M_k ~ L_k L_k' of every PSD block of X (which = 0) or S (1), by Cholesky with diagonal (complete)
+ * pivoting in its lazy left-looking form ("Low-rank factors"; csrc/lowrank.hip): with d the residual diagonal, d_i = m_ii at
+ * the start, column r takes the pivot p_r = argmax_i d_i over the rows not yet chosen (ties: the smallest index) while d_p > thr =
+ * tol max(max_i m_ii, 0) and r < min(n_k, rmax); L[p, r] = sqrt(d_p), L[i, r] = (m_ip - sum_{j<r} L[i, j] L[p, j]) / L[p, r],
+ * d_i <- d_i - L[i, r]^2.  The Schur complement is never formed: O(n r) scratch and O(n r^2) work for rank r, any block size the engine
+ * accepts.  No eigenvalue is computed.  tol: relative, 0 <= tol < 1.  rmax: 1 .. 8192, the column cap.
+ * What the factor promises, with E = M - L L', r the rank reported and u = 2^-53:
+ *   structure          L[piv[j], j] > 0; L[piv[i], j] == 0.0 exactly for i < j; columns >= r are zero.
+ *   residual diagonal  |E_ii - d_i| <= 2 (r + 2) u (m_ii + sum_j L_ij^2) for every row, d_i = 0 on pivot rows; resid is sum |d_i| of the
+ *                      computed values over the rows not chosen.
+ *   PSD input          for M >= 0, E >= 0 in exact arithmetic and ||E||_F <= tr E; in floating point ||M - L L'||_F <= resid +
+ *                      4 (n + 2) u tr M.
+ *   rank               after r columns max_i d_i >= tr E / n >= lambda_{r+1}(M) / n: a block of exact rank r0 (up to n u ||M|| << tol
+ *                      max_i m_ii) with lambda_{r0}(M) / n > tol max_i m_ii is reported with rank exactly r0.
+ * Results in the caller's units: behind a solve the scaled iterate is read where it lies and the numbers are rescaled (L by the root of
+ * the scale, resid, dneg and the trace by the scale); the deferred unscaling is not triggered and nothing the iteration reads changes: a
+ * following cuadmm_solve(..., if_first = 0) continues bit for bit.  A is not read: a failed cuadmm_update_A does not block the call.
+ * out8: [0] sum_k r_k, [1] max_k r_k, [2] its block (the first; -1: there is no PSD block), [3] sum_k resid_k, [4] min_k dneg_k,
+ * [5] blocks with flag 1, [6] milliseconds of device time (HIP events), [7] bytes of device memory held (lists and buffers, allocated on
+ * first use, regrown when rmax grows, kept).
+ * per_block (may be NULL): 6 mat_num doubles, [6k] rank r_k, [6k + 1] resid_k, [6k + 2] dneg_k = min(0, min_i d_i) over the rows not
+ * chosen (negative: the block is not PSD), [6k + 3] tr M_k, [6k + 4] flag: 0 complete (every remaining d_i <= thr), 1 stopped at the
+ * column cap with some d_i > thr, 2 unconstrained block (rank 0 and nothing else), 3 not factored: an entry is not finite or max |m_ij|
+ * lies outside [2^-500, 2^500] (rank 0, resid NaN), [6k + 5] offset of the block's factor in L_out, in doubles.
+ * L_out (may be NULL): cuadmm_lowrank_size doubles; block k holds n_k min(n_k, rmax) of them at its offset, column by column, n_k
+ * doubles per column in the block's row order, columns >= r_k zero.  piv_out (may be NULL): as many ints; block k's min(n_k, rmax)
+ * pivots stand at the same offset, -1 beyond r_k and everywhere else.
+ * CUADMM_ERR_INVALID, with the solver as it was: not initialised, out8 NULL, world > 1 or an in-process group, which outside 0 .. 1,
+ * tol not in [0, 1), rmax outside 1 .. 8192. */
+int cuadmm_lowrank(cuadmm_solver* s, int which, double tol, int rmax, double out8[8], double* per_block, double* L_out, int* piv_out);
+/* doubles of L_out (and ints of piv_out) that cuadmm_lowrank writes for this rmax: sum over the PSD blocks of n_k min(n_k, rmax).  Host only. */
+int cuadmm_lowrank_size(const cuadmm_solver* s, int rmax, long long* count_out);
 /* Trace bounds read off the constraints (the arrays of cuadmm_init).  R_out[k] = -1: nothing found (always for unconstrained blocks).
  * Rule 1: a constraint whose entries are exactly the diagonal slots of ONE PSD block, all with the same value c (c svec(I_k)), gives
  * tr X_k = b_j / c.  Rule 2: a block whose every diagonal entry is fixed by a constraint with that single entry has the sum of those
@@ -607,6 +639,11 @@ int cuadmm_op_ev_block_stats(int64_t n, double* X_inout, double* S_inout, double
  * the host (negative: unconstrained).  per_block3_host: 3 mat_num doubles, lo, hi, flag per block as in cuadmm_lambda_min.  Synchronises
  * the stream. */
 int cuadmm_op_block_lambda_min(const double* svec_dev, const int* blk_vals, int mat_num, int steps, double* per_block3_host, void* stream);
+/* The kernel of cuadmm_lowrank on a DEVICE svec vector whose blocks follow one another from slot 0 (csrc/lowrank.hip); blk_vals on the
+ * host (negative: unconstrained).  per_block6_host: 6 mat_num doubles; L_host, piv_host (each may be NULL): sum n_k min(n_k, rmax) doubles
+ * and ints, all three laid out as in cuadmm_lowrank.  Synchronises the stream. */
+int cuadmm_op_block_lowrank(const double* svec_dev, const int* blk_vals, int mat_num, double tol, int rmax, double* per_block6_host, double* L_host,
+                            int* piv_host, void* stream);
 int cuadmm_op_spmv_rows(int rows, int ncols, const int* row_ptrs, const int* col_ids, const double* vals, const double* X, const double* S, const double* C,
                         int want_x, int want_s, const int* rowmap, int out_len, double* outX, double* outS, int* info4);
 int cuadmm_op_rp_stats(int m, const double* ax, const double* b, const double* normA, const double* y, double bscale, const double* sums2, double* out4);

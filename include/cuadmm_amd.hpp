@@ -171,6 +171,28 @@ class SDPSolver {
     return LambdaMin{o[0], (int)o[1], o[2], o[3], (int)o[4], (int)o[5], o[6], o[7]};
   }
 
+  // cuadmm_lowrank: numerical rank and a factor M_k ~ L_k L_k' of the blocks of X (which = 0) or S (1) by pivoted Cholesky; per_block:
+  // [6k ..] = rank, resid, dneg, trace, flag, offset of L_k in L; L: n_k min(n_k, rmax) doubles per PSD block, column by column; piv: as
+  // many ints, a block's pivots at the same offset, -1 elsewhere; not in the reference
+  struct LowRank {
+    double rank_sum; int rank_max, block; double resid, dneg; int capped; double ms, bytes;
+    std::vector<double> per_block, L;
+    std::vector<int> piv;
+  };
+  LowRank lowrank(int which, double tol, int rmax, bool factors = true) {
+    double o[8] = {0};
+    int vl = 0, cn = 0, mn = 0;
+    long long count = 0;
+    check(cuadmm_get_dims(h_, &vl, &cn, &mn));
+    check(cuadmm_lowrank_size(h_, rmax, &count));
+    LowRank r;
+    r.per_block.assign(6 * (size_t)mn, 0.0);
+    if (factors) { r.L.assign((size_t)count, 0.0); r.piv.assign((size_t)count, -1); }
+    check(cuadmm_lowrank(h_, which, tol, rmax, o, r.per_block.data(), factors ? r.L.data() : nullptr, factors ? r.piv.data() : nullptr));
+    r.rank_sum = o[0]; r.rank_max = (int)o[1]; r.block = (int)o[2]; r.resid = o[3]; r.dneg = o[4]; r.capped = (int)o[5]; r.ms = o[6]; r.bytes = o[7];
+    return r;
+  }
+
   // cuadmm_update_bC: new b and / or C on the factored solver (nnz < 0: unchanged); not in the reference
   void update_bC(const int* cpu_b_indices, const double* cpu_b_vals, int b_nnz, const int* cpu_C_indices, const double* cpu_C_vals,
                  int C_nnz, bool keep_iterate = true, double sig = 0.0) {
