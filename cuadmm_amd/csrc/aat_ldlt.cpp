@@ -994,7 +994,7 @@ int cuadmm_aat_factor_arrays(const cuadmm_aat* f, const int64_t** Lp, const int*
 
 // The elimination forest of the factor: parent(j) = smallest row index of column j of L.  Independent trees never exchange
 // data in a solve, so many small trees (block-diagonal A A^T: one tree per group of coupled constraints) can be solved by
-// one GPU thread each (engine.hip: forest_solve_kernel) with the arithmetic order of the serial host sweeps.
+// one GPU thread each (vec_kernels.hip: forest_solve_kernel) with the arithmetic order of the serial host sweeps.
 int cuadmm_aat_forest(cuadmm_aat* f, int* n_trees, int* max_cols, const int** tree_ptr, const int** tree_cols) {
   if (!f || !n_trees || !max_cols || !tree_ptr || !tree_cols) { set_error("aat_forest: null argument"); return CUADMM_ERR_INVALID; }
   if (f->tail_k > 0) { set_error("aat_forest: the factor is split"); return CUADMM_ERR_INVALID; }

@@ -1,0 +1,589 @@
+// What the engine reports beside the iteration: the infeasibility check and the certified lower bound behind the iteration's steps, and
+// the reports on a point (cuadmm_lower_bound, cuadmm_evaluate, cuadmm_lambda_min, cuadmm_lowrank) with their C entry points.  Host code
+// only: the kernels are those of infeas.hip, lower_bound.hip, evaluate.hip, lambda_min.hip, lowrank.hip and the iteration's own.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <numeric>
+
+#include "engine_state.h"
+
+using namespace cuadmm;
+
+// ------------------------------------------------------------------------------------------
+// Infeasibility detection (option "infeas_check"): DESIGN.md, "Infeasibility certificates"
+// ------------------------------------------------------------------------------------------
+// Auxiliary projector (infeasibility check, lower bound)
+int AuxProj::ensure(cuadmm_solver& s) {
+  int rc;
+  if (!ev[1]) {
+    if ((rc = in.alloc((size_t)s.L)) || (rc = out.alloc((size_t)s.L)) || (!s.b_d.p && (rc = bcopy.alloc((size_t)std::max(s.m, 1))))) return rc;
+    for (auto& e : ev) if ((rc = e.create())) return rc;
+  }
+  if (bcopy.p && s.m > 0 && (rc = staged_h2d(bcopy.p, s.b_p.data(), sizeof(double) * (size_t)s.m, s.st))) return rc;
+  return CUADMM_OK;
+}
+int AuxProj::project(cuadmm_solver& s, const double* from, double* to) {
+  if (!plan) {
+    int rc;
+    size_t free0 = 0, free1 = 0, total = 0;
+    if (hipMemGetInfo(&free0, &total) != hipSuccess) { free0 = 0; (void)hipGetLastError(); }
+    plan = new PsdPlan();
+    plan->opt = s.plan.opt;
+    plan->eig_rank = 0;
+    if ((rc = plan->build(s.blk_local.data(), (int)s.blk_local.size()))) { delete plan; plan = nullptr; return rc; }
+    if (hipMemGetInfo(&free1, &total) != hipSuccess) { free1 = free0; (void)hipGetLastError(); }
+    plan_bytes = free0 > free1 ? (double)(free0 - free1) : 0.0;
+  }
+  projected = true;
+  return plan->project(from, to, s.st);
+}
+
+// The y a report reads, in the engine's scaled space and the factor's order, in a vector of the report's own.  y_caller: the caller's,
+// with the constants of materialise() inverted as cuadmm_init applies them.  Null: the y cuadmm_get_y would return -- behind a solve the
+// iterate is held scaled and is copied as it lies (the deferred unscaling is not triggered: a following solve(if_first = false)
+// continues from it bit for bit); otherwise y is in the caller's units, on the host, or on the device only where cuadmm_update_bC left
+// the current one there.
+int cuadmm_solver::stage_scaled_y(double* dst, const double* y_caller) {
+  int rc;
+  if (m <= 0) { CUADMM_HIP_TRY(hipMemsetAsync(dst, 0, sizeof(double), st)); return CUADMM_OK; }
+  if (!y_caller && pending_unscale && dev_solve) {
+    CUADMM_HIP_TRY(hipMemcpyAsync(dst, y_d.p, sizeof(double) * (size_t)m, hipMemcpyDeviceToDevice, st));
+    return CUADMM_OK;
+  }
+  std::vector<double> ys(y_p);
+  const double ics = 1 / Cscale;
+  if (y_caller) for (int i = 0; i < m; ++i) ys[i] = (y_caller[perm[i]] * normA_p[i]) * ics;
+  else if (!pending_unscale) {
+    if (y_host_stale && (rc = staged_d2h(ys.data(), y_d.p, sizeof(double) * (size_t)m, st))) return rc;
+    for (int i = 0; i < m; ++i) ys[i] = (ys[i] * normA_p[i]) * ics;
+  }
+  return staged_h2d(dst, ys.data(), sizeof(double) * (size_t)m, st);
+}
+
+// M = A'y - C by the iteration's kernel into the auxiliary projector's input vector (S^ = -Cscale M), and the slot sums of b'y
+int cuadmm_solver::dual_slack(const double* y, double* by_part) {
+  int rc;
+  if ((rc = launch_aty_xb(false, L, At_rp.p, At_ci.p, At_v.p, y, C.p, X.p, 1.0, aux.in.p, nullptr, st, &At_long))) return rc;
+  return launch_lb_dot(m, aux.b_dev(*this), y, by_part, st);
+}
+
+// start of every solve: buffers on first use, no snapshot
+int cuadmm_solver::infeas_begin_solve() {
+  int rc;
+  if (!inf.xprev.p) {
+    const size_t mm = (size_t)std::max(m, 1);
+    if ((rc = inf.xprev.alloc(L)) || (rc = inf.yprev.alloc(mm)) || (rc = inf.dy.alloc(mm)) ||
+        (rc = inf.adx.alloc(mm)) || (rc = inf.partials.alloc(kInfeasPartials)) || (rc = inf.stats_d.alloc(INF_NSTATS)) || (rc = inf.h_stats.alloc(INF_NSTATS)))
+      return rc;
+    long long off = 0;
+    for (int n : blk_local) { if (n < 0) inf.free_rng.emplace_back(off, blk_svec_len(n)); off += blk_svec_len(n); }
+  }
+  if ((rc = aux.ensure(*this))) return rc;
+  infeas_reset();
+  inf.ms = 0;
+  return CUADMM_OK;
+}
+
+// End of iteration `iter`, a multiple of the period.  y_d holds the y this iteration's A^T y kernel read (device y-solve: its result,
+// host y-solve: the uploaded copy), in the factor's order; X the new X.  The first call of a solve only copies the snapshot.
+int cuadmm_solver::infeas_step(int iter, double stop_tol) {
+  int rc;
+  if (std::max(maxfeas, relgap) < stop_tol) return CUADMM_OK;      // the loop is about to end as converged
+  if (!inf.have_snap) {          // the first multiple of the period: the snapshot alone
+    if (m > 0) CUADMM_HIP_TRY(hipMemcpyAsync(inf.yprev.p, y_d.p, sizeof(double) * (size_t)m, hipMemcpyDeviceToDevice, st));
+    CUADMM_HIP_TRY(hipMemcpyAsync(inf.xprev.p, X.p, sizeof(double) * (size_t)L, hipMemcpyDeviceToDevice, st));
+    inf.have_snap = true;
+    return CUADMM_OK;
+  }
+  double* const dbuf = aux.in.p;      // a difference, the input of a projection
+  double* const pbuf = aux.out.p;     // its PSD part
+  if ((rc = aux.begin(st))) return rc;
+  // d = cur - prev and prev <- cur in one pass each; the X difference is written negated: it is the input of P+(-dX), and the norm
+  // of A dX does not see the sign
+  if ((rc = launch_infeas_roll(m, y_d.p, inf.yprev.p, aux.b_dev(*this), inf.dy.p, 0, 0, nullptr, nullptr, inf.partials.p, inf.stats_d.p + INF_DY2, st))) return rc;
+  if ((rc = launch_infeas_roll(L, X.p, inf.xprev.p, C.p, dbuf, 1, 0, nullptr, nullptr, inf.partials.p, inf.stats_d.p + INF_DX2, st))) return rc;
+  inf.checks++;
+  double* hs = inf.h_stats.p;
+  CUADMM_HIP_TRY(hipMemcpyAsync(hs, inf.stats_d.p, sizeof(double) * 4, hipMemcpyDeviceToHost, st));
+  CUADMM_HIP_TRY(hipStreamSynchronize(st));
+  // a test's SpMV and projection run only when its scalar has the sign a certificate needs
+  const bool try_dual = hs[INF_CDX] < 0 && hs[INF_DX2] > 0, try_primal = hs[INF_BDY] > 0 && hs[INF_DY2] > 0;
+  int verdict = 0;
+  double o3[3] = {0, 0, 0}, stats[INF_NSTATS];
+  const double nan = std::nan("");
+  // The dual test first: its input -dX sits in dbuf, which the primal test overwrites.
+  if (try_dual) {      // A (-dX) over the whole svec; P+(-dX) with the unconstrained blocks' slices (copied through by the plan) left out
+    if ((rc = launch_spmv_rows(m, A_avg_nnz, A_rp.p, A_ci.p, A_v.p, dbuf, S.p, C.p, inf.adx.p, nullptr, st, &A_long))) return rc;
+    if ((rc = launch_infeas_norm2(m, inf.adx.p, inf.partials.p, inf.stats_d.p + INF_ADX2, st))) return rc;
+    if ((rc = aux.project(*this, dbuf, pbuf))) return rc;
+    for (auto& r : inf.free_rng) CUADMM_HIP_TRY(hipMemsetAsync(pbuf + r.first, 0, sizeof(double) * (size_t)r.second, st));
+    if ((rc = launch_infeas_norm2(L, pbuf, inf.partials.p, inf.stats_d.p + INF_PNEGDX2, st))) return rc;
+    CUADMM_HIP_TRY(hipMemcpyAsync(hs + INF_ADX2, inf.stats_d.p + INF_ADX2, sizeof(double) * 2, hipMemcpyDeviceToHost, st));
+    CUADMM_HIP_TRY(hipStreamSynchronize(st));
+    for (int q = 0; q < INF_NSTATS; ++q) stats[q] = hs[q];
+    stats[INF_DY2] = stats[INF_BDY] = stats[INF_PATY2] = nan; stats[INF_ATY2] = 0;
+    if ((rc = infeas_decide(stats, inf.tol, &verdict, o3))) return rc;
+  }
+  if (verdict == 0 && try_primal) {   // A^T dy (the kernel forms A^T y - C: pbuf, zeroed, stands in for C), its PSD part, its norm
+    CUADMM_HIP_TRY(hipMemsetAsync(pbuf, 0, sizeof(double) * (size_t)L, st));
+    if ((rc = launch_aty_xb(false, L, At_rp.p, At_ci.p, At_v.p, inf.dy.p, pbuf, X.p, 1.0, dbuf, nullptr, st, &At_long))) return rc;
+    if ((rc = launch_infeas_norm2(L, dbuf, inf.partials.p, inf.stats_d.p + INF_ATY2, st))) return rc;      // ||A^T dy||^2: the radius' rounding term
+    if ((rc = aux.project(*this, dbuf, pbuf))) return rc;
+    if ((rc = launch_infeas_norm2(L, pbuf, inf.partials.p, inf.stats_d.p + INF_PATY2, st))) return rc;
+    CUADMM_HIP_TRY(hipMemcpyAsync(hs + INF_PATY2, inf.stats_d.p + INF_PATY2, sizeof(double) * 4, hipMemcpyDeviceToHost, st));
+    CUADMM_HIP_TRY(hipStreamSynchronize(st));
+    for (int q = 0; q < INF_NSTATS; ++q) stats[q] = hs[q];
+    stats[INF_DX2] = stats[INF_CDX] = stats[INF_ADX2] = stats[INF_PNEGDX2] = nan;
+    if ((rc = infeas_decide(stats, inf.tol, &verdict, o3))) return rc;
+  }
+  float ms = 0;
+  bool bad = false;
+  if ((rc = aux.end(st, &ms, &bad))) return rc;
+  inf.ms += ms;
+  if (bad) { set_error("solve: a block projection of the infeasibility check hit the QL sweep cap"); return CUADMM_ERR_EIG; }
+  if (verdict == 0) return CUADMM_OK;
+  // the ray, as the check left it on the device (scaled space, the factor's order / the svec): dy, or -dX in dbuf
+  const size_t n = verdict == 3 ? (size_t)m : (size_t)L;
+  inf.cert.assign(n, 0.0);
+  if ((rc = staged_d2h(inf.cert.data(), verdict == 3 ? inf.dy.p : dbuf, sizeof(double) * n, st))) return rc;
+  if (verdict == 4) for (double& v : inf.cert) v = -v;
+  solve_status = verdict; solve_status_iter = iter;
+  inf.scalar = o3[0]; inf.eta = o3[1];
+  // The reported radius is scalar / (eta + eta_fl): eta is the norm of a projection the kernels evaluate to 1e-12 ||M||_F per entry
+  // (M = A^T dy or -dX: the projection's contract), so the true violation may exceed eta by eta_fl = 1e-12 sqrt(L) ||M||_F / ||d||, and
+  // only the smaller radius is certified.  In the caller's units: X = bscale X_scaled (primal test); S = Cscale S_scaled,
+  // y = Cscale y_scaled / normA (dual test).
+  const double eta_fl = kInfeasProjErr * std::sqrt((double)L) * (verdict == 3 ? std::sqrt(stats[INF_ATY2] / stats[INF_DY2]) : 1.0);
+  inf.radius = o3[0] / (o3[1] + eta_fl) * (verdict == 3 ? bscale : Cscale);
+  return CUADMM_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// Certified lower bound from trace bounds (cuadmm_lower_bound, option "gap_check"): DESIGN.md, "Certified lower bound"
+// ------------------------------------------------------------------------------------------
+// vectors and task lists on first use; R and (the auxiliary projector's, where the engine keeps none on the device) b on every call: both may have changed
+int cuadmm_solver::lb_prepare() {
+  int rc;
+  const int nb = (int)blk_local.size();
+  if ((int)lb.R.size() != nb) { set_error("lower bound: %d trace bounds are set, the solver has %d blocks", (int)lb.R.size(), nb); return CUADMM_ERR_INVALID; }
+  if (!lb.out_d.p) {
+    const size_t mm = (size_t)std::max(m, 1);
+    if (!btasks.built && (rc = btasks.build(blk_local.data(), nb, nullptr))) return rc;
+    if ((rc = lb.ybuf.alloc(mm)) || (rc = lb.R_d.alloc((size_t)nb)) || (rc = lb.pairs.alloc(2 * (size_t)nb)) || (rc = lb.dpart.alloc(kBrSlots)) ||
+        (rc = lb.h_out.alloc(4)) || (rc = lb.cpart.alloc(2 * (size_t)btasks.nchunk)))
+      return rc;
+    CUADMM_HIP_TRY(hipMemsetAsync(lb.pairs.p, 0, sizeof(double) * lb.pairs.n, st));
+    lb.R_dirty = true;
+    if ((rc = lb.out_d.alloc(4))) return rc;          // last: marks the set as complete
+  }
+  if (lb.R_dirty && (rc = staged_h2d(lb.R_d.p, lb.R.data(), sizeof(double) * (size_t)nb, st))) return rc;
+  lb.R_dirty = false;
+  return aux.ensure(*this);
+}
+
+// The bound at y (device, the engine's scaled space and the factor's order).  Reads y, A, C and b; writes only the bound's own vectors.
+// out6 = [LB, b'y, sum R_k nubar_k, worst block, its term] in the caller's units, [5] unused.
+int cuadmm_solver::lb_eval(const double* y, double out6[6], float* ms) {
+  int rc;
+  double* const mbuf = aux.in.p;
+  double* const pbuf = aux.out.p;
+  bool bad = false;
+  if ((rc = aux.begin(st))) return rc;
+  // M = A'y - C (S^ = -Cscale M), P = P+(M) with the unconstrained slices copied through
+  if ((rc = dual_slack(y, lb.dpart.p)) || (rc = aux.project(*this, mbuf, pbuf))) return rc;
+  if ((rc = launch_lb_block_norms(mbuf, pbuf, btasks.view(), lb.cpart.p, lb.pairs.p, st))) return rc;
+  if ((rc = launch_lb_combine((int)blk_local.size(), lb.pairs.p, lb.R_d.p, btasks.len.p, btasks.blk.p, lb.dpart.p, lb.out_d.p, st))) return rc;
+  CUADMM_HIP_TRY(hipMemcpyAsync(lb.h_out.p, lb.out_d.p, sizeof(double) * 4, hipMemcpyDeviceToHost, st));
+  if ((rc = aux.end(st, ms, &bad))) return rc;
+  if (bad) { set_error("lower bound: a block projection hit the QL sweep cap"); return CUADMM_ERR_EIG; }
+  const double* h = lb.h_out.p;
+  out6[1] = h[3] * objscale;
+  out6[2] = h[0] * Cscale;
+  out6[0] = out6[1] - out6[2];
+  out6[3] = h[1];
+  out6[4] = h[2] * Cscale;
+  out6[5] = 0;
+  return CUADMM_OK;
+}
+
+// cuadmm_lower_bound's numbers at the scaled y in lb.ybuf; per_block: [nu_k, ||S^_k||_F] in the caller's units
+int cuadmm_solver::lb_report(double o[8], double* per_block) {
+  int rc;
+  double r[6];
+  float ms = 0;
+  if ((rc = lb_eval(lb.ybuf.p, r, &ms))) return rc;
+  o[0] = r[0]; o[1] = r[1]; o[2] = r[2];
+  o[3] = std::fabs(pobj - r[0]) / (1 + std::fabs(pobj) + std::fabs(r[0]));
+  o[4] = r[3]; o[5] = r[4]; o[6] = ms; o[7] = lb.bytes() + btasks.bytes() + aux.bytes();
+  if (per_block) {
+    const size_t nb = blk_local.size();
+    std::vector<double> pr(2 * nb);
+    if ((rc = staged_d2h(pr.data(), lb.pairs.p, sizeof(double) * 2 * nb, st))) return rc;
+    for (size_t k = 0; k < nb; ++k) { per_block[2 * k] = std::sqrt(pr[2 * k + 1]) * Cscale; per_block[2 * k + 1] = std::sqrt(pr[2 * k]) * Cscale; }
+  }
+  return CUADMM_OK;
+}
+
+// End of iteration `iter`, a multiple of the period: y_d holds this iteration's y (infeas_step), pobj and errRp are this iteration's.
+int cuadmm_solver::lb_step(int iter, double stop_tol) {
+  int rc;
+  double o[6];
+  float ms = 0;
+  if ((rc = lb_eval(y_d.p, o, &ms))) return rc;
+  lb.checks++;
+  lb.ms += ms;
+  const double LB = o[0], g = std::fabs(pobj - LB) / (1 + std::fabs(pobj) + std::fabs(LB));
+  lb.last_lb = LB; lb.last_g = g;
+  if (std::isfinite(LB) && (lb.best_iter == 0 || LB > lb.best_lb)) { lb.best_lb = LB; lb.best_iter = iter; }
+  const double tol = lb.tol > 0 ? lb.tol : stop_tol;
+  if (g <= tol && errRp <= tol) {          // (false for a NaN)
+    solve_status = 5; solve_status_iter = iter;
+    lb.verdict_iter = iter;
+  }
+  return CUADMM_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// Evaluation of a point (cuadmm_evaluate): DESIGN.md, "Evaluation of a point"
+// ------------------------------------------------------------------------------------------
+// vectors and task lists on first use; the column norms (where the engine keeps none on the device) and the auxiliary projector's b on
+// every call: cuadmm_update_A / cuadmm_update_bC may have changed them
+int cuadmm_solver::ev_prepare() {
+  int rc;
+  const int nb = (int)blk_local.size();
+  const size_t mm = (size_t)std::max(m, 1);
+  if (!ev.out_d.p) {
+    if (!btasks.built && (rc = btasks.build(blk_local.data(), nb, nullptr))) return rc;
+    if ((rc = ev.px.alloc((size_t)L)) || (rc = ev.cons.alloc(mm)) || (!normA_d.p && (rc = ev.normA.alloc(mm))) || (rc = ev.sums.alloc(kEvSums * (size_t)nb)) ||
+        (rc = ev.cpart.alloc(kEvSums * (size_t)btasks.nchunk)) || (rc = ev.part.alloc(3 * (size_t)kBrSlots)) || (rc = ev.h_out.alloc(kEvGlobals)))
+      return rc;
+    CUADMM_HIP_TRY(hipMemsetAsync(ev.sums.p, 0, sizeof(double) * ev.sums.n, st));      // (a block without slots keeps zeros)
+    if ((rc = ev.out_d.alloc(kEvGlobals))) return rc;      // last: marks the set as complete
+  }
+  if (ev.normA.p && m > 0 && (rc = staged_h2d(ev.normA.p, normA_p.data(), sizeof(double) * (size_t)m, st))) return rc;
+  return aux.ensure(*this);
+}
+
+// One svec vector of the point in the engine's scaled space.  host: the caller's (this rank's L entries), scaled as init scales X0 / S0,
+// into `own`; null: the resident one -- read where it lies when a solve left it scaled, else a scaled copy in `own`.
+int cuadmm_solver::ev_point(const double* host, const DevBuf<double>& resident, double inv_scale, DevBuf<double>& own, const double** out) {
+  int rc;
+  if (!host && pending_unscale) { *out = resident.p; return CUADMM_OK; }
+  if (!own.p && (rc = own.alloc((size_t)L))) return rc;
+  if (host) {
+    std::vector<double> tmp((size_t)L);
+    for (long long i = 0; i < L; ++i) tmp[i] = host[i] * inv_scale;
+    if ((rc = staged_h2d(own.p, tmp.data(), sizeof(double) * (size_t)L, st))) return rc;
+  } else {
+    CUADMM_HIP_TRY(hipMemcpyAsync(own.p, resident.p, sizeof(double) * (size_t)L, hipMemcpyDeviceToDevice, st));
+    if ((rc = launch_scale(own.p, L, inv_scale, st))) return rc;
+  }
+  *out = own.p;
+  return CUADMM_OK;
+}
+
+// The report at (xs, y in ev.cons, ss), all scaled and in the engine's order.  Reads A, A', b, C; writes only the evaluation's and the
+// auxiliary projector's vectors.  The scalars go back to the caller's units as set_residual_scalars and lb_eval convert theirs:
+// X = bscale X_s, S = Cscale S_s, Rd = Cscale Rd_s, objectives and <X, S> times objscale; ev_rp forms ||A X - b|| in them itself.
+int cuadmm_solver::ev_run(const double* xs, const double* ss, double o[16], double* per_block) {
+  int rc;
+  const int nb = (int)blk_local.size();
+  double* const cons = ev.cons.p;
+  double* const rd1 = aux.in.p;      // A'y - C
+  double* const ps = aux.out.p;      // P+(S)
+  double *const cx_part = ev.part.p, *const by_part = ev.part.p + kBrSlots, *const rp_part = ev.part.p + 2 * kBrSlots;
+  const double* const normA_dev = normA_d.p ? normA_d.p : ev.normA.p;
+  float ms = 0;
+  bool bad = false;
+  if ((rc = aux.begin(st)) || (rc = dual_slack(cons, by_part))) return rc;
+  if ((rc = launch_lb_dot(L, C.p, xs, cx_part, st))) return rc;
+  // A X from the engine's whole A (kept in every mode: the fused and closed iterations evaluate rows of it elsewhere), over y in cons
+  if (m > 0 && (rc = launch_spmv_rows(m, A_avg_nnz, A_rp.p, A_ci.p, A_v.p, xs, ss, C.p, cons, nullptr, st, &A_long))) return rc;
+  if ((rc = launch_ev_rp(m, cons, aux.b_dev(*this), normA_dev, bscale, rp_part, st))) return rc;
+  if ((rc = aux.project(*this, xs, ev.px.p))) return rc;
+  if ((rc = aux.project(*this, ss, ps))) return rc;
+  if ((rc = launch_ev_block_stats(xs, ss, ev.px.p, ps, rd1, btasks.view(), ev.cpart.p, ev.sums.p, st))) return rc;
+  if ((rc = launch_ev_combine(nb, ev.sums.p, cx_part, by_part, rp_part, ev.out_d.p, st))) return rc;
+  CUADMM_HIP_TRY(hipMemcpyAsync(ev.h_out.p, ev.out_d.p, sizeof(double) * kEvGlobals, hipMemcpyDeviceToHost, st));
+  if ((rc = aux.end(st, &ms, &bad))) return rc;
+  ev.ms = ms;
+  ev.calls++;
+  if (bad) { set_error("evaluate: a block projection hit the QL sweep cap"); return CUADMM_ERR_EIG; }
+  const double* h = ev.h_out.p;
+  const double nb1 = norm_borg, nc1 = norm_Corg;      // 1 + ||b||, 1 + ||C||
+  o[0] = h[4] * objscale;
+  o[1] = h[5] * objscale;
+  o[2] = std::sqrt(h[6]);
+  o[3] = std::sqrt(h[3]) * Cscale;
+  o[4] = std::sqrt(h[0]) * bscale;
+  o[5] = std::sqrt(h[1]) * Cscale;
+  o[6] = h[2] * objscale;
+  o[7] = nb1 - 1;
+  o[8] = nc1 - 1;
+  const double den = 1 + std::fabs(o[0]) + std::fabs(o[1]);
+  o[9] = o[2] / nb1; o[10] = o[4] / nb1; o[11] = o[3] / nc1; o[12] = o[5] / nc1;
+  o[13] = (o[0] - o[1]) / den; o[14] = o[6] / den;
+  o[15] = ev.ms;
+  if (per_block) {
+    std::vector<double> q(kEvSums * (size_t)nb);
+    if (nb > 0 && (rc = staged_d2h(q.data(), ev.sums.p, sizeof(double) * q.size(), st))) return rc;
+    for (size_t k = 0; k < (size_t)nb; ++k) {
+      const double* v = q.data() + kEvSums * k;
+      double* w = per_block + kEvSums * k;
+      w[0] = std::sqrt(v[0]) * bscale; w[1] = std::sqrt(v[1]) * bscale; w[2] = std::sqrt(v[2]) * Cscale; w[3] = std::sqrt(v[3]) * Cscale;
+      w[4] = v[4] * objscale; w[5] = std::sqrt(v[5]) * Cscale;
+    }
+  }
+  return CUADMM_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// Certified lambda_min per block (cuadmm_lambda_min): DESIGN.md, "Certified lambda_min"
+// ------------------------------------------------------------------------------------------
+// lists and vectors on first use; the auxiliary projector's events, vectors and b (which may have changed) on every call
+int cuadmm_solver::lm_prepare(int which) {
+  int rc;
+  const int nb = (int)blk_local.size();
+  if (!btasks.built && (rc = btasks.build(blk_local.data(), nb, nullptr))) return rc;
+  if (!lm.out.p && (rc = lm.build(blk_local.data(), nb))) return rc;
+  if (which == 2 && !lm.dpart.p && ((rc = lm.ybuf.alloc((size_t)std::max(m, 1))) || (rc = lm.dpart.alloc(kBrSlots)))) return rc;
+  return aux.ensure(*this);
+}
+
+// which = 0: X, 1: S, read where they lie (scaled behind a solve, else in the caller's units); 2: S^ = C - A'y at the scaled y in lm.ybuf,
+// formed as -(A'y - C) by the iteration's kernel into the auxiliary projector's input vector.  The kernel's numbers are in the units of
+// the vector it read; lo goes to the caller's units rounded down.  Writes only the plan's own vectors and that input vector.
+int cuadmm_solver::lm_run(int which, int steps, double o[8], double* per_block) {
+  int rc;
+  const int nb = (int)blk_local.size();
+  const double* v = which == 0 ? X.p : S.p;
+  double sign = 1.0, unit = pending_unscale ? (which == 0 ? bscale : Cscale) : 1.0;
+  float ms = 0;
+  if ((rc = aux.begin(st))) return rc;
+  if (which == 2) {
+    if ((rc = dual_slack(lm.ybuf.p, lm.dpart.p))) return rc;
+    v = aux.in.p; sign = -1.0; unit = Cscale;
+  }
+  if ((rc = lm.run(v, sign, btasks.off.p, btasks.blk.p, steps, st))) return rc;
+  double* const h = lm.h_out.p;
+  CUADMM_HIP_TRY(hipMemcpyAsync(h, lm.out.p, sizeof(double) * kLmOut * (size_t)nb, hipMemcpyDeviceToHost, st));
+  if (which == 2) CUADMM_HIP_TRY(hipMemcpyAsync(h + kLmOut * (size_t)nb, lm.dpart.p, sizeof(double) * kBrSlots, hipMemcpyDeviceToHost, st));
+  if ((rc = aux.end(st, &ms, nullptr))) return rc;
+  lm.calls++;
+  const bool bound = which == 2 && !lb.R.empty();
+  double worst = INFINITY, pen = 0;
+  int arg = -1, unrefined = 0, at_floor = 0;
+  for (int k = 0; k < nb; ++k) {
+    const double* q = h + kLmOut * (size_t)k;
+    const int flag = (int)q[2];
+    double lo = q[0] * unit, hi = q[1] * unit;
+    if (unit != 1.0 && flag != kLmFree) lo = std::nextafter(lo, -INFINITY);
+    if (flag != kLmFree && lo < worst) { worst = lo; arg = k; }
+    unrefined += flag == kLmUnrefined; at_floor += flag == kLmPsdAtFloor;
+    if (bound) pen += lb.R[k] * (flag == kLmFree ? q[3] * unit : std::max(0.0, -lo));
+    if (per_block) { per_block[3 * k] = lo; per_block[3 * k + 1] = hi; per_block[3 * k + 2] = (double)flag; }
+  }
+  o[0] = arg >= 0 ? worst : 0.0;
+  o[1] = (double)arg;
+  o[2] = std::max(0.0, -o[0]) / (which == 0 ? norm_borg : norm_Corg);
+  o[3] = NAN;
+  if (bound) {
+    double by = 0;
+    for (int j = 0; j < kBrSlots; ++j) by += h[kLmOut * (size_t)nb + j];
+    o[3] = by * objscale - pen;
+  }
+  o[4] = (double)unrefined; o[5] = (double)at_floor;
+  o[6] = ms;
+  o[7] = lm.bytes() + btasks.bytes() + aux.bytes();
+  return CUADMM_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// Rank and low-rank factor per block (cuadmm_lowrank): DESIGN.md, "Low-rank factors"
+// ------------------------------------------------------------------------------------------
+// lists, events and buffers on first use; offsets and larger buffers when rmax changes
+int cuadmm_solver::lr_prepare(int rmax) {
+  int rc;
+  const int nb = (int)blk_local.size();
+  if (!btasks.built && (rc = btasks.build(blk_local.data(), nb, nullptr))) return rc;
+  return lr.prepare(blk_local.data(), nb, rmax);
+}
+
+// which = 0: X, 1: S, read where they lie (scaled behind a solve, else in the caller's units).  The kernel's numbers are in the units of the
+// vector it read: M = unit M_s, so L = sqrt(unit) L_s and the residual diagonal, its sums and the trace take the factor unit.  Writes only
+// the plan's own buffers.
+int cuadmm_solver::lr_run(int which, double tol, double o[8], double* per_block, double* L_out, int* piv_out) {
+  int rc;
+  const int nb = (int)blk_local.size();
+  const double* v = which == 0 ? X.p : S.p;
+  const double unit = pending_unscale ? (which == 0 ? bscale : Cscale) : 1.0;
+  CUADMM_HIP_TRY(hipEventRecord(lr.ev[0], st));
+  if ((rc = lr.run(v, 1.0, btasks.off.p, btasks.blk.p, tol, st))) return rc;
+  CUADMM_HIP_TRY(hipEventRecord(lr.ev[1], st));
+  CUADMM_HIP_TRY(hipStreamSynchronize(st));
+  const float ms = event_ms(lr.ev[0], lr.ev[1]);
+  lr.calls++;
+  std::vector<double> own;
+  if (!per_block) { own.resize(kLrOut * (size_t)nb); per_block = own.data(); }
+  if ((rc = lr.fetch(unit, per_block, L_out, piv_out))) return rc;
+  double sum_r = 0, max_r = 0, resid = 0, dneg = 0;
+  int arg = -1, capped = 0;
+  for (int k = 0; k < nb; ++k) {
+    const double* q = per_block + kLrOut * (size_t)k;
+    if ((int)q[4] == kLrFree) continue;
+    sum_r += q[0];
+    if (arg < 0 || q[0] > max_r) { max_r = q[0]; arg = k; }
+    resid += q[1];
+    if (q[2] < dneg) dneg = q[2];
+    capped += (int)q[4] == kLrCapped;
+  }
+  o[0] = sum_r; o[1] = max_r; o[2] = (double)arg; o[3] = resid; o[4] = dneg; o[5] = (double)capped;
+  o[6] = ms;
+  o[7] = lr.bytes() + btasks.bytes();
+  return CUADMM_OK;
+}
+
+extern "C" {
+
+int cuadmm_get_status(const cuadmm_solver* s, double o[8]) {
+  if (!s || !o) { set_error("get_status: null"); return CUADMM_ERR_INVALID; }
+  o[0] = (double)s->solve_status; o[1] = (double)s->solve_status_iter; o[2] = (double)s->inf.checks; o[3] = s->inf.scalar; o[4] = s->inf.eta;
+  o[5] = s->inf.radius; o[6] = s->inf.ms; o[7] = s->inf.bytes() + (s->inf.xprev.p ? s->aux.bytes() : 0.0);
+  return CUADMM_OK;
+}
+int cuadmm_get_certificate(cuadmm_solver* s, double* y_out, double* X_out) {
+  if (!s || !s->initialised) { set_error("get_certificate: solver not initialised"); return CUADMM_ERR_INVALID; }
+  if (s->solve_status != 3 && s->solve_status != 4) { set_error("get_certificate: the last solve found no certificate of infeasibility (status %d)", s->solve_status); return CUADMM_ERR_INVALID; }
+  const std::vector<double>& c = s->inf.cert;
+  if (s->solve_status == 3) {
+    if (!y_out) { set_error("get_certificate: status 3 returns a y ray: y_out is null"); return CUADMM_ERR_INVALID; }
+    // back to the caller's units and order as materialise / cuadmm_get_y map y, then b' y = 1 on the caller's b
+    for (int i = 0; i < s->m; ++i) y_out[s->perm[i]] = c[i] / s->normA_p[i];
+    long double t = 0;
+    for (size_t k = 0; k < s->upa.b_idx.size(); ++k) t += (long double)s->upa.b_val[k] * y_out[s->upa.b_idx[k]];
+    for (int i = 0; i < s->m; ++i) y_out[i] = (double)(y_out[i] / t);
+    return CUADMM_OK;
+  }
+  if (!X_out) { set_error("get_certificate: status 4 returns an X ray: X_out is null"); return CUADMM_ERR_INVALID; }
+  int rc = check_device(s->device);
+  if (rc) return rc;
+  std::vector<double> Ch((size_t)s->L);
+  if (s->L > 0 && (rc = staged_d2h(Ch.data(), s->C.p, sizeof(double) * (size_t)s->L, s->st))) return rc;
+  long double t = 0;
+  for (long long i = 0; i < s->L; ++i) t += (long double)(Ch[i] * s->Cscale) * c[i];      // <C, dX> in the caller's units of C
+  for (long long i = 0; i < s->L; ++i) X_out[i] = (double)(c[i] / -t);
+  return CUADMM_OK;
+}
+int cuadmm_infeas_decide(const double stats[8], double tol, int* verdict, double* radius) {
+  double o3[3];
+  int rc = infeas_decide(stats, tol, verdict, o3);
+  if (!rc && radius) *radius = o3[2];
+  return rc;
+}
+int cuadmm_set_trace_bounds(cuadmm_solver* s, const double* R, int mat_num) {
+  if (!s) { set_error("set_trace_bounds: null"); return CUADMM_ERR_INVALID; }
+  if (!R) {
+    if (s->initialised && s->lb.period > 0) { set_error("set_trace_bounds: option gap_check is on: the bounds cannot be cleared"); return CUADMM_ERR_INVALID; }
+    s->lb.R.clear();
+    return CUADMM_OK;
+  }
+  if (mat_num < 1) { set_error("set_trace_bounds: mat_num = %d", mat_num); return CUADMM_ERR_INVALID; }
+  if (s->initialised) {
+    int mn = 0;
+    cuadmm_get_dims(s, nullptr, nullptr, &mn);
+    if (mn != mat_num) { set_error("set_trace_bounds: %d bounds for a problem of %d blocks", mat_num, mn); return CUADMM_ERR_INVALID; }
+  }
+  for (int k = 0; k < mat_num; ++k)
+    if (!(R[k] >= 0) || !std::isfinite(R[k])) { set_error("set_trace_bounds: bound %d is %g: every bound must be finite and not negative", k, R[k]); return CUADMM_ERR_INVALID; }
+  s->lb.R.assign(R, R + mat_num);
+  s->lb.R_dirty = true;
+  return CUADMM_OK;
+}
+// What every report on a point refuses before it touches the device ("The front of the point reports").  what: the results that
+// are not all-reduced; reads_A: the report reads A', C, b and the scaling constants, which a failed cuadmm_update_A leaves half updated.
+static int report_guard(const cuadmm_solver* s, const void* out, const char* who, const char* what, bool reads_A) {
+  if (!s || !s->initialised || !out) { set_error("%s: solver not initialised or null argument", who); return CUADMM_ERR_INVALID; }
+  if (s->world > 1 || s->comm_world > 1 || s->local_mode || s->group || s->in_group_call) {
+    set_error("%s: works on one rank (world = %d%s): its %s are not all-reduced", who, std::max(s->world, s->comm_world), s->group ? ", in-process group" : "", what);
+    return CUADMM_ERR_INVALID;
+  }
+  if (s->L <= 0) { set_error("%s: the problem has no svec slots", who); return CUADMM_ERR_INVALID; }
+  if (reads_A && s->factor_bad) { set_error("%s: the last cuadmm_update_A could not factor the new A A^T; the solver needs a successful cuadmm_update_A first", who); return CUADMM_ERR_FACTOR; }
+  return check_device(s->device);
+}
+// Each report: the guard, its own checks, its vectors (*_prepare), the point staged in them, the run.
+int cuadmm_lower_bound(cuadmm_solver* s, double o[8], double* per_block) {
+  int rc = report_guard(s, o, "lower_bound", "sums", true);
+  if (rc) return rc;
+  if (s->lb.R.empty()) { set_error("lower_bound: no trace bounds are set (cuadmm_set_trace_bounds)"); return CUADMM_ERR_INVALID; }
+  if ((rc = s->lb_prepare()) || (rc = s->stage_scaled_y(s->lb.ybuf.p, nullptr))) return rc;
+  return s->lb_report(o, per_block);
+}
+int cuadmm_get_gap_info(const cuadmm_solver* s, double o[8]) {
+  if (!s || !o) { set_error("get_gap_info: null"); return CUADMM_ERR_INVALID; }
+  o[0] = (double)s->lb.checks; o[1] = s->lb.best_lb; o[2] = (double)s->lb.best_iter; o[3] = s->lb.last_lb; o[4] = s->lb.last_g;
+  o[5] = s->lb.ms; o[6] = s->lb.bytes() + (s->lb.out_d.p ? s->btasks.bytes() + s->aux.bytes() : 0.0); o[7] = (double)s->lb.verdict_iter;
+  return CUADMM_OK;
+}
+int cuadmm_evaluate(cuadmm_solver* s, const double* X, const double* y, const double* S, double o[16], double* per_block) {
+  int rc = report_guard(s, o, "evaluate", "sums", true);
+  if (rc) return rc;
+  // before anything is uploaded: a passed vector with an entry that is not finite
+  const struct { const char* name; const double* v; long long n; } in[3] = {{"X", X, s->L}, {"y", y, s->m}, {"S", S, s->L}};
+  for (const auto& q : in)
+    for (long long i = 0; q.v && i < q.n; ++i)
+      if (!std::isfinite(q.v[i])) { set_error("evaluate: %s[%lld] is not finite", q.name, i); return CUADMM_ERR_INVALID; }
+  if ((rc = s->ev_prepare())) return rc;
+  // The point in the engine's scaled space and order, in vectors of the evaluation's own (the constants of materialise(), inverted, as
+  // cuadmm_init and cuadmm_solve(if_first = 0) apply them).  A null vector is the one its getter would return: behind a solve the
+  // iterate is held scaled and is read as it lies, otherwise it is in the caller's units (stage_scaled_y has the cases of y).
+  const double *xs = nullptr, *ss = nullptr;
+  if ((rc = s->ev_point(X, s->X, 1 / s->bscale, s->ev.xs, &xs)) || (rc = s->ev_point(S, s->S, 1 / s->Cscale, s->ev.ss, &ss)) ||
+      (rc = s->stage_scaled_y(s->ev.cons.p, y)))
+    return rc;
+  return s->ev_run(xs, ss, o, per_block);
+}
+int cuadmm_lambda_min(cuadmm_solver* s, int which, int steps, double o[8], double* per_block) {
+  int rc = report_guard(s, o, "lambda_min", "results", which == 2);
+  if (rc) return rc;
+  if (which < 0 || which > 2) { set_error("lambda_min: which = %d (0: X, 1: S, 2: C - A'y)", which); return CUADMM_ERR_INVALID; }
+  if (steps < 1 || steps > kLmStepsMax) { set_error("lambda_min: steps = %d, allowed are 1 to %d", steps, kLmStepsMax); return CUADMM_ERR_INVALID; }
+  if (which == 2 && !s->lb.R.empty() && s->lb.R.size() != s->blk_local.size()) {
+    set_error("lambda_min: %d trace bounds are set, the solver has %d blocks", (int)s->lb.R.size(), (int)s->blk_local.size());
+    return CUADMM_ERR_INVALID;
+  }
+  if ((rc = s->lm_prepare(which)) || (which == 2 && (rc = s->stage_scaled_y(s->lm.ybuf.p, nullptr)))) return rc;
+  return s->lm_run(which, steps, o, per_block);
+}
+int cuadmm_lowrank_size(const cuadmm_solver* s, int rmax, long long* count_out) {
+  if (!s || !s->initialised || !count_out) { set_error("lowrank_size: solver not initialised or null argument"); return CUADMM_ERR_INVALID; }
+  if (rmax < 1 || rmax > kMaxBlockSize) { set_error("lowrank_size: rmax = %d, allowed are 1 to %d", rmax, kMaxBlockSize); return CUADMM_ERR_INVALID; }
+  long long c = 0;
+  for (int n : s->blk_local)
+    if (n > 0) c += (long long)n * std::min(n, rmax);
+  *count_out = c;
+  return CUADMM_OK;
+}
+int cuadmm_lowrank(cuadmm_solver* s, int which, double tol, int rmax, double o[8], double* per_block, double* L_out, int* piv_out) {
+  int rc = report_guard(s, o, "lowrank", "results", false);
+  if (rc) return rc;
+  if (which < 0 || which > 1) { set_error("lowrank: which = %d (0: X, 1: S)", which); return CUADMM_ERR_INVALID; }
+  if (!(tol >= 0.0 && tol < 1.0)) { set_error("lowrank: tol = %g, allowed is 0 <= tol < 1", tol); return CUADMM_ERR_INVALID; }
+  if (rmax < 1 || rmax > kMaxBlockSize) { set_error("lowrank: rmax = %d, allowed are 1 to %d", rmax, kMaxBlockSize); return CUADMM_ERR_INVALID; }
+  if ((rc = s->lr_prepare(rmax))) return rc;
+  return s->lr_run(which, tol, o, per_block, L_out, piv_out);
+}
+int cuadmm_get_evaluate_info(const cuadmm_solver* s, double o[4]) {
+  if (!s || !o) { set_error("get_evaluate_info: null"); return CUADMM_ERR_INVALID; }
+  o[0] = (double)s->ev.calls; o[1] = s->ev.bytes() + (s->ev.out_d.p ? s->btasks.bytes() : 0.0); o[2] = s->ev.out_d.p ? s->aux.bytes() : 0.0; o[3] = s->ev.ms;
+  return CUADMM_OK;
+}
+int cuadmm_trace_bounds_detect(int vec_len, int con_num, const int* At_csc_col_ptrs, const int* At_csc_row_ids, const double* At_csc_vals,
+                               const int* b_indices, const double* b_vals, int b_nnz, const int* blk_vals, int mat_num, double* R_out) {
+  return lb_trace_bounds_detect(vec_len, con_num, At_csc_col_ptrs, At_csc_row_ids, At_csc_vals, b_indices, b_vals, b_nnz, blk_vals, mat_num, R_out);
+}
+
+}  // extern "C"

@@ -1,0 +1,174 @@
+// What the reports on a point own beside the iteration's state, and what the op hooks build on their own: the auxiliary projector, the
+// per-block task lists, the plans of cuadmm_lambda_min and cuadmm_lowrank.  Nothing here is read by the iteration.
+#pragma once
+#include <algorithm>
+#include <cmath>
+
+#include "dev_buf.h"
+#include "psd_plan.h"
+#include "block_reduce.h"
+#include "lambda_min.h"
+#include "lowrank.h"
+
+struct cuadmm_solver;
+
+namespace cuadmm {
+
+// The auxiliary projector of the infeasibility check and the lower bound ("Infeasibility certificates"): a plan beside the
+// iteration's, an svec-length input and output vector, b on the device where the engine keeps none there, a pair of events.  The two
+// users never run inside one another and the plan carries no result from one projection to the next, so one object serves both.
+struct AuxProj {
+  PsdPlan* plan = nullptr;           // built at the first projection: the solver's psd_* options, the full projection
+  DevBuf<double> in, out, bcopy;
+  double plan_bytes = 0;
+  DevEvent ev[2];
+  bool projected = false;            // inside the open bracket
+  int ensure(cuadmm_solver& s);      // vectors and events on first use; b, which may have changed, on every call
+  const double* b_dev(const cuadmm_solver& s) const;      // (engine_state.h, behind the solver's definition)
+  int project(cuadmm_solver& s, const double* from, double* to);
+  bool failed(hipStream_t st) const { return plan && plan->fail_count(st) > 0; }
+  // The bracket around one user's work on the stream.  end: the stream is drained; *ms between the two events; *bad: a projection
+  // inside the bracket was made and the plan's (cumulative) failure count is not zero -- the user words its own CUADMM_ERR_EIG
+  // (null for a user that projects nothing).
+  int begin(hipStream_t st) { projected = false; CUADMM_HIP_TRY(hipEventRecord(ev[0], st)); return CUADMM_OK; }
+  int end(hipStream_t st, float* ms, bool* bad) {
+    CUADMM_HIP_TRY(hipEventRecord(ev[1], st));
+    CUADMM_HIP_TRY(hipStreamSynchronize(st));
+    *ms = event_ms(ev[0], ev[1]);
+    if (bad) *bad = projected && failed(st);
+    return CUADMM_OK;
+  }
+  double bytes() const { return 8.0 * (double)(in.n + out.n + bcopy.n) + plan_bytes; }
+  ~AuxProj() { delete plan; }
+};
+
+// The per-block task lists of block_reduce.h on the device, for the lower bound and the evaluation: built from blk_local by whichever
+// of lb_prepare / ev_prepare runs first.  blk_local never changes after init, so cuadmm_update_A / cuadmm_update_bC leave them alone.
+// Each of the two reports these bytes with its own, as it does the auxiliary projector's.
+struct BlockTasksDev {
+  DevBuf<long long> off, len;
+  DevBuf<int> blk, wave, chunk, large;
+  int nwave = 0, nchunk = 0, nlarge = 0;
+  bool built = false;
+  int build(const int* blk_h, int nb, const int64_t* off_h /* null: consecutive */) {
+    std::vector<long long> o((size_t)nb), l((size_t)nb);
+    long long next = 0;
+    for (int k = 0; k < nb; ++k) { l[k] = blk_svec_len(blk_h[k]); o[k] = off_h ? (long long)off_h[k] : next; next += l[k]; }
+    BlockTasks t;
+    int rc;
+    if ((rc = build_block_tasks(nb, l.data(), &t)) || (rc = off.from(o)) || (rc = len.from(l)) || (rc = blk.from(std::vector<int>(blk_h, blk_h + nb))) ||
+        (rc = wave.from(t.wave)) || (rc = chunk.from(t.chunk)) || (rc = large.from(t.large)))
+      return rc;
+    nwave = t.nwave(); nchunk = t.nchunk(); nlarge = t.nlarge();
+    built = true;
+    return CUADMM_OK;
+  }
+  BlockTasksView view() const { return {off.p, len.p, blk.p, wave.p, chunk.p, large.p, nwave, nchunk, nlarge}; }
+  double bytes() const { return 8.0 * (double)(off.n + len.n) + 4.0 * (double)(blk.n + wave.n + chunk.n + large.n); }
+};
+
+// Certified lambda_min per block (cuadmm_lambda_min, cuadmm_op_block_lambda_min; lambda_min.h, DESIGN.md "Certified lambda_min"): the
+// size classes' block lists on the device, the global scratch of the blocks beyond the LDS (only where there are such), the results.
+// The offsets and sizes per block are the task lists' (btasks).  Nothing here is read by the iteration.
+struct LmPlan {
+  LmClass cls[kLmClasses];
+  DevBuf<int> list[kLmClasses];
+  DevBuf<long long> work_off;
+  DevBuf<double> work, out, ybuf, dpart;
+  PinnedBuf<double> h_out;
+  int nb = 0;
+  long long calls = 0;
+  int build(const int* blk_h, int nblk) {
+    long long w = 0;
+    int rc = lm_build_classes(nblk, blk_h, cls, &w);
+    if (rc) return rc;
+    for (int q = 0; q < kLmClasses; ++q)
+      if ((rc = list[q].from(cls[q].blocks))) return rc;
+    if ((rc = work_off.from(cls[kLmClasses - 2].work)) || (rc = work.alloc((size_t)w)) || (rc = h_out.alloc(kLmOut * (size_t)nblk + kBrSlots))) return rc;
+    nb = nblk;
+    return out.alloc(kLmOut * (size_t)nblk);      // last: marks the set as complete
+  }
+  // out (device) <- the four numbers per block of sign * v; one launch per class that has blocks
+  int run(const double* v, double sign, const long long* off_d, const int* blk_d, int steps, hipStream_t st) {
+    int rc;
+    for (int q = 0; q < kLmClasses; ++q)
+      if ((rc = launch_lambda_min(q, (int)cls[q].blocks.size(), cls[q].nmax, list[q].p, v, sign, off_d, blk_d, steps, work.p, work_off.p, out.p, st))) return rc;
+    return CUADMM_OK;
+  }
+  double bytes() const {
+    double b = 8.0 * (double)(work_off.n + work.n + out.n + ybuf.n + dpart.n);
+    for (const auto& l : list) b += 4.0 * (double)l.n;
+    return b;
+  }
+};
+
+// Rank and low-rank factor per block (cuadmm_lowrank, cuadmm_op_block_lowrank; lowrank.h, DESIGN.md "Low-rank factors"): the size
+// classes' block lists, the offsets of the blocks' factors and pivots for the rmax of the last call, the factor, pivot and result
+// buffers (they grow with rmax and are kept), a pair of events.  The offsets and sizes per block are the task lists' (btasks).  Nothing
+// here is read by the iteration.
+struct LrPlan {
+  LrClass cls[kLrClasses];
+  DevBuf<int> list[kLrClasses], piv;
+  DevBuf<long long> loff_d, poff_d;
+  DevBuf<double> Lbuf, out;
+  std::vector<long long> loff, poff;      // of rmax_now, nb + 1 entries each
+  int nb = 0, rmax_now = 0;
+  DevEvent ev[2];
+  long long calls = 0;
+  int prepare(const int* blk_h, int nblk, int rmax) {
+    if (out.p && rmax == rmax_now) return CUADMM_OK;
+    int rc = lr_build_classes(nblk, blk_h, rmax, cls, &loff, &poff);
+    if (rc) return rc;
+    const bool first = !out.p;
+    if (first) {
+      for (int q = 0; q < kLrClasses; ++q)
+        if ((rc = list[q].from(cls[q].blocks))) return rc;
+      if ((rc = loff_d.alloc((size_t)nblk + 1)) || (rc = poff_d.alloc((size_t)nblk + 1))) return rc;
+      for (auto& e : ev) if ((rc = e.create())) return rc;
+    }
+    rmax_now = 0;                           // (until the offsets on the device are this rmax's)
+    if ((rc = loff_d.upload(loff.data(), loff.size())) || (rc = poff_d.upload(poff.data(), poff.size()))) return rc;
+    if (Lbuf.n < (size_t)loff.back() + 1 && (rc = Lbuf.alloc((size_t)loff.back() + 1))) return rc;      // (+ 1: never empty)
+    if (piv.n < (size_t)poff.back() + 1 && (rc = piv.alloc((size_t)poff.back() + 1))) return rc;
+    nb = nblk;
+    rmax_now = rmax;
+    return first ? out.alloc(kLrOut * (size_t)nblk) : CUADMM_OK;      // last: marks the set as complete
+  }
+  // out, Lbuf, piv (device) <- the kernel's results on sign * v; one launch per class that has blocks
+  int run(const double* v, double sign, const long long* off_d, const int* blk_d, double tol, hipStream_t st) {
+    int rc;
+    for (int q = 0; q < kLrClasses; ++q)
+      if ((rc = launch_lowrank(q, (int)cls[q].blocks.size(), cls[q].nmax, list[q].p, v, sign, off_d, blk_d, tol, rmax_now, loff_d.p, poff_d.p, Lbuf.p, piv.p,
+                               out.p, st)))
+        return rc;
+    return CUADMM_OK;
+  }
+  // The results behind a drained stream, on the host and in the units `unit` times the vector's: per_block (kLrOut nb, not null); L_out
+  // (may be null): loff.back() doubles; piv_out (may be null): as many ints, block k's min(n_k, rmax) pivots at loff[k], -1 elsewhere.
+  int fetch(double unit, double* per_block, double* L_out, int* piv_out) {
+    int rc;
+    if (nb > 0 && (rc = staged_d2h(per_block, out.p, sizeof(double) * kLrOut * (size_t)nb))) return rc;
+    for (int k = 0; k < nb; ++k)
+      for (int q = 1; q <= 3; ++q) per_block[kLrOut * (size_t)k + q] *= unit;
+    const size_t count = (size_t)loff.back();
+    if (L_out && count > 0) {
+      if ((rc = staged_d2h(L_out, Lbuf.p, sizeof(double) * count))) return rc;
+      const double root = std::sqrt(unit);
+      for (size_t e = 0; unit != 1.0 && e < count; ++e) L_out[e] *= root;
+    }
+    if (piv_out && count > 0) {
+      std::vector<int> h((size_t)poff.back() + 1);
+      if ((rc = staged_d2h(h.data(), piv.p, sizeof(int) * (size_t)poff.back()))) return rc;
+      std::fill(piv_out, piv_out + count, -1);
+      for (int k = 0; k < nb; ++k) std::copy(h.begin() + poff[k], h.begin() + poff[k + 1], piv_out + loff[k]);
+    }
+    return CUADMM_OK;
+  }
+  double bytes() const {
+    double b = 8.0 * (double)(loff_d.n + poff_d.n + Lbuf.n + out.n) + 4.0 * (double)piv.n;
+    for (const auto& l : list) b += 4.0 * (double)l.n;
+    return b;
+  }
+};
+
+}  // namespace cuadmm

@@ -751,7 +751,7 @@ int launch_scale(double* v, long long n, double s, hipStream_t st) {
 }
 
 // ------------------------------------------------------------------------------------------
-// cuadmm_update_bC (engine.hip): new b / C on a factored solver.  Every element goes through the rounded operations of
+// cuadmm_update_bC (engine_update.hip): new b / C on a factored solver.  Every element goes through the rounded operations of
 // materialise() followed by init's scaling, in that order, so the updated solver holds the bits a fresh init would hold.
 // ------------------------------------------------------------------------------------------
 // One streaming pass over the rank's svec: X <- (X x1) x2, S <- (S s1) s2 (ZERO: both <- 0, a cold start), C <- 0 when it is
@@ -840,7 +840,7 @@ int launch_closed_patch_b(ClosedRec* rec, int nslots, const double* b, hipStream
 }
 
 // ------------------------------------------------------------------------------------------
-// cuadmm_update_A (engine.hip): new values of A on the pattern of init.  The host normalises this rank's values with init's arithmetic
+// cuadmm_update_A (engine_update.hip): new values of A on the pattern of init.  The host normalises this rank's values with init's arithmetic
 // and uploads them once, in the caller's order; this kernel writes the value arrays of both device matrices from them through two index
 // maps (CSR slot -> position in the upload, built at the first update).  Stores are streaming and 16 bytes wide wherever the target is
 // 16-byte aligned (a leading element of a misaligned array and an odd last one go alone); the loads are the gather.  The long-row and

@@ -1,4 +1,4 @@
-"""numpy twin of the infeasibility check (option "infeas_check": DESIGN.md, "Infeasibility certificates"; csrc/engine.hip,
+"""numpy twin of the infeasibility check (option "infeas_check": DESIGN.md, "Infeasibility certificates"; csrc/engine_reports.hip,
 infeas_step) and the small problems its tests run on.
 
 The twin is oracle.cuadmm_oracle.OracleSolver with a ``stage_hook`` at the end of every iteration: at iteration p it takes the

@@ -1,5 +1,5 @@
 """numpy twin of the certified lower bound (cuadmm_lower_bound, option "gap_check": DESIGN.md, "Certified lower bound";
-csrc/engine.hip: lb_eval, lb_step) and problems with a known optimum.
+csrc/engine_reports.hip: lb_eval, lb_step) and problems with a known optimum.
 
 The bound at any y, in the caller's units, with S^ = C - A'y:
 

@@ -1,4 +1,4 @@
-"""cuadmm_evaluate on the GPU (include/cuadmm_amd.h; DESIGN.md, "Evaluation of a point"; csrc/evaluate.hip; csrc/engine.hip: ev_run):
+"""cuadmm_evaluate on the GPU (include/cuadmm_amd.h; DESIGN.md, "Evaluation of a point"; csrc/evaluate.hip; csrc/engine_reports.hip: ev_run):
 the per-block statistics kernel against numpy, the report against the longdouble twin (tests/_evaluate_twin.py) at a known optimum,
 at known violations, at the engine's own iterate and in the engine's other plans, its absence of side effects, the refusals and the
 command line.
@@ -373,7 +373,7 @@ def test_report_after_updates_and_with_gap_check():
 def test_the_report_and_the_bound_share_one_task_list():
     """Fixture B (odd offsets, a free block, a wavefront-owned block) at one random point, set with set_XyS: a handle that runs lower_bound()
     and then evaluate(), one that runs them the other way round, and two fresh handles with one call each.  The per-block task lists
-    on the device are built once per handle by whichever call comes first (csrc/engine.hip: BlockTasksDev): every number but ms is the
+    on the device are built once per handle by whichever call comes first (csrc/report_plans.h: BlockTasksDev): every number but ms is the
     same to the bit in all three, and each call reports the bytes it would report alone, the lists' included.  The bound's figure
     contains the auxiliary projector's, whose plan is sized from the device's free memory around its build and is no function of the
     handle alone: it is compared without them (evaluate_info's aux_bytes; the lone bound's handle evaluates afterwards to learn them)."""
@@ -440,7 +440,7 @@ def _one_y(fx, a, b, what):
 
 @pytest.mark.parametrize("name", ["A", "closed"])
 def test_the_three_reports_read_one_y_in_every_resident_state(name):
-    """lower_bound(), evaluate() and lambda_min("dual") stage the resident y through one routine (csrc/engine.hip: stage_scaled_y), whose
+    """lower_bound(), evaluate() and lambda_min("dual") stage the resident y through one routine (csrc/engine_reports.hip: stage_scaled_y), whose
     branches are the states y can be in: in the caller's units on the host (1: behind set_XyS), scaled behind a solve (2; on the host
     with the y-solve there: fixture A, on the device with it there: 256 blocks of 8, test_report_on_closed_blocks), in the caller's
     units on the device only (3: behind update_bC(keep_iterate) on the device y-solve, before any getter) and on the host again (4: a

@@ -1,5 +1,5 @@
 """Option "infeas_check": certificates of infeasibility from iterate differences ("Infeasibility certificates";
-csrc/infeas.hip, csrc/engine.hip: infeas_step).
+csrc/infeas.hip, csrc/engine_reports.hip: infeas_step).
 
 Op level: the roll kernel against numpy (bit-equal differences, sums against math.fsum).  Engine level: the four infeasible
 problems of tests/_infeas_twin.py against the numpy twin under both switch_admm settings; the returned certificates against the

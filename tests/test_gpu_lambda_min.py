@@ -1,5 +1,5 @@
 """Certified lambda_min on the GPU (include/cuadmm_amd.h: cuadmm_lambda_min, cuadmm_op_block_lambda_min; DESIGN.md, "Certified
-lambda_min"; csrc/lambda_min.hip; csrc/engine.hip: lm_run): the kernel on every size class and matrix family of
+lambda_min"; csrc/lambda_min.hip; csrc/engine_reports.hip: lm_run): the kernel on every size class and matrix family of
 tests/_lambda_min_twin.py against the two properties stated there, then the solver entry: its three matrices, LB_lambda against
 cuadmm_lower_bound and a known optimum, the DIMACS measures against cuadmm_evaluate's Frobenius ones, no side effects, refusals, and the
 three front ends.

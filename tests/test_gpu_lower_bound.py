@@ -1,5 +1,5 @@
 """The certified lower bound from trace bounds on the GPU ("Certified lower bound"; csrc/lower_bound.hip;
-csrc/engine.hip: lb_eval, lb_step): the per-block norm kernels against numpy, cuadmm_lower_bound against the numpy twin
+csrc/engine_reports.hip: lb_eval, lb_step): the per-block norm kernels against numpy, cuadmm_lower_bound against the numpy twin
 (tests/_lower_bound_twin.py) on problems with a known optimum p*, its absence of side effects, option "gap_check" against the twin's
 rule, the refusals and the command line.
 
@@ -244,7 +244,7 @@ def test_gap_check_without_a_verdict_is_the_run_with_the_option_off(name):
 
 def test_the_bound_and_the_infeasibility_check_share_one_projector():
     """Fixture A (a free block, PSD blocks of the register, one-wavefront, LDS and cluster classes) with trace bounds and infeas_check = 10:
-    the check and cuadmm_lower_bound project through the same auxiliary plan and work vectors (csrc/engine.hip: AuxProj).  Neither
+    the check and cuadmm_lower_bound project through the same auxiliary plan and work vectors (csrc/report_plans.h: AuxProj).  Neither
     sees the other: the trajectory is that of a handle with neither feature, both bounds are those of a handle without the check.
     stop_tol = 0: in each solve every multiple of the period behind the first (the snapshot) is a check, 5 of them.  That one of the
     first five passed a sign test and projected shows in the bytes: the plan is built at the first projection, and without it the check holds

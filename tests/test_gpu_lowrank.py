@@ -1,5 +1,5 @@
 """Per-block pivoted Cholesky on the GPU (include/cuadmm_amd.h: cuadmm_lowrank, cuadmm_lowrank_size, cuadmm_op_block_lowrank; DESIGN.md,
-"Low-rank factors"; csrc/lowrank.hip; csrc/engine.hip: lr_run): the kernel on every size class and matrix family of
+"Low-rank factors"; csrc/lowrank.hip; csrc/engine_reports.hip: lr_run): the kernel on every size class and matrix family of
 tests/_lowrank_twin.py against the four statements checked there, then the solver entry: the kernel's bits on a fresh solver, the
 statements behind a solve in the scaled state, no side effects, refusals, null outputs, the bytes held, and the three front ends.
 

@@ -1,4 +1,4 @@
-"""cuadmm_update_A: new values of A on the pattern of a factored solver (include/cuadmm_amd.h; csrc/engine.hip, the value pass in
+"""cuadmm_update_A: new values of A on the pattern of a factored solver (include/cuadmm_amd.h; csrc/engine_update.hip, the value pass in
 csrc/vec_kernels.hip, the host refactorisation in csrc/aat_ldlt.cpp).  The contract is "the state cuadmm_init with the new values and
 the current iterate would have left", and the engine is bit-reproducible, so the check is array_equal against a fresh init.
 

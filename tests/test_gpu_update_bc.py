@@ -1,4 +1,4 @@
-"""cuadmm_update_bC: new b and / or C on a factored solver (include/cuadmm_amd.h; csrc/engine.hip, the update kernels in
+"""cuadmm_update_bC: new b and / or C on a factored solver (include/cuadmm_amd.h; csrc/engine_update.hip, the update kernels in
 csrc/vec_kernels.hip).  The contract is "the state cuadmm_init with the new data and the current iterate would have left", and
 the engine is bit-reproducible, so the main check is array_equal against a freshly initialised solver.
 
