@@ -75,6 +75,8 @@ PROTOTYPES = {
     "cuadmm_sign_sched_simulate_hint": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, c_double_p, c_int_p]),
     "cuadmm_sign_sched_simulate": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_double_p]),
     "cuadmm_op_psd_project_ex": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "cuadmm_op_psd_project_opts": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_char_p), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "cuadmm_psd_sign_groups": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_char_p), C.c_void_p, C.c_int, C.c_void_p, C.c_int, c_int_p]),
     "cuadmm_op_psd_project_steps": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "cuadmm_get_info_iter_num": (C.c_int, [C.c_void_p]),
     "cuadmm_get_info_array": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int]),

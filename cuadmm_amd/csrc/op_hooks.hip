@@ -232,6 +232,57 @@ int cuadmm_op_psd_project_ex(const double* Xb, double* Xproj, const int* blk_hos
   return CUADMM_OK;
 }
 
+// the default options (NOT the environment's) changed by opt_keys[n_opts] = opt_vals[n_opts]
+static int psd_options_from_pairs(const char* who, const char* const* opt_keys, const double* opt_vals, int n_opts, PsdOptions& opt) {
+  if (n_opts < 0 || (n_opts > 0 && (!opt_keys || !opt_vals))) { set_error("%s: bad arguments", who); return CUADMM_ERR_INVALID; }
+  opt = PsdOptions();
+  for (int i = 0; i < n_opts; ++i)
+    if (!opt_keys[i] || !opt.set(opt_keys[i], opt_vals[i])) { set_error("%s: unknown option %s", who, opt_keys[i] ? opt_keys[i] : "(null)"); return CUADMM_ERR_INVALID; }
+  return CUADMM_OK;
+}
+
+// cuadmm_op_psd_project_ex on a plan whose options are PsdOptions() changed by the pairs given: no environment variable reaches it, so a
+// test runs the variant it names
+int cuadmm_op_psd_project_opts(const double* Xb, double* Xproj, const int* blk_host, int mat_num, int eig_rank, const char* const* opt_keys,
+                               const double* opt_vals, int n_opts, int* steps_dev, void* stream) {
+  if (!blk_host || mat_num < 0 || eig_rank < 0) { set_error("psd_project_opts: bad arguments"); return CUADMM_ERR_INVALID; }
+  PsdPlan plan;
+  int rc = psd_options_from_pairs("psd_project_opts", opt_keys, opt_vals, n_opts, plan.opt);
+  if (rc) return rc;
+  plan.eig_rank = eig_rank;
+  if ((rc = plan.build(blk_host, mat_num))) return rc;
+  if (steps_dev) {
+    CUADMM_HIP_TRY(hipMemsetAsync(steps_dev, 0, sizeof(int) * (size_t)mat_num, (hipStream_t)stream));
+    plan.d_steps = steps_dev;
+    plan.sign.d_steps = steps_dev;
+  }
+  if ((rc = plan.project(Xb, Xproj, (hipStream_t)stream))) return rc;
+  int fails = plan.fail_count((hipStream_t)stream);   // synchronises the stream
+  if (fails != 0) { set_error("psd_project_opts: %d blocks hit the QL sweep cap", fails); return CUADMM_ERR_EIG; }
+  return CUADMM_OK;
+}
+
+// host only: the sign path's groups of these blocks, merged ones first (they share the first launch), then the others in the order they run
+int cuadmm_psd_sign_groups(const int* blk_host, int mat_num, const char* const* opt_keys, const double* opt_vals, int n_opts, int* out, int cap,
+                           int* n_groups_out) {
+  if (!blk_host || mat_num < 0 || !out || cap < 0 || !n_groups_out) { set_error("psd_sign_groups: bad arguments"); return CUADMM_ERR_INVALID; }
+  PsdPlan plan;
+  int rc = psd_options_from_pairs("psd_sign_groups", opt_keys, opt_vals, n_opts, plan.opt);
+  if (rc || (rc = plan.build_host(blk_host, mat_num))) return rc;
+  std::vector<int> members, ids;
+  for (int k = 0; k < mat_num; ++k)
+    if (blk_host[k] >= plan.ranges.sign_min) members.push_back(k);
+  SignPsd::Sizes sz;
+  plan.sign.opt = plan.opt;
+  plan.sign.build_host(blk_host, members, ids, sz);
+  *n_groups_out = (int)plan.sign.groups.size();
+  if (*n_groups_out > cap) { set_error("psd_sign_groups: %d groups, room for %d", *n_groups_out, cap); return CUADMM_ERR_INVALID; }
+  for (int merged = 1; merged >= 0; --merged)
+    for (const SignPsd::Group& g : plan.sign.groups)
+      if ((int)g.merged == merged) { plan.sign.group_info(g, out); out += SignPsd::kGroupInfo; }
+  return CUADMM_OK;
+}
+
 // own: the test hooks' non-blocking stream (cuadmm_psd_plan_project_ordered), made on first use
 struct cuadmm_psd_plan {
   PsdPlan plan;

@@ -39,7 +39,16 @@ struct SignPsd {
                                              // not fused counts in set 0 and zeroes it at its start
   size_t bar_stride = 0;                     // members_cap (all groups' counts): distance between the two counter sets
   int* d_xcc = nullptr;                      // [member][tile]: XCD of every workgroup of the one-launch variant (run-time check)
+  // what build() allocates, as build_host() worked it out
+  struct Sizes { size_t elems = 1, members_cap = 1, max_cols = 1, cs_total = 1; int n_merged = 0; };
+  // the part of build() that needs no device: the groups (padding, the psd_lg_pad32 shrink, chunks of psd_sign_ws_mb, which of them share
+  // one launch, every offset), the members group after group, and the sizes of the buffers
+  void build_host(const int* blk, const std::vector<int>& members, std::vector<int>& ids, Sizes& sz);
   int build(const int* blk, const std::vector<int>& members);
+  // test hook (cuadmm_psd_sign_groups): N, count, merged, slot, tile, ntiles, decide_kernel, cluster, spread, cluster_wgs, superblock, fused --
+  // from the functions the launches themselves ask
+  static constexpr int kGroupInfo = 12;
+  void group_info(const Group& g, int* out) const;
   int launch_group(Group& g, const double* in, double* out, const long long* boff, const int* bn, int* d_fail, hipStream_t st, bool poll);
   void cluster_add(ClusterMulti& cm, const Group& g, int* d_fail, int max_steps) const;     // appends g to a one-launch set
   int cluster_run(ClusterMulti& cm, bool prologue, const double* in, double* out, const long long* boff, const int* bn, int* d_fail, hipStream_t st);

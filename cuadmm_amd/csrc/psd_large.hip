@@ -760,6 +760,10 @@ static bool lg_small_tiles(bool mirror, int N, int count, int tile_force = 0) {
   // 1.41 -> 1.02 ms)
   return tile_force ? tile_force == 32 : (mirror && N >= 128 && tiles64 < 1300);
 }
+// one big matrix: the tile sequence walks 8 x 8-tile super-blocks (lg_gemm_sym_body, sb > 0)
+static bool lg_super_blocks(int count, int nb) { return count == 1 && nb >= 16; }
+// the one-launch kernel does its own prologue and epilogue (psd_lg_fuse; only where the one-launch prologue applies at all, N <= 512)
+static bool lg_fused(const PsdOptions& opt, int N) { return opt.lg_fuse != 0 && !opt.debug && N <= 512; }
 // how a group's sign iteration is enqueued: tiles per member, decision as a launch of its own, everything in one launch
 struct LgPath { int ntiles; bool decide_kernel, cluster; int cluster_wgs, spread; };
 
@@ -768,8 +772,8 @@ static int lg_gemm_mirror(int N, int count, const double* A, const double* B, do
                           hipStream_t st, const SignArgs& sa, const double* B2, int tile_force = 0) {
   const bool small_tiles = lg_small_tiles(true, N, count, tile_force);
   const int nb = small_tiles ? N / 32 : N / 64;
-  if (count == 1 && nb >= 16) {
-    const int sb = (nb + 7) / 8;                               // 8x8-tile super-blocks per direction
+  if (lg_super_blocks(count, nb)) {
+    const int sb = (nb + 7) / 8;                             // 8x8-tile super-blocks per direction
     if (small_tiles) hipLaunchKernelGGL((lg_gemm_sym_kernel<true, 32, 32, ROLE>), dim3(sb * (sb + 1) / 2 * 64), dim3(256), 0, st, N, A, B, alpha, beta, E, C, sb, sa, B2);
     else hipLaunchKernelGGL((lg_gemm_sym_kernel<true, 64, 16, ROLE>), dim3(sb * (sb + 1) / 2 * 64), dim3(256), 0, st, N, A, B, alpha, beta, E, C, sb, sa, B2);
   } else {
@@ -804,14 +808,15 @@ __global__ void lg_steps_out_kernel(SignArgs sa, const int* __restrict__ ids, in
 // ------------------------------------------------------------------------------------------
 // Planner: groups by padded size, chunks of bounded workspace
 // ------------------------------------------------------------------------------------------
-int SignPsd::build(const int* blk, const std::vector<int>& members) {
-  release();
-  if (members.empty()) return CUADMM_OK;
+void SignPsd::build_host(const int* blk, const std::vector<int>& members, std::vector<int>& ids, Sizes& sz) {
+  groups.clear();
+  ids.clear();
+  sz = Sizes{};
+  if (members.empty()) return;
   size_t ws_cap = (size_t)8 << 30;   // bytes of workspace (4 matrices per member); 288 GB of HBM make this generous
   ws_cap = (size_t)std::max(1, opt.sign_ws_mb) << 20;
   std::map<int, std::vector<int>> by_pad;
   for (int k : members) by_pad[lg_pad(blk[k])].push_back(k);
-  std::vector<int> ids;
   size_t max_cols = 0;
   for (auto& kv : by_pad) {
     int N = kv.first;
@@ -885,14 +890,31 @@ int SignPsd::build(const int* blk, const std::vector<int>& members) {
     }
   size_t n_members = 0;                         // per-member state: every group its own range
   for (Group& g : groups) { g.mem_off = (int)n_members; n_members += (size_t)g.count; }
-  const size_t elems = std::max<size_t>(max_elems + side_elems, 1), members_cap = std::max<size_t>(n_members, 1);
+  size_t cs_total = 0;
+  for (Group& g : groups) { g.cs_off = cs_total; cs_total += (size_t)g.count * (size_t)g.N * LG_CS_ROWS; }
+  part_half = max_part + side_part;
+  sz.elems = std::max<size_t>(max_elems + side_elems, 1);
+  sz.members_cap = std::max<size_t>(n_members, 1);
+  sz.max_cols = std::max<size_t>(max_cols, 1);
+  sz.cs_total = std::max<size_t>(cs_total, 1);
+  sz.n_merged = n_merged;
+}
+
+int SignPsd::build(const int* blk, const std::vector<int>& members) {
+  release();
+  if (members.empty()) return CUADMM_OK;
+  std::vector<int> ids;
+  Sizes sz;
+  build_host(blk, members, ids, sz);
+  const size_t elems = sz.elems, members_cap = sz.members_cap;
+  const int n_merged = sz.n_merged;
   CUADMM_HIP_TRY(hipMalloc(&d_ids, sizeof(int) * ids.size()));
   { int rc_ = staged_h2d(d_ids, ids.data(), sizeof(int) * ids.size()); if (rc_) return rc_; }
   CUADMM_HIP_TRY(hipMalloc(&X0, sizeof(double) * elems));
   CUADMM_HIP_TRY(hipMalloc(&S, sizeof(double) * elems));
   CUADMM_HIP_TRY(hipMalloc(&Y, sizeof(double) * elems));
   CUADMM_HIP_TRY(hipMalloc(&T, sizeof(double) * elems));
-  CUADMM_HIP_TRY(hipMalloc(&colsum, sizeof(double) * std::max<size_t>(max_cols, 1)));
+  CUADMM_HIP_TRY(hipMalloc(&colsum, sizeof(double) * sz.max_cols));
   CUADMM_HIP_TRY(hipMalloc(&scale, sizeof(double) * members_cap));
   CUADMM_HIP_TRY(hipMalloc(&d_state, sizeof(SignDevState) * 2 * members_cap));
   CUADMM_HIP_TRY(hipMalloc(&d_done, sizeof(SignDone) * members_cap));
@@ -900,14 +922,9 @@ int SignPsd::build(const int* blk, const std::vector<int>& members) {
   CUADMM_HIP_TRY(hipMalloc(&d_bar, sizeof(unsigned) * 2 * members_cap));
   CUADMM_HIP_TRY(hipMemset(d_bar, 0, sizeof(unsigned) * 2 * members_cap));
   bar_stride = members_cap;
-  {
-    size_t cs_total = 0;
-    for (Group& g : groups) { g.cs_off = cs_total; cs_total += (size_t)g.count * (size_t)g.N * LG_CS_ROWS; }
-    CUADMM_HIP_TRY(hipMalloc(&colsum_f, sizeof(double) * std::max<size_t>(cs_total, 1)));
-  }
+  CUADMM_HIP_TRY(hipMalloc(&colsum_f, sizeof(double) * sz.cs_total));
   CUADMM_HIP_TRY(hipMalloc(&d_xcc, sizeof(int) * (size_t)(kClusterXccStride) * (size_t)(1 + n_merged)));
   CUADMM_HIP_TRY(hipHostMalloc(&h_group, sizeof(int) * 2, hipHostMallocDefault));
-  part_half = max_part + side_part;
   CUADMM_HIP_TRY(hipMalloc(&d_part, sizeof(double) * 2 * std::max<size_t>(part_half, 1)));   // p1 | p2 (two parities)
   return CUADMM_OK;
 }
@@ -937,6 +954,14 @@ static LgPath lg_path(const PsdOptions& opt, int N, int cnt) {
   p.spread = ((cnt + 7) / 8) * p.ntiles > 96 ? 1 : 0;
   p.cluster_wgs = p.spread ? cnt * p.ntiles : 8 * ((cnt + 7) / 8) * p.ntiles;
   return p;
+}
+
+void SignPsd::group_info(const Group& g, int* out) const {
+  const LgPath p = lg_path(opt, g.N, g.count);
+  const int tile = lg_small_tiles(true, g.N, g.count, opt.lg_tile) ? 32 : 64;
+  const int v[kGroupInfo] = {g.N, g.count, g.merged ? 1 : 0, g.slot, tile, p.ntiles, p.decide_kernel ? 1 : 0, p.cluster ? 1 : 0, p.spread, p.cluster_wgs,
+                             lg_super_blocks(g.count, g.N / tile) ? 1 : 0, lg_fused(opt, g.N) ? 1 : 0};
+  std::copy(v, v + kGroupInfo, out);
 }
 
 // out = svec(P_+(smat(in))) for every member block; boff / bn are the plan's device arrays (all blocks).  Asynchronous.
@@ -977,7 +1002,7 @@ void SignPsd::cluster_add(ClusterMulti& cm, const Group& g, int* d_fail, int max
   sa.step = 0;
   // fused prologue / epilogue (psd_lg_fuse; only where the one-launch prologue applies at all, N <= 512): this projection counts in set
   // g.bar_par of the group's counters and zeroes the other one.  A run that is not fused counts in set 0 and zeroes it at its start.
-  const bool fused = opt.lg_fuse != 0 && !opt.debug && g.N <= 512;
+  const bool fused = lg_fused(opt, g.N);
   const int par = fused ? g.bar_par : 0;
   if (fused) g.bar_par ^= 1;
   sa.bar = d_bar + (size_t)par * bar_stride + g.mem_off;

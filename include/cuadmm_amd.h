@@ -690,6 +690,18 @@ int cuadmm_psd_plan_ranges(const int* blk_host, int mat_num, int eig_rank, int t
  * copied through; eig_rank > 0 keeps only the eig_rank largest eigenvalues of every PSD block: V diag(max(W,0) * mask) V^T with
  * the mask of get_eig_rank_mask.cu:13-37 (dense_scalar.cu:51-57) -- computed through the eigensolver kernels. */
 int cuadmm_op_psd_project_ex(const double* Xb, double* Xproj, const int* blk_host, int mat_num, int eig_rank, int* steps_dev, void* stream);
+/* Test hook: cuadmm_op_psd_project_ex on a plan whose options are the built-in defaults changed by opt_keys[n_opts] = opt_vals[n_opts]
+ * ("psd_*"; an unknown key is an error).  The environment is NOT consulted, so no variable changes the kernel variant a test names. */
+int cuadmm_op_psd_project_opts(const double* Xb, double* Xproj, const int* blk_host, int mat_num, int eig_rank, const char* const* opt_keys,
+                               const double* opt_vals, int n_opts, int* steps_dev /* may be NULL */, void* stream);
+/* Test hook, host only (no device is touched): the groups the batched-GEMM matrix-sign path forms of these blocks under the default
+ * options changed by the pairs given -- the groups that share one launch first, then the others in the order they run.  out: 12 ints
+ * per group, room for cap groups (more is an error; *n_groups_out is set either way): padded size N, members, merged (shares the
+ * one launch of several padded sizes), slot, tile (32 | 64), tiles per member, decision kernel, one-launch kernel, spread (its
+ * workgroups in plain order over the chip), grid of the one-launch kernel, super-block tile order (one member, >= 16 tiles per side),
+ * fused (psd_lg_fuse and N <= 512: the one-launch kernel's own prologue and epilogue). */
+int cuadmm_psd_sign_groups(const int* blk_host, int mat_num, const char* const* opt_keys, const double* opt_vals, int n_opts, int* out, int cap,
+                           int* n_groups_out);
 /* Same, also returning how many Newton-Schulz steps the adaptive matrix-sign schedule took per block (device int array of
  * mat_num entries, 0 for blocks served by the eigensolver kernels); developer/diagnostic entry. */
 int cuadmm_op_psd_project_steps(const double* Xb, double* Xproj, const int* blk_host, int mat_num, int* steps_dev, void* stream);

@@ -10,13 +10,28 @@ from cuadmm_amd._lib import check
 from cuadmm_amd.devbuf import Dev  # noqa: E402,F401  (the tests' device buffers are the package's)
 
 
-def psd_project_gpu(x, blk, eig_rank=0):
+def opt_pairs(opts):
+    """{"psd_*": value} -> (keys, vals, n) as the option-taking hooks expect them"""
+    keys = (C.c_char_p * max(len(opts), 1))(*[k.encode() for k in opts])
+    vals = np.array(list(opts.values()) + [0.0], np.float64)
+    return keys, vals, len(opts)
+
+
+def psd_project_gpu(x, blk, eig_rank=0, opts=None, steps=False):
+    """opts: None = the plan's options come from the environment (cuadmm_op_psd_project_ex); a dict (an empty one too) = the built-in
+    defaults changed by it and nothing else (cuadmm_op_psd_project_opts).  steps: -> (proj, Newton-Schulz steps per block)"""
     lib = cuadmm_amd.load()
     blk = np.ascontiguousarray(blk, dtype=np.int32)
     din = Dev(np.ascontiguousarray(x, dtype=np.float64))
     dout = Dev(shape=(x.size,), dtype=np.float64)
-    check(lib.cuadmm_op_psd_project_ex(din.ptr, dout.ptr, blk.ctypes.data_as(C.c_void_p), int(blk.size), int(eig_rank), None, None))
-    return dout.get()
+    dst = Dev(np.zeros(max(int(blk.size), 1), np.int32)) if steps else None
+    if opts is None:
+        check(lib.cuadmm_op_psd_project_ex(din.ptr, dout.ptr, blk.ctypes.data_as(C.c_void_p), int(blk.size), int(eig_rank), dst.ptr if steps else None, None))
+    else:
+        keys, vals, n = opt_pairs(opts)
+        check(lib.cuadmm_op_psd_project_opts(din.ptr, dout.ptr, blk.ctypes.data_as(C.c_void_p), int(blk.size), int(eig_rank), keys,
+                                             vals.ctypes.data_as(C.c_void_p), n, dst.ptr if steps else None, None))
+    return (dout.get(), dst.get()[:blk.size]) if steps else dout.get()
 
 
 def batch_eig_gpu(mats):
@@ -351,6 +366,30 @@ def plan_matrix(n, kind, rng):
         return U @ U.T + 1e-12 * (G + G.T)
     from tests.test_gpu_psd import _spectrum_matrix          # (that module imports this one)
     return _spectrum_matrix(n, kind, rng)
+
+
+# The launch variants of the batched-GEMM sign path (csrc/psd_large.hip) as tests/test_gpu_sign_variants.py forces them: name -> options (on top
+# of the built-in defaults), block lists (the smallest shapes that reach the variant), spectrum families, and whether the group runs the
+# multi-launch chain (ROLE 1 / 2 | 4 / 3) -- there the final product reads S or T by the parity of the step count, and both must occur.
+# tests/test_sign_groups_host.py pins on the CPU that every (blk, opts) pair below reaches the variant it names.
+_FOUR = ("randn", "lowrank", "graded", "clustered")
+SIGN_VARIANTS = {
+    "tile64_inline": dict(opts={"psd_lg_tile": 64}, blks=[[65], [129], [100, 100, 128]], kinds=FAMILIES, multi=True),
+    "tile64_decide": dict(opts={"psd_lg_tile": 64, "psd_lg_decide": 2}, blks=[[65], [129, 192]], kinds=FAMILIES, multi=True),
+    "tile32_inline": dict(opts={"psd_lg_cluster": 0}, blks=[[65], [270], [130, 192]], kinds=FAMILIES, multi=True),
+    "tile32_decide": dict(opts={"psd_lg_cluster": 0, "psd_lg_decide": 2}, blks=[[65], [270]], kinds=FAMILIES, multi=True),
+    "default_window": dict(opts={}, blks=[[720], [768]], kinds=_FOUR, multi=True),
+    "inline_forced": dict(opts={"psd_lg_decide": 1}, blks=[[800]], kinds=("randn", "graded"), multi=True),
+    "superblock32": dict(opts={"psd_lg_cluster": 0}, blks=[[512], [520]], kinds=_FOUR, multi=True),
+    "superblock64": dict(opts={"psd_lg_tile": 64}, blks=[[1024], [1030]], kinds=("randn", "lowrank", "graded"), multi=True),
+    "no_pad32": dict(opts={"psd_lg_pad32": 0}, blks=[[270], [410]], kinds=FAMILIES, multi=False),
+}
+SIGN_WS_CHUNKS = dict(opts={"psd_sign_ws_mb": 1}, blks=[[100] * 5, [150] * 3])
+SIGN_NO_POLL = dict(opts={"psd_lg_cluster": 0, "psd_sign_sync": 0}, opts_poll={"psd_lg_cluster": 0, "psd_sign_sync": 1}, blk=[65, 100, 270])
+SIGN_STEP_CAP = [({"psd_lg_cluster": 0}, [65, 100, 270]), ({}, [100, 128])]
+SIGN_NON_FINITE = [({"psd_lg_cluster": 0}, [100, 65]), ({"psd_lg_tile": 64}, [100, 65]), ({}, [720])]
+SIGN_ZERO_BLOCK = [({"psd_lg_tile": 64}, [100, 65]), ({"psd_lg_cluster": 0}, [100, 65]), ({"psd_lg_cluster": 0, "psd_lg_decide": 2}, [100, 65])]
+SIGN_MIXED_CALL = dict(opts={}, blk=[65, 700, 130, 130, 40, 8, 700])
 
 
 def block_scale(k):

@@ -459,3 +459,74 @@ def test_project_every_mid_size_one_wavefront_per_block(kind, wave4_min, monkeyp
         nrm = max(np.linalg.norm(M, 2), 1e-300)
         assert np.max(np.abs(got[sl] - ref[sl])) <= 2e-12 * nrm * np.sqrt(2), (k, M.shape[0])
     assert np.all(got[int(bidx.off[zero_k]):int(bidx.off[zero_k + 1])] == 0.0)
+
+
+# ------------------------------------------------------------------------------------------------------------
+# The register eigensolver (psd_small_reg.h: Householder + implicit QL) as a projection and as cuadmm_op_batch_eig, and the workgroup
+# eigensolver below n = 129, on the spectra families -- by default they only ever see hard spectra at n = 5.
+# ------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("kind", ["randn", "lowrank", "graded", "psd", "nsd", "clustered"])
+def test_project_every_mid_size_register_eigensolver(kind):
+    """test_project_every_mid_size_one_wavefront_per_block with psd_n16 = 0, psd_n32 = 0, psd_mid = 1: every size 9 ... 64 through the
+    register eigensolver (NMAX = 16, 32, 64), which a rank mask and cuadmm_lambda_min use as well; same inputs, same tolerance."""
+    sizes = np.repeat(np.arange(9, 65), 3)
+    rng = np.random.default_rng(77 + len(kind))
+    sizes = sizes[rng.permutation(sizes.size)]
+    blk = sizes.astype(np.int32)
+    bidx = orc.BlockIndex(blk)
+    mats = [_spectrum_matrix(int(n), kind, rng) for n in sizes]
+    zero_k = 5
+    mats[zero_k] = np.zeros_like(mats[zero_k])
+    x = np.concatenate([orc.BlockIndex([M.shape[0]]).pack([M[None]]) for M in mats])
+    got = psd_project_gpu(x, blk, opts={"psd_n16": 0, "psd_n32": 0, "psd_mid": 1})
+    ref = orc.psd_project_svec(bidx, x)
+    for k, M in enumerate(mats):
+        sl = slice(int(bidx.off[k]), int(bidx.off[k + 1]))
+        nrm = max(np.linalg.norm(M, 2), 1e-300)
+        assert np.max(np.abs(got[sl] - ref[sl])) <= 2e-12 * nrm * np.sqrt(2), (k, M.shape[0])
+    assert np.all(got[int(bidx.off[zero_k]):int(bidx.off[zero_k + 1])] == 0.0)
+
+
+@pytest.mark.parametrize("kind", ["randn", "lowrank", "graded", "psd", "nsd", "clustered", "rank1"])
+def test_project_tiny_blocks_spectra(kind):
+    """n = 1 ... 8 (always the register eigensolver), 16 blocks per size permuted into one call: several blocks share a wavefront and
+    need different numbers of QL sweeps.  The sign path's families plus rank one, an exactly zero block, the same tolerance per block."""
+    sizes = np.repeat(np.arange(1, 9), 16)
+    rng = np.random.default_rng(99 + len(kind))
+    sizes = sizes[rng.permutation(sizes.size)]
+    blk = sizes.astype(np.int32)
+    bidx = orc.BlockIndex(blk)
+    mats = []
+    for n in sizes:
+        if kind == "rank1":
+            v = rng.standard_normal(int(n)); mats.append(np.outer(v, v) * rng.choice([-1.0, 1.0]))
+        else:
+            mats.append(_spectrum_matrix(int(n), kind, rng))
+    zero_k = int(np.nonzero(sizes == 8)[0][0])
+    mats[zero_k] = np.zeros_like(mats[zero_k])
+    x = np.concatenate([orc.BlockIndex([M.shape[0]]).pack([M[None]]) for M in mats])
+    got = psd_project_gpu(x, blk, opts={})
+    ref = orc.psd_project_svec(bidx, x)
+    for k, M in enumerate(mats):
+        sl = slice(int(bidx.off[k]), int(bidx.off[k + 1]))
+        nrm = max(np.linalg.norm(M, 2), 1e-300)
+        assert np.max(np.abs(got[sl] - ref[sl])) <= 2e-12 * nrm * np.sqrt(2), (k, M.shape[0])
+    assert np.all(got[int(bidx.off[zero_k]):int(bidx.off[zero_k + 1])] == 0.0)
+
+
+_EIG_KINDS = ["randn", "rank1", "lowrank", "identity", "zero", "diag", "graded", "clustered", "tight"]
+
+
+@pytest.mark.parametrize("kind", _EIG_KINDS + ["mixed"])
+@pytest.mark.parametrize("n", [2, 3, 4, 5, 8, 9, 16, 17, 32, 33, 64, 65, 100, 128])
+def test_batch_eig_below_the_whole_chip_path_spectra(n, kind):
+    """cuadmm_op_batch_eig on the nine families on both sides of every boundary below n = 129: the size classes of the register eigensolver
+    (4 | 5, 8 | 9, 16 | 17, 32 | 33, 64) and the workgroup eigensolver with the matrix in LDS (65 ... 128: one, two wavefronts of QL; its HBM
+    variant starts at n = 137, beyond the whole-chip path's first size, so this entry point never reaches it).  Three members per call;
+    "mixed": three different families, so the members' sweep counts differ."""
+    rng = np.random.default_rng(5000 + 10 * n + len(kind))
+    kinds = ("graded", "rank1", "clustered") if kind == "mixed" else (kind,) * 3
+    A = np.stack([_eig_family(n, k, rng) for k in kinds])
+    W, V, info = batch_eig_gpu(A)
+    for i in range(3):
+        _check_eig(A[i], W[i], V[i], int(info[i]))
