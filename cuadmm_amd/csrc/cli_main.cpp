@@ -23,6 +23,10 @@
 //   --lowrank=TOL[,RMAX]: behind every solve, the numerical rank of every block of X and of S by pivoted Cholesky (cuadmm_lowrank with the
 //   relative tolerance TOL and at most RMAX columns per block, default the largest block size), one line each, and "lowrank" in the sidecar
 //   --lowrank-out=DIR/ (with --lowrank): the factors, DIR/L_X_<k>.txt and DIR/L_S_<k>.txt per PSD block k, n_k r_k numbers column by column
+//   --start-lowrank=DIR/: the first solve starts from factors as --lowrank-out writes them (cuadmm_set_lowrank): DIR/L_X_<k>.txt and
+//   DIR/L_S_<k>.txt hold n_k r_k numbers, so r_k = count / n_k; a matrix none of whose files is present is left alone, otherwise a missing
+//   block has rank 0; DIR/y.txt (con_num numbers), where present, is y.  A file whose count is no multiple of n_k or exceeds n_k^2 ends the
+//   program with exit code 1 before any device work.  One line per matrix set, and "start_lowrank" in the sidecar
 //   --json=<file>: a sidecar with the run's figures (iterations, residuals, iters/s, per-phase milliseconds, the projection's
 //   nominal TFLOP/s = 10.67 sum n^3 per projection and the vector kernels' algorithmic GB/s: SURVEY.md 8d); switches the
 //   engine's per-phase HIP-event timers on (option "profile").  Nothing is written unless asked for: the reference writes X_opt.txt only.
@@ -111,8 +115,62 @@ static void write_lowrank(FILE* f, const LowRankReport& r) {
   }
   fprintf(f, "}");
 }
+// --start-lowrank: the factors of X (0) and S (1) in the layout of cuadmm_set_lowrank, and what the calls returned
+struct LowRankStart {
+  bool have[2] = {false, false}, have_y = false;
+  int rmax[2] = {1, 1};
+  std::vector<int> ranks[2];
+  std::vector<double> L[2], y;
+  double o[2][4] = {{0}};
+};
+// DIR/L_<X|S>_<k>.txt of every PSD block -> st; false (with a message) on a file whose count does not fit its block
+static bool read_lowrank_start(const std::string& dir, const cuadmm_problem_view& v, LowRankStart& st) {
+  for (int w = 0; w < 2; ++w) {
+    std::vector<std::vector<double>> cols((size_t)v.mat_num);
+    st.ranks[w].assign((size_t)v.mat_num, 0);
+    for (int k = 0; k < v.mat_num; ++k) {
+      const long long n = v.blk_vals[k];
+      if (n <= 0) continue;
+      const std::string fn = dir + "L_" + (w == 0 ? "X" : "S") + "_" + std::to_string(k) + ".txt";
+      FILE* f = fopen(fn.c_str(), "r");
+      if (!f) continue;
+      st.have[w] = true;
+      double x = 0;
+      while ((long long)cols[k].size() <= n * n && fscanf(f, "%lf", &x) == 1) cols[k].push_back(x);
+      fclose(f);
+      const long long count = (long long)cols[k].size();
+      if (count % n != 0 || count > n * n) {
+        std::cerr << "--start-lowrank: '" << fn << "' holds " << (count > n * n ? "more than " : "") << std::min(count, n * n) << " numbers; block " << k
+                  << " of size " << n << " takes a multiple of " << n << ", at most " << n * n << std::endl;
+        return false;
+      }
+      st.ranks[w][k] = (int)(count / n);
+      st.rmax[w] = std::max(st.rmax[w], st.ranks[w][k]);
+    }
+    if (!st.have[w]) continue;
+    st.L[w].clear();
+    for (int k = 0; k < v.mat_num; ++k) {
+      const long long n = v.blk_vals[k];
+      if (n <= 0) continue;
+      const size_t at = st.L[w].size();
+      st.L[w].resize(at + (size_t)(n * std::min<long long>(n, st.rmax[w])), 0.0);
+      std::copy(cols[k].begin(), cols[k].end(), st.L[w].begin() + at);
+    }
+    st.L[w].push_back(0.0);      // never empty
+  }
+  return true;
+}
+// "start_lowrank": {"X": {...}, "S": {...}} with the four numbers of cuadmm_set_lowrank for each matrix that was set
+static void write_start(FILE* f, const LowRankStart& st) {
+  fprintf(f, " \"start_lowrank\": {\"y\": %s", st.have_y ? "true" : "false");
+  for (int w = 0; w < 2; ++w)
+    if (st.have[w])
+      fprintf(f, ", \"%s\": {\"blocks\": %.0f, \"rank_sum\": %.0f, \"ms\": %.17g, \"bytes_staged\": %.0f, \"rmax\": %d}", w == 0 ? "X" : "S", st.o[w][0], st.o[w][1],
+              st.o[w][2], st.o[w][3], st.rmax[w]);
+  fprintf(f, "}");
+}
 // <dir/>name.txt, one number per line (cuadmm_write_dense_txt); a missing file: zeros
-static bool read_point_vec(const std::string& fn, std::vector<double>& out, size_t n) {
+static bool read_point_vec(const std::string& fn, std::vector<double>& out, size_t n, const char* who = "--kkt-point") {
   out.assign(n, 0.0);
   FILE* f = fopen(fn.c_str(), "r");
   if (!f) return true;
@@ -121,14 +179,14 @@ static bool read_point_vec(const std::string& fn, std::vector<double>& out, size
   while (got < n && fscanf(f, "%lf", &x) == 1) out[got++] = x;
   const bool more = fscanf(f, "%lf", &x) == 1;
   fclose(f);
-  if (got != n || more) { std::cerr << "--kkt-point: '" << fn << "' must hold " << n << " numbers" << std::endl; return false; }
+  if (got != n || more) { std::cerr << who << ": '" << fn << "' must hold " << n << " numbers" << std::endl; return false; }
   return true;
 }
 
 // --json=<file>: one object; every number printed with %.17g
 static bool write_sidecar(const std::string& path, const std::string& prefix, cuadmm_solver* solver, const cuadmm_problem_view& v, bool have_bounds,
                           const double* kkt = nullptr, const std::vector<double>& kkt_blocks = std::vector<double>(), int lm_steps = 0,
-                          const double (*lm)[8] = nullptr, const LowRankReport* lr = nullptr) {
+                          const double (*lm)[8] = nullptr, const LowRankReport* lr = nullptr, const LowRankStart* start = nullptr) {
   FILE* f = fopen(path.c_str(), "w");
   if (!f) return false;
   const int iters = cuadmm_get_info_iter_num(solver);
@@ -169,6 +227,7 @@ static bool write_sidecar(const std::string& path, const std::string& prefix, cu
   if (kkt) { write_kkt(f, kkt, kkt_blocks); fprintf(f, ",\n"); }
   if (lm) { write_lambda_min(f, lm_steps, lm); fprintf(f, ",\n"); }
   if (lr) { write_lowrank(f, *lr); fprintf(f, ",\n"); }
+  if (start) { write_start(f, *start); fprintf(f, ",\n"); }
   double acc[8] = {0};
   cuadmm_get_accel_info(solver, acc);
   if (acc[0] > 0)
@@ -211,7 +270,7 @@ int main(int argc, char* argv[]) {
   int lm_steps = 0;      // --lambda-min: 0 = off
   LowRankReport lr;      // --lowrank: rmax = 0 = off
   bool lr_on = false;
-  std::string json_path, bounds_arg, kkt_point, lr_out;
+  std::string json_path, bounds_arg, kkt_point, lr_out, start_dir;
   std::vector<std::string> then_dirs;
   std::vector<char> then_is_A;
   for (int i = 2; i < argc; ++i) {
@@ -246,6 +305,7 @@ int main(int argc, char* argv[]) {
       continue;
     }
     if (strncmp(argv[i], "--lowrank-out=", 14) == 0) { lr_out = argv[i] + 14; continue; }
+    if (strncmp(argv[i], "--start-lowrank=", 16) == 0) { start_dir = argv[i] + 16; continue; }
     std::cerr << "unknown option " << argv[i] << std::endl;
     return 1;
   }
@@ -265,6 +325,16 @@ int main(int argc, char* argv[]) {
   }
   cuadmm_problem_view v;
   cuadmm_problem_view_get(prob, &v);
+
+  LowRankStart start;      // --start-lowrank: read and checked before any device work
+  if (!start_dir.empty()) {
+    FILE* yf = fopen((start_dir + "y.txt").c_str(), "r");
+    if (yf) { fclose(yf); start.have_y = true; }
+    if (!read_lowrank_start(start_dir, v, start) || (start.have_y && !read_point_vec(start_dir + "y.txt", start.y, (size_t)v.con_num, "--start-lowrank"))) {
+      cuadmm_problem_free(prob);
+      return 1;
+    }
+  }
 
   cuadmm_solver* solver = nullptr;
   cuadmm_create(&solver);
@@ -379,7 +449,21 @@ int main(int argc, char* argv[]) {
     }
     return true;
   };
-  rc = cuadmm_solve(solver, (int)max_iter, stop_tol, (int)threshold, (int)stage1, (int)stage2, (int)switch_admm, sigscale, 1);
+  // --start-lowrank: the point replaces init's zeros, and the solve takes the iterate as it stands (if_first = 0)
+  const bool started = start.have[0] || start.have[1] || start.have_y;
+  for (int w = 0; w < 2 && rc == CUADMM_OK; ++w) {
+    if (!start.have[w]) continue;
+    rc = cuadmm_set_lowrank(solver, w, start.L[w].data(), start.ranks[w].data(), start.rmax[w], 0.0, start.o[w]);
+    if (rc == CUADMM_OK) printf(" start(%s): %.0f blocks from factors, rank sum %.0f, %.3f ms\n", lm_names[w], start.o[w][0], start.o[w][1], start.o[w][2]);
+  }
+  if (rc == CUADMM_OK && start.have_y) rc = cuadmm_set_XyS(solver, nullptr, start.y.data(), nullptr, 0.0);
+  if (rc != CUADMM_OK) {
+    std::cerr << cuadmm_last_error() << std::endl;
+    cuadmm_destroy(solver);
+    cuadmm_problem_free(prob);
+    return 1;
+  }
+  rc = cuadmm_solve(solver, (int)max_iter, stop_tol, (int)threshold, (int)stage1, (int)stage2, (int)switch_admm, sigscale, started ? 0 : 1);
   if (rc != CUADMM_OK) std::cerr << cuadmm_last_error() << std::endl;
   bool have_kkt = kkt_report();
   bool have_lm = lm_report();
@@ -392,7 +476,7 @@ int main(int argc, char* argv[]) {
   }
   std::vector<double> X((size_t)v.vec_len);
   if (cuadmm_get_X(solver, X.data()) == CUADMM_OK) cuadmm_write_dense_txt((prefix + "X_opt.txt").c_str(), X.data(), v.vec_len);
-  if (!json_path.empty() && !write_sidecar(json_path, prefix, solver, v, !bounds_arg.empty(), have_kkt ? kk : nullptr, kkb, lm_steps, have_lm ? lm : nullptr, have_lr ? &lr : nullptr)) std::cerr << "cannot write " << json_path << std::endl;
+  if (!json_path.empty() && !write_sidecar(json_path, prefix, solver, v, !bounds_arg.empty(), have_kkt ? kk : nullptr, kkb, lm_steps, have_lm ? lm : nullptr, have_lr ? &lr : nullptr, started ? &start : nullptr)) std::cerr << "cannot write " << json_path << std::endl;
   for (size_t k = 0; k < then_dirs.size() && rc == CUADMM_OK; ++k) {
     const std::string& d = then_dirs[k];
     std::vector<int> bi, ci;

@@ -375,6 +375,8 @@ struct cuadmm_solver {
   int lr_prepare(int rmax);
   int lr_run(int which, double tol, double out8[8], double* per_block, double* L_out, int* piv_out);
 
+  LoPlan lo;                   // (report_plans.h): cuadmm_set_lowrank
+
   // profiling
   DevEvent ev0[K_NUM][2], ev1[K_NUM][2];
   int ev_used[K_NUM] = {0};

@@ -35,6 +35,54 @@ int cuadmm_set_XyS(cuadmm_solver* s, const double* X, const double* y, const dou
   return CUADMM_OK;
 }
 
+// X or S from per-block factors, X_k = L_k L_k' (lowrank_apply.h): cuadmm_set_XyS for that one vector without the vector -- the factors are
+// staged (one copy of the factor buffer) and one kernel pass writes svec(L_k L_k') into the resident iterate.  Every check runs before
+// anything changes, materialise() included.
+int cuadmm_set_lowrank(cuadmm_solver* s, int which, const double* L, const int* ranks, int rmax, double sig, double out4[4]) {
+  if (!s || !s->initialised) { set_error("set_lowrank: not initialised"); return CUADMM_ERR_INVALID; }
+  if (which < 0 || which > 1) { set_error("set_lowrank: which = %d (0: X, 1: S)", which); return CUADMM_ERR_INVALID; }
+  if (rmax < 1 || rmax > kMaxBlockSize) { set_error("set_lowrank: rmax = %d, allowed are 1 to %d", rmax, kMaxBlockSize); return CUADMM_ERR_INVALID; }
+  if (!ranks) { set_error("set_lowrank: ranks is null"); return CUADMM_ERR_INVALID; }
+  if (s->world > 1 || s->comm_world > 1 || s->local_mode || s->group || s->in_group_call) {
+    set_error("set_lowrank: works on one rank (world = %d%s)", std::max(s->world, s->comm_world), s->group ? ", in-process group" : "");
+    return CUADMM_ERR_INVALID;
+  }
+  const int nb = (int)s->blk_local.size();
+  double blocks = 0, rank_sum = 0;
+  {
+    long long at = 0;                    // first double of block k's factor
+    for (int k = 0; k < nb; ++k) {
+      const int n = s->blk_local[k];
+      if (n <= 0) continue;
+      const int rc_k = std::min(n, rmax), r = ranks[k];
+      if (r < 0 || r > rc_k) { set_error("set_lowrank: block %d of size %d has rank %d, allowed are 0 to %d", k, n, r, rc_k); return CUADMM_ERR_INVALID; }
+      if (r > 0 && !L) { set_error("set_lowrank: L is null and block %d has rank %d", k, r); return CUADMM_ERR_INVALID; }
+      for (long long e = at, end = at + (long long)n * r; e < end; ++e)
+        if (!std::isfinite(L[e])) { set_error("set_lowrank: block %d, row %lld of column %lld is not finite", k, (e - at) % n, (e - at) / n); return CUADMM_ERR_INVALID; }
+      at += (long long)n * rc_k;
+      blocks += 1;
+      rank_sum += r;
+    }
+  }
+  int rc = check_device(s->device);
+  if (rc) return rc;
+  // the plan and the staged factors: buffers of the call's own
+  double bytes = 0;
+  if (!s->btasks.built && (rc = s->btasks.build(s->blk_local.data(), nb, nullptr))) return rc;
+  if ((rc = s->lo.prepare(s->blk_local.data(), nb, rmax)) || (rc = s->lo.stage(L, ranks, &bytes))) return rc;
+  // --- from here on the solver changes
+  if ((rc = s->materialise())) return rc;       // the vectors NOT replaced must be in the caller's units too
+  CUADMM_HIP_TRY(hipEventRecord(s->lo.ev[0], s->st));
+  if ((rc = s->lo.run(s->btasks.off.p, s->btasks.blk.p, which == 0 ? s->X.p : s->S.p, s->st))) return rc;
+  CUADMM_HIP_TRY(hipEventRecord(s->lo.ev[1], s->st));
+  CUADMM_HIP_TRY(hipStreamSynchronize(s->st));
+  if (sig > 0) s->sig = sig;
+  s->infeas_reset();                            // snapshots and status describe another iterate
+  s->lb_reset();
+  if (out4) { out4[0] = blocks; out4[1] = rank_sum; out4[2] = event_ms(s->lo.ev[0], s->lo.ev[1]); out4[3] = bytes; }
+  return CUADMM_OK;
+}
+
 // New b and / or C on a factored solver.  Nothing that depends on A alone is touched: ordering, factor, GPU tail, tree tops, CSR
 // matrices, projection plan.  What changes: the scaling constants, b (host, device, the closed blocks' records), C, the units of the
 // resident X, y, S -- rescaled where they live, with the rounded operations of materialise() followed by init's scaling -- and the

@@ -560,6 +560,45 @@ int cuadmm_op_block_lowrank(const double* svec_dev, const int* blk_vals, int mat
   return plan.fetch(1.0, per_block6_host, L_host, piv_host);
 }
 
+// the kernel of cuadmm_set_lowrank on a DEVICE svec vector whose blocks follow one another from slot 0 (csrc/lowrank_apply.hip); the factor
+// buffer (cuadmm_lowrank's L_out layout for rmax), ranks and blk_vals on the host.  Synchronises the stream.
+int cuadmm_op_block_outer(const double* L_host, const int* ranks, const int* blk_vals, int mat_num, int rmax, double* svec_dev_inout, void* stream) {
+  if (!ranks || !blk_vals || mat_num < 1 || rmax < 1 || rmax > kMaxBlockSize || !svec_dev_inout) { set_error("op_block_outer: invalid argument"); return CUADMM_ERR_INVALID; }
+  for (int k = 0; k < mat_num; ++k) {
+    const int n = blk_vals[k];
+    if (n == 0 || n > kMaxBlockSize) { set_error("op_block_outer: block %d has size %d", k, n); return CUADMM_ERR_INVALID; }
+    if (n > 0 && (ranks[k] < 0 || ranks[k] > std::min(n, rmax) || (ranks[k] > 0 && !L_host))) {
+      set_error("op_block_outer: block %d of size %d has rank %d%s", k, n, ranks[k], L_host ? "" : " and L is null");
+      return CUADMM_ERR_INVALID;
+    }
+  }
+  int rc, ndev = 0;      // the current device is the vector's: it is not changed
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_error("no HIP device available; this engine has no CPU fallback"); return CUADMM_ERR_NO_DEVICE; }
+  hipStream_t st = (hipStream_t)stream;
+  BlockTasksDev t;
+  LoPlan plan;
+  double bytes = 0;
+  if ((rc = t.build(blk_vals, mat_num, nullptr)) || (rc = plan.prepare(blk_vals, mat_num, rmax)) || (rc = plan.stage(L_host, ranks, &bytes))) return rc;
+  if ((rc = plan.run(t.off.p, t.blk.p, svec_dev_inout, st))) return rc;
+  CUADMM_HIP_TRY(hipStreamSynchronize(st));
+  return CUADMM_OK;
+}
+
+// the host side of that kernel: loff_out (mat_num + 1, may be null) <- the factor offsets for rmax; tasks_out (may be null) <- up to
+// cap_slots wavefront slots of four ints (k, t0, t1, step).  split_from: the size from which a block is split over workgroups (0: the
+// engine's).  Returns the number of slots.  Host only.
+int cuadmm_op_block_outer_plan(const int* blk_vals, int mat_num, int rmax, int split_from, long long* loff_out, int* tasks_out, int cap_slots) {
+  std::vector<LoTask> tasks;
+  std::vector<long long> loff;
+  int rc = lo_build_tasks(mat_num, blk_vals, rmax, split_from ? split_from : kLoSplitFrom, &tasks, &loff);
+  if (rc) return rc;
+  if (loff_out) std::copy(loff.begin(), loff.end(), loff_out);
+  for (size_t q = 0; tasks_out && q < tasks.size() && (int)q < cap_slots; ++q) {
+    tasks_out[4 * q] = tasks[q].k; tasks_out[4 * q + 1] = tasks[q].t0; tasks_out[4 * q + 2] = tasks[q].t1; tasks_out[4 * q + 3] = tasks[q].step;
+  }
+  return (int)tasks.size();
+}
+
 int cuadmm_dev_malloc(void** ptr, size_t bytes) { CUADMM_HIP_TRY(hipMalloc(ptr, bytes ? bytes : 8)); return CUADMM_OK; }
 int cuadmm_dev_free(void* ptr) { if (ptr) CUADMM_HIP_TRY(hipFree(ptr)); return CUADMM_OK; }
 int cuadmm_memcpy_h2d(void* dst, const void* src, size_t bytes) { return staged_h2d(dst, src, bytes); }

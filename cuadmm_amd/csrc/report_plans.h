@@ -1,5 +1,5 @@
 // What the reports on a point own beside the iteration's state, and what the op hooks build on their own: the auxiliary projector, the
-// per-block task lists, the plans of cuadmm_lambda_min and cuadmm_lowrank.  Nothing here is read by the iteration.
+// per-block task lists, the plans of cuadmm_lambda_min, cuadmm_lowrank and cuadmm_set_lowrank.  Nothing here is read by the iteration.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -9,6 +9,7 @@
 #include "block_reduce.h"
 #include "lambda_min.h"
 #include "lowrank.h"
+#include "lowrank_apply.h"
 
 struct cuadmm_solver;
 
@@ -168,6 +169,49 @@ struct LrPlan {
     double b = 8.0 * (double)(loff_d.n + poff_d.n + Lbuf.n + out.n) + 4.0 * (double)piv.n;
     for (const auto& l : list) b += 4.0 * (double)l.n;
     return b;
+  }
+};
+
+// Start from low-rank factors (cuadmm_set_lowrank, cuadmm_op_block_outer; lowrank_apply.h, DESIGN.md "Starting from low-rank factors"):
+// the wavefront task list (it depends on the block sizes alone), the offsets of the blocks' factors for the rmax of the last call, the
+// device copy of the factor buffer and of the ranks (they grow with rmax and are kept), a pair of events.  The offsets and sizes per
+// block are the task lists' (btasks).  Nothing here is read by the iteration.
+struct LoPlan {
+  std::vector<LoTask> tasks;
+  std::vector<long long> loff;              // of rmax_now, nb + 1 entries
+  DevBuf<LoTask> tasks_d;
+  DevBuf<long long> loff_d;
+  DevBuf<int> ranks_d;
+  DevBuf<double> Lbuf;
+  int nb = 0, rmax_now = 0;
+  DevEvent ev[2];
+  int prepare(const int* blk_h, int nblk, int rmax, int split_from = kLoSplitFrom) {
+    if (ranks_d.p && rmax == rmax_now) return CUADMM_OK;
+    int rc = lo_build_tasks(nblk, blk_h, rmax, split_from, &tasks, &loff);
+    if (rc) return rc;
+    const bool first = !ranks_d.p;
+    if (first) {
+      if ((rc = tasks_d.from(tasks, 1)) || (rc = loff_d.alloc((size_t)nblk + 1))) return rc;      // (+ 1: never empty)
+      for (auto& e : ev) if ((rc = e.create())) return rc;
+    }
+    rmax_now = 0;                           // (until the offsets on the device are this rmax's)
+    if ((rc = loff_d.upload(loff.data(), loff.size()))) return rc;
+    if (Lbuf.n < (size_t)loff.back() + 1 && (rc = Lbuf.alloc((size_t)loff.back() + 1))) return rc;
+    nb = nblk;
+    rmax_now = rmax;
+    return first ? ranks_d.alloc((size_t)nblk + 1) : CUADMM_OK;      // last: marks the set as complete
+  }
+  // the factor buffer (whole, one copy; null: nothing, every rank is 0) and the ranks to the device; *bytes: those of the factor
+  int stage(const double* L_host, const int* ranks, double* bytes) {
+    int rc;
+    const size_t count = L_host ? (size_t)loff.back() : 0;
+    if (count > 0 && (rc = Lbuf.upload(L_host, count))) return rc;
+    *bytes = 8.0 * (double)count;
+    return ranks_d.upload(ranks, (size_t)nb);
+  }
+  // v (device) <- svec(L_k L_k') on every PSD block, one launch
+  int run(const long long* off_d, const int* blk_d, double* v, hipStream_t st) {
+    return launch_block_outer((int)tasks.size(), tasks_d.p, Lbuf.p, loff_d.p, ranks_d.p, off_d, blk_d, v, st);
   }
 };
 

@@ -27,6 +27,31 @@ def _p(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
+def pack_lowrank(blk_vals, Ls):
+    """(L, ranks, rmax) as cuadmm_set_lowrank takes them from a list of (n_k, r_k) arrays, one entry per block (those of unconstrained
+    blocks are ignored): rmax = max(1, max r_k), block k at the prefix sum of n_j min(n_j, rmax) over the PSD blocks before it, column by
+    column, the columns >= r_k zero.  ValueError on a wrong number of entries, a wrong row count or more columns than rows."""
+    blk = [int(n) for n in blk_vals]
+    if len(Ls) != len(blk):
+        raise ValueError("set_lowrank: %d factors for %d blocks" % (len(Ls), len(blk)))
+    ranks = np.zeros(len(blk), np.int32)
+    mats = [None] * len(blk)
+    for k, n in enumerate(blk):
+        if n <= 0:
+            continue
+        A = _f64(Ls[k])
+        if A.ndim != 2 or A.shape[0] != n or A.shape[1] > n:
+            raise ValueError("set_lowrank: block %d has size %d, its factor the shape %s" % (k, n, A.shape))
+        mats[k], ranks[k] = A, A.shape[1]
+    rmax = max(1, int(ranks.max()) if ranks.size else 1)
+    off = np.concatenate([[0], np.cumsum([n * min(n, rmax) if n > 0 else 0 for n in blk])]).astype(np.int64)
+    L = np.zeros(max(int(off[-1]), 1))
+    for k, A in enumerate(mats):
+        if A is not None:
+            L[off[k]:off[k] + A.size] = A.T.ravel()
+    return L, ranks, rmax
+
+
 class Problem:
     """TXT problem directory (blk.txt, con_num.txt, At.txt, b.txt, C.txt), src/problem.cu:11-83."""
 
@@ -249,6 +274,20 @@ class SDPSolver:
         return {"rank_sum": int(o[0]), "rank_max": int(o[1]), "block": int(o[2]), "resid_sum": float(o[3]), "dneg_min": float(o[4]), "capped": int(o[5]),
                 "ms": float(o[6]), "bytes": float(o[7]), "rank": rank, "resid": pb[:, 1].copy(), "dneg": pb[:, 2].copy(), "trace": pb[:, 3].copy(),
                 "flag": pb[:, 4].astype(int), "L": L, "piv": piv}
+
+    def set_lowrank(self, X=None, S=None, sig=0.0):
+        """Start the next solve from per-block factors (cuadmm_set_lowrank): X and / or S as the list of (n_k, r_k) arrays lowrank()["L"]
+        returns, every PSD block becoming L_k L_k'.  Entries of unconstrained blocks are ignored, and those blocks, y and a matrix left
+        None keep their values.  Returns {"X": ..., "S": ...} with "blocks", "rank_sum", "ms", "bytes_staged" for each matrix set."""
+        out = {}
+        for name, Ls in (("X", X), ("S", S)):
+            if Ls is None:
+                continue
+            Lv, ranks, rmax = pack_lowrank(self.blk_vals, Ls)
+            o = np.zeros(4)
+            check(self._lib.cuadmm_set_lowrank(self._h, self.LOWRANK_WHICH[name], _p(Lv), _p(ranks), rmax, float(sig), _p(o)))
+            out[name] = {"blocks": int(o[0]), "rank_sum": int(o[1]), "ms": float(o[2]), "bytes_staged": float(o[3])}
+        return out
 
     def set_allreduce(self, fn):
         """fn(dev_ptr:int, count:int, hip_stream:int) -> None : in-place sum over ranks on that stream."""

@@ -173,6 +173,25 @@ int cuadmm_get_S(cuadmm_solver* s, double* host_out /* vec_len */);
  * writing through X.vals/y.vals/S.vals before solve(..., if_first=false) (solver.cu:385-409);
  * NULL leaves that vector untouched */
 int cuadmm_set_XyS(cuadmm_solver* s, const double* X, const double* y, const double* S, double sig);
+/* Replace X (which = 0) or S (1) between two solves by per-block factors: every PSD block k becomes L_k L_k' with r_k = ranks[k] columns
+ * ("Starting from low-rank factors"; csrc/lowrank_apply.h).  L is laid out as cuadmm_lowrank's L_out for this rmax: block k at the
+ * prefix sum of n_j min(n_j, rmax) over the PSD blocks before it, column by column, n_k doubles per column; unconstrained blocks occupy
+ * nothing and their entries of ranks (mat_num ints) are ignored.  Columns >= r_k are never read (they may hold NaN); r_k = 0 writes +0.0.
+ * One kernel pass on the fp64 matrix cores writes v[off_k + i (i + 1) / 2 + j] = c_ij sum_t L[i, t] L[j, t] (i >= j, c_ii = 1, c_ij =
+ * 1.4142135623730951) into the resident vector; for any order of the sums, with u = 2^-53,
+ *   |computed - exact| <= (r_k + 4) u c_ij sum_t |L_it| |L_jt|
+ * (r_k products and sums, the multiplication by the constant, the constant's own rounding).
+ * Otherwise the call is cuadmm_set_XyS for that one vector, in the caller's units: the deferred unscaling runs first, sig > 0 sets sigma,
+ * status, infeasibility snapshots and gap information are reset; y, the other matrix and the unconstrained blocks of the target keep
+ * their bits (set those through cuadmm_set_XyS first where needed).
+ * out4 (may be NULL): [0] PSD blocks written, [1] sum of r_k, [2] device milliseconds of the kernel pass (HIP events), [3] bytes of
+ * factors staged from the host: 8 sum n_k min(n_k, rmax) -- the factor buffer travels whole, in one copy -- or 0 where L is NULL (the
+ * 4 mat_num bytes of ranks are not counted).
+ * Refused with CUADMM_ERR_INVALID before anything changes (the deferred unscaling included), the solver left as it was: solver not
+ * initialised; which outside 0..1; rmax outside 1..8192; ranks NULL; a ranks[k] of a PSD block outside 0..min(n_k, rmax); L NULL while
+ * some rank is positive; an entry that is not finite in a column that would be read; world > 1 or a handle that leads an in-process
+ * group (one rank only, like cuadmm_lowrank). */
+int cuadmm_set_lowrank(cuadmm_solver* s, int which, const double* L, const int* ranks, int rmax, double sig, double out4[4]);
 /* Replace b and/or C of an initialised solver without touching anything that depends on A alone (ordering, factor, GPU tail,
  * tree tops, plans).  b / C in the caller's numbering and units exactly as in cuadmm_init; b_nnz < 0 (or C_nnz < 0) leaves that
  * one unchanged.  keep_iterate = 1: the current X, y, S (caller's units) become the start of the next solve (warm start);
@@ -262,7 +281,7 @@ int cuadmm_get_accel_info(const cuadmm_solver* s, double out8[8]);
  * 1 <= cols <= 16, by Cholesky in long double.  Host only (no device needed).  CUADMM_ERR_FACTOR when a pivot is not positive. */
 int cuadmm_accel_solve_ls(const double* gram, const double* rhs, int cols, double reg, double* gamma_out);
 /* How the last cuadmm_solve ended.  [0] status: 0 = no solve yet (or the problem / iterate was replaced since: cuadmm_update_bC,
- * cuadmm_update_A, cuadmm_set_XyS), 1 = converged, 2 = iteration limit, 3 = primal infeasible, 4 = dual infeasible (primal unbounded),
+ * cuadmm_update_A, cuadmm_set_XyS, cuadmm_set_lowrank), 1 = converged, 2 = iteration limit, 3 = primal infeasible, 4 = dual infeasible (primal unbounded),
  * 5 = certified gap (option "gap_check": cuadmm_get_gap_info has the bound);
  * [1] iteration of the verdict; then, of option "infeas_check" (zeros while it is off): [2] checks run in that solve, [3] beta = b'dy / ||dy||
  * (status 3) or gamma = -C'dX / ||dX|| (status 4) in the engine's scaled space, [4] eta = ||P+(A'dy)|| / ||dy|| (status 3) or
@@ -644,6 +663,15 @@ int cuadmm_op_block_lambda_min(const double* svec_dev, const int* blk_vals, int 
  * and ints, all three laid out as in cuadmm_lowrank.  Synchronises the stream. */
 int cuadmm_op_block_lowrank(const double* svec_dev, const int* blk_vals, int mat_num, double tol, int rmax, double* per_block6_host, double* L_host,
                             int* piv_host, void* stream);
+/* The kernel of cuadmm_set_lowrank on a DEVICE svec vector whose blocks follow one another from slot 0 (csrc/lowrank_apply.hip): every
+ * slot of every PSD block is written, the slots of unconstrained blocks (blk_vals negative) keep their bits.  L_host (NULL where every
+ * rank is 0), ranks and blk_vals on the host, L_host laid out as in cuadmm_set_lowrank.  Synchronises the stream. */
+int cuadmm_op_block_outer(const double* L_host, const int* ranks, const int* blk_vals, int mat_num, int rmax, double* svec_dev_inout, void* stream);
+/* The host side of that kernel.  loff_out (may be NULL): mat_num + 1 offsets of the blocks' factors for rmax.  tasks_out (may be NULL): up
+ * to cap_slots wavefront slots of four ints (block or -1, first tile, end, step) over the tiles of the block's lower triangle numbered
+ * row by row; four consecutive slots are one workgroup.  split_from: the size from which a block is split over workgroups (0: the
+ * engine's; at least 33).  Returns the number of slots, or an error.  Host only (no device needed). */
+int cuadmm_op_block_outer_plan(const int* blk_vals, int mat_num, int rmax, int split_from, long long* loff_out, int* tasks_out, int cap_slots);
 int cuadmm_op_spmv_rows(int rows, int ncols, const int* row_ptrs, const int* col_ids, const double* vals, const double* X, const double* S, const double* C,
                         int want_x, int want_s, const int* rowmap, int out_len, double* outX, double* outS, int* info4);
 int cuadmm_op_rp_stats(int m, const double* ax, const double* b, const double* normA, const double* y, double bscale, const double* sums2, double* out4);

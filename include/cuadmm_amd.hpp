@@ -193,6 +193,15 @@ class SDPSolver {
     return r;
   }
 
+  // cuadmm_set_lowrank: X (which = 0) or S (1) <- L_k L_k' per PSD block between two solves; L in the layout of LowRank::L for this rmax,
+  // ranks: mat_num column counts (per_block[6k] of a LowRank; unconstrained blocks ignored); not in the reference
+  struct LowRankStart { int blocks; double rank_sum, ms, bytes_staged; };
+  LowRankStart set_lowrank(int which, const double* L, const int* ranks, int rmax, double sig = 0.0) {
+    double o[4] = {0};
+    check(cuadmm_set_lowrank(h_, which, L, ranks, rmax, sig, o));
+    return LowRankStart{(int)o[0], o[1], o[2], o[3]};
+  }
+
   // cuadmm_update_bC: new b and / or C on the factored solver (nnz < 0: unchanged); not in the reference
   void update_bC(const int* cpu_b_indices, const double* cpu_b_vals, int b_nnz, const int* cpu_C_indices, const double* cpu_C_vals,
                  int C_nnz, bool keep_iterate = true, double sig = 0.0) {
