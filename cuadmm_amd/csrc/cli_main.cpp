@@ -27,6 +27,11 @@
 //   DIR/L_S_<k>.txt hold n_k r_k numbers, so r_k = count / n_k; a matrix none of whose files is present is left alone, otherwise a missing
 //   block has rank 0; DIR/y.txt (con_num numbers), where present, is y.  A file whose count is no multiple of n_k or exceeds n_k^2 ends the
 //   program with exit code 1 before any device work.  One line per matrix set, and "start_lowrank" in the sidecar
+//   --block-mult=X|S|dual,DIR/ (repeatable): behind every solve, W_k = M_k V_k for every PSD block of X, S or C - A'y (cuadmm_block_multiply)
+//   with V_k from factor files as --lowrank-out writes them, read by the reader of --start-lowrank: DIR/L_X_<k>.txt where any is present,
+//   otherwise DIR/L_S_<k>.txt (files of the matrix that is not used are not opened); a missing block has rank 0.  One line per call, and "block_mult" (one object per call) in the sidecar
+//   --block-mult-out=DIR2/ (with --block-mult): DIR2/W_<k>.txt per PSD block k, n_k r_k numbers column by column with 17 significant
+//   digits (of the last --block-mult where there are several)
 //   --json=<file>: a sidecar with the run's figures (iterations, residuals, iters/s, per-phase milliseconds, the projection's
 //   nominal TFLOP/s = 10.67 sum n^3 per projection and the vector kernels' algorithmic GB/s: SURVEY.md 8d); switches the
 //   engine's per-phase HIP-event timers on (option "profile").  Nothing is written unless asked for: the reference writes X_opt.txt only.
@@ -123,9 +128,11 @@ struct LowRankStart {
   std::vector<double> L[2], y;
   double o[2][4] = {{0}};
 };
-// DIR/L_<X|S>_<k>.txt of every PSD block -> st; false (with a message) on a file whose count does not fit its block
-static bool read_lowrank_start(const std::string& dir, const cuadmm_problem_view& v, LowRankStart& st) {
+// DIR/L_<X|S>_<k>.txt of every PSD block -> st (only >= 0: that matrix alone, the other's files are not opened); false (with a message) on
+// a file whose count does not fit its block
+static bool read_lowrank_start(const std::string& dir, const cuadmm_problem_view& v, LowRankStart& st, int only = -1) {
   for (int w = 0; w < 2; ++w) {
+    if (only >= 0 && w != only) continue;
     std::vector<std::vector<double>> cols((size_t)v.mat_num);
     st.ranks[w].assign((size_t)v.mat_num, 0);
     for (int k = 0; k < v.mat_num; ++k) {
@@ -169,6 +176,34 @@ static void write_start(FILE* f, const LowRankStart& st) {
               st.o[w][2], st.o[w][3], st.rmax[w]);
   fprintf(f, "}");
 }
+// --block-mult: one call of cuadmm_block_multiply -- the matrix, the factors (those of X where DIR/ has any, else those of S) and the results
+struct BlockMultCall {
+  int which = 0, rmax = 1;
+  std::string dir;
+  std::vector<int> ranks;
+  std::vector<double> V, W;
+  double o[8] = {0};
+};
+static bool read_block_mult(const cuadmm_problem_view& v, BlockMultCall& c) {
+  LowRankStart st;
+  if (!read_lowrank_start(c.dir, v, st, 0)) return false;                 // the factors of X; those of S only where there are none
+  if (!st.have[0] && !read_lowrank_start(c.dir, v, st, 1)) return false;
+  const int w = st.have[0] ? 0 : 1;
+  if (!st.have[w]) { std::cerr << "--block-mult: no factor file L_X_<k>.txt or L_S_<k>.txt in '" << c.dir << "'" << std::endl; return false; }
+  c.rmax = st.rmax[w]; c.ranks = st.ranks[w]; c.V = st.L[w];
+  c.W.assign(c.V.size(), 0.0);
+  return true;
+}
+// "block_mult": [{...}, ...] with the eight numbers of cuadmm_block_multiply per call
+static void write_block_mult(FILE* f, const std::vector<BlockMultCall>& calls) {
+  fprintf(f, " \"block_mult\": [");
+  for (size_t q = 0; q < calls.size(); ++q) {
+    const double* o = calls[q].o;
+    fprintf(f, "%s{\"which\": \"%s\", \"rmax\": %d, \"norm\": %.17g, \"inner\": %.17g, \"block\": %.0f, \"block_norm\": %.17g, \"blocks\": %.0f, \"rank_sum\": %.0f, "
+            "\"ms\": %.17g, \"bytes\": %.0f}", q ? ", " : "", lm_names[calls[q].which], calls[q].rmax, o[0], o[1], o[2], o[3], o[4], o[5], o[6], o[7]);
+  }
+  fprintf(f, "]");
+}
 // <dir/>name.txt, one number per line (cuadmm_write_dense_txt); a missing file: zeros
 static bool read_point_vec(const std::string& fn, std::vector<double>& out, size_t n, const char* who = "--kkt-point") {
   out.assign(n, 0.0);
@@ -186,7 +221,8 @@ static bool read_point_vec(const std::string& fn, std::vector<double>& out, size
 // --json=<file>: one object; every number printed with %.17g
 static bool write_sidecar(const std::string& path, const std::string& prefix, cuadmm_solver* solver, const cuadmm_problem_view& v, bool have_bounds,
                           const double* kkt = nullptr, const std::vector<double>& kkt_blocks = std::vector<double>(), int lm_steps = 0,
-                          const double (*lm)[8] = nullptr, const LowRankReport* lr = nullptr, const LowRankStart* start = nullptr) {
+                          const double (*lm)[8] = nullptr, const LowRankReport* lr = nullptr, const LowRankStart* start = nullptr,
+                          const std::vector<BlockMultCall>* bmc = nullptr) {
   FILE* f = fopen(path.c_str(), "w");
   if (!f) return false;
   const int iters = cuadmm_get_info_iter_num(solver);
@@ -228,6 +264,7 @@ static bool write_sidecar(const std::string& path, const std::string& prefix, cu
   if (lm) { write_lambda_min(f, lm_steps, lm); fprintf(f, ",\n"); }
   if (lr) { write_lowrank(f, *lr); fprintf(f, ",\n"); }
   if (start) { write_start(f, *start); fprintf(f, ",\n"); }
+  if (bmc) { write_block_mult(f, *bmc); fprintf(f, ",\n"); }
   double acc[8] = {0};
   cuadmm_get_accel_info(solver, acc);
   if (acc[0] > 0)
@@ -270,7 +307,8 @@ int main(int argc, char* argv[]) {
   int lm_steps = 0;      // --lambda-min: 0 = off
   LowRankReport lr;      // --lowrank: rmax = 0 = off
   bool lr_on = false;
-  std::string json_path, bounds_arg, kkt_point, lr_out, start_dir;
+  std::string json_path, bounds_arg, kkt_point, lr_out, start_dir, bm_out;
+  std::vector<BlockMultCall> bmc;      // --block-mult, in the order given
   std::vector<std::string> then_dirs;
   std::vector<char> then_is_A;
   for (int i = 2; i < argc; ++i) {
@@ -306,11 +344,25 @@ int main(int argc, char* argv[]) {
     }
     if (strncmp(argv[i], "--lowrank-out=", 14) == 0) { lr_out = argv[i] + 14; continue; }
     if (strncmp(argv[i], "--start-lowrank=", 16) == 0) { start_dir = argv[i] + 16; continue; }
+    if (strncmp(argv[i], "--block-mult=", 13) == 0) {
+      const char* a = argv[i] + 13;
+      const char* comma = strchr(a, ',');
+      BlockMultCall c;
+      c.which = -1;
+      for (int w = 0; comma && w < 3; ++w)
+        if (std::string(a, comma) == lm_names[w]) c.which = w;
+      if (c.which < 0 || !comma[1]) { std::cerr << "--block-mult=X|S|dual,DIR/" << std::endl; return 1; }
+      c.dir = comma + 1;
+      bmc.push_back(c);
+      continue;
+    }
+    if (strncmp(argv[i], "--block-mult-out=", 17) == 0) { bm_out = argv[i] + 17; continue; }
     std::cerr << "unknown option " << argv[i] << std::endl;
     return 1;
   }
 
   if (!lr_out.empty() && !lr_on) { std::cerr << "--lowrank-out needs --lowrank=TOL[,RMAX]" << std::endl; return 1; }
+  if (!bm_out.empty() && bmc.empty()) { std::cerr << "--block-mult-out needs --block-mult=X|S|dual,DIR/" << std::endl; return 1; }
   for (size_t k = 0; k < then_dirs.size(); ++k) {   // before any work: a stage that cannot be read must not cost the stages before it
     const std::string& d = then_dirs[k];
     DIR* dp = d.empty() ? nullptr : opendir(d.c_str());
@@ -335,6 +387,9 @@ int main(int argc, char* argv[]) {
       return 1;
     }
   }
+
+  for (auto& c : bmc)      // --block-mult: read and checked before any device work
+    if (!read_block_mult(v, c)) { cuadmm_problem_free(prob); return 1; }
 
   cuadmm_solver* solver = nullptr;
   cuadmm_create(&solver);
@@ -449,6 +504,26 @@ int main(int argc, char* argv[]) {
     }
     return true;
   };
+  // --block-mult: the products at the point a solve returns, taken before anything reads the iterate
+  auto bm_report = [&]() {
+    for (auto& c : bmc) {
+      if (cuadmm_block_multiply(solver, c.which, c.V.data(), c.ranks.data(), c.rmax, c.W.data(), c.o, nullptr) != CUADMM_OK) { std::cerr << cuadmm_last_error() << std::endl; return false; }
+      printf(" block_mult(%s): ||W||_F = %.10e, <V, W> = %.10e, largest block %.0f (%.3e), %.0f blocks, rank sum %.0f, %.3f ms\n", lm_names[c.which], c.o[0], c.o[1],
+             c.o[2], c.o[3], c.o[4], c.o[5], c.o[6]);
+      size_t at = 0;
+      for (int k = 0; k < v.mat_num && !bm_out.empty(); ++k) {
+        const long long n = v.blk_vals[k];
+        if (n <= 0) continue;
+        const std::string fn = bm_out + "W_" + std::to_string(k) + ".txt";
+        FILE* f = fopen(fn.c_str(), "w");
+        if (!f) { std::cerr << "cannot write " << fn << std::endl; return false; }
+        for (long long e = 0; e < n * c.ranks[k]; ++e) fprintf(f, "%.17g\n", c.W[at + (size_t)e]);
+        fclose(f);
+        at += (size_t)(n * std::min<long long>(n, c.rmax));
+      }
+    }
+    return !bmc.empty();
+  };
   // --start-lowrank: the point replaces init's zeros, and the solve takes the iterate as it stands (if_first = 0)
   const bool started = start.have[0] || start.have[1] || start.have_y;
   for (int w = 0; w < 2 && rc == CUADMM_OK; ++w) {
@@ -468,6 +543,7 @@ int main(int argc, char* argv[]) {
   bool have_kkt = kkt_report();
   bool have_lm = lm_report();
   bool have_lr = lr_report();
+  bool have_bm = bm_report();
 
   if (accel != 0) {
     double acc[8] = {0};
@@ -476,7 +552,7 @@ int main(int argc, char* argv[]) {
   }
   std::vector<double> X((size_t)v.vec_len);
   if (cuadmm_get_X(solver, X.data()) == CUADMM_OK) cuadmm_write_dense_txt((prefix + "X_opt.txt").c_str(), X.data(), v.vec_len);
-  if (!json_path.empty() && !write_sidecar(json_path, prefix, solver, v, !bounds_arg.empty(), have_kkt ? kk : nullptr, kkb, lm_steps, have_lm ? lm : nullptr, have_lr ? &lr : nullptr, started ? &start : nullptr)) std::cerr << "cannot write " << json_path << std::endl;
+  if (!json_path.empty() && !write_sidecar(json_path, prefix, solver, v, !bounds_arg.empty(), have_kkt ? kk : nullptr, kkb, lm_steps, have_lm ? lm : nullptr, have_lr ? &lr : nullptr, started ? &start : nullptr, have_bm ? &bmc : nullptr)) std::cerr << "cannot write " << json_path << std::endl;
   for (size_t k = 0; k < then_dirs.size() && rc == CUADMM_OK; ++k) {
     const std::string& d = then_dirs[k];
     std::vector<int> bi, ci;
@@ -503,9 +579,10 @@ int main(int argc, char* argv[]) {
     have_kkt = kkt_report();
     have_lm = lm_report();
     have_lr = lr_report();
+    have_bm = bm_report();
     if (cuadmm_get_X(solver, X.data()) == CUADMM_OK) cuadmm_write_dense_txt((d + "X_opt.txt").c_str(), X.data(), v.vec_len);
     const std::string side = json_path + "." + std::to_string(k + 1);
-    if (!json_path.empty() && !write_sidecar(side, d, solver, v, !bounds_arg.empty(), have_kkt ? kk : nullptr, kkb, lm_steps, have_lm ? lm : nullptr, have_lr ? &lr : nullptr)) std::cerr << "cannot write " << side << std::endl;
+    if (!json_path.empty() && !write_sidecar(side, d, solver, v, !bounds_arg.empty(), have_kkt ? kk : nullptr, kkb, lm_steps, have_lm ? lm : nullptr, have_lr ? &lr : nullptr, nullptr, have_bm ? &bmc : nullptr)) std::cerr << "cannot write " << side << std::endl;
   }
   cuadmm_destroy(solver);
   cuadmm_problem_free(prob);

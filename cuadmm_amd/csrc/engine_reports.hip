@@ -1,6 +1,7 @@
 // What the engine reports beside the iteration: the infeasibility check and the certified lower bound behind the iteration's steps, and
-// the reports on a point (cuadmm_lower_bound, cuadmm_evaluate, cuadmm_lambda_min, cuadmm_lowrank) with their C entry points.  Host code
-// only: the kernels are those of infeas.hip, lower_bound.hip, evaluate.hip, lambda_min.hip, lowrank.hip and the iteration's own.
+// the reports on a point (cuadmm_lower_bound, cuadmm_evaluate, cuadmm_lambda_min, cuadmm_lowrank, cuadmm_block_multiply) with their C
+// entry points.  Host code only: the kernels are those of infeas.hip, lower_bound.hip, evaluate.hip, lambda_min.hip, lowrank.hip,
+// block_mult.hip and the iteration's own.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -446,6 +447,72 @@ int cuadmm_solver::lr_run(int which, double tol, double o[8], double* per_block,
   return CUADMM_OK;
 }
 
+// ------------------------------------------------------------------------------------------
+// Blocks times factors (cuadmm_block_multiply): DESIGN.md, "Blocks times factors"
+// ------------------------------------------------------------------------------------------
+// task list, events and buffers on first use; offsets and larger buffers when rmax changes; for which = 2 the y vector and
+// the auxiliary projector's vectors
+int cuadmm_solver::bm_prepare(int which, int rmax) {
+  int rc;
+  const int nb = (int)blk_local.size();
+  if (!btasks.built && (rc = btasks.build(blk_local.data(), nb, nullptr))) return rc;
+  if ((rc = bm.prepare(blk_local.data(), nb, rmax))) return rc;
+  if (which != 2) return CUADMM_OK;
+  if (!bm.ybuf.p && (rc = bm.ybuf.alloc((size_t)std::max(m, 1)))) return rc;
+  return aux.ensure(*this);
+}
+
+// which = 0: X, 1: S, read where they lie (scaled behind a solve, else in the caller's units); 2: S^ = C - A'y at the scaled y in bm.ybuf,
+// formed as -(A'y - C) by the iteration's kernel into the auxiliary projector's input vector (the launch of dual_slack without its b'y
+// sums, which nothing here reads: the timed interval is that launch and the product).  The kernel's W is in the units of
+// the vector it read and goes to the caller's on the host, one multiplication per entry.  The norms and inner products are plain double
+// sums over the returned W and the caller's V in index order (no contraction: a caller reproduces them bit for bit).  Writes only the
+// plan's own buffers and that input vector.
+int cuadmm_solver::bm_run(int which, const double* V, const int* ranks, double* W_out, double o[8], double* per_block) {
+  int rc;
+  const int nb = (int)blk_local.size();
+  const double* v = which == 0 ? X.p : S.p;
+  double sign = 1.0, unit = pending_unscale ? (which == 0 ? bscale : Cscale) : 1.0;
+  if ((rc = bm.stage(V, ranks))) return rc;
+  CUADMM_HIP_TRY(hipEventRecord(bm.ev[0], st));
+  if (which == 2) {
+    if ((rc = launch_aty_xb(false, L, At_rp.p, At_ci.p, At_v.p, bm.ybuf.p, C.p, X.p, 1.0, aux.in.p, nullptr, st, &At_long))) return rc;
+    v = aux.in.p; sign = -1.0; unit = Cscale;
+  }
+  if ((rc = bm.run(v, sign, btasks.off.p, btasks.blk.p, st))) return rc;
+  CUADMM_HIP_TRY(hipEventRecord(bm.ev[1], st));
+  CUADMM_HIP_TRY(hipStreamSynchronize(st));
+  const float ms = event_ms(bm.ev[0], bm.ev[1]);
+  bm.calls++;
+  if ((rc = bm.fetch(blk_local.data(), ranks, unit, W_out))) return rc;
+  double sq_all = 0, dot_all = 0, best = 0, blocks = 0, rank_sum = 0;
+  int arg = -1;
+  for (int k = 0; k < nb; ++k) {
+    const int n = blk_local[k];
+    double sq = 0, dot = 0, vsq = 0;
+    if (n > 0) {
+#pragma clang fp contract(off)
+      const double *w = W_out + bm.loff[k], *x = V ? V + bm.loff[k] : nullptr;
+      for (size_t e = 0, used = (size_t)n * (size_t)ranks[k]; e < used; ++e) {
+        const double ww = w[e] * w[e], vw = x[e] * w[e], vv = x[e] * x[e];
+        sq = sq + ww; dot = dot + vw; vsq = vsq + vv;
+      }
+      sq_all = sq_all + sq; dot_all = dot_all + dot;
+      blocks += 1; rank_sum += ranks[k];
+      const double nrm = std::sqrt(sq);
+      if (arg < 0 || nrm > best) { best = nrm; arg = k; }
+    }
+    if (per_block) {
+      double* q = per_block + 4 * (size_t)k;
+      q[0] = std::sqrt(sq); q[1] = dot; q[2] = std::sqrt(vsq); q[3] = n > 0 ? 0.0 : 2.0;
+    }
+  }
+  o[0] = std::sqrt(sq_all); o[1] = dot_all; o[2] = (double)arg; o[3] = best; o[4] = blocks; o[5] = rank_sum;
+  o[6] = ms;
+  o[7] = bm.bytes() + btasks.bytes() + (bm.ybuf.p ? aux.bytes() : 0.0);
+  return CUADMM_OK;
+}
+
 extern "C" {
 
 int cuadmm_get_status(const cuadmm_solver* s, double o[8]) {
@@ -575,6 +642,26 @@ int cuadmm_lowrank(cuadmm_solver* s, int which, double tol, int rmax, double o[8
   if (rmax < 1 || rmax > kMaxBlockSize) { set_error("lowrank: rmax = %d, allowed are 1 to %d", rmax, kMaxBlockSize); return CUADMM_ERR_INVALID; }
   if ((rc = s->lr_prepare(rmax))) return rc;
   return s->lr_run(which, tol, o, per_block, L_out, piv_out);
+}
+int cuadmm_block_multiply(cuadmm_solver* s, int which, const double* V, const int* ranks, int rmax, double* W_out, double o[8], double* per_block) {
+  int rc = report_guard(s, o, "block_multiply", "results", which == 2);
+  if (rc) return rc;
+  if (which < 0 || which > 2) { set_error("block_multiply: which = %d (0: X, 1: S, 2: C - A'y)", which); return CUADMM_ERR_INVALID; }
+  if (rmax < 1 || rmax > kMaxBlockSize) { set_error("block_multiply: rmax = %d, allowed are 1 to %d", rmax, kMaxBlockSize); return CUADMM_ERR_INVALID; }
+  if (!W_out || !ranks) { set_error("block_multiply: W_out or ranks is null"); return CUADMM_ERR_INVALID; }
+  long long at = 0;                      // first double of block k's V_k
+  for (int k = 0; k < (int)s->blk_local.size(); ++k) {
+    const int n = s->blk_local[k];
+    if (n <= 0) continue;
+    const int rc_k = std::min(n, rmax), r = ranks[k];
+    if (r < 0 || r > rc_k) { set_error("block_multiply: block %d of size %d has rank %d, allowed are 0 to %d", k, n, r, rc_k); return CUADMM_ERR_INVALID; }
+    if (r > 0 && !V) { set_error("block_multiply: V is null and block %d has rank %d", k, r); return CUADMM_ERR_INVALID; }
+    for (long long e = at, end = at + (long long)n * r; e < end; ++e)
+      if (!std::isfinite(V[e])) { set_error("block_multiply: block %d, row %lld of column %lld is not finite", k, (e - at) % n, (e - at) / n); return CUADMM_ERR_INVALID; }
+    at += (long long)n * rc_k;
+  }
+  if ((rc = s->bm_prepare(which, rmax)) || (which == 2 && (rc = s->stage_scaled_y(s->bm.ybuf.p, nullptr)))) return rc;
+  return s->bm_run(which, V, ranks, W_out, o, per_block);
 }
 int cuadmm_get_evaluate_info(const cuadmm_solver* s, double o[4]) {
   if (!s || !o) { set_error("get_evaluate_info: null"); return CUADMM_ERR_INVALID; }

@@ -377,6 +377,10 @@ struct cuadmm_solver {
 
   LoPlan lo;                   // (report_plans.h): cuadmm_set_lowrank
 
+  BmPlan bm;                   // (report_plans.h): cuadmm_block_multiply
+  int bm_prepare(int which, int rmax);
+  int bm_run(int which, const double* V, const int* ranks, double* W_out, double out8[8], double* per_block);
+
   // profiling
   DevEvent ev0[K_NUM][2], ev1[K_NUM][2];
   int ev_used[K_NUM] = {0};

@@ -599,6 +599,46 @@ int cuadmm_op_block_outer_plan(const int* blk_vals, int mat_num, int rmax, int s
   return (int)tasks.size();
 }
 
+// the kernel of cuadmm_block_multiply on a DEVICE svec vector whose blocks follow one another from slot 0 (csrc/block_mult.hip): W_host <-
+// sign * M_k V_k per PSD block, + 0.0 in the columns >= ranks[k]; V_host (null where every rank is 0) and W_host laid out as
+// cuadmm_lowrank's L_out for rmax, ranks and blk_vals on the host.  The vector is only read.  Synchronises the stream.
+int cuadmm_op_block_mult(const double* svec_dev, const int* blk_vals, int mat_num, double sign, const double* V_host, const int* ranks, int rmax, double* W_host,
+                         void* stream) {
+  if (!svec_dev || !ranks || !blk_vals || mat_num < 1 || rmax < 1 || rmax > kMaxBlockSize || !W_host || !(sign == 1.0 || sign == -1.0)) {
+    set_error("op_block_mult: invalid argument");
+    return CUADMM_ERR_INVALID;
+  }
+  for (int k = 0; k < mat_num; ++k) {
+    const int n = blk_vals[k];
+    if (n == 0 || n > kMaxBlockSize) { set_error("op_block_mult: block %d has size %d", k, n); return CUADMM_ERR_INVALID; }
+    if (n > 0 && (ranks[k] < 0 || ranks[k] > std::min(n, rmax) || (ranks[k] > 0 && !V_host))) {
+      set_error("op_block_mult: block %d of size %d has rank %d%s", k, n, ranks[k], V_host ? "" : " and V is null");
+      return CUADMM_ERR_INVALID;
+    }
+  }
+  int rc, ndev = 0;      // the current device is the vector's: it is not changed
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_error("no HIP device available; this engine has no CPU fallback"); return CUADMM_ERR_NO_DEVICE; }
+  hipStream_t st = (hipStream_t)stream;
+  BlockTasksDev t;
+  BmPlan plan;
+  if ((rc = t.build(blk_vals, mat_num, nullptr)) || (rc = plan.prepare(blk_vals, mat_num, rmax)) || (rc = plan.stage(V_host, ranks))) return rc;
+  if ((rc = plan.run(svec_dev, sign, t.off.p, t.blk.p, st))) return rc;
+  CUADMM_HIP_TRY(hipStreamSynchronize(st));
+  return plan.fetch(blk_vals, ranks, 1.0, W_host);
+}
+
+// the host side of that kernel: loff_out (mat_num + 1, may be null) <- the offsets of V_k / W_k for rmax; tasks_out (may be null) <- up to
+// cap_slots wavefront slots of two ints (k, panel; k < 0: an empty slot).  Returns the number of slots.  Host only.
+int cuadmm_op_block_mult_plan(const int* blk_vals, int mat_num, int rmax, long long* loff_out, int* tasks_out, int cap_slots) {
+  std::vector<BmTask> tasks;
+  std::vector<long long> loff;
+  int rc = bm_build_tasks(mat_num, blk_vals, rmax, &tasks, &loff);
+  if (rc) return rc;
+  if (loff_out) std::copy(loff.begin(), loff.end(), loff_out);
+  for (size_t q = 0; tasks_out && q < tasks.size() && (int)q < cap_slots; ++q) { tasks_out[2 * q] = tasks[q].k; tasks_out[2 * q + 1] = tasks[q].p; }
+  return (int)tasks.size();
+}
+
 int cuadmm_dev_malloc(void** ptr, size_t bytes) { CUADMM_HIP_TRY(hipMalloc(ptr, bytes ? bytes : 8)); return CUADMM_OK; }
 int cuadmm_dev_free(void* ptr) { if (ptr) CUADMM_HIP_TRY(hipFree(ptr)); return CUADMM_OK; }
 int cuadmm_memcpy_h2d(void* dst, const void* src, size_t bytes) { return staged_h2d(dst, src, bytes); }

@@ -1,5 +1,6 @@
 // What the reports on a point own beside the iteration's state, and what the op hooks build on their own: the auxiliary projector, the
-// per-block task lists, the plans of cuadmm_lambda_min, cuadmm_lowrank and cuadmm_set_lowrank.  Nothing here is read by the iteration.
+// per-block task lists, the plans of cuadmm_lambda_min, cuadmm_lowrank, cuadmm_set_lowrank and cuadmm_block_multiply.  Nothing here is
+// read by the iteration.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -10,6 +11,7 @@
 #include "lambda_min.h"
 #include "lowrank.h"
 #include "lowrank_apply.h"
+#include "block_mult.h"
 
 struct cuadmm_solver;
 
@@ -213,6 +215,67 @@ struct LoPlan {
   int run(const long long* off_d, const int* blk_d, double* v, hipStream_t st) {
     return launch_block_outer((int)tasks.size(), tasks_d.p, Lbuf.p, loff_d.p, ranks_d.p, off_d, blk_d, v, st);
   }
+};
+
+// Blocks times factors (cuadmm_block_multiply, cuadmm_op_block_mult; block_mult.h, DESIGN.md "Blocks times factors"): the wavefront
+// task list (it depends on the block sizes alone), the offsets of the blocks' V_k / W_k for the rmax of the last call, the device V, W and
+// ranks (they grow with rmax and are kept), the y of which = 2, a pair of events.  V travels whole in one staged copy and W comes back
+// whole, padding columns included; both copies lie outside the timed interval.  The offsets and
+// sizes per block are the task lists' (btasks).  Nothing here is read by the iteration.
+struct BmPlan {
+  std::vector<BmTask> tasks;
+  std::vector<long long> loff;              // of rmax_now, nb + 1 entries
+  DevBuf<BmTask> tasks_d;
+  DevBuf<long long> loff_d;
+  DevBuf<int> ranks_d;
+  DevBuf<double> Vbuf, Wbuf, ybuf;
+  int nb = 0, rmax_now = 0;
+  DevEvent ev[2];
+  long long calls = 0;
+  int prepare(const int* blk_h, int nblk, int rmax) {
+    if (ranks_d.p && rmax == rmax_now) return CUADMM_OK;
+    int rc = bm_build_tasks(nblk, blk_h, rmax, &tasks, &loff);
+    if (rc) return rc;
+    const bool first = !ranks_d.p;
+    if (first) {
+      if ((rc = tasks_d.from(tasks, 1)) || (rc = loff_d.alloc((size_t)nblk + 1))) return rc;      // (+ 1: never empty)
+      for (auto& e : ev) if ((rc = e.create())) return rc;
+    }
+    rmax_now = 0;                           // (until the offsets on the device are this rmax's)
+    if ((rc = loff_d.upload(loff.data(), loff.size()))) return rc;
+    const size_t need = (size_t)loff.back() + 1;
+    if (Vbuf.n < need && (rc = Vbuf.alloc(need))) return rc;
+    if (Wbuf.n < need && (rc = Wbuf.alloc(need))) return rc;
+    nb = nblk;
+    rmax_now = rmax;
+    return first ? ranks_d.alloc((size_t)nblk + 1) : CUADMM_OK;      // last: marks the set as complete
+  }
+  // V (whole, one copy; null: nothing, every rank is 0) and the ranks to the device
+  int stage(const double* V_host, const int* ranks) {
+    int rc;
+    const size_t count = V_host ? (size_t)loff.back() : 0;
+    if (count > 0 && (rc = Vbuf.upload(V_host, count))) return rc;
+    return ranks_d.upload(ranks, (size_t)nb);
+  }
+  // Wbuf (device) <- sign * M_k V_k on every PSD block of v, one launch
+  int run(const double* v, double sign, const long long* off_d, const int* blk_d, hipStream_t st) {
+    return launch_block_mult((int)tasks.size(), tasks_d.p, v, sign, Vbuf.p, Wbuf.p, loff_d.p, ranks_d.p, off_d, blk_d, st);
+  }
+  // W_out (loff.back() doubles, host) behind a drained stream: the kernel's entries times `unit`, + 0.0 in the columns >= ranks[k]
+  int fetch(const int* blk_h, const int* ranks, double unit, double* W_out) {
+    int rc;
+    const size_t count = (size_t)loff.back();
+    if (count > 0 && (rc = staged_d2h(W_out, Wbuf.p, sizeof(double) * count))) return rc;
+    for (int k = 0; k < nb; ++k) {
+      if (blk_h[k] <= 0) continue;
+      double* const w = W_out + loff[k];
+      const size_t used = (size_t)blk_h[k] * (size_t)ranks[k];
+      for (size_t e = 0; unit != 1.0 && e < used; ++e) w[e] *= unit;
+      std::fill(w + used, W_out + loff[k + 1], 0.0);
+    }
+    return CUADMM_OK;
+  }
+  double bytes() const { return 8.0 * (double)(loff_d.n + Vbuf.n + Wbuf.n + ybuf.n + tasks_d.n) + 4.0 * (double)ranks_d.n; }
 };
 
 }  // namespace cuadmm

@@ -27,13 +27,13 @@ def _p(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
-def pack_lowrank(blk_vals, Ls):
-    """(L, ranks, rmax) as cuadmm_set_lowrank takes them from a list of (n_k, r_k) arrays, one entry per block (those of unconstrained
+def pack_lowrank(blk_vals, Ls, who="set_lowrank"):
+    """(L, ranks, rmax) as cuadmm_set_lowrank and cuadmm_block_multiply take them from a list of (n_k, r_k) arrays, one entry per block (those of unconstrained
     blocks are ignored): rmax = max(1, max r_k), block k at the prefix sum of n_j min(n_j, rmax) over the PSD blocks before it, column by
     column, the columns >= r_k zero.  ValueError on a wrong number of entries, a wrong row count or more columns than rows."""
     blk = [int(n) for n in blk_vals]
     if len(Ls) != len(blk):
-        raise ValueError("set_lowrank: %d factors for %d blocks" % (len(Ls), len(blk)))
+        raise ValueError("%s: %d factors for %d blocks" % (who, len(Ls), len(blk)))
     ranks = np.zeros(len(blk), np.int32)
     mats = [None] * len(blk)
     for k, n in enumerate(blk):
@@ -41,7 +41,7 @@ def pack_lowrank(blk_vals, Ls):
             continue
         A = _f64(Ls[k])
         if A.ndim != 2 or A.shape[0] != n or A.shape[1] > n:
-            raise ValueError("set_lowrank: block %d has size %d, its factor the shape %s" % (k, n, A.shape))
+            raise ValueError("%s: block %d has size %d, its factor the shape %s" % (who, k, n, A.shape))
         mats[k], ranks[k] = A, A.shape[1]
     rmax = max(1, int(ranks.max()) if ranks.size else 1)
     off = np.concatenate([[0], np.cumsum([n * min(n, rmax) if n > 0 else 0 for n in blk])]).astype(np.int64)
@@ -288,6 +288,27 @@ class SDPSolver:
             check(self._lib.cuadmm_set_lowrank(self._h, self.LOWRANK_WHICH[name], _p(Lv), _p(ranks), rmax, float(sig), _p(o)))
             out[name] = {"blocks": int(o[0]), "rank_sum": int(o[1]), "ms": float(o[2]), "bytes_staged": float(o[3])}
         return out
+
+    def block_multiply(self, which, V):
+        """W_k = M_k V_k for every PSD block of X, S or ("dual") C - A'y at the current y (cuadmm_block_multiply).  V: a list of (n_k, r_k)
+        arrays, one entry per block, as lowrank()["L"] returns (entries of unconstrained blocks are ignored).  Returns "W": the list of
+        (n_k, r_k) products ((0, 0) for unconstrained blocks); "per_block": (mat_num, 4) rows ||W_k||_F, <V_k, W_k>, ||V_k||_F, flag
+        (0 multiplied, 2 unconstrained); "norm" = ||W||_F, "inner" = sum <V_k, W_k>, "block" / "block_norm": the block of the largest
+        ||W_k||_F, "blocks", "rank_sum", "ms", "bytes".  Behind a solve the call leaves the pending scaled state as it is."""
+        if which not in self.LAMBDA_MIN_WHICH:
+            raise ValueError("block_multiply: which must be 'X', 'S' or 'dual'")
+        Vv, ranks, rmax = pack_lowrank(self.blk_vals, V, "block_multiply")
+        Wv = np.zeros(Vv.size)
+        o = np.zeros(8)
+        pb = np.zeros(4 * self.mat_num)
+        check(self._lib.cuadmm_block_multiply(self._h, self.LAMBDA_MIN_WHICH[which], _p(Vv), _p(ranks), rmax, _p(Wv), _p(o), _p(pb)))
+        W, at = [], 0
+        for k, n in enumerate(int(n) for n in self.blk_vals):
+            r = int(ranks[k])
+            W.append(Wv[at:at + max(n, 0) * r].reshape(r, max(n, 0)).T.copy())
+            at += n * min(n, rmax) if n > 0 else 0
+        return {"W": W, "per_block": pb.reshape(self.mat_num, 4), "norm": float(o[0]), "inner": float(o[1]), "block": int(o[2]), "block_norm": float(o[3]),
+                "blocks": int(o[4]), "rank_sum": int(o[5]), "ms": float(o[6]), "bytes": float(o[7])}
 
     def set_allreduce(self, fn):
         """fn(dev_ptr:int, count:int, hip_stream:int) -> None : in-place sum over ranks on that stream."""

@@ -173,6 +173,34 @@ int cuadmm_get_S(cuadmm_solver* s, double* host_out /* vec_len */);
  * writing through X.vals/y.vals/S.vals before solve(..., if_first=false) (solver.cu:385-409);
  * NULL leaves that vector untouched */
 int cuadmm_set_XyS(cuadmm_solver* s, const double* X, const double* y, const double* S, double sig);
+/* W_k = M_k V_k for every PSD block k of the resident point: M = X (which = 0), S (1) or S^ = C - A'y at the current y (2); V_k is n_k x r_k,
+ * r_k = ranks[k] ("Blocks times factors"; csrc/block_mult.h).  V and W_out hold cuadmm_lowrank_size(rmax) doubles in the layout
+ * of cuadmm_lowrank's L_out for this rmax: block k at the prefix sum of n_j min(n_j, rmax) over the PSD blocks before it, column by
+ * column, n_k doubles per column; unconstrained blocks occupy nothing, are not read, and their entries of ranks (mat_num ints) are
+ * ignored.  Columns >= r_k of V are never read (they may hold NaN); in W_out they are +0.0 (r_k = 0: the whole block).
+ * One kernel pass on the fp64 matrix cores reads the svec slots where they lie and forms, with s_ij the raw slot of (i, j),
+ *   W[i, t] = sign * fma(0.7071067811865476, sum_{j != i} s_ij V[j, t], s_ii * V[i, t])        (sign = -1 for which = 2, else 1),
+ * every row of W owned by one wavefront (no atomics: the same bits on every run).  For any order of the sums, with u = 2^-53 and M_ij
+ * the exact matrix entry (s_ij / sqrt(2) or s_ii),
+ *   |W[i, t] - exact| <= (n_k + 4) u sum_j |M_ij| |V[j, t]|
+ * (n_k products and sums, the scaling, the constant's own rounding and one spare); with small-integer slots and V the result is the
+ * correctly rounded value of the exact one.  For which = 2 the vector is formed as cuadmm_lambda_min forms it, -(A'y - C) by the
+ * iteration's kernel in the engine's scaled space, and its own rounding comes on top.  Behind a solve the scaled iterate is read and W
+ * is multiplied on the host by the unit (bscale for X, Cscale for S and S^: one more u); the deferred unscaling is not triggered and a
+ * following cuadmm_solve(..., if_first = 0) continues bit for bit.  Nothing of the solver changes.
+ * per_block (may be NULL), 4 mat_num doubles: [4k] ||W_k||_F, [4k + 1] <V_k, W_k>, [4k + 2] ||V_k||_F, [4k + 3] flag: 0 multiplied, 2
+ * unconstrained (then the three numbers are 0).  They are formed on the host from the returned W_out and V over the entries e of the
+ * r_k columns in index order with plain doubles: q = 0; q = q + a[e] * b[e] (the product rounded, then the sum), the norms the square
+ * roots of such sums.
+ * out8: [0] sqrt of the sum over k, in block order, of the sums of squares behind [4k]; [1] the sum over k of [4k + 1]; [2] the PSD
+ * block with the largest ||W_k||_F, the first of equals (-1: no PSD block); [3] that norm; [4] PSD blocks; [5] sum of r_k; [6] device
+ * milliseconds of the kernel pass (HIP events), with the formation of S^ for which = 2 -- the staged copy of V to the device and of W
+ * back, both whole buffers, are not in it; [7] bytes of device memory the call holds.
+ * CUADMM_ERR_INVALID, the solver as it was: solver not initialised; out8, W_out or ranks NULL; which outside 0..2; rmax outside 1..8192;
+ * a ranks[k] of a PSD block outside 0..min(n_k, rmax); V NULL while some rank is positive; an entry that is not finite in a column
+ * that would be read; world > 1 or a handle that leads an in-process group.  CUADMM_ERR_FACTOR for which = 2 behind a failed
+ * cuadmm_update_A. */
+int cuadmm_block_multiply(cuadmm_solver* s, int which, const double* V, const int* ranks, int rmax, double* W_out, double out8[8], double* per_block);
 /* Replace X (which = 0) or S (1) between two solves by per-block factors: every PSD block k becomes L_k L_k' with r_k = ranks[k] columns
  * ("Starting from low-rank factors"; csrc/lowrank_apply.h).  L is laid out as cuadmm_lowrank's L_out for this rmax: block k at the
  * prefix sum of n_j min(n_j, rmax) over the PSD blocks before it, column by column, n_k doubles per column; unconstrained blocks occupy
@@ -672,6 +700,15 @@ int cuadmm_op_block_outer(const double* L_host, const int* ranks, const int* blk
  * row by row; four consecutive slots are one workgroup.  split_from: the size from which a block is split over workgroups (0: the
  * engine's; at least 33).  Returns the number of slots, or an error.  Host only (no device needed). */
 int cuadmm_op_block_outer_plan(const int* blk_vals, int mat_num, int rmax, int split_from, long long* loff_out, int* tasks_out, int cap_slots);
+/* The kernel of cuadmm_block_multiply on a DEVICE svec vector whose blocks follow one another from slot 0 (csrc/block_mult.hip): W_host <-
+ * sign * M_k V_k per PSD block (sign = 1 or -1), +0.0 in the columns >= ranks[k]; the vector is only read.  V_host (NULL where every rank
+ * is 0) and W_host are laid out as in cuadmm_block_multiply for rmax; ranks and blk_vals on the host.  Synchronises the stream. */
+int cuadmm_op_block_mult(const double* svec_dev, const int* blk_vals, int mat_num, double sign, const double* V_host, const int* ranks, int rmax, double* W_host,
+                         void* stream);
+/* The host side of that kernel.  loff_out (may be NULL): mat_num + 1 offsets of the blocks' V_k / W_k for rmax.  tasks_out (may be NULL):
+ * up to cap_slots wavefront slots of two ints (block or -1, panel of 16 rows); four consecutive slots are one workgroup and hold panels
+ * of one block, or blocks of one panel.  Returns the number of slots, or an error.  Host only (no device needed). */
+int cuadmm_op_block_mult_plan(const int* blk_vals, int mat_num, int rmax, long long* loff_out, int* tasks_out, int cap_slots);
 int cuadmm_op_spmv_rows(int rows, int ncols, const int* row_ptrs, const int* col_ids, const double* vals, const double* X, const double* S, const double* C,
                         int want_x, int want_s, const int* rowmap, int out_len, double* outX, double* outS, int* info4);
 int cuadmm_op_rp_stats(int m, const double* ax, const double* b, const double* normA, const double* y, double bscale, const double* sums2, double* out4);

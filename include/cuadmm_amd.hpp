@@ -202,6 +202,27 @@ class SDPSolver {
     return LowRankStart{(int)o[0], o[1], o[2], o[3]};
   }
 
+  // cuadmm_block_multiply: W_k = M_k V_k per PSD block, M = X (which = 0), S (1) or C - A'y (2); V in the layout of LowRank::L for this rmax,
+  // ranks: mat_num column counts; W in the same layout, per_block: [4k ..] = ||W_k||_F, <V_k, W_k>, ||V_k||_F, flag; not in the reference
+  struct BlockMultiply {
+    double norm, inner; int block; double block_norm; int blocks; double rank_sum, ms, bytes;
+    std::vector<double> W, per_block;
+  };
+  BlockMultiply block_multiply(int which, const double* V, const int* ranks, int rmax) {
+    double o[8] = {0};
+    int vl = 0, cn = 0, mn = 0;
+    long long count = 0;
+    check(cuadmm_get_dims(h_, &vl, &cn, &mn));
+    check(cuadmm_lowrank_size(h_, rmax, &count));
+    BlockMultiply r;
+    r.W.assign((size_t)count + 1, 0.0);
+    r.per_block.assign(4 * (size_t)mn, 0.0);
+    check(cuadmm_block_multiply(h_, which, V, ranks, rmax, r.W.data(), o, r.per_block.data()));
+    r.W.resize((size_t)count);
+    r.norm = o[0]; r.inner = o[1]; r.block = (int)o[2]; r.block_norm = o[3]; r.blocks = (int)o[4]; r.rank_sum = o[5]; r.ms = o[6]; r.bytes = o[7];
+    return r;
+  }
+
   // cuadmm_update_bC: new b and / or C on the factored solver (nnz < 0: unchanged); not in the reference
   void update_bC(const int* cpu_b_indices, const double* cpu_b_vals, int b_nnz, const int* cpu_C_indices, const double* cpu_C_vals,
                  int C_nnz, bool keep_iterate = true, double sig = 0.0) {
