@@ -223,5 +223,27 @@ int launch_slot_partials(long long n, const Term& term, double* partials, hipStr
   CUADMM_HIP_TRY(hipGetLastError());
   return CUADMM_OK;
 }
+// The same with N sums per index: partials[q kBrSlots + slot], q < N.  Term: add(s, i) with double (&s)[N]; it may write vectors of
+// its own at index i (every index is visited by exactly one thread).
+template <int N, class Term>
+__global__ __launch_bounds__(kBrThreads) void slot_partials_kernel(long long n, Term term, double* partials) {
+  __shared__ double lds[4];
+  double s[N];
+#pragma unroll
+  for (int q = 0; q < N; ++q) s[q] = 0;
+  for (long long i = (long long)blockIdx.x * kBrThreads + threadIdx.x; i < n; i += (long long)kBrSlots * kBrThreads) term.add(s, i);
+#pragma unroll
+  for (int q = 0; q < N; ++q) s[q] = block_sum(s[q], lds);
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int q = 0; q < N; ++q) partials[q * kBrSlots + blockIdx.x] = s[q];
+  }
+}
+template <int N, class Term>
+int launch_slot_partials(long long n, const Term& term, double* partials, hipStream_t st) {
+  hipLaunchKernelGGL((slot_partials_kernel<N, Term>), dim3(kBrSlots), dim3(kBrThreads), 0, st, n, term, partials);
+  CUADMM_HIP_TRY(hipGetLastError());
+  return CUADMM_OK;
+}
 
 }  // namespace cuadmm

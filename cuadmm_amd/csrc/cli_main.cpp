@@ -30,6 +30,9 @@
 //   --block-mult=X|S|dual,DIR/ (repeatable): behind every solve, W_k = M_k V_k for every PSD block of X, S or C - A'y (cuadmm_block_multiply)
 //   with V_k from factor files as --lowrank-out writes them, read by the reader of --start-lowrank: DIR/L_X_<k>.txt where any is present,
 //   otherwise DIR/L_S_<k>.txt (files of the matrix that is not used are not opened); a missing block has rank 0.  One line per call, and "block_mult" (one object per call) in the sidecar
+//   --lowrank-grad=DIR/[,SIGMA]: behind every solve, value and gradient of <C, x> - y'r + (SIGMA / 2) ||r||^2 at the factors DIR/L_X_<k>.txt
+//   (as --lowrank-out writes them; else DIR/L_S_<k>.txt) with y from DIR/y.txt when present, else the resident y (cuadmm_lowrank_grad);
+//   one line, and "lowrank_grad" in the sidecar.  --lowrank-grad-out=DIR2/: DIR2/G_<k>.txt per PSD block (as W_<k>.txt) and DIR2/r.txt
 //   --block-mult-out=DIR2/ (with --block-mult): DIR2/W_<k>.txt per PSD block k, n_k r_k numbers column by column with 17 significant
 //   digits (of the last --block-mult where there are several)
 //   --json=<file>: a sidecar with the run's figures (iterations, residuals, iters/s, per-phase milliseconds, the projection's
@@ -204,6 +207,22 @@ static void write_block_mult(FILE* f, const std::vector<BlockMultCall>& calls) {
   }
   fprintf(f, "]");
 }
+// --lowrank-grad: the factors, y (when DIR/y.txt exists), sigma and the results of cuadmm_lowrank_grad
+struct LowRankGradCall {
+  bool on = false, have_y = false;
+  int rmax = 1;
+  double sigma = 0;
+  std::string dir;
+  std::vector<int> ranks;
+  std::vector<double> L, G, y, r;
+  double o[8] = {0};
+};
+// "lowrank_grad": {...} with the eight numbers of cuadmm_lowrank_grad
+static void write_lowrank_grad(FILE* f, const LowRankGradCall& c) {
+  const double* o = c.o;
+  fprintf(f, " \"lowrank_grad\": {\"sigma\": %.17g, \"rmax\": %d, \"y\": %s, \"f\": %.17g, \"cx\": %.17g, \"yr\": %.17g, \"rnorm\": %.17g, \"gnorm\": %.17g, "
+          "\"lg\": %.17g, \"ms\": %.17g, \"bytes\": %.0f}", c.sigma, c.rmax, c.have_y ? "true" : "false", o[0], o[1], o[2], o[3], o[4], o[5], o[6], o[7]);
+}
 // <dir/>name.txt, one number per line (cuadmm_write_dense_txt); a missing file: zeros
 static bool read_point_vec(const std::string& fn, std::vector<double>& out, size_t n, const char* who = "--kkt-point") {
   out.assign(n, 0.0);
@@ -222,7 +241,7 @@ static bool read_point_vec(const std::string& fn, std::vector<double>& out, size
 static bool write_sidecar(const std::string& path, const std::string& prefix, cuadmm_solver* solver, const cuadmm_problem_view& v, bool have_bounds,
                           const double* kkt = nullptr, const std::vector<double>& kkt_blocks = std::vector<double>(), int lm_steps = 0,
                           const double (*lm)[8] = nullptr, const LowRankReport* lr = nullptr, const LowRankStart* start = nullptr,
-                          const std::vector<BlockMultCall>* bmc = nullptr) {
+                          const std::vector<BlockMultCall>* bmc = nullptr, const LowRankGradCall* lgc = nullptr) {
   FILE* f = fopen(path.c_str(), "w");
   if (!f) return false;
   const int iters = cuadmm_get_info_iter_num(solver);
@@ -265,6 +284,7 @@ static bool write_sidecar(const std::string& path, const std::string& prefix, cu
   if (lr) { write_lowrank(f, *lr); fprintf(f, ",\n"); }
   if (start) { write_start(f, *start); fprintf(f, ",\n"); }
   if (bmc) { write_block_mult(f, *bmc); fprintf(f, ",\n"); }
+  if (lgc) { write_lowrank_grad(f, *lgc); fprintf(f, ",\n"); }
   double acc[8] = {0};
   cuadmm_get_accel_info(solver, acc);
   if (acc[0] > 0)
@@ -307,7 +327,8 @@ int main(int argc, char* argv[]) {
   int lm_steps = 0;      // --lambda-min: 0 = off
   LowRankReport lr;      // --lowrank: rmax = 0 = off
   bool lr_on = false;
-  std::string json_path, bounds_arg, kkt_point, lr_out, start_dir, bm_out;
+  std::string json_path, bounds_arg, kkt_point, lr_out, start_dir, bm_out, lg_out;
+  LowRankGradCall lgc;                 // --lowrank-grad
   std::vector<BlockMultCall> bmc;      // --block-mult, in the order given
   std::vector<std::string> then_dirs;
   std::vector<char> then_is_A;
@@ -357,12 +378,27 @@ int main(int argc, char* argv[]) {
       continue;
     }
     if (strncmp(argv[i], "--block-mult-out=", 17) == 0) { bm_out = argv[i] + 17; continue; }
+    if (strncmp(argv[i], "--lowrank-grad-out=", 19) == 0) { lg_out = argv[i] + 19; continue; }
+    if (strncmp(argv[i], "--lowrank-grad=", 15) == 0) {
+      const char* a = argv[i] + 15;
+      const char* comma = strchr(a, ',');
+      lgc.dir = comma ? std::string(a, comma) : std::string(a);
+      char* end = nullptr;
+      if (comma) lgc.sigma = strtod(comma + 1, &end);
+      if (lgc.dir.empty() || (comma && (end == comma + 1 || *end != 0 || !(lgc.sigma >= 0) || !std::isfinite(lgc.sigma)))) {
+        std::cerr << "--lowrank-grad=DIR/[,SIGMA]: SIGMA >= 0" << std::endl;
+        return 1;
+      }
+      lgc.on = true;
+      continue;
+    }
     std::cerr << "unknown option " << argv[i] << std::endl;
     return 1;
   }
 
   if (!lr_out.empty() && !lr_on) { std::cerr << "--lowrank-out needs --lowrank=TOL[,RMAX]" << std::endl; return 1; }
   if (!bm_out.empty() && bmc.empty()) { std::cerr << "--block-mult-out needs --block-mult=X|S|dual,DIR/" << std::endl; return 1; }
+  if (!lg_out.empty() && !lgc.on) { std::cerr << "--lowrank-grad-out needs --lowrank-grad=DIR/[,SIGMA]" << std::endl; return 1; }
   for (size_t k = 0; k < then_dirs.size(); ++k) {   // before any work: a stage that cannot be read must not cost the stages before it
     const std::string& d = then_dirs[k];
     DIR* dp = d.empty() ? nullptr : opendir(d.c_str());
@@ -390,6 +426,20 @@ int main(int argc, char* argv[]) {
 
   for (auto& c : bmc)      // --block-mult: read and checked before any device work
     if (!read_block_mult(v, c)) { cuadmm_problem_free(prob); return 1; }
+
+  if (lgc.on) {            // --lowrank-grad: read and checked before any device work
+    LowRankStart st;
+    bool ok = read_lowrank_start(lgc.dir, v, st, 0) && (st.have[0] || read_lowrank_start(lgc.dir, v, st, 1));
+    const int w = st.have[0] ? 0 : 1;
+    if (ok && !st.have[w]) { std::cerr << "--lowrank-grad: no factor file L_X_<k>.txt or L_S_<k>.txt in '" << lgc.dir << "'" << std::endl; ok = false; }
+    FILE* yf = ok ? fopen((lgc.dir + "y.txt").c_str(), "r") : nullptr;
+    if (yf) { fclose(yf); lgc.have_y = true; }
+    if (ok && lgc.have_y) ok = read_point_vec(lgc.dir + "y.txt", lgc.y, (size_t)v.con_num, "--lowrank-grad");
+    if (!ok) { cuadmm_problem_free(prob); return 1; }
+    lgc.rmax = st.rmax[w]; lgc.ranks = st.ranks[w]; lgc.L = st.L[w];
+    lgc.G.assign(lgc.L.size(), 0.0);
+    lgc.r.assign((size_t)v.con_num + 1, 0.0);
+  }
 
   cuadmm_solver* solver = nullptr;
   cuadmm_create(&solver);
@@ -524,6 +574,34 @@ int main(int argc, char* argv[]) {
     }
     return !bmc.empty();
   };
+  // --lowrank-grad: value and gradient at the point a solve returns, taken before anything reads the iterate
+  auto lg_report = [&]() {
+    if (!lgc.on) return false;
+    LowRankGradCall& c = lgc;
+    if (cuadmm_lowrank_grad(solver, c.L.data(), c.ranks.data(), c.rmax, c.have_y ? c.y.data() : nullptr, c.sigma, c.G.data(), c.r.data(), nullptr, c.o, nullptr) != CUADMM_OK) {
+      std::cerr << cuadmm_last_error() << std::endl;
+      return false;
+    }
+    printf(" lowrank_grad(sigma = %g): f = %.10e, <C, x> = %.10e, y'r = %.10e, ||r|| = %.10e, ||G||_F = %.10e, <L, G> = %.10e, %.3f ms\n", c.sigma, c.o[0], c.o[1], c.o[2],
+           c.o[3], c.o[4], c.o[5], c.o[6]);
+    if (lg_out.empty()) return true;
+    size_t at = 0;
+    for (int k = 0; k < v.mat_num; ++k) {
+      const long long n = v.blk_vals[k];
+      if (n <= 0) continue;
+      const std::string fn = lg_out + "G_" + std::to_string(k) + ".txt";
+      FILE* f = fopen(fn.c_str(), "w");
+      if (!f) { std::cerr << "cannot write " << fn << std::endl; return false; }
+      for (long long e = 0; e < n * c.ranks[k]; ++e) fprintf(f, "%.17g\n", c.G[at + (size_t)e]);
+      fclose(f);
+      at += (size_t)(n * std::min<long long>(n, c.rmax));
+    }
+    FILE* f = fopen((lg_out + "r.txt").c_str(), "w");
+    if (!f) { std::cerr << "cannot write " << lg_out << "r.txt" << std::endl; return false; }
+    for (int i = 0; i < v.con_num; ++i) fprintf(f, "%.17g\n", c.r[(size_t)i]);
+    fclose(f);
+    return true;
+  };
   // --start-lowrank: the point replaces init's zeros, and the solve takes the iterate as it stands (if_first = 0)
   const bool started = start.have[0] || start.have[1] || start.have_y;
   for (int w = 0; w < 2 && rc == CUADMM_OK; ++w) {
@@ -544,6 +622,7 @@ int main(int argc, char* argv[]) {
   bool have_lm = lm_report();
   bool have_lr = lr_report();
   bool have_bm = bm_report();
+  bool have_lg = lg_report();
 
   if (accel != 0) {
     double acc[8] = {0};
@@ -552,7 +631,7 @@ int main(int argc, char* argv[]) {
   }
   std::vector<double> X((size_t)v.vec_len);
   if (cuadmm_get_X(solver, X.data()) == CUADMM_OK) cuadmm_write_dense_txt((prefix + "X_opt.txt").c_str(), X.data(), v.vec_len);
-  if (!json_path.empty() && !write_sidecar(json_path, prefix, solver, v, !bounds_arg.empty(), have_kkt ? kk : nullptr, kkb, lm_steps, have_lm ? lm : nullptr, have_lr ? &lr : nullptr, started ? &start : nullptr, have_bm ? &bmc : nullptr)) std::cerr << "cannot write " << json_path << std::endl;
+  if (!json_path.empty() && !write_sidecar(json_path, prefix, solver, v, !bounds_arg.empty(), have_kkt ? kk : nullptr, kkb, lm_steps, have_lm ? lm : nullptr, have_lr ? &lr : nullptr, started ? &start : nullptr, have_bm ? &bmc : nullptr, have_lg ? &lgc : nullptr)) std::cerr << "cannot write " << json_path << std::endl;
   for (size_t k = 0; k < then_dirs.size() && rc == CUADMM_OK; ++k) {
     const std::string& d = then_dirs[k];
     std::vector<int> bi, ci;
@@ -580,9 +659,10 @@ int main(int argc, char* argv[]) {
     have_lm = lm_report();
     have_lr = lr_report();
     have_bm = bm_report();
+    have_lg = lg_report();
     if (cuadmm_get_X(solver, X.data()) == CUADMM_OK) cuadmm_write_dense_txt((d + "X_opt.txt").c_str(), X.data(), v.vec_len);
     const std::string side = json_path + "." + std::to_string(k + 1);
-    if (!json_path.empty() && !write_sidecar(side, d, solver, v, !bounds_arg.empty(), have_kkt ? kk : nullptr, kkb, lm_steps, have_lm ? lm : nullptr, have_lr ? &lr : nullptr, nullptr, have_bm ? &bmc : nullptr)) std::cerr << "cannot write " << side << std::endl;
+    if (!json_path.empty() && !write_sidecar(side, d, solver, v, !bounds_arg.empty(), have_kkt ? kk : nullptr, kkb, lm_steps, have_lm ? lm : nullptr, have_lr ? &lr : nullptr, nullptr, have_bm ? &bmc : nullptr, have_lg ? &lgc : nullptr)) std::cerr << "cannot write " << side << std::endl;
   }
   cuadmm_destroy(solver);
   cuadmm_problem_free(prob);

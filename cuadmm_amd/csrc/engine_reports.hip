@@ -1,7 +1,7 @@
 // What the engine reports beside the iteration: the infeasibility check and the certified lower bound behind the iteration's steps, and
-// the reports on a point (cuadmm_lower_bound, cuadmm_evaluate, cuadmm_lambda_min, cuadmm_lowrank, cuadmm_block_multiply) with their C
-// entry points.  Host code only: the kernels are those of infeas.hip, lower_bound.hip, evaluate.hip, lambda_min.hip, lowrank.hip,
-// block_mult.hip and the iteration's own.
+// the reports on a point (cuadmm_lower_bound, cuadmm_evaluate, cuadmm_lambda_min, cuadmm_lowrank, cuadmm_block_multiply,
+// cuadmm_lowrank_grad) with their C entry points.  Host code only: the kernels are those of infeas.hip, lower_bound.hip, evaluate.hip,
+// lambda_min.hip, lowrank.hip, lowrank_apply.hip, block_mult.hip, lowrank_grad.hip and the iteration's own.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -513,6 +513,101 @@ int cuadmm_solver::bm_run(int which, const double* V, const int* ranks, double* 
   return CUADMM_OK;
 }
 
+// ------------------------------------------------------------------------------------------
+// Value and gradient at factors (cuadmm_lowrank_grad): DESIGN.md, "Value and gradient at factors"
+// ------------------------------------------------------------------------------------------
+// the two factor plans for this rmax, the plan's own vectors on first use; the column norms (where the engine keeps none on the device)
+// and the auxiliary projector's vectors and b on every call
+int cuadmm_solver::lg_prepare(int rmax) {
+  int rc;
+  const int nb = (int)blk_local.size();
+  if (!btasks.built && (rc = btasks.build(blk_local.data(), nb, nullptr))) return rc;
+  if ((rc = bm.prepare(blk_local.data(), nb, rmax)) || (rc = lo.prepare(blk_local.data(), nb, rmax)) || (rc = lg.prepare(L, m, nb, btasks.nchunk, !normA_d.p))) return rc;
+  if (lg.normA.p && m > 0 && (rc = staged_h2d(lg.normA.p, normA_p.data(), sizeof(double) * (size_t)m, st))) return rc;
+  return aux.ensure(*this);
+}
+
+// The chain at the scaled y in lg.ybuf.  x is assembled in lg.xv in the units X lies in (X = ux xv: ux = bscale behind a solve, else 1): a
+// device copy of X, then svec(L_k L_k') over its PSD blocks from the factors in those units -- the caller's own, as the block product's V
+// holds them, where ux = 1, else a second staged copy times fl(1 / sqrt(ux)).  Then A x, the multiplier pass, M = A'ytilde - C into the
+// auxiliary projector's input vector (S^ = -Cscale M), W = -M_k L_k with the caller's L (the launch and the unit of
+// cuadmm_block_multiply(2): sigma = 0 gives its bits) and the per-block terms.  G = 2 (Cscale W), the doubling exact.  The sums over G and L
+// are plain double sums in index order, as in bm_run.  Reads X, y, A, A', b, C; writes only the plans' own buffers and that input vector.
+int cuadmm_solver::lg_run(const double* Lf, const int* ranks, double sigma, double* G_out, double* r_out, double* Shat_out, double o[8], double* per_block) {
+  int rc;
+  const int nb = (int)blk_local.size();
+  const double ux = pending_unscale ? bscale : 1.0;
+  const double* const normA_dev = normA_d.p ? normA_d.p : lg.normA.p;
+  if ((rc = bm.stage(Lf, ranks))) return rc;
+  const double* Lx = bm.Vbuf.p;
+  if (ux != 1.0 && Lf) {
+    const double root = 1 / std::sqrt(ux);
+    std::vector<double>& tmp = lg.h_stage;      // (kept by the plan: a caller's optimiser makes this call in a loop)
+    tmp.assign((size_t)lo.loff.back(), 0.0);
+    for (int k = 0; k < nb; ++k)                // the columns that are read; the others travel as zeros
+      for (size_t e = (size_t)lo.loff[k], end = e + (blk_local[k] > 0 ? (size_t)blk_local[k] * (size_t)ranks[k] : 0); e < end; ++e) tmp[e] = Lf[e] * root;
+    double bytes = 0;
+    if ((rc = lo.stage(tmp.data(), ranks, &bytes))) return rc;
+    Lx = lo.Lbuf.p;
+  }
+  CUADMM_HIP_TRY(hipEventRecord(lg.ev[0], st));
+  CUADMM_HIP_TRY(hipMemcpyAsync(lg.xv.p, X.p, sizeof(double) * (size_t)L, hipMemcpyDeviceToDevice, st));
+  if ((rc = launch_block_outer((int)lo.tasks.size(), lo.tasks_d.p, Lx, bm.loff_d.p, bm.ranks_d.p, btasks.off.p, btasks.blk.p, lg.xv.p, st))) return rc;
+  if (m > 0 && (rc = launch_spmv_rows(m, A_avg_nnz, A_rp.p, A_ci.p, A_v.p, lg.xv.p, S.p, C.p, lg.ax.p, nullptr, st, &A_long))) return rc;
+  if ((rc = launch_lrg_multiplier(m, lg.ax.p, aux.b_dev(*this), normA_dev, lg.ybuf.p, pending_unscale ? 1.0 : 1 / bscale, bscale, 1 / Cscale, sigma, lg.ytilde.p,
+                                  lg.r.p, lg.part.p, st)))
+    return rc;
+  if ((rc = launch_aty_xb(false, L, At_rp.p, At_ci.p, At_v.p, lg.ytilde.p, C.p, X.p, 1.0, aux.in.p, nullptr, st, &At_long))) return rc;
+  if ((rc = bm.run(aux.in.p, -1.0, btasks.off.p, btasks.blk.p, st))) return rc;
+  if ((rc = launch_lrg_block_terms(C.p, lg.xv.p, aux.in.p, btasks.view(), lg.cpart.p, lg.sums.p, st))) return rc;
+  CUADMM_HIP_TRY(hipEventRecord(lg.ev[1], st));
+  CUADMM_HIP_TRY(hipStreamSynchronize(st));
+  const float ms = event_ms(lg.ev[0], lg.ev[1]);
+  // --- back to the host and to the caller's units (the host scratch is the plan's and is kept)
+  std::vector<double>& h = lg.h_back;
+  h.resize((size_t)std::max(m, 1) + 2 * (size_t)kBrSlots + kLgSums * (size_t)nb);
+  if (!G_out) { lg.h_G.resize((size_t)bm.loff.back() + 1); G_out = lg.h_G.data(); }
+  if ((rc = bm.fetch(blk_local.data(), ranks, Cscale, G_out))) return rc;
+  double *const rh = h.data(), *const part = rh + std::max(m, 1), *const sums = part + 2 * kBrSlots;
+  if (m > 0 && (rc = staged_d2h(rh, lg.r.p, sizeof(double) * (size_t)m, st))) return rc;
+  if ((rc = staged_d2h(part, lg.part.p, sizeof(double) * 2 * kBrSlots, st))) return rc;
+  if (nb > 0 && (rc = staged_d2h(sums, lg.sums.p, sizeof(double) * kLgSums * (size_t)nb, st))) return rc;
+  for (int i = 0; r_out && i < m; ++i) r_out[perm[i]] = rh[i];
+  if (Shat_out) {
+    if ((rc = staged_d2h(Shat_out, aux.in.p, sizeof(double) * (size_t)L, st))) return rc;
+    for (long long i = 0; i < L; ++i) Shat_out[i] = -(Shat_out[i] * Cscale);
+  }
+  double yr = 0, rn2 = 0, cx = 0, sq_all = 0, dot_all = 0;
+  for (int j = 0; j < kBrSlots; ++j) { yr += part[j]; rn2 += part[kBrSlots + j]; }
+  yr *= objscale;
+  const double cxu = Cscale * ux;
+  for (int k = 0; k < nb; ++k) {
+    const int n = blk_local[k];
+    const double cxk = sums[kLgSums * (size_t)k] * cxu;
+    double sq = 0, dot = 0, lsq = 0;
+    if (n > 0) {
+#pragma clang fp contract(off)
+      double* g = G_out + bm.loff[k];
+      const double* x = Lf ? Lf + bm.loff[k] : nullptr;
+      for (size_t e = 0, used = (size_t)n * (size_t)ranks[k]; e < used; ++e) {
+        g[e] = 2.0 * g[e];
+        const double gg = g[e] * g[e], lg_ = x[e] * g[e], ll = x[e] * x[e];
+        sq = sq + gg; dot = dot + lg_; lsq = lsq + ll;
+      }
+      sq_all = sq_all + sq; dot_all = dot_all + dot;
+    }
+    cx = cx + cxk;
+    if (per_block) {
+      double* q = per_block + 4 * (size_t)k;
+      q[0] = cxk; q[1] = n > 0 ? std::sqrt(sq) : std::sqrt(sums[kLgSums * (size_t)k + 1]) * Cscale; q[2] = dot; q[3] = lsq;
+    }
+  }
+  o[0] = cx - yr + (0.5 * sigma) * rn2; o[1] = cx; o[2] = yr; o[3] = std::sqrt(rn2); o[4] = std::sqrt(sq_all); o[5] = dot_all;
+  o[6] = ms;
+  o[7] = lg.bytes() + bm.bytes() + 8.0 * (double)(lo.Lbuf.n + lo.loff_d.n) + btasks.bytes() + aux.bytes();
+  return CUADMM_OK;
+}
+
 extern "C" {
 
 int cuadmm_get_status(const cuadmm_solver* s, double o[8]) {
@@ -662,6 +757,29 @@ int cuadmm_block_multiply(cuadmm_solver* s, int which, const double* V, const in
   }
   if ((rc = s->bm_prepare(which, rmax)) || (which == 2 && (rc = s->stage_scaled_y(s->bm.ybuf.p, nullptr)))) return rc;
   return s->bm_run(which, V, ranks, W_out, o, per_block);
+}
+int cuadmm_lowrank_grad(cuadmm_solver* s, const double* Lf, const int* ranks, int rmax, const double* y, double sigma, double* G_out, double* r_out,
+                        double* Shat_out, double o[8], double* per_block) {
+  int rc = report_guard(s, o, "lowrank_grad", "results", true);
+  if (rc) return rc;
+  if (!(sigma >= 0.0) || !std::isfinite(sigma)) { set_error("lowrank_grad: sigma = %g, allowed is a finite sigma >= 0", sigma); return CUADMM_ERR_INVALID; }
+  if (rmax < 1 || rmax > kMaxBlockSize) { set_error("lowrank_grad: rmax = %d, allowed are 1 to %d", rmax, kMaxBlockSize); return CUADMM_ERR_INVALID; }
+  if (!ranks) { set_error("lowrank_grad: ranks is null"); return CUADMM_ERR_INVALID; }
+  long long at = 0;                      // first double of block k's L_k
+  for (int k = 0; k < (int)s->blk_local.size(); ++k) {
+    const int n = s->blk_local[k];
+    if (n <= 0) continue;
+    const int rc_k = std::min(n, rmax), r = ranks[k];
+    if (r < 0 || r > rc_k) { set_error("lowrank_grad: block %d of size %d has rank %d, allowed are 0 to %d", k, n, r, rc_k); return CUADMM_ERR_INVALID; }
+    if (r > 0 && !Lf) { set_error("lowrank_grad: L is null and block %d has rank %d", k, r); return CUADMM_ERR_INVALID; }
+    for (long long e = at, end = at + (long long)n * r; e < end; ++e)
+      if (!std::isfinite(Lf[e])) { set_error("lowrank_grad: block %d, row %lld of column %lld is not finite", k, (e - at) % n, (e - at) / n); return CUADMM_ERR_INVALID; }
+    at += (long long)n * rc_k;
+  }
+  for (int i = 0; y && i < s->m; ++i)
+    if (!std::isfinite(y[i])) { set_error("lowrank_grad: y[%d] is not finite", i); return CUADMM_ERR_INVALID; }
+  if ((rc = s->lg_prepare(rmax)) || (rc = s->stage_scaled_y(s->lg.ybuf.p, y))) return rc;
+  return s->lg_run(Lf, ranks, sigma, G_out, r_out, Shat_out, o, per_block);
 }
 int cuadmm_get_evaluate_info(const cuadmm_solver* s, double o[4]) {
   if (!s || !o) { set_error("get_evaluate_info: null"); return CUADMM_ERR_INVALID; }

@@ -381,6 +381,10 @@ struct cuadmm_solver {
   int bm_prepare(int which, int rmax);
   int bm_run(int which, const double* V, const int* ranks, double* W_out, double out8[8], double* per_block);
 
+  LgPlan lg;                   // (report_plans.h): cuadmm_lowrank_grad
+  int lg_prepare(int rmax);
+  int lg_run(const double* Lf, const int* ranks, double sigma, double* G_out, double* r_out, double* Shat_out, double out8[8], double* per_block);
+
   // profiling
   DevEvent ev0[K_NUM][2], ev1[K_NUM][2];
   int ev_used[K_NUM] = {0};

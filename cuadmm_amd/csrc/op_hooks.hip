@@ -639,6 +639,35 @@ int cuadmm_op_block_mult_plan(const int* blk_vals, int mat_num, int rmax, long l
   return (int)tasks.size();
 }
 
+// the multiplier pass of cuadmm_lowrank_grad on host arrays of m doubles in the engine's scaled space (csrc/lowrank_grad.h, xunit = 1):
+// ytilde_out <- the scaled y - sigma r, r_out <- r in the caller's units, out2 <- [y'r in the caller's units, ||r||^2] from the kernel's
+// slot partials added in slot order.  The default stream, synchronised.
+int cuadmm_op_lrg_multiplier(int m, const double* ax, const double* b, const double* normA, const double* y, double bscale, double Cscale, double sigma,
+                             double* ytilde_out, double* r_out, double out2[2]) {
+  if (m < 1 || !ax || !b || !normA || !y || !ytilde_out || !r_out || !out2 || !(sigma >= 0.0) || !std::isfinite(sigma) || !(bscale > 0) || !(Cscale > 0)) {
+    set_error("op_lrg_multiplier: invalid argument");
+    return CUADMM_ERR_INVALID;
+  }
+  int rc, ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_error("no HIP device available; this engine has no CPU fallback"); return CUADMM_ERR_NO_DEVICE; }
+  DevBuf<double> in[4], yt, r, part;
+  const double* const src[4] = {ax, b, normA, y};
+  for (int q = 0; q < 4; ++q)
+    if ((rc = in[q].alloc((size_t)m)) || (rc = in[q].upload(src[q], (size_t)m))) return rc;
+  if ((rc = yt.alloc((size_t)m)) || (rc = r.alloc((size_t)m)) || (rc = part.alloc(2 * (size_t)kBrSlots))) return rc;
+  if ((rc = launch_lrg_multiplier(m, in[0].p, in[1].p, in[2].p, in[3].p, 1.0, bscale, 1 / Cscale, sigma, yt.p, r.p, part.p, nullptr))) return rc;
+  CUADMM_HIP_TRY(hipStreamSynchronize(nullptr));
+  std::vector<double> h(2 * (size_t)kBrSlots);
+  if ((rc = staged_d2h(ytilde_out, yt.p, sizeof(double) * (size_t)m)) || (rc = staged_d2h(r_out, r.p, sizeof(double) * (size_t)m)) ||
+      (rc = staged_d2h(h.data(), part.p, sizeof(double) * h.size())))
+    return rc;
+  double yr = 0, rn2 = 0;
+  for (int j = 0; j < kBrSlots; ++j) { yr += h[j]; rn2 += h[kBrSlots + j]; }
+  out2[0] = yr * (bscale * Cscale);
+  out2[1] = rn2;
+  return CUADMM_OK;
+}
+
 int cuadmm_dev_malloc(void** ptr, size_t bytes) { CUADMM_HIP_TRY(hipMalloc(ptr, bytes ? bytes : 8)); return CUADMM_OK; }
 int cuadmm_dev_free(void* ptr) { if (ptr) CUADMM_HIP_TRY(hipFree(ptr)); return CUADMM_OK; }
 int cuadmm_memcpy_h2d(void* dst, const void* src, size_t bytes) { return staged_h2d(dst, src, bytes); }

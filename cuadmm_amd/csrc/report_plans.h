@@ -1,6 +1,6 @@
 // What the reports on a point own beside the iteration's state, and what the op hooks build on their own: the auxiliary projector, the
-// per-block task lists, the plans of cuadmm_lambda_min, cuadmm_lowrank, cuadmm_set_lowrank and cuadmm_block_multiply.  Nothing here is
-// read by the iteration.
+// per-block task lists, the plans of cuadmm_lambda_min, cuadmm_lowrank, cuadmm_set_lowrank, cuadmm_block_multiply and cuadmm_lowrank_grad.
+// Nothing here is read by the iteration.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -12,6 +12,7 @@
 #include "lowrank.h"
 #include "lowrank_apply.h"
 #include "block_mult.h"
+#include "lowrank_grad.h"
 
 struct cuadmm_solver;
 
@@ -276,6 +277,28 @@ struct BmPlan {
     return CUADMM_OK;
   }
   double bytes() const { return 8.0 * (double)(loff_d.n + Vbuf.n + Wbuf.n + ybuf.n + tasks_d.n) + 4.0 * (double)ranks_d.n; }
+};
+
+// Value and gradient at factors (cuadmm_lowrank_grad; lowrank_grad.h, DESIGN.md "Value and gradient at factors"): the svec vector x is
+// assembled in (a device copy of X with svec(L_k L_k') over its PSD blocks), the m-vectors of the multiplier pass (y, A x, ytilde, r; the
+// column norms where the engine keeps none on the device), the slot partials, the per-block sums and a pair of events.  The factors are
+// the block product's V (BmPlan) and the outer product reads them there (LoPlan's task list) where x is in the caller's units; the
+// products go to BmPlan's W and A'ytilde - C to the auxiliary projector's input vector.  Nothing here is read by the iteration.
+struct LgPlan {
+  DevBuf<double> xv, ybuf, ax, ytilde, r, normA, part, sums, cpart;
+  std::vector<double> h_stage, h_back, h_G;      // host scratch kept between calls: the scaled factors, what comes back, G where the caller wants none
+  DevEvent ev[2];
+  int prepare(long long L, int m, int nb, int nchunk, bool own_normA) {
+    if (sums.p) return CUADMM_OK;
+    int rc;
+    const size_t mm = (size_t)std::max(m, 1);
+    if ((rc = xv.alloc((size_t)L)) || (rc = ybuf.alloc(mm)) || (rc = ax.alloc(mm)) || (rc = ytilde.alloc(mm)) || (rc = r.alloc(mm)) ||
+        (own_normA && (rc = normA.alloc(mm))) || (rc = part.alloc(2 * (size_t)kBrSlots)) || (rc = cpart.alloc(kLgSums * (size_t)std::max(nchunk, 1))))
+      return rc;
+    for (auto& e : ev) if ((rc = e.create())) return rc;
+    return sums.alloc(kLgSums * (size_t)std::max(nb, 1));      // last: marks the set as complete
+  }
+  double bytes() const { return 8.0 * (double)(xv.n + ybuf.n + ax.n + ytilde.n + r.n + normA.n + part.n + sums.n + cpart.n); }
 };
 
 }  // namespace cuadmm

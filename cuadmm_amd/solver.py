@@ -52,6 +52,30 @@ def pack_lowrank(blk_vals, Ls, who="set_lowrank"):
     return L, ranks, rmax
 
 
+def unpack_lowrank(blk_vals, ranks, rmax, buf):
+    """the list of (n_k, r_k) arrays held by a buffer in the layout of pack_lowrank for this rmax ((0, 0) for unconstrained blocks)"""
+    out, at = [], 0
+    for k, n in enumerate(int(n) for n in blk_vals):
+        r = int(ranks[k]) if n > 0 else 0
+        out.append(buf[at:at + max(n, 0) * r].reshape(r, max(n, 0)).T.copy())
+        at += n * min(n, rmax) if n > 0 else 0
+    return out
+
+
+def lowrank_grad_args(blk_vals, con_num, L, y, sigma):
+    """(L buffer, ranks, rmax, y or None, sigma) as cuadmm_lowrank_grad takes them; ValueError on factors that do not fit the blocks, a y
+    of another length than con_num, a sigma that is negative or not finite"""
+    sigma = float(sigma)
+    if not (sigma >= 0.0 and np.isfinite(sigma)):
+        raise ValueError("lowrank_grad: sigma = %r, allowed is a finite sigma >= 0" % sigma)
+    Lv, ranks, rmax = pack_lowrank(blk_vals, L, "lowrank_grad")
+    if y is not None:
+        y = _f64(y).ravel()
+        if y.size != int(con_num):
+            raise ValueError("lowrank_grad: y has %d entries, the problem %d" % (y.size, int(con_num)))
+    return Lv, ranks, rmax, y, sigma
+
+
 class Problem:
     """TXT problem directory (blk.txt, con_num.txt, At.txt, b.txt, C.txt), src/problem.cu:11-83."""
 
@@ -309,6 +333,26 @@ class SDPSolver:
             at += n * min(n, rmax) if n > 0 else 0
         return {"W": W, "per_block": pb.reshape(self.mat_num, 4), "norm": float(o[0]), "inner": float(o[1]), "block": int(o[2]), "block_norm": float(o[3]),
                 "blocks": int(o[4]), "rank_sum": int(o[5]), "ms": float(o[6]), "bytes": float(o[7])}
+
+    def lowrank_grad(self, L, y=None, sigma=0.0, want_S=False):
+        """Value and gradient of f = <C, x> - y'r + (sigma / 2) ||r||^2, r = A x - b, at the factors L (cuadmm_lowrank_grad): x is the
+        resident X with every PSD block replaced by L_k L_k'.  L: a list of (n_k, r_k) arrays as lowrank()["L"] returns; y: con_num values
+        or None for the resident y; sigma >= 0 in the caller's units.  Returns "G": the list of gradients 2 (C - A'(y - sigma r))_k L_k,
+        shaped like L; "f", "cx" = <C, x>, "yr" = y'r, "rnorm" = ||r||, "r", "gnorm" = ||G||_F, "lg" = <L, G>, "ms", "bytes"; "per_block":
+        (mat_num, 4) rows <C_k, x_k>, ||G_k||_F (unconstrained: ||S^_k||_F), <L_k, G_k>, ||L_k||_F^2; with want_S, "Shat": C - A'(y - sigma r)
+        as a vector of vec_len.  The solver is left as it was: behind a solve the pending scaled state stays pending."""
+        Lv, ranks, rmax, yv, sigma = lowrank_grad_args(self.blk_vals, self.con_num, L, y, sigma)
+        Gv = np.zeros(Lv.size)
+        r = np.zeros(max(self.con_num, 1))
+        Sh = np.zeros(max(self.vec_len, 1)) if want_S else None
+        o = np.zeros(8)
+        pb = np.zeros(4 * self.mat_num)
+        check(self._lib.cuadmm_lowrank_grad(self._h, _p(Lv), _p(ranks), rmax, _p(yv), sigma, _p(Gv), _p(r), _p(Sh), _p(o), _p(pb)))
+        out = {"G": unpack_lowrank(self.blk_vals, ranks, rmax, Gv), "f": float(o[0]), "cx": float(o[1]), "yr": float(o[2]), "rnorm": float(o[3]),
+               "r": r[:self.con_num], "gnorm": float(o[4]), "lg": float(o[5]), "ms": float(o[6]), "bytes": float(o[7]), "per_block": pb.reshape(self.mat_num, 4)}
+        if want_S:
+            out["Shat"] = Sh[:self.vec_len]
+        return out
 
     def set_allreduce(self, fn):
         """fn(dev_ptr:int, count:int, hip_stream:int) -> None : in-place sum over ranks on that stream."""

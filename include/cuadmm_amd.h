@@ -201,6 +201,31 @@ int cuadmm_set_XyS(cuadmm_solver* s, const double* X, const double* y, const dou
  * that would be read; world > 1 or a handle that leads an in-process group.  CUADMM_ERR_FACTOR for which = 2 behind a failed
  * cuadmm_update_A. */
 int cuadmm_block_multiply(cuadmm_solver* s, int which, const double* V, const int* ranks, int rmax, double* W_out, double out8[8], double* per_block);
+/* Value and gradient of the augmented Lagrangian at per-block factors ("Value and gradient at factors"; csrc/lowrank_grad.h).
+ * With x the resident X in which every PSD block k is replaced by L_k L_k' (unconstrained blocks keep their resident slices), y the
+ * caller's vector of con_num doubles (NULL: the resident y) and sigma >= 0 in the caller's units (not the solver's sig):
+ *   r = A x - b,   f = <C, x> - y'r + (sigma / 2) ||r||^2,   ytilde = y - sigma r,   S^ = C - A'ytilde,   G_k = 2 S^_k L_k.
+ * G is the gradient of f with respect to the factors, the unconstrained slices of S^ the gradient with respect to those slices of x.
+ * L, ranks, rmax and G_out as V, ranks, rmax and W_out of cuadmm_block_multiply: columns >= r_k of L are never read (they may hold NaN)
+ * and are +0.0 in G_out.  G_out (cuadmm_lowrank_size(rmax) doubles), r_out (con_num, the caller's order), Shat_out (vec_len; one more
+ * copy back when asked for) and per_block may be NULL.
+ * The chain runs on the solver's stream in the engine's scaled space: a device copy of X into a vector of the call's own, svec(L_k L_k')
+ * over its PSD blocks (the kernel of cuadmm_set_lowrank), A x (the iteration's SpMV), one streaming pass that forms r, ytilde and the
+ * slot sums of y'r and ||r||^2, A'ytilde - C (the iteration's kernel), the product of cuadmm_block_multiply(2) and one pass of per-block
+ * sums.  No atomics: the same bits on every run.  With sigma = 0, ytilde is y bit for bit and G is bit for bit 2 W of
+ * cuadmm_block_multiply(s, 2, L, ...) at the same y.  Nothing the iteration reads is written and the deferred unscaling is not
+ * triggered: a following cuadmm_solve(..., if_first = 0) continues bit for bit.
+ * out8: [0] f, [1] <C, x> (the sum over k of [4k] in block order), [2] y'r, [3] ||r||, [4] ||G||_F, [5] <L, G> (= 2 <S^, x> on the PSD
+ * part), [6] device milliseconds of the chain (HIP events; the staged copies are not in it), [7] bytes of device memory the call holds.
+ * per_block, 4 mat_num doubles: [4k] <C_k, x_k>, [4k + 1] ||G_k||_F (unconstrained: ||S^_k||_F), [4k + 2] <L_k, G_k> (unconstrained: 0),
+ * [4k + 3] ||L_k||_F^2 (unconstrained: 0).  The sums over G and L are formed on the host from the returned G_out and L as
+ * cuadmm_block_multiply forms its own: q = 0; q = q + a[e] * b[e] in index order, [4] from the blocks' sums of squares in block order.
+ * CUADMM_ERR_INVALID, the solver as it was: solver not initialised; out8 or ranks NULL; sigma negative or not finite; rmax outside
+ * 1..8192; a ranks[k] of a PSD block outside 0..min(n_k, rmax); L NULL while some rank is positive; an entry of y or of a column of L that
+ * would be read that is not finite; world > 1 or a handle that leads an in-process group.  CUADMM_ERR_FACTOR behind a failed
+ * cuadmm_update_A. */
+int cuadmm_lowrank_grad(cuadmm_solver* s, const double* L, const int* ranks, int rmax, const double* y, double sigma, double* G_out, double* r_out,
+                        double* Shat_out, double out8[8], double* per_block);
 /* Replace X (which = 0) or S (1) between two solves by per-block factors: every PSD block k becomes L_k L_k' with r_k = ranks[k] columns
  * ("Starting from low-rank factors"; csrc/lowrank_apply.h).  L is laid out as cuadmm_lowrank's L_out for this rmax: block k at the
  * prefix sum of n_j min(n_j, rmax) over the PSD blocks before it, column by column, n_k doubles per column; unconstrained blocks occupy
@@ -709,6 +734,12 @@ int cuadmm_op_block_mult(const double* svec_dev, const int* blk_vals, int mat_nu
  * up to cap_slots wavefront slots of two ints (block or -1, panel of 16 rows); four consecutive slots are one workgroup and hold panels
  * of one block, or blocks of one panel.  Returns the number of slots, or an error.  Host only (no device needed). */
 int cuadmm_op_block_mult_plan(const int* blk_vals, int mat_num, int rmax, long long* loff_out, int* tasks_out, int cap_slots);
+/* The multiplier pass of cuadmm_lowrank_grad alone (csrc/lowrank_grad.hip) on host arrays of m >= 1 doubles in the engine's scaled space
+ * and order: rs_i = ax_i - b_i, r_out_i = (normA_i rs_i) bscale, ytilde_out_i = y_i - ((sigma r_out_i) normA_i) fl(1 / Cscale) (sigma = 0:
+ * the bits of y_i), out2 = [bscale Cscale sum y_i rs_i, sum r_out_i^2] from 256 slot partials added in slot order.  Every operation is
+ * rounded once.  The default stream, synchronised. */
+int cuadmm_op_lrg_multiplier(int m, const double* ax, const double* b, const double* normA, const double* y, double bscale, double Cscale, double sigma,
+                             double* ytilde_out, double* r_out, double out2[2]);
 int cuadmm_op_spmv_rows(int rows, int ncols, const int* row_ptrs, const int* col_ids, const double* vals, const double* X, const double* S, const double* C,
                         int want_x, int want_s, const int* rowmap, int out_len, double* outX, double* outS, int* info4);
 int cuadmm_op_rp_stats(int m, const double* ax, const double* b, const double* normA, const double* y, double bscale, const double* sums2, double* out4);

@@ -223,6 +223,32 @@ class SDPSolver {
     return r;
   }
 
+  // cuadmm_lowrank_grad: f = <C, x> - y'r + (sigma / 2) ||r||^2 and G_k = 2 (C - A'(y - sigma r))_k L_k at the factors L (x: X with every
+  // PSD block replaced by L_k L_k', r = A x - b); L, ranks, rmax as block_multiply's V; y: con_num values or null for the resident y; G in
+  // the layout of L, per_block: [4k ..] = <C_k, x_k>, ||G_k||_F, <L_k, G_k>, ||L_k||_F^2; Shat only with want_S; not in the reference
+  struct LowRankGrad {
+    double f, cx, yr, rnorm, gnorm, lg, ms, bytes;
+    std::vector<double> G, r, Shat, per_block;
+  };
+  LowRankGrad lowrank_grad(const double* L, const int* ranks, int rmax, const double* y = nullptr, double sigma = 0.0, bool want_S = false) {
+    double o[8] = {0};
+    int vl = 0, cn = 0, mn = 0;
+    long long count = 0;
+    check(cuadmm_get_dims(h_, &vl, &cn, &mn));
+    check(cuadmm_lowrank_size(h_, rmax, &count));
+    LowRankGrad g;
+    g.G.assign((size_t)count + 1, 0.0);
+    g.r.assign((size_t)cn + 1, 0.0);
+    if (want_S) g.Shat.assign((size_t)vl + 1, 0.0);
+    g.per_block.assign(4 * (size_t)mn, 0.0);
+    check(cuadmm_lowrank_grad(h_, L, ranks, rmax, y, sigma, g.G.data(), g.r.data(), want_S ? g.Shat.data() : nullptr, o, g.per_block.data()));
+    g.G.resize((size_t)count);
+    g.r.resize((size_t)cn);
+    if (want_S) g.Shat.resize((size_t)vl);
+    g.f = o[0]; g.cx = o[1]; g.yr = o[2]; g.rnorm = o[3]; g.gnorm = o[4]; g.lg = o[5]; g.ms = o[6]; g.bytes = o[7];
+    return g;
+  }
+
   // cuadmm_update_bC: new b and / or C on the factored solver (nnz < 0: unchanged); not in the reference
   void update_bC(const int* cpu_b_indices, const double* cpu_b_vals, int b_nnz, const int* cpu_C_indices, const double* cpu_C_vals,
                  int C_nnz, bool keep_iterate = true, double sig = 0.0) {
