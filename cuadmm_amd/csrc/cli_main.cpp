@@ -33,6 +33,9 @@
 //   --lowrank-grad=DIR/[,SIGMA]: behind every solve, value and gradient of <C, x> - y'r + (SIGMA / 2) ||r||^2 at the factors DIR/L_X_<k>.txt
 //   (as --lowrank-out writes them; else DIR/L_S_<k>.txt) with y from DIR/y.txt when present, else the resident y (cuadmm_lowrank_grad);
 //   one line, and "lowrank_grad" in the sidecar.  --lowrank-grad-out=DIR2/: DIR2/G_<k>.txt per PSD block (as W_<k>.txt) and DIR2/r.txt
+//   --lowrank-line=LDIR/,DDIR/[,SIGMA[,TMAX]]: behind every solve, the quartic t -> f(L + t D) of that value along the direction read from
+//   DDIR/ (factor files as LDIR/'s, the same ranks), y from LDIR/y.txt when present, and its minimiser on [0, TMAX] (default: inf, which
+//   needs SIGMA > 0) (cuadmm_lowrank_line); one line with c0 .. c4, t* and f(t*), and "lowrank_line" in the sidecar
 //   --block-mult-out=DIR2/ (with --block-mult): DIR2/W_<k>.txt per PSD block k, n_k r_k numbers column by column with 17 significant
 //   digits (of the last --block-mult where there are several)
 //   --json=<file>: a sidecar with the run's figures (iterations, residuals, iters/s, per-phase milliseconds, the projection's
@@ -223,6 +226,25 @@ static void write_lowrank_grad(FILE* f, const LowRankGradCall& c) {
   fprintf(f, " \"lowrank_grad\": {\"sigma\": %.17g, \"rmax\": %d, \"y\": %s, \"f\": %.17g, \"cx\": %.17g, \"yr\": %.17g, \"rnorm\": %.17g, \"gnorm\": %.17g, "
           "\"lg\": %.17g, \"ms\": %.17g, \"bytes\": %.0f}", c.sigma, c.rmax, c.have_y ? "true" : "false", o[0], o[1], o[2], o[3], o[4], o[5], o[6], o[7]);
 }
+// --lowrank-line: the factors, the direction, y (when LDIR/y.txt exists), sigma, t_max and the results of cuadmm_lowrank_line
+struct LowRankLineCall {
+  bool on = false, have_y = false;
+  int rmax = 1;
+  double sigma = 0, t_max = INFINITY;
+  std::string ldir, ddir;
+  std::vector<int> ranks;
+  std::vector<double> L, D, y;
+  double coef[5] = {0}, o[8] = {0};
+};
+// "lowrank_line": {...} with the coefficients and the eight numbers of cuadmm_lowrank_line (t_max: null for inf)
+static void write_lowrank_line(FILE* f, const LowRankLineCall& c) {
+  const double* o = c.o;
+  fprintf(f, " \"lowrank_line\": {\"sigma\": %.17g, \"t_max\": ", c.sigma);
+  if (std::isfinite(c.t_max)) fprintf(f, "%.17g", c.t_max); else fprintf(f, "null");
+  fprintf(f, ", \"rmax\": %d, \"y\": %s, \"coef\": [%.17g, %.17g, %.17g, %.17g, %.17g], \"t\": %.17g, \"f\": %.17g, \"decrease\": %.17g, \"pnorm\": %.17g, "
+          "\"qnorm\": %.17g, \"critical\": %.0f, \"ms\": %.17g, \"bytes\": %.0f}", c.rmax, c.have_y ? "true" : "false", c.coef[0], c.coef[1], c.coef[2], c.coef[3],
+          c.coef[4], o[0], o[1], o[2], o[3], o[4], o[5], o[6], o[7]);
+}
 // <dir/>name.txt, one number per line (cuadmm_write_dense_txt); a missing file: zeros
 static bool read_point_vec(const std::string& fn, std::vector<double>& out, size_t n, const char* who = "--kkt-point") {
   out.assign(n, 0.0);
@@ -241,7 +263,8 @@ static bool read_point_vec(const std::string& fn, std::vector<double>& out, size
 static bool write_sidecar(const std::string& path, const std::string& prefix, cuadmm_solver* solver, const cuadmm_problem_view& v, bool have_bounds,
                           const double* kkt = nullptr, const std::vector<double>& kkt_blocks = std::vector<double>(), int lm_steps = 0,
                           const double (*lm)[8] = nullptr, const LowRankReport* lr = nullptr, const LowRankStart* start = nullptr,
-                          const std::vector<BlockMultCall>* bmc = nullptr, const LowRankGradCall* lgc = nullptr) {
+                          const std::vector<BlockMultCall>* bmc = nullptr, const LowRankGradCall* lgc = nullptr,
+                          const LowRankLineCall* llc = nullptr) {
   FILE* f = fopen(path.c_str(), "w");
   if (!f) return false;
   const int iters = cuadmm_get_info_iter_num(solver);
@@ -285,6 +308,7 @@ static bool write_sidecar(const std::string& path, const std::string& prefix, cu
   if (start) { write_start(f, *start); fprintf(f, ",\n"); }
   if (bmc) { write_block_mult(f, *bmc); fprintf(f, ",\n"); }
   if (lgc) { write_lowrank_grad(f, *lgc); fprintf(f, ",\n"); }
+  if (llc) { write_lowrank_line(f, *llc); fprintf(f, ",\n"); }
   double acc[8] = {0};
   cuadmm_get_accel_info(solver, acc);
   if (acc[0] > 0)
@@ -329,6 +353,7 @@ int main(int argc, char* argv[]) {
   bool lr_on = false;
   std::string json_path, bounds_arg, kkt_point, lr_out, start_dir, bm_out, lg_out;
   LowRankGradCall lgc;                 // --lowrank-grad
+  LowRankLineCall llc;                 // --lowrank-line
   std::vector<BlockMultCall> bmc;      // --block-mult, in the order given
   std::vector<std::string> then_dirs;
   std::vector<char> then_is_A;
@@ -392,6 +417,19 @@ int main(int argc, char* argv[]) {
       lgc.on = true;
       continue;
     }
+    if (strncmp(argv[i], "--lowrank-line=", 15) == 0) {
+      std::vector<std::string> part(1);
+      for (const char* a = argv[i] + 15; *a; ++a)
+        if (*a == ',') part.emplace_back(); else part.back() += *a;
+      bool ok = part.size() >= 2 && part.size() <= 4 && !part[0].empty() && !part[1].empty();
+      char* end = nullptr;
+      if (ok && part.size() >= 3) { llc.sigma = strtod(part[2].c_str(), &end); ok = !part[2].empty() && *end == 0 && llc.sigma >= 0 && std::isfinite(llc.sigma); }
+      if (ok && part.size() == 4) { llc.t_max = strtod(part[3].c_str(), &end); ok = !part[3].empty() && *end == 0 && !std::isnan(llc.t_max); }
+      if (!ok) { std::cerr << "--lowrank-line=LDIR/,DDIR/[,SIGMA[,TMAX]]: SIGMA >= 0, TMAX a number" << std::endl; return 1; }
+      llc.ldir = part[0]; llc.ddir = part[1];
+      llc.on = true;
+      continue;
+    }
     std::cerr << "unknown option " << argv[i] << std::endl;
     return 1;
   }
@@ -439,6 +477,23 @@ int main(int argc, char* argv[]) {
     lgc.rmax = st.rmax[w]; lgc.ranks = st.ranks[w]; lgc.L = st.L[w];
     lgc.G.assign(lgc.L.size(), 0.0);
     lgc.r.assign((size_t)v.con_num + 1, 0.0);
+  }
+
+  if (llc.on) {            // --lowrank-line: read and checked before any device work
+    LowRankStart sl, sd;
+    bool ok = read_lowrank_start(llc.ldir, v, sl, 0) && (sl.have[0] || read_lowrank_start(llc.ldir, v, sl, 1));
+    ok = ok && read_lowrank_start(llc.ddir, v, sd, 0) && (sd.have[0] || read_lowrank_start(llc.ddir, v, sd, 1));
+    const int wl = sl.have[0] ? 0 : 1, wd = sd.have[0] ? 0 : 1;
+    if (ok && (!sl.have[wl] || !sd.have[wd])) {
+      std::cerr << "--lowrank-line: no factor file L_X_<k>.txt or L_S_<k>.txt in '" << (sl.have[wl] ? llc.ddir : llc.ldir) << "'" << std::endl;
+      ok = false;
+    }
+    if (ok && sl.ranks[wl] != sd.ranks[wd]) { std::cerr << "--lowrank-line: the direction's ranks are not the factors'" << std::endl; ok = false; }
+    FILE* yf = ok ? fopen((llc.ldir + "y.txt").c_str(), "r") : nullptr;
+    if (yf) { fclose(yf); llc.have_y = true; }
+    if (ok && llc.have_y) ok = read_point_vec(llc.ldir + "y.txt", llc.y, (size_t)v.con_num, "--lowrank-line");
+    if (!ok) { cuadmm_problem_free(prob); return 1; }
+    llc.rmax = sl.rmax[wl]; llc.ranks = sl.ranks[wl]; llc.L = sl.L[wl]; llc.D = sd.L[wd];   // (equal ranks: equal rmax, one layout)
   }
 
   cuadmm_solver* solver = nullptr;
@@ -602,6 +657,19 @@ int main(int argc, char* argv[]) {
     fclose(f);
     return true;
   };
+  // --lowrank-line: the quartic along the direction at the point a solve returns, taken before anything reads the iterate
+  auto ll_report = [&]() {
+    if (!llc.on) return false;
+    LowRankLineCall& c = llc;
+    if (cuadmm_lowrank_line(solver, c.L.data(), c.D.data(), c.ranks.data(), c.rmax, c.have_y ? c.y.data() : nullptr, c.sigma, c.t_max, c.coef, nullptr, nullptr, nullptr,
+                            c.o, nullptr) != CUADMM_OK) {
+      std::cerr << cuadmm_last_error() << std::endl;
+      return false;
+    }
+    printf(" lowrank_line(sigma = %g, t_max = %g): c = [%.10e, %.10e, %.10e, %.10e, %.10e], t* = %.10e, f(t*) = %.10e, %.3f ms\n", c.sigma, c.t_max, c.coef[0],
+           c.coef[1], c.coef[2], c.coef[3], c.coef[4], c.o[0], c.o[1], c.o[6]);
+    return true;
+  };
   // --start-lowrank: the point replaces init's zeros, and the solve takes the iterate as it stands (if_first = 0)
   const bool started = start.have[0] || start.have[1] || start.have_y;
   for (int w = 0; w < 2 && rc == CUADMM_OK; ++w) {
@@ -623,6 +691,7 @@ int main(int argc, char* argv[]) {
   bool have_lr = lr_report();
   bool have_bm = bm_report();
   bool have_lg = lg_report();
+  bool have_ll = ll_report();
 
   if (accel != 0) {
     double acc[8] = {0};
@@ -631,7 +700,7 @@ int main(int argc, char* argv[]) {
   }
   std::vector<double> X((size_t)v.vec_len);
   if (cuadmm_get_X(solver, X.data()) == CUADMM_OK) cuadmm_write_dense_txt((prefix + "X_opt.txt").c_str(), X.data(), v.vec_len);
-  if (!json_path.empty() && !write_sidecar(json_path, prefix, solver, v, !bounds_arg.empty(), have_kkt ? kk : nullptr, kkb, lm_steps, have_lm ? lm : nullptr, have_lr ? &lr : nullptr, started ? &start : nullptr, have_bm ? &bmc : nullptr, have_lg ? &lgc : nullptr)) std::cerr << "cannot write " << json_path << std::endl;
+  if (!json_path.empty() && !write_sidecar(json_path, prefix, solver, v, !bounds_arg.empty(), have_kkt ? kk : nullptr, kkb, lm_steps, have_lm ? lm : nullptr, have_lr ? &lr : nullptr, started ? &start : nullptr, have_bm ? &bmc : nullptr, have_lg ? &lgc : nullptr, have_ll ? &llc : nullptr)) std::cerr << "cannot write " << json_path << std::endl;
   for (size_t k = 0; k < then_dirs.size() && rc == CUADMM_OK; ++k) {
     const std::string& d = then_dirs[k];
     std::vector<int> bi, ci;
@@ -660,9 +729,10 @@ int main(int argc, char* argv[]) {
     have_lr = lr_report();
     have_bm = bm_report();
     have_lg = lg_report();
+    have_ll = ll_report();
     if (cuadmm_get_X(solver, X.data()) == CUADMM_OK) cuadmm_write_dense_txt((d + "X_opt.txt").c_str(), X.data(), v.vec_len);
     const std::string side = json_path + "." + std::to_string(k + 1);
-    if (!json_path.empty() && !write_sidecar(side, d, solver, v, !bounds_arg.empty(), have_kkt ? kk : nullptr, kkb, lm_steps, have_lm ? lm : nullptr, have_lr ? &lr : nullptr, nullptr, have_bm ? &bmc : nullptr, have_lg ? &lgc : nullptr)) std::cerr << "cannot write " << side << std::endl;
+    if (!json_path.empty() && !write_sidecar(side, d, solver, v, !bounds_arg.empty(), have_kkt ? kk : nullptr, kkb, lm_steps, have_lm ? lm : nullptr, have_lr ? &lr : nullptr, nullptr, have_bm ? &bmc : nullptr, have_lg ? &lgc : nullptr, have_ll ? &llc : nullptr)) std::cerr << "cannot write " << side << std::endl;
   }
   cuadmm_destroy(solver);
   cuadmm_problem_free(prob);

@@ -1,7 +1,8 @@
 // What the engine reports beside the iteration: the infeasibility check and the certified lower bound behind the iteration's steps, and
 // the reports on a point (cuadmm_lower_bound, cuadmm_evaluate, cuadmm_lambda_min, cuadmm_lowrank, cuadmm_block_multiply,
-// cuadmm_lowrank_grad) with their C entry points.  Host code only: the kernels are those of infeas.hip, lower_bound.hip, evaluate.hip,
-// lambda_min.hip, lowrank.hip, lowrank_apply.hip, block_mult.hip, lowrank_grad.hip and the iteration's own.
+// cuadmm_lowrank_grad, cuadmm_lowrank_line) with their C entry points.  Host code only: the kernels are those of infeas.hip,
+// lower_bound.hip, evaluate.hip, lambda_min.hip, lowrank.hip, lowrank_apply.hip, block_mult.hip, lowrank_grad.hip, lowrank_line.hip and the
+// iteration's own.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -608,6 +609,115 @@ int cuadmm_solver::lg_run(const double* Lf, const int* ranks, double sigma, doub
   return CUADMM_OK;
 }
 
+// ------------------------------------------------------------------------------------------
+// The quartic along a line in factor space (cuadmm_lowrank_line): DESIGN.md, "Line search along factor steps"
+// ------------------------------------------------------------------------------------------
+// the outer product's plan for this rmax, the plan's own vectors on first use and a device D that grows with rmax; the column norms
+// (where the engine keeps none on the device) and the auxiliary projector's b on every call
+int cuadmm_solver::ll_prepare(int rmax) {
+  int rc;
+  const int nb = (int)blk_local.size();
+  if (!btasks.built && (rc = btasks.build(blk_local.data(), nb, nullptr))) return rc;
+  if ((rc = lo.prepare(blk_local.data(), nb, rmax)) || (rc = ll.prepare(L, m, nb, btasks.nchunk, !normA_d.p, st))) return rc;
+  if (ll.Dbuf.n < (size_t)lo.loff.back() + 1 && (rc = ll.Dbuf.alloc((size_t)lo.loff.back() + 1))) return rc;
+  if (ll.normA.p && m > 0 && (rc = staged_h2d(ll.normA.p, normA_p.data(), sizeof(double) * (size_t)m, st))) return rc;
+  return aux.ensure(*this);
+}
+
+// The chain at the scaled y in ll.ybuf.  L and D are staged in the units X lies in (X = ux x: ux = bscale behind a solve, else 1), times
+// fl(1 / sqrt(ux)) where ux != 1 exactly as lg_run stages L, so that x0 and with it r0 carry lg_run's bits.  Then the device copy of X into
+// ll.x0, the three outer products, three A x, the streaming pass and the per-block terms; the coefficients on the host in the order
+// lowrank_line.h states.  Reads X, A, b, C; writes only the plans' own buffers.  Every output of the caller is written behind the last
+// refusal.
+int cuadmm_solver::ll_run(const double* Lf, const double* Df, const int* ranks, double sigma, double t_max, double coef5[5], double* r_out, double* p_out,
+                          double* q_out, double o[8], double* per_block) {
+#pragma clang fp contract(off)
+  int rc;
+  const int nb = (int)blk_local.size();
+  const double ux = pending_unscale ? bscale : 1.0;
+  const double* const normA_dev = normA_d.p ? normA_d.p : ll.normA.p;
+  const double *Ls = Lf, *Ds = Df;
+  if (ux != 1.0 && Lf) {
+    const double root = 1 / std::sqrt(ux);
+    ll.h_L.assign((size_t)lo.loff.back(), 0.0);
+    ll.h_D.assign((size_t)lo.loff.back(), 0.0);
+    for (int k = 0; k < nb; ++k)                // the columns that are read; the others travel as zeros
+      for (size_t e = (size_t)lo.loff[k], end = e + (blk_local[k] > 0 ? (size_t)blk_local[k] * (size_t)ranks[k] : 0); e < end; ++e) {
+        ll.h_L[e] = Lf[e] * root;
+        ll.h_D[e] = Df[e] * root;
+      }
+    Ls = ll.h_L.data(); Ds = ll.h_D.data();
+  }
+  double bytes = 0;
+  if ((rc = lo.stage(Ls, ranks, &bytes))) return rc;
+  if (Ds && lo.loff.back() > 0 && (rc = ll.Dbuf.upload(Ds, (size_t)lo.loff.back()))) return rc;
+  CUADMM_HIP_TRY(hipEventRecord(ll.ev[0], st));
+  CUADMM_HIP_TRY(hipMemcpyAsync(ll.x0.p, X.p, sizeof(double) * (size_t)L, hipMemcpyDeviceToDevice, st));
+  if ((rc = launch_block_outer3((int)lo.tasks.size(), lo.tasks_d.p, lo.Lbuf.p, ll.Dbuf.p, lo.loff_d.p, lo.ranks_d.p, btasks.off.p, btasks.blk.p, ll.x0.p, ll.x1.p,
+                                ll.x2.p, st)))
+    return rc;
+  if (m > 0) {
+    const double* const xs[3] = {ll.x0.p, ll.x1.p, ll.x2.p};
+    double* const axs[3] = {ll.ax0.p, ll.ax1.p, ll.ax2.p};
+    for (int j = 0; j < 3; ++j)
+      if ((rc = launch_spmv_rows(m, A_avg_nnz, A_rp.p, A_ci.p, A_v.p, xs[j], S.p, C.p, axs[j], nullptr, st, &A_long))) return rc;
+  }
+  if ((rc = launch_lrl_sums(m, ll.ax0.p, ll.ax1.p, ll.ax2.p, aux.b_dev(*this), normA_dev, ll.ybuf.p, pending_unscale ? 1.0 : 1 / bscale, bscale, ll.r0.p, ll.p.p, ll.q.p,
+                            ll.part.p, st)))
+    return rc;
+  if ((rc = launch_lrl_block_terms(C.p, ll.x0.p, ll.x1.p, ll.x2.p, btasks.view(), ll.cpart.p, ll.sums.p, st))) return rc;
+  CUADMM_HIP_TRY(hipEventRecord(ll.ev[1], st));
+  CUADMM_HIP_TRY(hipStreamSynchronize(st));
+  const float ms = event_ms(ll.ev[0], ll.ev[1]);
+  // --- back to the host and to the caller's units (the host scratch is the plan's and is kept)
+  const size_t mm = (size_t)std::max(m, 1);
+  std::vector<double>& h = ll.h_back;
+  h.resize(3 * mm + kLlParts * (size_t)kBrSlots + kLlSums * (size_t)std::max(nb, 1));
+  double *const rh = h.data(), *const ph = rh + mm, *const qh = ph + mm, *const part = qh + mm, *const sums = part + kLlParts * (size_t)kBrSlots;
+  if (m > 0 && r_out && (rc = staged_d2h(rh, ll.r0.p, sizeof(double) * (size_t)m, st))) return rc;
+  if (m > 0 && p_out && (rc = staged_d2h(ph, ll.p.p, sizeof(double) * (size_t)m, st))) return rc;
+  if (m > 0 && q_out && (rc = staged_d2h(qh, ll.q.p, sizeof(double) * (size_t)m, st))) return rc;
+  if ((rc = staged_d2h(part, ll.part.p, sizeof(double) * kLlParts * (size_t)kBrSlots, st))) return rc;
+  if (nb > 0 && (rc = staged_d2h(sums, ll.sums.p, sizeof(double) * kLlSums * (size_t)nb, st))) return rc;
+  double sm[kLlParts], cx[kLlSums] = {0, 0, 0};
+  for (int j = 0; j < kLlParts; ++j) {
+    sm[j] = 0;
+    for (int i = 0; i < kBrSlots; ++i) sm[j] = sm[j] + part[(size_t)j * kBrSlots + i];
+  }
+  const double cxu = Cscale * ux;
+  for (int k = 0; k < nb; ++k)
+    for (int j = 0; j < kLlSums; ++j) cx[j] = cx[j] + sums[kLlSums * (size_t)k + j] * cxu;
+  const double yr0 = sm[0] * objscale, yr1 = sm[1] * objscale, yr2 = sm[2] * objscale, hs = 0.5 * sigma;
+  double c[5];
+  c[0] = (cx[0] - yr0) + hs * sm[3];
+  c[1] = (cx[1] - yr1) + sigma * sm[4];
+  c[2] = (cx[2] - yr2) + hs * (sm[5] + 2.0 * sm[6]);
+  c[3] = sigma * sm[7];
+  c[4] = hs * sm[8];
+  double q4[4] = {0.0, c[0], 0.0, 0.0};
+  if (t_max > 0.0) {
+    for (int j = 0; j < 5; ++j)
+      if (!std::isfinite(c[j])) { set_error("lowrank_line: c%d = %g is not finite", j, c[j]); return CUADMM_ERR_INVALID; }
+    if ((rc = cuadmm_quartic_min(c, t_max, q4))) return rc;
+  }
+  // --- nothing is refused from here on
+  for (int j = 0; j < 5; ++j) coef5[j] = c[j];
+  for (int i = 0; i < m; ++i) {
+    if (r_out) r_out[perm[i]] = rh[i];
+    if (p_out) p_out[perm[i]] = ph[i];
+    if (q_out) q_out[perm[i]] = qh[i];
+  }
+  for (int k = 0; per_block && k < nb; ++k) {
+    double* w = per_block + 4 * (size_t)k;
+    for (int j = 0; j < kLlSums; ++j) w[j] = sums[kLlSums * (size_t)k + j] * cxu;
+    w[3] = blk_local[k] > 0 ? 0.0 : 2.0;
+  }
+  o[0] = q4[0]; o[1] = q4[1]; o[2] = q4[2]; o[3] = std::sqrt(sm[5]); o[4] = std::sqrt(sm[8]); o[5] = q4[3];
+  o[6] = ms;
+  o[7] = ll.bytes() + 8.0 * (double)(lo.Lbuf.n + lo.loff_d.n + lo.tasks_d.n) + 4.0 * (double)lo.ranks_d.n + btasks.bytes() + aux.bytes();
+  return CUADMM_OK;
+}
+
 extern "C" {
 
 int cuadmm_get_status(const cuadmm_solver* s, double o[8]) {
@@ -780,6 +890,35 @@ int cuadmm_lowrank_grad(cuadmm_solver* s, const double* Lf, const int* ranks, in
     if (!std::isfinite(y[i])) { set_error("lowrank_grad: y[%d] is not finite", i); return CUADMM_ERR_INVALID; }
   if ((rc = s->lg_prepare(rmax)) || (rc = s->stage_scaled_y(s->lg.ybuf.p, y))) return rc;
   return s->lg_run(Lf, ranks, sigma, G_out, r_out, Shat_out, o, per_block);
+}
+int cuadmm_lowrank_line(cuadmm_solver* s, const double* Lf, const double* Df, const int* ranks, int rmax, const double* y, double sigma, double t_max,
+                        double coef5[5], double* r_out, double* p_out, double* q_out, double o[8], double* per_block) {
+  int rc = report_guard(s, o, "lowrank_line", "results", true);
+  if (rc) return rc;
+  if (!coef5) { set_error("lowrank_line: coef5 is null"); return CUADMM_ERR_INVALID; }
+  if (!(sigma >= 0.0) || !std::isfinite(sigma)) { set_error("lowrank_line: sigma = %g, allowed is a finite sigma >= 0", sigma); return CUADMM_ERR_INVALID; }
+  if (std::isnan(t_max)) { set_error("lowrank_line: t_max is not a number"); return CUADMM_ERR_INVALID; }
+  if (rmax < 1 || rmax > kMaxBlockSize) { set_error("lowrank_line: rmax = %d, allowed are 1 to %d", rmax, kMaxBlockSize); return CUADMM_ERR_INVALID; }
+  if (!ranks) { set_error("lowrank_line: ranks is null"); return CUADMM_ERR_INVALID; }
+  long long at = 0;                      // first double of block k's L_k and D_k
+  for (int k = 0; k < (int)s->blk_local.size(); ++k) {
+    const int n = s->blk_local[k];
+    if (n <= 0) continue;
+    const int rc_k = std::min(n, rmax), r = ranks[k];
+    if (r < 0 || r > rc_k) { set_error("lowrank_line: block %d of size %d has rank %d, allowed are 0 to %d", k, n, r, rc_k); return CUADMM_ERR_INVALID; }
+    if (r > 0 && (!Lf || !Df)) { set_error("lowrank_line: %s is null and block %d has rank %d", Lf ? "D" : "L", k, r); return CUADMM_ERR_INVALID; }
+    for (long long e = at, end = at + (long long)n * r; e < end; ++e)
+      if (!std::isfinite(Lf[e]) || !std::isfinite(Df[e])) {
+        set_error("lowrank_line: block %d, row %lld of column %lld of %s is not finite", k, (e - at) % n, (e - at) / n, std::isfinite(Lf[e]) ? "D" : "L");
+        return CUADMM_ERR_INVALID;
+      }
+    at += (long long)n * rc_k;
+  }
+  for (int i = 0; y && i < s->m; ++i)
+    if (!std::isfinite(y[i])) { set_error("lowrank_line: y[%d] is not finite", i); return CUADMM_ERR_INVALID; }
+  if (!Lf || !Df) Lf = Df = nullptr;     // every rank is 0: neither is read
+  if ((rc = s->ll_prepare(rmax)) || (rc = s->stage_scaled_y(s->ll.ybuf.p, y))) return rc;
+  return s->ll_run(Lf, Df, ranks, sigma, t_max, coef5, r_out, p_out, q_out, o, per_block);
 }
 int cuadmm_get_evaluate_info(const cuadmm_solver* s, double o[4]) {
   if (!s || !o) { set_error("get_evaluate_info: null"); return CUADMM_ERR_INVALID; }

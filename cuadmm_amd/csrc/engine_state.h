@@ -385,6 +385,11 @@ struct cuadmm_solver {
   int lg_prepare(int rmax);
   int lg_run(const double* Lf, const int* ranks, double sigma, double* G_out, double* r_out, double* Shat_out, double out8[8], double* per_block);
 
+  LlPlan ll;                   // (report_plans.h): cuadmm_lowrank_line
+  int ll_prepare(int rmax);
+  int ll_run(const double* Lf, const double* Df, const int* ranks, double sigma, double t_max, double coef5[5], double* r_out, double* p_out, double* q_out,
+             double out8[8], double* per_block);
+
   // profiling
   DevEvent ev0[K_NUM][2], ev1[K_NUM][2];
   int ev_used[K_NUM] = {0};

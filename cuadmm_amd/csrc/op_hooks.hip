@@ -668,6 +668,78 @@ int cuadmm_op_lrg_multiplier(int m, const double* ax, const double* b, const dou
   return CUADMM_OK;
 }
 
+// the outer-product kernel of cuadmm_lowrank_line on three DEVICE svec vectors whose blocks follow one another from slot 0
+// (csrc/lowrank_line.hip); the factor buffers (one layout), ranks and blk_vals on the host.  The task list is LoPlan's, that of
+// cuadmm_op_block_outer_plan(split_from).  Synchronises the stream.
+int cuadmm_op_block_outer3(const double* L_host, const double* D_host, const int* ranks, const int* blk_vals, int mat_num, int rmax, int split_from,
+                           double* x0_dev_inout, double* x1_dev_inout, double* x2_dev_inout, void* stream) {
+  if (!ranks || !blk_vals || mat_num < 1 || rmax < 1 || rmax > kMaxBlockSize || !x0_dev_inout || !x1_dev_inout || !x2_dev_inout) {
+    set_error("op_block_outer3: invalid argument");
+    return CUADMM_ERR_INVALID;
+  }
+  for (int k = 0; k < mat_num; ++k) {
+    const int n = blk_vals[k];
+    if (n == 0 || n > kMaxBlockSize) { set_error("op_block_outer3: block %d has size %d", k, n); return CUADMM_ERR_INVALID; }
+    if (n > 0 && (ranks[k] < 0 || ranks[k] > std::min(n, rmax) || (ranks[k] > 0 && (!L_host || !D_host)))) {
+      set_error("op_block_outer3: block %d of size %d has rank %d%s", k, n, ranks[k], L_host && D_host ? "" : " and L or D is null");
+      return CUADMM_ERR_INVALID;
+    }
+  }
+  std::vector<LoTask> probe;             // the planner's own refusals (split_from) before any device work
+  std::vector<long long> probe_off;
+  int rc = lo_build_tasks(mat_num, blk_vals, rmax, split_from ? split_from : kLoSplitFrom, &probe, &probe_off), ndev = 0;
+  if (rc) return rc;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_error("no HIP device available; this engine has no CPU fallback"); return CUADMM_ERR_NO_DEVICE; }
+  hipStream_t st = (hipStream_t)stream;  // the current device is the vectors': it is not changed
+  BlockTasksDev t;
+  LoPlan plan;
+  DevBuf<double> Dbuf;
+  double bytes = 0;
+  if ((rc = t.build(blk_vals, mat_num, nullptr)) || (rc = plan.prepare(blk_vals, mat_num, rmax, split_from ? split_from : kLoSplitFrom)) ||
+      (rc = plan.stage(L_host && D_host ? L_host : nullptr, ranks, &bytes)) || (rc = Dbuf.alloc((size_t)plan.loff.back() + 1)))
+    return rc;
+  if (L_host && D_host && plan.loff.back() > 0 && (rc = Dbuf.upload(D_host, (size_t)plan.loff.back()))) return rc;
+  if ((rc = launch_block_outer3((int)plan.tasks.size(), plan.tasks_d.p, plan.Lbuf.p, Dbuf.p, plan.loff_d.p, plan.ranks_d.p, t.off.p, t.blk.p, x0_dev_inout,
+                                x1_dev_inout, x2_dev_inout, st)))
+    return rc;
+  CUADMM_HIP_TRY(hipStreamSynchronize(st));
+  return CUADMM_OK;
+}
+
+// the streaming pass of cuadmm_lowrank_line on host arrays of m doubles in the engine's scaled space (csrc/lowrank_line.h, xunit = 1).
+// Each device vector starts in the 16-byte phase of its host array, so that a caller's view chooses the element-to-thread map.  out9 from
+// the kernel's slot partials added in slot order, the first three times bscale Cscale.  The default stream, synchronised.
+int cuadmm_op_lrl_sums(int m, const double* ax0, const double* ax1, const double* ax2, const double* b, const double* normA, const double* y, double bscale,
+                       double Cscale, double* r_out, double* p_out, double* q_out, double out9[9]) {
+  if (m < 1 || !ax0 || !ax1 || !ax2 || !b || !normA || !y || !r_out || !p_out || !q_out || !out9 || !(bscale > 0) || !(Cscale > 0)) {
+    set_error("op_lrl_sums: invalid argument");
+    return CUADMM_ERR_INVALID;
+  }
+  int rc, ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_error("no HIP device available; this engine has no CPU fallback"); return CUADMM_ERR_NO_DEVICE; }
+  DevBuf<double> buf[9], part;
+  double* dev[9];
+  const double* const src[9] = {ax0, ax1, ax2, b, normA, y, r_out, p_out, q_out};
+  for (int v = 0; v < 9; ++v) {
+    if ((rc = buf[v].alloc((size_t)m + 2))) return rc;
+    dev[v] = buf[v].p + ((reinterpret_cast<uintptr_t>(src[v]) >> 3) & 1);
+    if (v < 6 && (rc = staged_h2d(dev[v], src[v], sizeof(double) * (size_t)m))) return rc;
+  }
+  if ((rc = part.alloc(kLlParts * (size_t)kBrSlots))) return rc;
+  if ((rc = launch_lrl_sums(m, dev[0], dev[1], dev[2], dev[3], dev[4], dev[5], 1.0, bscale, dev[6], dev[7], dev[8], part.p, nullptr))) return rc;
+  CUADMM_HIP_TRY(hipStreamSynchronize(nullptr));
+  std::vector<double> h(kLlParts * (size_t)kBrSlots);
+  if ((rc = staged_d2h(r_out, dev[6], sizeof(double) * (size_t)m)) || (rc = staged_d2h(p_out, dev[7], sizeof(double) * (size_t)m)) ||
+      (rc = staged_d2h(q_out, dev[8], sizeof(double) * (size_t)m)) || (rc = staged_d2h(h.data(), part.p, sizeof(double) * h.size())))
+    return rc;
+  for (int j = 0; j < kLlParts; ++j) {
+    double sum = 0;
+    for (int i = 0; i < kBrSlots; ++i) sum += h[(size_t)j * kBrSlots + i];
+    out9[j] = j < 3 ? sum * (bscale * Cscale) : sum;
+  }
+  return CUADMM_OK;
+}
+
 int cuadmm_dev_malloc(void** ptr, size_t bytes) { CUADMM_HIP_TRY(hipMalloc(ptr, bytes ? bytes : 8)); return CUADMM_OK; }
 int cuadmm_dev_free(void* ptr) { if (ptr) CUADMM_HIP_TRY(hipFree(ptr)); return CUADMM_OK; }
 int cuadmm_memcpy_h2d(void* dst, const void* src, size_t bytes) { return staged_h2d(dst, src, bytes); }

@@ -1,6 +1,6 @@
 // What the reports on a point own beside the iteration's state, and what the op hooks build on their own: the auxiliary projector, the
-// per-block task lists, the plans of cuadmm_lambda_min, cuadmm_lowrank, cuadmm_set_lowrank, cuadmm_block_multiply and cuadmm_lowrank_grad.
-// Nothing here is read by the iteration.
+// per-block task lists, the plans of cuadmm_lambda_min, cuadmm_lowrank, cuadmm_set_lowrank, cuadmm_block_multiply, cuadmm_lowrank_grad
+// and cuadmm_lowrank_line.  Nothing here is read by the iteration.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -13,6 +13,7 @@
 #include "lowrank_apply.h"
 #include "block_mult.h"
 #include "lowrank_grad.h"
+#include "lowrank_line.h"
 
 struct cuadmm_solver;
 
@@ -299,6 +300,34 @@ struct LgPlan {
     return sums.alloc(kLgSums * (size_t)std::max(nb, 1));      // last: marks the set as complete
   }
   double bytes() const { return 8.0 * (double)(xv.n + ybuf.n + ax.n + ytilde.n + r.n + normA.n + part.n + sums.n + cpart.n); }
+};
+
+// The quartic along a line in factor space (cuadmm_lowrank_line; lowrank_line.h, DESIGN.md "Line search along factor steps"): the three
+// svec vectors x0 (a device copy of X with svec(L_k L_k') over its PSD blocks), x1 and x2 (zeroed once, here: the kernel writes their PSD
+// slots only, and always all of them, so the unconstrained slices stay zero), the device copy of D (it grows with rmax; L travels in
+// LoPlan's buffer, whose offsets, ranks and task list the launch reads), the m-vectors of the streaming pass (y, the three A x, r0, p, q;
+// the column norms where the engine keeps none on the device), the slot partials, the per-block sums and a pair of events.  Nothing here is
+// read by the iteration.
+struct LlPlan {
+  DevBuf<double> x0, x1, x2, Dbuf, ybuf, ax0, ax1, ax2, r0, p, q, normA, part, sums, cpart;
+  std::vector<double> h_L, h_D, h_back;          // host scratch kept between calls: the scaled factors, what comes back
+  DevEvent ev[2];
+  int prepare(long long L, int m, int nb, int nchunk, bool own_normA, hipStream_t st) {
+    if (sums.p) return CUADMM_OK;
+    int rc;
+    const size_t mm = (size_t)std::max(m, 1);
+    if ((rc = x0.alloc((size_t)L)) || (rc = x1.alloc((size_t)L)) || (rc = x2.alloc((size_t)L)) || (rc = ybuf.alloc(mm)) || (rc = ax0.alloc(mm)) ||
+        (rc = ax1.alloc(mm)) || (rc = ax2.alloc(mm)) || (rc = r0.alloc(mm)) || (rc = p.alloc(mm)) || (rc = q.alloc(mm)) || (own_normA && (rc = normA.alloc(mm))) ||
+        (rc = part.alloc(kLlParts * (size_t)kBrSlots)) || (rc = cpart.alloc(kLlSums * (size_t)std::max(nchunk, 1))))
+      return rc;
+    CUADMM_HIP_TRY(hipMemsetAsync(x1.p, 0, sizeof(double) * (size_t)L, st));
+    CUADMM_HIP_TRY(hipMemsetAsync(x2.p, 0, sizeof(double) * (size_t)L, st));
+    for (auto& e : ev) if ((rc = e.create())) return rc;
+    return sums.alloc(kLlSums * (size_t)std::max(nb, 1));      // last: marks the set as complete
+  }
+  double bytes() const {
+    return 8.0 * (double)(x0.n + x1.n + x2.n + Dbuf.n + ybuf.n + ax0.n + ax1.n + ax2.n + r0.n + p.n + q.n + normA.n + part.n + sums.n + cpart.n);
+  }
 };
 
 }  // namespace cuadmm

@@ -76,6 +76,38 @@ def lowrank_grad_args(blk_vals, con_num, L, y, sigma):
     return Lv, ranks, rmax, y, sigma
 
 
+def lowrank_line_args(blk_vals, con_num, L, D, y, sigma, t_max):
+    """(L buffer, D buffer, ranks, rmax, y or None, sigma, t_max) as cuadmm_lowrank_line takes them; ValueError where lowrank_grad_args
+    raises one, on a D whose shapes are not those of L, and on a t_max that is not a number"""
+    t_max = float(t_max)
+    if np.isnan(t_max):
+        raise ValueError("lowrank_line: t_max is not a number")
+    sigma = float(sigma)
+    if not (sigma >= 0.0 and np.isfinite(sigma)):
+        raise ValueError("lowrank_line: sigma = %r, allowed is a finite sigma >= 0" % sigma)
+    Lv, ranks, rmax = pack_lowrank(blk_vals, L, "lowrank_line")
+    Dv, dranks, _ = pack_lowrank(blk_vals, D, "lowrank_line")
+    if not np.array_equal(ranks, dranks):
+        raise ValueError("lowrank_line: D has the ranks %s, L the ranks %s" % (dranks.tolist(), ranks.tolist()))
+    if y is not None:
+        y = _f64(y).ravel()
+        if y.size != int(con_num):
+            raise ValueError("lowrank_line: y has %d entries, the problem %d" % (y.size, int(con_num)))
+    return Lv, Dv, ranks, rmax, y, sigma, t_max
+
+
+def quartic_min(c, t_max):
+    """The global minimiser of c[0] + c[1] t + ... + c[4] t^4 on [0, t_max] (cuadmm_quartic_min; no device is needed): a dict with "t",
+    "f" = f(t), "decrease" = f(t) - c[0] and "critical", the number of interior critical points found.  t_max = inf where c[4] > 0, or
+    c[4] = c[3] = 0 and c[2] > 0.  CuadmmError on coefficients that are not finite, a negative or NaN t_max, an unbounded problem."""
+    c = _f64(c).ravel()
+    if c.size != 5:
+        raise ValueError("quartic_min: %d coefficients, expected 5" % c.size)
+    o = np.zeros(4)
+    check(_lib.load().cuadmm_quartic_min(_p(c), float(t_max), _p(o)))
+    return {"t": float(o[0]), "f": float(o[1]), "decrease": float(o[2]), "critical": int(o[3])}
+
+
 class Problem:
     """TXT problem directory (blk.txt, con_num.txt, At.txt, b.txt, C.txt), src/problem.cu:11-83."""
 
@@ -353,6 +385,51 @@ class SDPSolver:
         if want_S:
             out["Shat"] = Sh[:self.vec_len]
         return out
+
+    def lowrank_line(self, L, D, y=None, sigma=0.0, t_max=float("inf")):
+        """The exact quartic t -> f(L + t D) of lowrank_grad's f along the direction D, and its global minimiser on [0, t_max]
+        (cuadmm_lowrank_line).  L, D: lists of (n_k, r_k) arrays of the same shapes, as lowrank()["L"] returns; y, sigma as in
+        lowrank_grad.  Returns "coef": c0 .. c4; "t", "f" = f(t) by Horner, "decrease" = f(t) - c0, "critical" (t_max <= 0: coefficients
+        only, t = 0); "r", "p", "q": r(t) = r + t p + t^2 q; "pnorm", "qnorm", "ms", "bytes"; "per_block": (mat_num, 4) rows <C_k, x0_k>,
+        <C_k, x1_k>, <C_k, x2_k>, flag (0 PSD, 2 unconstrained).  t_max = inf needs a quartic that is bounded below (sigma > 0 and
+        A (D D') != 0); otherwise CuadmmError.  The solver is left as it was: behind a solve the pending scaled state stays pending."""
+        Lv, Dv, ranks, rmax, yv, sigma, t_max = lowrank_line_args(self.blk_vals, self.con_num, L, D, y, sigma, t_max)
+        n = max(self.con_num, 1)
+        coef, r, p, q, o, pb = np.zeros(5), np.zeros(n), np.zeros(n), np.zeros(n), np.zeros(8), np.zeros(4 * self.mat_num)
+        check(self._lib.cuadmm_lowrank_line(self._h, _p(Lv), _p(Dv), _p(ranks), rmax, _p(yv), sigma, t_max, _p(coef), _p(r), _p(p), _p(q), _p(o), _p(pb)))
+        m = self.con_num
+        return {"coef": coef, "t": float(o[0]), "f": float(o[1]), "decrease": float(o[2]), "pnorm": float(o[3]), "qnorm": float(o[4]), "critical": int(o[5]),
+                "ms": float(o[6]), "bytes": float(o[7]), "r": r[:m], "p": p[:m], "q": q[:m], "per_block": pb.reshape(self.mat_num, 4)}
+
+    def lowrank_descent(self, L, y=None, sigma=1.0, steps=10, t_max=float("inf")):
+        """An example that closes the loop of lowrank, lowrank_grad and lowrank_line: `steps` steps of Polak-Ribiere+ nonlinear conjugate
+        gradients on f(L) = <C, x> - y'r + (sigma / 2) ||r||^2 over the factors of the PSD blocks, each one lowrank_grad call, one
+        lowrank_line call (the exact minimiser of f along the direction on [0, t_max]) and L <- L + t D on the host.  The direction
+        restarts to steepest descent where <G, D> >= 0.  The unconstrained slices of x stay at their resident values throughout: only the
+        factors move.  Stops early where the line search returns t = 0.  Returns {"L": the final factors, "trace": one dict per step
+        with "f", "gnorm", "t", "predicted" (the quartic's f(t)), "restart"}.  Not a tuned optimiser: no multiplier update, no rank
+        adaptation."""
+        Ls = [np.array(_f64(m), copy=True) for m in L]
+        inner = lambda A, B: float(sum(np.sum(a * b) for a, b in zip(A, B)))
+        trace, D, G_old = [], None, None
+        for _ in range(int(steps)):
+            g = self.lowrank_grad(Ls, y, sigma)
+            G = g["G"]
+            restart = D is None
+            if not restart:
+                gg = inner(G_old, G_old)
+                beta = max(0.0, (inner(G, G) - inner(G, G_old)) / gg) if gg > 0 else 0.0
+                D = [-a + beta * d for a, d in zip(G, D)]
+                restart = inner(G, D) >= 0
+            if restart:
+                D = [-a for a in G]
+            ln = self.lowrank_line(Ls, D, y, sigma, t_max)
+            trace.append({"f": g["f"], "gnorm": g["gnorm"], "t": ln["t"], "predicted": ln["f"], "restart": bool(restart)})
+            if ln["t"] == 0:
+                break
+            Ls = [a + ln["t"] * d for a, d in zip(Ls, D)]
+            G_old = G
+        return {"L": Ls, "trace": trace}
 
     def set_allreduce(self, fn):
         """fn(dev_ptr:int, count:int, hip_stream:int) -> None : in-place sum over ranks on that stream."""

@@ -226,6 +226,49 @@ int cuadmm_block_multiply(cuadmm_solver* s, int which, const double* V, const in
  * cuadmm_update_A. */
 int cuadmm_lowrank_grad(cuadmm_solver* s, const double* L, const int* ranks, int rmax, const double* y, double sigma, double* G_out, double* r_out,
                         double* Shat_out, double out8[8], double* per_block);
+/* The augmented Lagrangian of cuadmm_lowrank_grad along a line in factor space, as an exact quartic ("Line search along factor
+ * steps"; csrc/lowrank_line.h).  With x(t) the resident X in which every PSD block k is replaced by (L_k + t D_k)(L_k + t D_k)'
+ * (unconstrained blocks keep their resident slices for every t), y and sigma as in cuadmm_lowrank_grad:
+ *   x(t) = x0 + t x1 + t^2 x2,  x0 = L L',  x1 = L D' + D L',  x2 = D D';    r(t) = r0 + t p + t^2 q,  r0 = A x0 - b,  p = A x1,  q = A x2
+ *   f(t) = <C, x(t)> - y'r(t) + (sigma / 2) ||r(t)||^2 = c0 + c1 t + c2 t^2 + c3 t^3 + c4 t^4
+ *   c0 = <C, x0> - y'r0 + (sigma / 2) r0'r0      c1 = <C, x1> - y'p + sigma r0'p      c2 = <C, x2> - y'q + (sigma / 2)(p'p + 2 r0'q)
+ *   c3 = sigma p'q                               c4 = (sigma / 2) q'q
+ * L, ranks, rmax as in cuadmm_lowrank_grad; D has the layout and the ranks of L.  Columns >= r_k of L and of D are never read (they may
+ * hold NaN).  coef5 <- c0 .. c4.  r_out, p_out, q_out (con_num doubles each, the caller's order) and per_block may be NULL.
+ * The chain runs on the solver's stream in the engine's scaled space: a device copy of X into the call's own x0, one launch that forms
+ * svec of the three outer products over the PSD blocks of x0, x1, x2 (three accumulators per 16 x 16 tile on the fp64 matrix cores; x0 is
+ * bit for bit the vector cuadmm_lowrank_grad assembles), the iteration's SpMV three times, one streaming pass that forms r0, p, q and
+ * nine slot sums, one pass of per-block sums.  No atomics: the same bits on every run.  r_out is bit for bit cuadmm_lowrank_grad's r_out
+ * at the same L, y, sigma.  Negating D negates c1 and c3 bit for bit and keeps c0, c2, c4.  Nothing the iteration reads is written and the
+ * deferred unscaling is not triggered: a following cuadmm_solve(..., if_first = 0) continues bit for bit.
+ * t_max > 0 (+inf included): the coefficients go through cuadmm_quartic_min(coef5, t_max, .).  t_max <= 0: coefficients only.
+ * out8: [0] t* (t_max <= 0: 0), [1] f(t*) by Horner (t_max <= 0: c0), [2] f(t*) - c0, [3] ||p||, [4] ||q||, [5] interior critical points
+ * found, [6] device milliseconds of the chain (HIP events; the staged copies are not in it), [7] bytes of device memory the call holds.
+ * per_block, 4 mat_num doubles: [4k] <C_k, x0_k>, [4k + 1] <C_k, x1_k>, [4k + 2] <C_k, x2_k>, [4k + 3] 0 for a PSD block, 2 for an
+ * unconstrained one (there [4k + 1] = [4k + 2] = 0).
+ * Rounding (u = 2^-53, gamma(K) = K u / (1 - K u) times the absolute-value chain of each quantity; c / c' the most entries in a row of
+ * A / A', R the largest rank), counted launch by launch as for cuadmm_lowrank_grad.  A slot of x0 or x2: the outer product's R + 4 and 6
+ * for the factors' unit (or 2 for fl(1 / bscale) in A x), R + 10; a slot of x1: 2 R + 10.
+ *   r0, q  K_r = c + R + 16 (cuadmm_lowrank_grad's; q has no b and lies inside it)        p  K_p = c + 2 R + 16
+ *   <C, x0>, <C, x2>  K_cx = vec_len + R + 16                                               <C, x1>  K_cx1 = vec_len + 2 R + 16
+ *   y'v   K_v + m + 270 for v = r0, p, q                 v'w   K_v + K_w + m + 266 for v, w among r0, p, q
+ *   c0  max(K_cx, K_r + m + 270, 2 K_r + m + 266) + 2 (= cuadmm_lowrank_grad's K_f)         c1  max(K_cx1, K_p + m + 270, K_r + K_p + m + 266) + 3
+ *   c2  max(K_cx, K_r + m + 270, 2 K_p + m + 266) + 4        c3  K_p + K_r + m + 268        c4  2 K_r + m + 268
+ * (tests/_lowrank_line_twin.py has the chains.)
+ * CUADMM_ERR_INVALID, the solver and every output as they were: the list of cuadmm_lowrank_grad, applied to L and to D (D NULL while some
+ * rank is positive; an entry of a column of D that would be read that is not finite); coef5 NULL; t_max NaN; a t_max > 0 that
+ * cuadmm_quartic_min refuses for these coefficients (+inf on a quartic that is not bounded below).  CUADMM_ERR_FACTOR behind a failed
+ * cuadmm_update_A. */
+int cuadmm_lowrank_line(cuadmm_solver* s, const double* L, const double* D, const int* ranks, int rmax, const double* y, double sigma, double t_max,
+                        double coef5[5], double* r_out, double* p_out, double* q_out, double out8[8], double* per_block);
+/* The global minimiser of c[0] + c[1] t + c[2] t^2 + c[3] t^3 + c[4] t^4 on [0, t_max].  Host only: no device, no solver handle.
+ * t_max = +inf is allowed where c[4] > 0, or c[4] = c[3] = 0 and c[2] > 0.  Candidates: 0, a finite t_max and the real roots of the
+ * derivative inside the interval (bracketed by the closed-form stationary points of the derivative, refined by Newton steps safeguarded
+ * by bisection); each is evaluated by Horner, the smallest value wins, ties go to the smallest t.
+ * out4: [0] t*, [1] f(t*), [2] f(t*) - c[0], [3] interior critical points found.
+ * CUADMM_ERR_INVALID: c or out4 NULL, a coefficient that is not finite, t_max negative or NaN, t_max = +inf on a quartic that is not
+ * bounded below by the rule above. */
+int cuadmm_quartic_min(const double c[5], double t_max, double out4[4]);
 /* Replace X (which = 0) or S (1) between two solves by per-block factors: every PSD block k becomes L_k L_k' with r_k = ranks[k] columns
  * ("Starting from low-rank factors"; csrc/lowrank_apply.h).  L is laid out as cuadmm_lowrank's L_out for this rmax: block k at the
  * prefix sum of n_j min(n_j, rmax) over the PSD blocks before it, column by column, n_k doubles per column; unconstrained blocks occupy
@@ -740,6 +783,21 @@ int cuadmm_op_block_mult_plan(const int* blk_vals, int mat_num, int rmax, long l
  * rounded once.  The default stream, synchronised. */
 int cuadmm_op_lrg_multiplier(int m, const double* ax, const double* b, const double* normA, const double* y, double bscale, double Cscale, double sigma,
                              double* ytilde_out, double* r_out, double out2[2]);
+/* The outer-product kernel of cuadmm_lowrank_line on three DEVICE svec vectors whose blocks follow one another from slot 0
+ * (csrc/lowrank_line.hip): x0 <- svec(L_k L_k'), x1 <- svec(L_k D_k' + D_k L_k'), x2 <- svec(D_k D_k') on every PSD block; the slots of
+ * unconstrained blocks keep their bits.  L_host, D_host (one layout, cuadmm_lowrank's L_out for rmax), ranks and blk_vals on the host.
+ * split_from as in cuadmm_op_block_outer_plan, whose task list this launch walks (0: the engine's; else at least 33).  Synchronises the
+ * stream. */
+int cuadmm_op_block_outer3(const double* L_host, const double* D_host, const int* ranks, const int* blk_vals, int mat_num, int rmax, int split_from,
+                           double* x0_dev_inout, double* x1_dev_inout, double* x2_dev_inout, void* stream);
+/* The streaming pass of cuadmm_lowrank_line alone (csrc/lowrank_line.hip) on host arrays of m >= 1 doubles in the engine's scaled space
+ * and order: rs0_i = ax0_i - b_i, r_out_i = (normA_i rs0_i) bscale, p_out_i = (normA_i ax1_i) bscale, q_out_i = (normA_i ax2_i) bscale,
+ * out9 = [u sum y rs0, u sum y ax1, u sum y ax2 (u = bscale Cscale), sum r^2, sum r p, sum p^2, sum r q, sum p q, sum q^2], each from
+ * 256 slot partials added in slot order.  Every operation is rounded once.  A device vector starts in the 16-byte phase its host
+ * array has: arrays that are all 16-byte aligned take the two-constraint map, any other the one-constraint map.  The default stream,
+ * synchronised. */
+int cuadmm_op_lrl_sums(int m, const double* ax0, const double* ax1, const double* ax2, const double* b, const double* normA, const double* y, double bscale,
+                       double Cscale, double* r_out, double* p_out, double* q_out, double out9[9]);
 int cuadmm_op_spmv_rows(int rows, int ncols, const int* row_ptrs, const int* col_ids, const double* vals, const double* X, const double* S, const double* C,
                         int want_x, int want_s, const int* rowmap, int out_len, double* outX, double* outS, int* info4);
 int cuadmm_op_rp_stats(int m, const double* ax, const double* b, const double* normA, const double* y, double bscale, const double* sums2, double* out4);

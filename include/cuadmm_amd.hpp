@@ -5,6 +5,7 @@
 // device pointers through DeviceDenseVector::vals), and failures throw std::runtime_error instead of
 // printing and continuing (include/cuadmm/check.h:17-56).
 #pragma once
+#include <limits>
 #include <stdexcept>
 #include <string>
 #include <tuple>
@@ -246,6 +247,32 @@ class SDPSolver {
     g.r.resize((size_t)cn);
     if (want_S) g.Shat.resize((size_t)vl);
     g.f = o[0]; g.cx = o[1]; g.yr = o[2]; g.rnorm = o[3]; g.gnorm = o[4]; g.lg = o[5]; g.ms = o[6]; g.bytes = o[7];
+    return g;
+  }
+
+  // cuadmm_lowrank_line: the quartic t -> f(L + t D) of lowrank_grad's f (coef: c0 .. c4) and its global minimiser on [0, t_max]
+  // (t_max <= 0: coefficients only); L, D, ranks, rmax as lowrank_grad's L; r(t) = r + t p + t^2 q; per_block: [4k ..] = <C_k, x0_k>,
+  // <C_k, x1_k>, <C_k, x2_k>, flag; not in the reference
+  struct LowRankLine {
+    double coef[5], t, f, decrease, pnorm, qnorm, ms, bytes;
+    int critical;
+    std::vector<double> r, p, q, per_block;
+  };
+  LowRankLine lowrank_line(const double* L, const double* D, const int* ranks, int rmax, const double* y = nullptr, double sigma = 0.0,
+                           double t_max = std::numeric_limits<double>::infinity()) {
+    double o[8] = {0};
+    int vl = 0, cn = 0, mn = 0;
+    check(cuadmm_get_dims(h_, &vl, &cn, &mn));
+    LowRankLine g;
+    g.r.assign((size_t)cn + 1, 0.0);
+    g.p.assign((size_t)cn + 1, 0.0);
+    g.q.assign((size_t)cn + 1, 0.0);
+    g.per_block.assign(4 * (size_t)mn, 0.0);
+    check(cuadmm_lowrank_line(h_, L, D, ranks, rmax, y, sigma, t_max, g.coef, g.r.data(), g.p.data(), g.q.data(), o, g.per_block.data()));
+    g.r.resize((size_t)cn);
+    g.p.resize((size_t)cn);
+    g.q.resize((size_t)cn);
+    g.t = o[0]; g.f = o[1]; g.decrease = o[2]; g.pnorm = o[3]; g.qnorm = o[4]; g.critical = (int)o[5]; g.ms = o[6]; g.bytes = o[7];
     return g;
   }
 
