@@ -175,6 +175,17 @@ PROTOTYPES = {
     "cuadmm_op_post": (C.c_int, [C.c_int, C.c_int64] + [C.c_void_p] * 5 + [C.c_double, C.c_double, C.c_void_p, C.c_int] + [C.c_void_p] * 5),
     "cuadmm_op_spmv_rows": (C.c_int, [C.c_int, C.c_int] + [C.c_void_p] * 6 + [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "cuadmm_op_rp_stats": (C.c_int, [C.c_int] + [C.c_void_p] * 4 + [C.c_double, C.c_void_p, C.c_void_p]),
+    "cuadmm_op_aty_xb_idx": (C.c_int, [C.c_int64, C.c_int] + [C.c_void_p] * 6 + [C.c_double, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cuadmm_op_post_rest": (C.c_int, [C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_int] + [C.c_void_p] * 6 + [C.c_double, C.c_double, C.c_int] + [C.c_void_p] * 3),
+    "cuadmm_op_reduce_quads": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "cuadmm_op_reduce_quads_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_void_p]),
+    "cuadmm_op_closed_rows": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 6),
+    "cuadmm_op_copy": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p]),
+    "cuadmm_op_copy_multi": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cuadmm_op_scale": (C.c_int, [C.c_void_p, C.c_int64, C.c_double]),
+    "cuadmm_op_update_svec": (C.c_int, [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int] + [C.c_double] * 4),
+    "cuadmm_op_update_cons": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_double]),
+    "cuadmm_op_scatter_scaled": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_double]),
     "cuadmm_op_batch_eig": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "cuadmm_op_max_zero": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p]),
     "cuadmm_op_mul_diag_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),

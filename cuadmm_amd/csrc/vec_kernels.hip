@@ -14,6 +14,8 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cstddef>
+#include <cstring>
 #include <vector>
 
 #include "device_util.h"
@@ -1199,6 +1201,211 @@ int cuadmm_op_rp_stats(int m, const double* ax, const double* b, const double* n
   if ((rc = launch_rp_stats(m, d_ax.p, d_b.p, d_n.p, d_y.p, bscale, d_sums.p, d_part.p, d_out.p, nullptr))) return rc;
   CUADMM_HIP_TRY(hipStreamSynchronize(nullptr));
   return d_out.to(out4, 4);
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------
+// Test hooks only: the fused step's list kernels, the quad sums, the copies and the update passes (tests/test_gpu_step_kernels.py).
+// Same rules as above: host pointers, everything checked before a launch, the default stream, synchronised before the return.
+// ------------------------------------------------------------------------------------------
+namespace {
+// n entries, each in [0, len), no entry twice
+bool list_ok(long long n, const int* idx, long long len) {
+  if (n < 0 || n > len || (n > 0 && !idx)) return false;
+  std::vector<unsigned char> seen((size_t)std::max<long long>(len, 1), 0);
+  for (long long k = 0; k < n; ++k) {
+    if (idx[k] < 0 || idx[k] >= len || seen[(size_t)idx[k]]) return false;
+    seen[(size_t)idx[k]] = 1;
+  }
+  return true;
+}
+const double kHookNaN = __builtin_nan("");
+// `n` doubles of h (may be null: none) followed by `pad` NaNs
+std::vector<double> nan_padded(const double* h, size_t n, size_t pad) {
+  std::vector<double> v(n + pad, kHookNaN);
+  if (h && n) std::copy(h, h + n, v.begin());
+  return v;
+}
+int hook_invalid(const char* who) { set_error("%s: bad arguments", who); return CUADMM_ERR_INVALID; }
+}  // namespace
+
+extern "C" {
+
+int cuadmm_op_aty_xb_idx(int64_t L, int m, const int* rp, const int* ci, const double* av, const double* y, const double* C, const double* X, double sig,
+                         int64_t nidx, const int* idx, double* Rd1, double* Xb) {
+  if (L < 1 || m < 1 || !av || !y || !C || !X || !Rd1 || !Xb || !csr_ok(L, m, rp, ci) || !list_ok(nidx, idx, L)) return hook_invalid("op_aty_xb_idx");
+  const size_t nnz = (size_t)rp[L];
+  int rc;
+  HookBuf<int> d_rp, d_ci, d_idx;
+  HookBuf<double> d_av, d_y, d_C, d_X, d_Rd1, d_Xb;
+  if ((rc = d_rp.from(rp, (size_t)L + 1)) || (rc = d_ci.from(ci, nnz)) || (rc = d_av.from(av, nnz)) || (rc = d_y.from(y, (size_t)m)) || (rc = d_C.from(C, (size_t)L)) ||
+      (rc = d_X.from(X, (size_t)L)) || (rc = d_Rd1.from(Rd1, (size_t)L)) || (rc = d_Xb.from(Xb, (size_t)L)) || (rc = d_idx.from(idx, (size_t)nidx)))
+    return rc;
+  if ((rc = launch_aty_xb_idx(nidx, d_idx.p, d_rp.p, d_ci.p, d_av.p, d_y.p, d_C.p, d_X.p, sig, d_Rd1.p, d_Xb.p, nullptr))) return rc;
+  CUADMM_HIP_TRY(hipStreamSynchronize(nullptr));
+  if ((rc = d_Rd1.to(Rd1, (size_t)L)) || (rc = d_Xb.to(Xb, (size_t)L))) return rc;
+  return CUADMM_OK;
+}
+
+int cuadmm_op_post_rest(int mode, int64_t L, int64_t nidx, const int* idx, int nfused, const double* fused_pairs, const double* Xproj, const double* Rd1,
+                        const double* C, double* X, double* S, double inv_sig, double tau_sig, int use_quads, double* sums2, double* partials_out,
+                        int* nparts_out) {
+  if (mode < 0 || mode > 1 || L < 1 || nfused < 0 || nfused > (1 << 24) || (nidx == 0 && nfused == 0) || (nfused > 0 && !fused_pairs) || !Xproj || !Rd1 || !C || !X ||
+      !S || !sums2 || !partials_out || !nparts_out || !list_ok(nidx, idx, L))
+    return hook_invalid("op_post_rest");
+  const int grid = nidx > 0 ? post_grid(nidx) : 0;
+  const std::vector<double> part = nan_padded(fused_pairs, 2 * (size_t)nfused, 2 * (size_t)grid);
+  int rc, nparts = -1;
+  HookBuf<int> d_idx;
+  HookBuf<double> d_Xp, d_Rd1, d_C, d_X, d_S, d_part, d_sums;
+  if ((rc = d_idx.from(idx, (size_t)nidx)) || (rc = d_Xp.from(Xproj, (size_t)L)) || (rc = d_Rd1.from(Rd1, (size_t)L)) || (rc = d_C.from(C, (size_t)L)) ||
+      (rc = d_X.from(X, (size_t)L)) || (rc = d_S.from(S, (size_t)L)) || (rc = d_part.from(part.data(), part.size())) || (rc = d_sums.from(sums2, 2)))
+    return rc;
+  if ((rc = launch_post_rest(mode, nidx, d_idx.p, nfused, d_Xp.p, d_Rd1.p, d_C.p, d_X.p, d_S.p, inv_sig, tau_sig, d_part.p, d_sums.p, nullptr,
+                             use_quads ? &nparts : nullptr)))
+    return rc;
+  CUADMM_HIP_TRY(hipStreamSynchronize(nullptr));
+  if ((rc = d_X.to(X, (size_t)L)) || (rc = d_S.to(S, (size_t)L)) || (rc = d_sums.to(sums2, 2)) || (rc = d_part.to(partials_out, part.size()))) return rc;
+  *nparts_out = nparts;
+  return CUADMM_OK;
+}
+
+int cuadmm_op_reduce_quads(const double* p1, int n1, const double* p2, int n2, int pad_pairs, int with_scratch, double* out4, double* sums2) {
+  if (n1 < 0 || n2 < 0 || (n1 > 0 && !p1) || (n2 > 0 && !p2) || pad_pairs < 0 || pad_pairs > 1024 || !out4 || !sums2) return hook_invalid("op_reduce_quads");
+  const std::vector<double> h1 = nan_padded(p1, 2 * (size_t)n1, 2 * (size_t)pad_pairs), h2 = nan_padded(p2, 2 * (size_t)n2, 2 * (size_t)pad_pairs);
+  const std::vector<double> hs = nan_padded(nullptr, 0, 4 * (size_t)reduce_quads_segments(n1, n2)), ho = nan_padded(nullptr, 0, 6);
+  int rc;
+  HookBuf<double> d_1, d_2, d_scr, d_out, d_sums;
+  if ((rc = d_1.from(h1.data(), h1.size())) || (rc = d_2.from(h2.data(), h2.size())) || (with_scratch && (rc = d_scr.from(hs.data(), hs.size()))) ||
+      (rc = d_out.from(ho.data(), 4)) || (rc = d_sums.from(ho.data() + 4, 2)))
+    return rc;
+  const int rc_launch = launch_reduce_quads(d_1.p, n1, d_2.p, n2, d_out.p, d_sums.p, with_scratch ? d_scr.p : nullptr, nullptr);
+  CUADMM_HIP_TRY(hipStreamSynchronize(nullptr));
+  if ((rc = d_out.to(out4, 4)) || (rc = d_sums.to(sums2, 2))) return rc;      // (a refusal leaves both as they were filled)
+  return rc_launch;
+}
+
+int cuadmm_op_reduce_quads_batch(const double* p1, const double* p2, int n, int64_t stride, int iters, double* out4) {
+  if (!p1 || !p2 || !out4 || n < 0 || stride < 2 || (stride & 1) || stride < 2 * (int64_t)n || stride > ((int64_t)1 << 26) || iters < 1 || iters > 64)
+    return hook_invalid("op_reduce_quads_batch");
+  const size_t len = (size_t)stride * (size_t)iters, nout = 4 * (size_t)iters + 4;
+  int rc;
+  HookBuf<double> d_1, d_2, d_out;
+  if ((rc = d_1.from(p1, len)) || (rc = d_2.from(p2, len)) || (rc = d_out.from(out4, nout))) return rc;
+  if ((rc = launch_reduce_quads_batch(d_1.p, d_2.p, n, stride, iters, d_out.p, nullptr))) return rc;
+  CUADMM_HIP_TRY(hipStreamSynchronize(nullptr));
+  return d_out.to(out4, nout);
+}
+
+int cuadmm_op_closed_rows(int nslots, const int* nk, const int* rows, int m, const double* ax, const double* as, const double* b, double* cl_out, double* b_out,
+                          int64_t* changed_out) {
+  if (nslots < 1 || nslots > (1 << 20) || m < 1 || !nk || !rows || !ax || !as || !b || !cl_out || !b_out || !changed_out) return hook_invalid("op_closed_rows");
+  for (int s = 0; s < nslots; ++s) {
+    if (nk[s] < 1 || nk[s] > kClosedMaxRows) return hook_invalid("op_closed_rows");
+    for (int k = 0; k < nk[s]; ++k)
+      if (rows[kClosedMaxRows * (size_t)s + k] < 0 || rows[kClosedMaxRows * (size_t)s + k] >= m) return hook_invalid("op_closed_rows");
+  }
+  std::vector<ClosedRec> up((size_t)nslots), down((size_t)nslots);
+  memset(static_cast<void*>(up.data()), 0xA5, sizeof(ClosedRec) * up.size());
+  for (int s = 0; s < nslots; ++s) {
+    up[s].nk = nk[s];
+    for (int k = 0; k < nk[s]; ++k) up[s].rows[k] = rows[kClosedMaxRows * (size_t)s + k];
+  }
+  int rc;
+  HookBuf<ClosedRec> d_rec;
+  HookBuf<double> d_ax, d_as, d_b, d_cl;
+  if ((rc = d_rec.from(up.data(), up.size())) || (rc = d_ax.from(ax, (size_t)m)) || (rc = d_as.from(as, (size_t)m)) || (rc = d_b.from(b, (size_t)m)) ||
+      (rc = d_cl.from(cl_out, 16 * (size_t)nslots)))
+    return rc;
+  if ((rc = launch_closed_gather_out(d_rec.p, nslots, d_ax.p, d_as.p, d_cl.p, nullptr)) || (rc = launch_closed_patch_b(d_rec.p, nslots, d_b.p, nullptr))) return rc;
+  CUADMM_HIP_TRY(hipStreamSynchronize(nullptr));
+  if ((rc = d_cl.to(cl_out, 16 * (size_t)nslots)) || (rc = d_rec.to(down.data(), down.size()))) return rc;
+  int64_t changed = 0;
+  for (int s = 0; s < nslots; ++s) {
+    const unsigned char* u = reinterpret_cast<const unsigned char*>(&up[s]);
+    const unsigned char* d = reinterpret_cast<const unsigned char*>(&down[s]);
+    const size_t b0 = offsetof(ClosedRec, b), b1 = b0 + sizeof(double) * (size_t)nk[s];
+    for (size_t q = 0; q < sizeof(ClosedRec); ++q)
+      if ((q < b0 || q >= b1) && u[q] != d[q]) ++changed;
+    memcpy(b_out + kClosedMaxRows * (size_t)s, down[s].b, sizeof(double) * kClosedMaxRows);
+  }
+  *changed_out = changed;
+  return CUADMM_OK;
+}
+
+int cuadmm_op_copy(const double* src, int64_t n, double* dst) {
+  if (n < 1 || n > ((int64_t)1 << 28) || !src || !dst) return hook_invalid("op_copy");
+  int rc;
+  HookBuf<double> d_src, d_dst;
+  if ((rc = d_src.from(src, (size_t)n)) || (rc = d_dst.from(dst, (size_t)n + 4))) return rc;
+  if ((rc = launch_copy(d_dst.p, d_src.p, n, nullptr))) return rc;
+  CUADMM_HIP_TRY(hipStreamSynchronize(nullptr));
+  return d_dst.to(dst, (size_t)n + 4);
+}
+
+int cuadmm_op_copy_multi(int count, const int64_t* nbytes, const void* const* src, void* const* dst) {
+  if (count < 1 || count > 6 || !nbytes || !src || !dst) return hook_invalid("op_copy_multi");
+  for (int q = 0; q < count; ++q)
+    if (nbytes[q] < 0 || nbytes[q] > ((int64_t)1 << 30) || (nbytes[q] > 0 && !src[q]) || !dst[q]) return hook_invalid("op_copy_multi");
+  int rc;
+  HookBuf<unsigned char> d_src[6], d_dst[6];
+  CopyJobs jobs{};
+  jobs.count = count;
+  for (int q = 0; q < count; ++q) {
+    if ((rc = d_src[q].from(static_cast<const unsigned char*>(src[q]), (size_t)nbytes[q])) ||
+        (rc = d_dst[q].from(static_cast<const unsigned char*>(dst[q]), (size_t)nbytes[q] + 32)))
+      return rc;
+    jobs.dst[q] = d_dst[q].p; jobs.src[q] = d_src[q].p; jobs.nbytes[q] = nbytes[q];
+  }
+  if ((rc = launch_copy_multi(jobs, nullptr))) return rc;                    // (a length that is no multiple of 4 is refused there, before the launch)
+  CUADMM_HIP_TRY(hipStreamSynchronize(nullptr));
+  for (int q = 0; q < count; ++q)
+    if ((rc = d_dst[q].to(static_cast<unsigned char*>(dst[q]), (size_t)nbytes[q] + 32))) return rc;
+  return CUADMM_OK;
+}
+
+int cuadmm_op_scale(double* v, int64_t n, double s) {
+  if (n < 1 || n > ((int64_t)1 << 28) || !v) return hook_invalid("op_scale");
+  int rc;
+  HookBuf<double> d_v;
+  if ((rc = d_v.from(v, (size_t)n + 4))) return rc;
+  if ((rc = launch_scale(d_v.p, n, s, nullptr))) return rc;
+  CUADMM_HIP_TRY(hipStreamSynchronize(nullptr));
+  return d_v.to(v, (size_t)n + 4);
+}
+
+int cuadmm_op_update_svec(int64_t n, double* X, double* S, double* C, int zero, double x1, double x2, double s1, double s2) {
+  if (n < 1 || n > ((int64_t)1 << 28) || !X || !S) return hook_invalid("op_update_svec");
+  int rc;
+  HookBuf<double> d_X, d_S, d_C;
+  if ((rc = d_X.from(X, (size_t)n + 2)) || (rc = d_S.from(S, (size_t)n + 2)) || (C && (rc = d_C.from(C, (size_t)n + 2)))) return rc;
+  if ((rc = launch_update_svec(d_X.p, d_S.p, C ? d_C.p : nullptr, n, zero != 0, x1, x2, s1, s2, nullptr))) return rc;
+  CUADMM_HIP_TRY(hipStreamSynchronize(nullptr));
+  if ((rc = d_X.to(X, (size_t)n + 2)) || (rc = d_S.to(S, (size_t)n + 2)) || (C && (rc = d_C.to(C, (size_t)n + 2)))) return rc;
+  return CUADMM_OK;
+}
+
+int cuadmm_op_update_cons(int m, double* b, double* y, const double* normA, int ymode, double cs_old, double ics_new) {
+  if (m < 1 || ymode < 0 || ymode > 2 || (ymode != 0 && !y) || (ymode == 2 && !normA)) return hook_invalid("op_update_cons");
+  int rc;
+  HookBuf<double> d_b, d_y, d_n;
+  if ((b && (rc = d_b.from(b, (size_t)m + 2))) || (y && (rc = d_y.from(y, (size_t)m + 2))) || (normA && (rc = d_n.from(normA, (size_t)m)))) return rc;
+  if ((rc = launch_update_cons(m, b ? d_b.p : nullptr, y ? d_y.p : nullptr, normA ? d_n.p : nullptr, ymode, cs_old, ics_new, nullptr))) return rc;
+  CUADMM_HIP_TRY(hipStreamSynchronize(nullptr));
+  if ((b && (rc = d_b.to(b, (size_t)m + 2))) || (y && (rc = d_y.to(y, (size_t)m + 2)))) return rc;
+  return CUADMM_OK;
+}
+
+int cuadmm_op_scatter_scaled(int len, double* dst, int n, const int* idx, const double* val, double s) {
+  if (len < 1 || !dst || (n > 0 && !val) || !list_ok(n, idx, len)) return hook_invalid("op_scatter_scaled");
+  int rc;
+  HookBuf<int> d_idx;
+  HookBuf<double> d_dst, d_val;
+  if ((rc = d_dst.from(dst, (size_t)len)) || (rc = d_idx.from(idx, (size_t)n)) || (rc = d_val.from(val, (size_t)n))) return rc;
+  if ((rc = launch_scatter_scaled(d_dst.p, d_idx.p, d_val.p, n, s, nullptr))) return rc;
+  CUADMM_HIP_TRY(hipStreamSynchronize(nullptr));
+  return d_dst.to(dst, (size_t)len);
 }
 
 }  // extern "C"

@@ -801,6 +801,41 @@ int cuadmm_op_lrl_sums(int m, const double* ax0, const double* ax1, const double
 int cuadmm_op_spmv_rows(int rows, int ncols, const int* row_ptrs, const int* col_ids, const double* vals, const double* X, const double* S, const double* C,
                         int want_x, int want_s, const int* rowmap, int out_len, double* outX, double* outS, int* info4);
 int cuadmm_op_rp_stats(int m, const double* ax, const double* b, const double* normA, const double* y, double bscale, const double* sums2, double* out4);
+/* Test hooks only: the fused step's list kernels, the quad sums, the copies and the update passes as ops (csrc/vec_kernels.hip).  Host
+ * pointers; every index and length is checked before anything is launched; in/out arrays are uploaded as given, so what a kernel leaves
+ * untouched comes back bit for bit; the default stream, synchronised.
+ *   aty_xb_idx : Rd1[i] = (At y)[i] - C[i], Xb[i] = X[i] + sig Rd1[i] on the nidx rows i = idx[k] (each in [0, L)) only
+ *   post_rest  : mode 0 / 1 of post over the rows of idx.  The partial array of 2 (nfused + post_grid(nidx)) doubles starts as fused_pairs
+ *                followed by NaN and is returned whole in partials_out.  use_quads = 0: the launcher reduces into sums2 (mode 0);
+ *                use_quads = 1: it reduces nothing and says in *nparts_out how many pairs there are (else *nparts_out = -1).
+ *                nidx = 0 needs nfused > 0.
+ *   reduce_quads: out4 = {sum p2.x, sum p2.y, sum p1.x, sum p1.y}, sums2 = out4[2..3] over n1 / n2 pairs; the device arrays hold pad_pairs
+ *                NaN pairs behind the data; the segment scratch (with_scratch) starts as NaN; out4 and sums2 start as NaN and are copied
+ *                back even where the launcher refuses (more than one segment without scratch: CUADMM_ERR_INVALID)
+ *   reduce_quads_batch: p1, p2 hold iters x stride doubles (stride even, >= 2 n; iters in [1, 64]); out4 holds 4 iters + 4 doubles, uploaded
+ *                as given: the last four are a canary
+ *   closed_rows: nslots records whose every byte is 0xA5 except nk (1..8) and rows[0, nk) (each in [0, m)); cl_out (16 nslots, in/out) from
+ *                closed_gather_out, then closed_patch_b; b_out[8 s + k] = rec[s].b[k]; *changed_out = record bytes outside b[0, nk) that
+ *                differ from the upload
+ *   copy       : dst_inout holds n + 4 doubles (4 canaries); scale: v_inout likewise
+ *   copy_multi : count in [1, 6] jobs; dst_inout[q] holds nbytes[q] + 32 bytes
+ *   update_svec: X, S and (may be NULL) C hold n + 2 doubles; update_cons: b, y (each may be NULL) hold m + 2; the launchers see n and m
+ *   scatter_scaled: dst[idx[k]] = val[k] s; idx distinct and in [0, len) */
+int cuadmm_op_aty_xb_idx(int64_t L, int m, const int* row_ptrs, const int* col_ids, const double* vals, const double* y, const double* C, const double* X,
+                         double sig, int64_t nidx, const int* idx, double* Rd1_inout, double* Xb_inout);
+int cuadmm_op_post_rest(int mode, int64_t L, int64_t nidx, const int* idx, int nfused, const double* fused_pairs, const double* Xproj, const double* Rd1,
+                        const double* C, double* X_inout, double* S_inout, double inv_sig, double tau_sig, int use_quads, double* sums2_inout,
+                        double* partials_out, int* nparts_out);
+int cuadmm_op_reduce_quads(const double* p1, int n1, const double* p2, int n2, int pad_pairs, int with_scratch, double* out4, double* sums2);
+int cuadmm_op_reduce_quads_batch(const double* p1, const double* p2, int n, int64_t stride, int iters, double* out4_inout);
+int cuadmm_op_closed_rows(int nslots, const int* nk, const int* rows, int m, const double* ax, const double* as, const double* b, double* cl_out,
+                          double* b_out, int64_t* changed_out);
+int cuadmm_op_copy(const double* src, int64_t n, double* dst_inout);
+int cuadmm_op_copy_multi(int count, const int64_t* nbytes, const void* const* src, void* const* dst_inout);
+int cuadmm_op_scale(double* v_inout, int64_t n, double s);
+int cuadmm_op_update_svec(int64_t n, double* X_inout, double* S_inout, double* C_inout, int zero, double x1, double x2, double s1, double s2);
+int cuadmm_op_update_cons(int m, double* b_inout, double* y_inout, const double* normA, int ymode, double cs_old, double ics_new);
+int cuadmm_op_scatter_scaled(int len, double* dst_inout, int n, const int* idx, const double* val, double s);
 /* Same with the factorisation on the GPU too: z <- S^-1 z for a symmetric S given by its lower triangle with
  * diagonal (CSR over k rows, host pointers), dense LDL^T without pivoting (what cuadmm_aat_create_split hands over). */
 int cuadmm_op_tail_factor_solve(const int64_t* row_ptr, const int* col, const double* val, int k, double* z_host, int nrhs);
