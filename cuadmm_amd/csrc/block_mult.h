@@ -1,14 +1,13 @@
-// W_k = M_k V_k for a list of blocks held as svec (cuadmm_block_multiply, cuadmm_op_block_mult): the layout of V and W, the task list and
-// the kernel (block_mult.hip).  DESIGN.md, "Blocks times factors".
+// W_k = M_k V_k for a list of blocks held as svec (cuadmm_block_multiply, cuadmm_op_block_mult): the task list and the kernel
+// (block_mult.hip).  DESIGN.md, "Blocks times factors"; factor_layout.h has the layout of V and W.
 //
 // For PSD block k of size n, first slot off_k, with r = ranks[k] columns of V_k:
 //   offd_it = sum_{j != i} s_ij V[j, t],   s_ij = v[off_k + max(i, j) (max(i, j) + 1) / 2 + min(i, j)]   (the raw svec slots)
 //   W[i, t] = sign * fma(kInvSqrt2, offd_it, s_ii * V[i, t])
 // The off-diagonal slots enter the sum as they lie; the 1 / sqrt(2) they carry is taken out once per output by that fma (n r scalings
-// instead of n^2), with the projection kernels' rounded constant (psd_device.h: kSqrt2Inv, the same double).  V and W are laid out as
-// cuadmm_lowrank's L_out for the given rmax: block k at the prefix sum of n_j min(n_j, rmax) over the PSD blocks before it, column by
-// column, n_k doubles per column; unconstrained blocks occupy nothing and are not read.  Columns >= r of V are never read (they may hold
-// NaN) and the kernel writes nothing there (r = 0: nothing at all): the host puts + 0.0 into those entries of W.
+// instead of n^2), with the projection kernels' rounded constant (psd_device.h: kSqrt2Inv, the same double).  Unconstrained blocks are not read.
+// Columns >= r of V are never read (they may hold NaN) and the kernel writes nothing there (r = 0: nothing at all): the host puts + 0.0
+// into those entries of W.
 //
 // Arithmetic: every size takes the fp64 matrix cores.  One wavefront owns a panel of 16 rows of W and walks K = n in steps of 4 on
 // v_mfma_f64_16x16x4_f64: the part j < i of its rows is read along the packed rows, the part j > i from the rows below (the transposed
@@ -38,9 +37,9 @@ struct BmTask { int k, p; };
 
 inline int bm_panels(int n) { return (n + kBmPanel - 1) / kBmPanel; }
 
-// The wavefront slots (a multiple of 4) for the PSD blocks of blk, and loff (nblk + 1): first double of block k's V_k / W_k for this
-// rmax.  First the blocks of several panels, the largest first, each padded to whole workgroups (a workgroup holds panels of one
-// block), then the blocks of one panel, four to a workgroup.  Host only.
+// The wavefront slots (a multiple of 4) for the PSD blocks of blk; they depend on the block sizes alone.  First the blocks of several
+// panels, the largest first, each padded to whole workgroups (a workgroup holds panels of one block), then the blocks of one panel, four
+// to a workgroup.  loff (may be null): factor_offsets' for this rmax.  Host only.
 int bm_build_tasks(int nblk, const int* blk, int rmax, std::vector<BmTask>* tasks, std::vector<long long>* loff);
 
 // One launch over nslots wavefront slots (device list).  v: the svec vector read; V, W, loff, ranks: the two factor buffers, their

@@ -1,5 +1,5 @@
-// W_k = M_k V_k per block on the fp64 matrix cores, M_k read as it lies in an svec vector: block_mult.h has the layout, the task list and
-// the rounding contract, DESIGN.md, "Blocks times factors", the sizes and what was measured.
+// W_k = M_k V_k per block on the fp64 matrix cores, M_k read as it lies in an svec vector: block_mult.h has the task list and the
+// rounding contract, factor_layout.h the layout of V and W, DESIGN.md, "Blocks times factors", the sizes and what was measured.
 //
 // One wavefront owns 16 rows of W.  v_mfma_f64_16x16x4_f64: lane l feeds A[i = l & 15][k = l >> 4] and B[k = l >> 4][j = l & 15] and holds
 // D[row = (l >> 4) + 4 reg][col = l & 15].  A is the panel's 16 x 4 piece of M (raw slots, the diagonal lane 0.0), B the 4 x 16 piece of V.
@@ -10,6 +10,7 @@
 #include <algorithm>
 
 #include "block_mult.h"
+#include "factor_layout.h"
 #include "device_util.h"
 
 namespace cuadmm {
@@ -69,17 +70,11 @@ __global__ __launch_bounds__(256) void block_mult_kernel(const BmTask* __restric
 }  // namespace
 
 int bm_build_tasks(int nblk, const int* blk, int rmax, std::vector<BmTask>* tasks, std::vector<long long>* loff) {
-  if (nblk < 0 || (nblk > 0 && !blk) || rmax < 1 || rmax > kMaxBlockSize || !tasks || !loff) {
-    set_error("block_mult: invalid argument");
-    return CUADMM_ERR_INVALID;
-  }
+  std::vector<long long> own;
+  if (!tasks) { set_error("block_mult: invalid argument"); return CUADMM_ERR_INVALID; }
+  int rc = factor_offsets("block_mult", nblk, blk, rmax, loff ? loff : &own);
+  if (rc) return rc;
   tasks->clear();
-  loff->assign((size_t)nblk + 1, 0);
-  for (int k = 0; k < nblk; ++k) {
-    const int n = blk[k];
-    if (n == 0 || n > kMaxBlockSize) { set_error("block_mult: block %d has size %d", k, n); return CUADMM_ERR_INVALID; }
-    (*loff)[k + 1] = (*loff)[k] + (n > 0 ? (long long)n * (n < rmax ? n : rmax) : 0);
-  }
   std::vector<int> big;
   for (int k = 0; k < nblk; ++k)
     if (blk[k] > kBmPanel) big.push_back(k);

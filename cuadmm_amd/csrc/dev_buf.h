@@ -22,6 +22,7 @@ struct DevBuf {
     CUADMM_HIP_TRY(hipMalloc(&p, sizeof(T) * count));
     return CUADMM_OK;
   }
+  int grow(size_t count) { return n < count ? alloc(count) : CUADMM_OK; }      // at least count elements; a larger buffer loses its contents
   int upload(const T* h, size_t count) {
     if (count == 0) return CUADMM_OK;
     return staged_h2d(p, h, sizeof(T) * count);   // never hipMemcpy on caller / vector memory (staging.hip)

@@ -393,9 +393,7 @@ int cuadmm_solver::lm_run(int which, int steps, double o[8], double* per_block) 
   o[2] = std::max(0.0, -o[0]) / (which == 0 ? norm_borg : norm_Corg);
   o[3] = NAN;
   if (bound) {
-    double by = 0;
-    for (int j = 0; j < kBrSlots; ++j) by += h[kLmOut * (size_t)nb + j];
-    o[3] = by * objscale - pen;
+    o[3] = slot_sum(h + kLmOut * (size_t)nb) * objscale - pen;
   }
   o[4] = (double)unrefined; o[5] = (double)at_floor;
   o[6] = ms;
@@ -451,13 +449,13 @@ int cuadmm_solver::lr_run(int which, double tol, double o[8], double* per_block,
 // ------------------------------------------------------------------------------------------
 // Blocks times factors (cuadmm_block_multiply): DESIGN.md, "Blocks times factors"
 // ------------------------------------------------------------------------------------------
-// task list, events and buffers on first use; offsets and larger buffers when rmax changes; for which = 2 the y vector and
-// the auxiliary projector's vectors
+// the factor layout for this rmax; task list and events on first use, larger buffers when the layout grew; for which = 2 the y vector
+// and the auxiliary projector's vectors
 int cuadmm_solver::bm_prepare(int which, int rmax) {
   int rc;
   const int nb = (int)blk_local.size();
   if (!btasks.built && (rc = btasks.build(blk_local.data(), nb, nullptr))) return rc;
-  if ((rc = bm.prepare(blk_local.data(), nb, rmax))) return rc;
+  if ((rc = fl.prepare(blk_local.data(), nb, rmax)) || (rc = bm.prepare(fl, blk_local.data()))) return rc;
   if (which != 2) return CUADMM_OK;
   if (!bm.ybuf.p && (rc = bm.ybuf.alloc((size_t)std::max(m, 1)))) return rc;
   return aux.ensure(*this);
@@ -474,18 +472,18 @@ int cuadmm_solver::bm_run(int which, const double* V, const int* ranks, double* 
   const int nb = (int)blk_local.size();
   const double* v = which == 0 ? X.p : S.p;
   double sign = 1.0, unit = pending_unscale ? (which == 0 ? bscale : Cscale) : 1.0;
-  if ((rc = bm.stage(V, ranks))) return rc;
+  if ((rc = fl.stage(bm.Vbuf, V)) || (rc = fl.stage_ranks(ranks))) return rc;
   CUADMM_HIP_TRY(hipEventRecord(bm.ev[0], st));
   if (which == 2) {
     if ((rc = launch_aty_xb(false, L, At_rp.p, At_ci.p, At_v.p, bm.ybuf.p, C.p, X.p, 1.0, aux.in.p, nullptr, st, &At_long))) return rc;
     v = aux.in.p; sign = -1.0; unit = Cscale;
   }
-  if ((rc = bm.run(v, sign, btasks.off.p, btasks.blk.p, st))) return rc;
+  if ((rc = bm.run(fl, v, sign, btasks.off.p, btasks.blk.p, st))) return rc;
   CUADMM_HIP_TRY(hipEventRecord(bm.ev[1], st));
   CUADMM_HIP_TRY(hipStreamSynchronize(st));
   const float ms = event_ms(bm.ev[0], bm.ev[1]);
   bm.calls++;
-  if ((rc = bm.fetch(blk_local.data(), ranks, unit, W_out))) return rc;
+  if ((rc = bm.fetch(fl, blk_local.data(), ranks, unit, W_out))) return rc;
   double sq_all = 0, dot_all = 0, best = 0, blocks = 0, rank_sum = 0;
   int arg = -1;
   for (int k = 0; k < nb; ++k) {
@@ -493,7 +491,7 @@ int cuadmm_solver::bm_run(int which, const double* V, const int* ranks, double* 
     double sq = 0, dot = 0, vsq = 0;
     if (n > 0) {
 #pragma clang fp contract(off)
-      const double *w = W_out + bm.loff[k], *x = V ? V + bm.loff[k] : nullptr;
+      const double *w = W_out + fl.loff[k], *x = V ? V + fl.loff[k] : nullptr;
       for (size_t e = 0, used = (size_t)n * (size_t)ranks[k]; e < used; ++e) {
         const double ww = w[e] * w[e], vw = x[e] * w[e], vv = x[e] * x[e];
         sq = sq + ww; dot = dot + vw; vsq = vsq + vv;
@@ -510,27 +508,29 @@ int cuadmm_solver::bm_run(int which, const double* V, const int* ranks, double* 
   }
   o[0] = std::sqrt(sq_all); o[1] = dot_all; o[2] = (double)arg; o[3] = best; o[4] = blocks; o[5] = rank_sum;
   o[6] = ms;
-  o[7] = bm.bytes() + btasks.bytes() + (bm.ybuf.p ? aux.bytes() : 0.0);
+  o[7] = bm.bytes() + fl.bytes() + btasks.bytes() + (bm.ybuf.p ? aux.bytes() : 0.0);
   return CUADMM_OK;
 }
 
 // ------------------------------------------------------------------------------------------
 // Value and gradient at factors (cuadmm_lowrank_grad): DESIGN.md, "Value and gradient at factors"
 // ------------------------------------------------------------------------------------------
-// the two factor plans for this rmax, the plan's own vectors on first use; the column norms (where the engine keeps none on the device)
+// the factor layout for this rmax and the two kernels' plans on it, the plan's own vectors on first use; the column norms (where the engine keeps none on the device)
 // and the auxiliary projector's vectors and b on every call
 int cuadmm_solver::lg_prepare(int rmax) {
   int rc;
   const int nb = (int)blk_local.size();
   if (!btasks.built && (rc = btasks.build(blk_local.data(), nb, nullptr))) return rc;
-  if ((rc = bm.prepare(blk_local.data(), nb, rmax)) || (rc = lo.prepare(blk_local.data(), nb, rmax)) || (rc = lg.prepare(L, m, nb, btasks.nchunk, !normA_d.p))) return rc;
+  if ((rc = fl.prepare(blk_local.data(), nb, rmax)) || (rc = bm.prepare(fl, blk_local.data())) || (rc = lo.prepare(fl, blk_local.data())) ||
+      (rc = lg.prepare(L, m, nb, btasks.nchunk, !normA_d.p)))
+    return rc;
   if (lg.normA.p && m > 0 && (rc = staged_h2d(lg.normA.p, normA_p.data(), sizeof(double) * (size_t)m, st))) return rc;
   return aux.ensure(*this);
 }
 
 // The chain at the scaled y in lg.ybuf.  x is assembled in lg.xv in the units X lies in (X = ux xv: ux = bscale behind a solve, else 1): a
 // device copy of X, then svec(L_k L_k') over its PSD blocks from the factors in those units -- the caller's own, as the block product's V
-// holds them, where ux = 1, else a second staged copy times fl(1 / sqrt(ux)).  Then A x, the multiplier pass, M = A'ytilde - C into the
+// holds them, where ux = 1, else a second staged copy through scale_factors.  Then A x, the multiplier pass, M = A'ytilde - C into the
 // auxiliary projector's input vector (S^ = -Cscale M), W = -M_k L_k with the caller's L (the launch and the unit of
 // cuadmm_block_multiply(2): sigma = 0 gives its bits) and the per-block terms.  G = 2 (Cscale W), the doubling exact.  The sums over G and L
 // are plain double sums in index order, as in bm_run.  Reads X, y, A, A', b, C; writes only the plans' own buffers and that input vector.
@@ -539,27 +539,22 @@ int cuadmm_solver::lg_run(const double* Lf, const int* ranks, double sigma, doub
   const int nb = (int)blk_local.size();
   const double ux = pending_unscale ? bscale : 1.0;
   const double* const normA_dev = normA_d.p ? normA_d.p : lg.normA.p;
-  if ((rc = bm.stage(Lf, ranks))) return rc;
+  if ((rc = fl.stage(bm.Vbuf, Lf)) || (rc = fl.stage_ranks(ranks))) return rc;
   const double* Lx = bm.Vbuf.p;
   if (ux != 1.0 && Lf) {
-    const double root = 1 / std::sqrt(ux);
-    std::vector<double>& tmp = lg.h_stage;      // (kept by the plan: a caller's optimiser makes this call in a loop)
-    tmp.assign((size_t)lo.loff.back(), 0.0);
-    for (int k = 0; k < nb; ++k)                // the columns that are read; the others travel as zeros
-      for (size_t e = (size_t)lo.loff[k], end = e + (blk_local[k] > 0 ? (size_t)blk_local[k] * (size_t)ranks[k] : 0); e < end; ++e) tmp[e] = Lf[e] * root;
-    double bytes = 0;
-    if ((rc = lo.stage(tmp.data(), ranks, &bytes))) return rc;
+    scale_factors(fl, blk_local.data(), ranks, Lf, ux, lg.h_stage);      // (kept by the plan: a caller's optimiser makes this call in a loop)
+    if ((rc = fl.stage(lo.Lbuf, lg.h_stage.data()))) return rc;
     Lx = lo.Lbuf.p;
   }
   CUADMM_HIP_TRY(hipEventRecord(lg.ev[0], st));
   CUADMM_HIP_TRY(hipMemcpyAsync(lg.xv.p, X.p, sizeof(double) * (size_t)L, hipMemcpyDeviceToDevice, st));
-  if ((rc = launch_block_outer((int)lo.tasks.size(), lo.tasks_d.p, Lx, bm.loff_d.p, bm.ranks_d.p, btasks.off.p, btasks.blk.p, lg.xv.p, st))) return rc;
+  if ((rc = lo.run(fl, Lx, btasks.off.p, btasks.blk.p, lg.xv.p, st))) return rc;
   if (m > 0 && (rc = launch_spmv_rows(m, A_avg_nnz, A_rp.p, A_ci.p, A_v.p, lg.xv.p, S.p, C.p, lg.ax.p, nullptr, st, &A_long))) return rc;
   if ((rc = launch_lrg_multiplier(m, lg.ax.p, aux.b_dev(*this), normA_dev, lg.ybuf.p, pending_unscale ? 1.0 : 1 / bscale, bscale, 1 / Cscale, sigma, lg.ytilde.p,
                                   lg.r.p, lg.part.p, st)))
     return rc;
   if ((rc = launch_aty_xb(false, L, At_rp.p, At_ci.p, At_v.p, lg.ytilde.p, C.p, X.p, 1.0, aux.in.p, nullptr, st, &At_long))) return rc;
-  if ((rc = bm.run(aux.in.p, -1.0, btasks.off.p, btasks.blk.p, st))) return rc;
+  if ((rc = bm.run(fl, aux.in.p, -1.0, btasks.off.p, btasks.blk.p, st))) return rc;
   if ((rc = launch_lrg_block_terms(C.p, lg.xv.p, aux.in.p, btasks.view(), lg.cpart.p, lg.sums.p, st))) return rc;
   CUADMM_HIP_TRY(hipEventRecord(lg.ev[1], st));
   CUADMM_HIP_TRY(hipStreamSynchronize(st));
@@ -567,20 +562,19 @@ int cuadmm_solver::lg_run(const double* Lf, const int* ranks, double sigma, doub
   // --- back to the host and to the caller's units (the host scratch is the plan's and is kept)
   std::vector<double>& h = lg.h_back;
   h.resize((size_t)std::max(m, 1) + 2 * (size_t)kBrSlots + kLgSums * (size_t)nb);
-  if (!G_out) { lg.h_G.resize((size_t)bm.loff.back() + 1); G_out = lg.h_G.data(); }
-  if ((rc = bm.fetch(blk_local.data(), ranks, Cscale, G_out))) return rc;
+  if (!G_out) { lg.h_G.resize(fl.count() + 1); G_out = lg.h_G.data(); }
+  if ((rc = bm.fetch(fl, blk_local.data(), ranks, Cscale, G_out))) return rc;
   double *const rh = h.data(), *const part = rh + std::max(m, 1), *const sums = part + 2 * kBrSlots;
   if (m > 0 && (rc = staged_d2h(rh, lg.r.p, sizeof(double) * (size_t)m, st))) return rc;
   if ((rc = staged_d2h(part, lg.part.p, sizeof(double) * 2 * kBrSlots, st))) return rc;
   if (nb > 0 && (rc = staged_d2h(sums, lg.sums.p, sizeof(double) * kLgSums * (size_t)nb, st))) return rc;
-  for (int i = 0; r_out && i < m; ++i) r_out[perm[i]] = rh[i];
+  unpermute(perm, m, rh, r_out);
   if (Shat_out) {
     if ((rc = staged_d2h(Shat_out, aux.in.p, sizeof(double) * (size_t)L, st))) return rc;
     for (long long i = 0; i < L; ++i) Shat_out[i] = -(Shat_out[i] * Cscale);
   }
-  double yr = 0, rn2 = 0, cx = 0, sq_all = 0, dot_all = 0;
-  for (int j = 0; j < kBrSlots; ++j) { yr += part[j]; rn2 += part[kBrSlots + j]; }
-  yr *= objscale;
+  double cx = 0, sq_all = 0, dot_all = 0;
+  const double yr = slot_sum(part) * objscale, rn2 = slot_sum(part + kBrSlots);
   const double cxu = Cscale * ux;
   for (int k = 0; k < nb; ++k) {
     const int n = blk_local[k];
@@ -588,8 +582,8 @@ int cuadmm_solver::lg_run(const double* Lf, const int* ranks, double sigma, doub
     double sq = 0, dot = 0, lsq = 0;
     if (n > 0) {
 #pragma clang fp contract(off)
-      double* g = G_out + bm.loff[k];
-      const double* x = Lf ? Lf + bm.loff[k] : nullptr;
+      double* g = G_out + fl.loff[k];
+      const double* x = Lf ? Lf + fl.loff[k] : nullptr;
       for (size_t e = 0, used = (size_t)n * (size_t)ranks[k]; e < used; ++e) {
         g[e] = 2.0 * g[e];
         const double gg = g[e] * g[e], lg_ = x[e] * g[e], ll = x[e] * x[e];
@@ -605,27 +599,28 @@ int cuadmm_solver::lg_run(const double* Lf, const int* ranks, double sigma, doub
   }
   o[0] = cx - yr + (0.5 * sigma) * rn2; o[1] = cx; o[2] = yr; o[3] = std::sqrt(rn2); o[4] = std::sqrt(sq_all); o[5] = dot_all;
   o[6] = ms;
-  o[7] = lg.bytes() + bm.bytes() + 8.0 * (double)(lo.Lbuf.n + lo.loff_d.n) + btasks.bytes() + aux.bytes();
+  o[7] = lg.bytes() + bm.bytes() + lo.bytes() + fl.bytes() + btasks.bytes() + aux.bytes();
   return CUADMM_OK;
 }
 
 // ------------------------------------------------------------------------------------------
 // The quartic along a line in factor space (cuadmm_lowrank_line): DESIGN.md, "Line search along factor steps"
 // ------------------------------------------------------------------------------------------
-// the outer product's plan for this rmax, the plan's own vectors on first use and a device D that grows with rmax; the column norms
+// the factor layout for this rmax and the outer product's plan on it, the plan's own vectors on first use and a device D that grows with it; the column norms
 // (where the engine keeps none on the device) and the auxiliary projector's b on every call
 int cuadmm_solver::ll_prepare(int rmax) {
   int rc;
   const int nb = (int)blk_local.size();
   if (!btasks.built && (rc = btasks.build(blk_local.data(), nb, nullptr))) return rc;
-  if ((rc = lo.prepare(blk_local.data(), nb, rmax)) || (rc = ll.prepare(L, m, nb, btasks.nchunk, !normA_d.p, st))) return rc;
-  if (ll.Dbuf.n < (size_t)lo.loff.back() + 1 && (rc = ll.Dbuf.alloc((size_t)lo.loff.back() + 1))) return rc;
+  if ((rc = fl.prepare(blk_local.data(), nb, rmax)) || (rc = lo.prepare(fl, blk_local.data())) || (rc = ll.prepare(L, m, nb, btasks.nchunk, !normA_d.p, st)) ||
+      (rc = ll.Dbuf.grow(fl.count() + 1)))
+    return rc;
   if (ll.normA.p && m > 0 && (rc = staged_h2d(ll.normA.p, normA_p.data(), sizeof(double) * (size_t)m, st))) return rc;
   return aux.ensure(*this);
 }
 
-// The chain at the scaled y in ll.ybuf.  L and D are staged in the units X lies in (X = ux x: ux = bscale behind a solve, else 1), times
-// fl(1 / sqrt(ux)) where ux != 1 exactly as lg_run stages L, so that x0 and with it r0 carry lg_run's bits.  Then the device copy of X into
+// The chain at the scaled y in ll.ybuf.  L and D are staged in the units X lies in (X = ux x: ux = bscale behind a solve, else 1), through
+// scale_factors where ux != 1 as lg_run stages L, so that x0 and with it r0 carry lg_run's bits.  Then the device copy of X into
 // ll.x0, the three outer products, three A x, the streaming pass and the per-block terms; the coefficients on the host in the order
 // lowrank_line.h states.  Reads X, A, b, C; writes only the plans' own buffers.  Every output of the caller is written behind the last
 // refusal.
@@ -638,22 +633,14 @@ int cuadmm_solver::ll_run(const double* Lf, const double* Df, const int* ranks, 
   const double* const normA_dev = normA_d.p ? normA_d.p : ll.normA.p;
   const double *Ls = Lf, *Ds = Df;
   if (ux != 1.0 && Lf) {
-    const double root = 1 / std::sqrt(ux);
-    ll.h_L.assign((size_t)lo.loff.back(), 0.0);
-    ll.h_D.assign((size_t)lo.loff.back(), 0.0);
-    for (int k = 0; k < nb; ++k)                // the columns that are read; the others travel as zeros
-      for (size_t e = (size_t)lo.loff[k], end = e + (blk_local[k] > 0 ? (size_t)blk_local[k] * (size_t)ranks[k] : 0); e < end; ++e) {
-        ll.h_L[e] = Lf[e] * root;
-        ll.h_D[e] = Df[e] * root;
-      }
+    scale_factors(fl, blk_local.data(), ranks, Lf, ux, ll.h_L);
+    scale_factors(fl, blk_local.data(), ranks, Df, ux, ll.h_D);
     Ls = ll.h_L.data(); Ds = ll.h_D.data();
   }
-  double bytes = 0;
-  if ((rc = lo.stage(Ls, ranks, &bytes))) return rc;
-  if (Ds && lo.loff.back() > 0 && (rc = ll.Dbuf.upload(Ds, (size_t)lo.loff.back()))) return rc;
+  if ((rc = fl.stage(lo.Lbuf, Ls)) || (rc = fl.stage(ll.Dbuf, Ds)) || (rc = fl.stage_ranks(ranks))) return rc;
   CUADMM_HIP_TRY(hipEventRecord(ll.ev[0], st));
   CUADMM_HIP_TRY(hipMemcpyAsync(ll.x0.p, X.p, sizeof(double) * (size_t)L, hipMemcpyDeviceToDevice, st));
-  if ((rc = launch_block_outer3((int)lo.tasks.size(), lo.tasks_d.p, lo.Lbuf.p, ll.Dbuf.p, lo.loff_d.p, lo.ranks_d.p, btasks.off.p, btasks.blk.p, ll.x0.p, ll.x1.p,
+  if ((rc = launch_block_outer3((int)lo.tasks.size(), lo.tasks_d.p, lo.Lbuf.p, ll.Dbuf.p, fl.loff_d.p, fl.ranks_d.p, btasks.off.p, btasks.blk.p, ll.x0.p, ll.x1.p,
                                 ll.x2.p, st)))
     return rc;
   if (m > 0) {
@@ -680,10 +667,7 @@ int cuadmm_solver::ll_run(const double* Lf, const double* Df, const int* ranks, 
   if ((rc = staged_d2h(part, ll.part.p, sizeof(double) * kLlParts * (size_t)kBrSlots, st))) return rc;
   if (nb > 0 && (rc = staged_d2h(sums, ll.sums.p, sizeof(double) * kLlSums * (size_t)nb, st))) return rc;
   double sm[kLlParts], cx[kLlSums] = {0, 0, 0};
-  for (int j = 0; j < kLlParts; ++j) {
-    sm[j] = 0;
-    for (int i = 0; i < kBrSlots; ++i) sm[j] = sm[j] + part[(size_t)j * kBrSlots + i];
-  }
+  for (int j = 0; j < kLlParts; ++j) sm[j] = slot_sum(part + (size_t)j * kBrSlots);
   const double cxu = Cscale * ux;
   for (int k = 0; k < nb; ++k)
     for (int j = 0; j < kLlSums; ++j) cx[j] = cx[j] + sums[kLlSums * (size_t)k + j] * cxu;
@@ -702,11 +686,9 @@ int cuadmm_solver::ll_run(const double* Lf, const double* Df, const int* ranks, 
   }
   // --- nothing is refused from here on
   for (int j = 0; j < 5; ++j) coef5[j] = c[j];
-  for (int i = 0; i < m; ++i) {
-    if (r_out) r_out[perm[i]] = rh[i];
-    if (p_out) p_out[perm[i]] = ph[i];
-    if (q_out) q_out[perm[i]] = qh[i];
-  }
+  unpermute(perm, m, rh, r_out);
+  unpermute(perm, m, ph, p_out);
+  unpermute(perm, m, qh, q_out);
   for (int k = 0; per_block && k < nb; ++k) {
     double* w = per_block + 4 * (size_t)k;
     for (int j = 0; j < kLlSums; ++j) w[j] = sums[kLlSums * (size_t)k + j] * cxu;
@@ -714,7 +696,7 @@ int cuadmm_solver::ll_run(const double* Lf, const double* Df, const int* ranks, 
   }
   o[0] = q4[0]; o[1] = q4[1]; o[2] = q4[2]; o[3] = std::sqrt(sm[5]); o[4] = std::sqrt(sm[8]); o[5] = q4[3];
   o[6] = ms;
-  o[7] = ll.bytes() + 8.0 * (double)(lo.Lbuf.n + lo.loff_d.n + lo.tasks_d.n) + 4.0 * (double)lo.ranks_d.n + btasks.bytes() + aux.bytes();
+  o[7] = ll.bytes() + lo.bytes() + fl.bytes() + btasks.bytes() + aux.bytes();
   return CUADMM_OK;
 }
 
@@ -833,10 +815,10 @@ int cuadmm_lambda_min(cuadmm_solver* s, int which, int steps, double o[8], doubl
 int cuadmm_lowrank_size(const cuadmm_solver* s, int rmax, long long* count_out) {
   if (!s || !s->initialised || !count_out) { set_error("lowrank_size: solver not initialised or null argument"); return CUADMM_ERR_INVALID; }
   if (rmax < 1 || rmax > kMaxBlockSize) { set_error("lowrank_size: rmax = %d, allowed are 1 to %d", rmax, kMaxBlockSize); return CUADMM_ERR_INVALID; }
-  long long c = 0;
-  for (int n : s->blk_local)
-    if (n > 0) c += (long long)n * std::min(n, rmax);
-  *count_out = c;
+  std::vector<long long> loff;
+  int rc = factor_offsets("lowrank_size", (int)s->blk_local.size(), s->blk_local.data(), rmax, &loff);
+  if (rc) return rc;
+  *count_out = loff.back();
   return CUADMM_OK;
 }
 int cuadmm_lowrank(cuadmm_solver* s, int which, double tol, int rmax, double o[8], double* per_block, double* L_out, int* piv_out) {
@@ -854,17 +836,7 @@ int cuadmm_block_multiply(cuadmm_solver* s, int which, const double* V, const in
   if (which < 0 || which > 2) { set_error("block_multiply: which = %d (0: X, 1: S, 2: C - A'y)", which); return CUADMM_ERR_INVALID; }
   if (rmax < 1 || rmax > kMaxBlockSize) { set_error("block_multiply: rmax = %d, allowed are 1 to %d", rmax, kMaxBlockSize); return CUADMM_ERR_INVALID; }
   if (!W_out || !ranks) { set_error("block_multiply: W_out or ranks is null"); return CUADMM_ERR_INVALID; }
-  long long at = 0;                      // first double of block k's V_k
-  for (int k = 0; k < (int)s->blk_local.size(); ++k) {
-    const int n = s->blk_local[k];
-    if (n <= 0) continue;
-    const int rc_k = std::min(n, rmax), r = ranks[k];
-    if (r < 0 || r > rc_k) { set_error("block_multiply: block %d of size %d has rank %d, allowed are 0 to %d", k, n, r, rc_k); return CUADMM_ERR_INVALID; }
-    if (r > 0 && !V) { set_error("block_multiply: V is null and block %d has rank %d", k, r); return CUADMM_ERR_INVALID; }
-    for (long long e = at, end = at + (long long)n * r; e < end; ++e)
-      if (!std::isfinite(V[e])) { set_error("block_multiply: block %d, row %lld of column %lld is not finite", k, (e - at) % n, (e - at) / n); return CUADMM_ERR_INVALID; }
-    at += (long long)n * rc_k;
-  }
+  if ((rc = check_factors("block_multiply", (int)s->blk_local.size(), s->blk_local.data(), ranks, rmax, "V", V, nullptr, nullptr, nullptr, nullptr))) return rc;
   if ((rc = s->bm_prepare(which, rmax)) || (which == 2 && (rc = s->stage_scaled_y(s->bm.ybuf.p, nullptr)))) return rc;
   return s->bm_run(which, V, ranks, W_out, o, per_block);
 }
@@ -875,17 +847,7 @@ int cuadmm_lowrank_grad(cuadmm_solver* s, const double* Lf, const int* ranks, in
   if (!(sigma >= 0.0) || !std::isfinite(sigma)) { set_error("lowrank_grad: sigma = %g, allowed is a finite sigma >= 0", sigma); return CUADMM_ERR_INVALID; }
   if (rmax < 1 || rmax > kMaxBlockSize) { set_error("lowrank_grad: rmax = %d, allowed are 1 to %d", rmax, kMaxBlockSize); return CUADMM_ERR_INVALID; }
   if (!ranks) { set_error("lowrank_grad: ranks is null"); return CUADMM_ERR_INVALID; }
-  long long at = 0;                      // first double of block k's L_k
-  for (int k = 0; k < (int)s->blk_local.size(); ++k) {
-    const int n = s->blk_local[k];
-    if (n <= 0) continue;
-    const int rc_k = std::min(n, rmax), r = ranks[k];
-    if (r < 0 || r > rc_k) { set_error("lowrank_grad: block %d of size %d has rank %d, allowed are 0 to %d", k, n, r, rc_k); return CUADMM_ERR_INVALID; }
-    if (r > 0 && !Lf) { set_error("lowrank_grad: L is null and block %d has rank %d", k, r); return CUADMM_ERR_INVALID; }
-    for (long long e = at, end = at + (long long)n * r; e < end; ++e)
-      if (!std::isfinite(Lf[e])) { set_error("lowrank_grad: block %d, row %lld of column %lld is not finite", k, (e - at) % n, (e - at) / n); return CUADMM_ERR_INVALID; }
-    at += (long long)n * rc_k;
-  }
+  if ((rc = check_factors("lowrank_grad", (int)s->blk_local.size(), s->blk_local.data(), ranks, rmax, "L", Lf, nullptr, nullptr, nullptr, nullptr))) return rc;
   for (int i = 0; y && i < s->m; ++i)
     if (!std::isfinite(y[i])) { set_error("lowrank_grad: y[%d] is not finite", i); return CUADMM_ERR_INVALID; }
   if ((rc = s->lg_prepare(rmax)) || (rc = s->stage_scaled_y(s->lg.ybuf.p, y))) return rc;
@@ -900,20 +862,7 @@ int cuadmm_lowrank_line(cuadmm_solver* s, const double* Lf, const double* Df, co
   if (std::isnan(t_max)) { set_error("lowrank_line: t_max is not a number"); return CUADMM_ERR_INVALID; }
   if (rmax < 1 || rmax > kMaxBlockSize) { set_error("lowrank_line: rmax = %d, allowed are 1 to %d", rmax, kMaxBlockSize); return CUADMM_ERR_INVALID; }
   if (!ranks) { set_error("lowrank_line: ranks is null"); return CUADMM_ERR_INVALID; }
-  long long at = 0;                      // first double of block k's L_k and D_k
-  for (int k = 0; k < (int)s->blk_local.size(); ++k) {
-    const int n = s->blk_local[k];
-    if (n <= 0) continue;
-    const int rc_k = std::min(n, rmax), r = ranks[k];
-    if (r < 0 || r > rc_k) { set_error("lowrank_line: block %d of size %d has rank %d, allowed are 0 to %d", k, n, r, rc_k); return CUADMM_ERR_INVALID; }
-    if (r > 0 && (!Lf || !Df)) { set_error("lowrank_line: %s is null and block %d has rank %d", Lf ? "D" : "L", k, r); return CUADMM_ERR_INVALID; }
-    for (long long e = at, end = at + (long long)n * r; e < end; ++e)
-      if (!std::isfinite(Lf[e]) || !std::isfinite(Df[e])) {
-        set_error("lowrank_line: block %d, row %lld of column %lld of %s is not finite", k, (e - at) % n, (e - at) / n, std::isfinite(Lf[e]) ? "D" : "L");
-        return CUADMM_ERR_INVALID;
-      }
-    at += (long long)n * rc_k;
-  }
+  if ((rc = check_factors("lowrank_line", (int)s->blk_local.size(), s->blk_local.data(), ranks, rmax, "L", Lf, "D", Df, nullptr, nullptr))) return rc;
   for (int i = 0; y && i < s->m; ++i)
     if (!std::isfinite(y[i])) { set_error("lowrank_line: y[%d] is not finite", i); return CUADMM_ERR_INVALID; }
   if (!Lf || !Df) Lf = Df = nullptr;     // every rank is 0: neither is read

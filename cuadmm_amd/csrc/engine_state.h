@@ -375,6 +375,7 @@ struct cuadmm_solver {
   int lr_prepare(int rmax);
   int lr_run(int which, double tol, double out8[8], double* per_block, double* L_out, int* piv_out);
 
+  FactorLayoutDev fl;          // (report_plans.h): the callers' factor layout of the four calls below, prepared by each for its rmax
   LoPlan lo;                   // (report_plans.h): cuadmm_set_lowrank
 
   BmPlan bm;                   // (report_plans.h): cuadmm_block_multiply

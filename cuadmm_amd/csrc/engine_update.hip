@@ -49,31 +49,18 @@ int cuadmm_set_lowrank(cuadmm_solver* s, int which, const double* L, const int* 
   }
   const int nb = (int)s->blk_local.size();
   double blocks = 0, rank_sum = 0;
-  {
-    long long at = 0;                    // first double of block k's factor
-    for (int k = 0; k < nb; ++k) {
-      const int n = s->blk_local[k];
-      if (n <= 0) continue;
-      const int rc_k = std::min(n, rmax), r = ranks[k];
-      if (r < 0 || r > rc_k) { set_error("set_lowrank: block %d of size %d has rank %d, allowed are 0 to %d", k, n, r, rc_k); return CUADMM_ERR_INVALID; }
-      if (r > 0 && !L) { set_error("set_lowrank: L is null and block %d has rank %d", k, r); return CUADMM_ERR_INVALID; }
-      for (long long e = at, end = at + (long long)n * r; e < end; ++e)
-        if (!std::isfinite(L[e])) { set_error("set_lowrank: block %d, row %lld of column %lld is not finite", k, (e - at) % n, (e - at) / n); return CUADMM_ERR_INVALID; }
-      at += (long long)n * rc_k;
-      blocks += 1;
-      rank_sum += r;
-    }
-  }
-  int rc = check_device(s->device);
-  if (rc) return rc;
-  // the plan and the staged factors: buffers of the call's own
-  double bytes = 0;
+  int rc = check_factors("set_lowrank", nb, s->blk_local.data(), ranks, rmax, "L", L, nullptr, nullptr, &blocks, &rank_sum);
+  if (rc || (rc = check_device(s->device))) return rc;
+  // the layout, the plan and the staged factors: buffers of the low-rank calls' own
   if (!s->btasks.built && (rc = s->btasks.build(s->blk_local.data(), nb, nullptr))) return rc;
-  if ((rc = s->lo.prepare(s->blk_local.data(), nb, rmax)) || (rc = s->lo.stage(L, ranks, &bytes))) return rc;
+  if ((rc = s->fl.prepare(s->blk_local.data(), nb, rmax)) || (rc = s->lo.prepare(s->fl, s->blk_local.data())) || (rc = s->fl.stage(s->lo.Lbuf, L)) ||
+      (rc = s->fl.stage_ranks(ranks)))
+    return rc;
+  const double bytes = L ? 8.0 * (double)s->fl.count() : 0.0;
   // --- from here on the solver changes
   if ((rc = s->materialise())) return rc;       // the vectors NOT replaced must be in the caller's units too
   CUADMM_HIP_TRY(hipEventRecord(s->lo.ev[0], s->st));
-  if ((rc = s->lo.run(s->btasks.off.p, s->btasks.blk.p, which == 0 ? s->X.p : s->S.p, s->st))) return rc;
+  if ((rc = s->lo.run(s->fl, s->lo.Lbuf.p, s->btasks.off.p, s->btasks.blk.p, which == 0 ? s->X.p : s->S.p, s->st))) return rc;
   CUADMM_HIP_TRY(hipEventRecord(s->lo.ev[1], s->st));
   CUADMM_HIP_TRY(hipStreamSynchronize(s->st));
   if (sig > 0) s->sig = sig;

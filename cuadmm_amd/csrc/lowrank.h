@@ -29,9 +29,9 @@ struct LrClass {
   int nmax = 0;                           // largest size in the class: with rmax it sizes the dynamic LDS
 };
 // classes by size: <= 32 together with the unconstrained blocks (one wavefront), <= 128, <= 1024, the rest (a workgroup of 256 each; they
-// differ in the LDS a workgroup asks for, which sets how many share a CU).  loff[k]: first double of block k's L in the factor buffer, a PSD
-// block of size n holding n min(n, rmax) and an unconstrained one none; poff[k]: first int of its min(n, rmax) pivots in the device's
-// pivot buffer, which is kept dense (the caller's pivot array uses the factor's offsets).  nblk + 1 entries each.
+// differ in the LDS a workgroup asks for, which sets how many share a CU).  loff: factor_offsets' (factor_layout.h); poff[k]: first int of
+// block k's factor_cols pivots in the device's pivot buffer, which is kept dense (the caller's pivot array uses the factor's offsets).
+// nblk + 1 entries each.
 constexpr int kLrClasses = 4;
 int lr_build_classes(int nblk, const int* blk, int rmax, LrClass (&cls)[kLrClasses], std::vector<long long>* loff, std::vector<long long>* poff);
 

@@ -12,6 +12,7 @@
 #include <cmath>
 
 #include "lowrank.h"
+#include "factor_layout.h"
 #include "device_util.h"
 
 namespace cuadmm {
@@ -154,21 +155,19 @@ __global__ __launch_bounds__(NT) void lowrank_kernel(const int* __restrict__ lis
 }  // namespace
 
 int lr_build_classes(int nblk, const int* blk, int rmax, LrClass (&cls)[kLrClasses], std::vector<long long>* loff, std::vector<long long>* poff) {
-  if (nblk < 0 || (nblk > 0 && !blk) || rmax < 1 || rmax > kMaxBlockSize || !loff || !poff) { set_error("lowrank: invalid argument"); return CUADMM_ERR_INVALID; }
+  if (!loff || !poff) { set_error("lowrank: invalid argument"); return CUADMM_ERR_INVALID; }
+  int rc = factor_offsets("lowrank", nblk, blk, rmax, loff);
+  if (rc) return rc;
   static const int top[kLrClasses] = {kLrSmall, 128, 1024, kMaxBlockSize};
   for (auto& c : cls) { c.blocks.clear(); c.nmax = 0; }
-  loff->assign((size_t)nblk + 1, 0);
   poff->assign((size_t)nblk + 1, 0);
   for (int k = 0; k < nblk; ++k) {
     const int n = blk[k];
-    if (n > kMaxBlockSize) { set_error("lowrank: block %d has size %d", k, n); return CUADMM_ERR_INVALID; }
     int q = 0;
     while (n > top[q]) ++q;
     cls[q].blocks.push_back(k);
     if (n > cls[q].nmax) cls[q].nmax = n;
-    const long long rc = n > 0 ? (n < rmax ? n : rmax) : 0;
-    (*loff)[k + 1] = (*loff)[k] + rc * n;
-    (*poff)[k + 1] = (*poff)[k] + rc;
+    (*poff)[k + 1] = (*poff)[k] + (n > 0 ? factor_cols(n, rmax) : 0);
   }
   return CUADMM_OK;
 }

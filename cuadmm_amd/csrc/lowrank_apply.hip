@@ -1,5 +1,6 @@
-// svec(L_k L_k') per block on the fp64 matrix cores, written into an svec vector where the blocks lie: lowrank_apply.h has the layout, the
-// task list and the rounding contract, DESIGN.md, "Starting from low-rank factors", the sizes and what was measured.
+// svec(L_k L_k') per block on the fp64 matrix cores, written into an svec vector where the blocks lie: lowrank_apply.h has the task
+// list and the rounding contract, factor_layout.h the layout of L, DESIGN.md, "Starting from low-rank factors", the sizes and what
+// was measured.
 //
 // One wavefront forms one 16 x 16 tile at a time.  v_mfma_f64_16x16x4_f64: lane l feeds A[i = l & 15][k = l >> 4] and B[k = l >> 4][j = l & 15]
 // and holds D[row = (l >> 4) + 4 reg][col = l & 15], so a register is four rows of 16 consecutive svec slots (128 bytes each).  No LDS,
@@ -7,6 +8,7 @@
 #include <hip/hip_runtime.h>
 
 #include "lowrank_apply.h"
+#include "factor_layout.h"
 #include "device_util.h"
 
 namespace cuadmm {
@@ -26,11 +28,7 @@ __global__ __launch_bounds__(256) void block_outer_kernel(const LoTask* __restri
   double* x = v + off[t.k];
   const int r16 = lane & 15, kk = lane >> 4;
   for (int tile = t.t0; tile < t.t1; tile += t.step) {
-    // tile -> (ti, tj): the root in floating point, then at most a step either way
-    int ti = (int)((sqrt(8.0 * (double)tile + 1.0) - 1.0) * 0.5);
-    if ((ti + 1) * (ti + 2) / 2 <= tile) ++ti;
-    if (ti * (ti + 1) / 2 > tile) --ti;
-    const int tj = tile - ti * (ti + 1) / 2;
+    const int ti = lo_tile_row(tile), tj = tile - ti * (ti + 1) / 2;
     const int ia = kLoTile * ti + r16, ib = kLoTile * tj + r16;
     lo_v4f64 acc = lo_v4f64{0.0, 0.0, 0.0, 0.0};
     for (int k0 = 0; k0 < r; k0 += 4) {      // wave-uniform trip count
@@ -51,17 +49,11 @@ __global__ __launch_bounds__(256) void block_outer_kernel(const LoTask* __restri
 }  // namespace
 
 int lo_build_tasks(int nblk, const int* blk, int rmax, int split_from, std::vector<LoTask>* tasks, std::vector<long long>* loff) {
-  if (nblk < 0 || (nblk > 0 && !blk) || rmax < 1 || rmax > kMaxBlockSize || split_from <= kLoWaveMax || !tasks || !loff) {
-    set_error("block_outer: invalid argument");
-    return CUADMM_ERR_INVALID;
-  }
+  std::vector<long long> own;
+  if (split_from <= kLoWaveMax || !tasks) { set_error("block_outer: invalid argument"); return CUADMM_ERR_INVALID; }
+  int rc = factor_offsets("block_outer", nblk, blk, rmax, loff ? loff : &own);
+  if (rc) return rc;
   tasks->clear();
-  loff->assign((size_t)nblk + 1, 0);
-  for (int k = 0; k < nblk; ++k) {
-    const int n = blk[k];
-    if (n == 0 || n > kMaxBlockSize) { set_error("block_outer: block %d has size %d", k, n); return CUADMM_ERR_INVALID; }
-    (*loff)[k + 1] = (*loff)[k] + (n > 0 ? (long long)n * (n < rmax ? n : rmax) : 0);
-  }
   auto team = [&](int k, int t0, int t1) {   // one workgroup: its four wavefronts interleaved over [t0, t1)
     for (int w = 0; w < 4; ++w) tasks->push_back(LoTask{k, t0 + w, t1, 4});
   };

@@ -31,11 +31,7 @@ __global__ __launch_bounds__(256) void block_outer3_kernel(const LoTask* __restr
   const long long o = off[t.k];
   const int r16 = lane & 15, kk = lane >> 4;
   for (int tile = t.t0; tile < t.t1; tile += t.step) {
-    // tile -> (ti, tj): the root in floating point, then at most a step either way
-    int ti = (int)((sqrt(8.0 * (double)tile + 1.0) - 1.0) * 0.5);
-    if ((ti + 1) * (ti + 2) / 2 <= tile) ++ti;
-    if (ti * (ti + 1) / 2 > tile) --ti;
-    const int tj = tile - ti * (ti + 1) / 2;
+    const int ti = lo_tile_row(tile), tj = tile - ti * (ti + 1) / 2;
     const int ia = kLoTile * ti + r16, ib = kLoTile * tj + r16;
     ll_v4f64 acc0 = ll_v4f64{0.0, 0.0, 0.0, 0.0}, acc1 = acc0, acc2 = acc0;
     for (int k0 = 0; k0 < r; k0 += 4) {      // wave-uniform trip count

@@ -560,26 +560,35 @@ int cuadmm_op_block_lowrank(const double* svec_dev, const int* blk_vals, int mat
   return plan.fetch(1.0, per_block6_host, L_host, piv_host);
 }
 
-// the kernel of cuadmm_set_lowrank on a DEVICE svec vector whose blocks follow one another from slot 0 (csrc/lowrank_apply.hip); the factor
-// buffer (cuadmm_lowrank's L_out layout for rmax), ranks and blk_vals on the host.  Synchronises the stream.
-int cuadmm_op_block_outer(const double* L_host, const int* ranks, const int* blk_vals, int mat_num, int rmax, double* svec_dev_inout, void* stream) {
-  if (!ranks || !blk_vals || mat_num < 1 || rmax < 1 || rmax > kMaxBlockSize || !svec_dev_inout) { set_error("op_block_outer: invalid argument"); return CUADMM_ERR_INVALID; }
+// What the three factor hooks below refuse block by block, in their own wording: a size the plans do not take, a rank outside
+// 0 .. factor_cols, a positive rank while a buffer is missing (have = false; null_text says which).
+static int op_check_ranks(const char* who, const int* blk_vals, int mat_num, const int* ranks, int rmax, bool have, const char* null_text) {
   for (int k = 0; k < mat_num; ++k) {
     const int n = blk_vals[k];
-    if (n == 0 || n > kMaxBlockSize) { set_error("op_block_outer: block %d has size %d", k, n); return CUADMM_ERR_INVALID; }
-    if (n > 0 && (ranks[k] < 0 || ranks[k] > std::min(n, rmax) || (ranks[k] > 0 && !L_host))) {
-      set_error("op_block_outer: block %d of size %d has rank %d%s", k, n, ranks[k], L_host ? "" : " and L is null");
+    if (n == 0 || n > kMaxBlockSize) { set_error("%s: block %d has size %d", who, k, n); return CUADMM_ERR_INVALID; }
+    if (n > 0 && (ranks[k] < 0 || ranks[k] > factor_cols(n, rmax) || (ranks[k] > 0 && !have))) {
+      set_error("%s: block %d of size %d has rank %d%s", who, k, n, ranks[k], have ? "" : null_text);
       return CUADMM_ERR_INVALID;
     }
   }
-  int rc, ndev = 0;      // the current device is the vector's: it is not changed
+  return CUADMM_OK;
+}
+
+// the kernel of cuadmm_set_lowrank on a DEVICE svec vector whose blocks follow one another from slot 0 (csrc/lowrank_apply.hip); the factor
+// buffer (csrc/factor_layout.h, for rmax), ranks and blk_vals on the host.  Synchronises the stream.
+int cuadmm_op_block_outer(const double* L_host, const int* ranks, const int* blk_vals, int mat_num, int rmax, double* svec_dev_inout, void* stream) {
+  if (!ranks || !blk_vals || mat_num < 1 || rmax < 1 || rmax > kMaxBlockSize || !svec_dev_inout) { set_error("op_block_outer: invalid argument"); return CUADMM_ERR_INVALID; }
+  int rc = op_check_ranks("op_block_outer", blk_vals, mat_num, ranks, rmax, L_host != nullptr, " and L is null"), ndev = 0;
+  if (rc) return rc;      // the current device is the vector's: it is not changed
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_error("no HIP device available; this engine has no CPU fallback"); return CUADMM_ERR_NO_DEVICE; }
   hipStream_t st = (hipStream_t)stream;
   BlockTasksDev t;
+  FactorLayoutDev fl;
   LoPlan plan;
-  double bytes = 0;
-  if ((rc = t.build(blk_vals, mat_num, nullptr)) || (rc = plan.prepare(blk_vals, mat_num, rmax)) || (rc = plan.stage(L_host, ranks, &bytes))) return rc;
-  if ((rc = plan.run(t.off.p, t.blk.p, svec_dev_inout, st))) return rc;
+  if ((rc = t.build(blk_vals, mat_num, nullptr)) || (rc = fl.prepare(blk_vals, mat_num, rmax)) || (rc = plan.prepare(fl, blk_vals)) ||
+      (rc = fl.stage(plan.Lbuf, L_host)) || (rc = fl.stage_ranks(ranks)))
+    return rc;
+  if ((rc = plan.run(fl, plan.Lbuf.p, t.off.p, t.blk.p, svec_dev_inout, st))) return rc;
   CUADMM_HIP_TRY(hipStreamSynchronize(st));
   return CUADMM_OK;
 }
@@ -608,23 +617,19 @@ int cuadmm_op_block_mult(const double* svec_dev, const int* blk_vals, int mat_nu
     set_error("op_block_mult: invalid argument");
     return CUADMM_ERR_INVALID;
   }
-  for (int k = 0; k < mat_num; ++k) {
-    const int n = blk_vals[k];
-    if (n == 0 || n > kMaxBlockSize) { set_error("op_block_mult: block %d has size %d", k, n); return CUADMM_ERR_INVALID; }
-    if (n > 0 && (ranks[k] < 0 || ranks[k] > std::min(n, rmax) || (ranks[k] > 0 && !V_host))) {
-      set_error("op_block_mult: block %d of size %d has rank %d%s", k, n, ranks[k], V_host ? "" : " and V is null");
-      return CUADMM_ERR_INVALID;
-    }
-  }
-  int rc, ndev = 0;      // the current device is the vector's: it is not changed
+  int rc = op_check_ranks("op_block_mult", blk_vals, mat_num, ranks, rmax, V_host != nullptr, " and V is null"), ndev = 0;
+  if (rc) return rc;      // the current device is the vector's: it is not changed
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_error("no HIP device available; this engine has no CPU fallback"); return CUADMM_ERR_NO_DEVICE; }
   hipStream_t st = (hipStream_t)stream;
   BlockTasksDev t;
+  FactorLayoutDev fl;
   BmPlan plan;
-  if ((rc = t.build(blk_vals, mat_num, nullptr)) || (rc = plan.prepare(blk_vals, mat_num, rmax)) || (rc = plan.stage(V_host, ranks))) return rc;
-  if ((rc = plan.run(svec_dev, sign, t.off.p, t.blk.p, st))) return rc;
+  if ((rc = t.build(blk_vals, mat_num, nullptr)) || (rc = fl.prepare(blk_vals, mat_num, rmax)) || (rc = plan.prepare(fl, blk_vals)) ||
+      (rc = fl.stage(plan.Vbuf, V_host)) || (rc = fl.stage_ranks(ranks)))
+    return rc;
+  if ((rc = plan.run(fl, svec_dev, sign, t.off.p, t.blk.p, st))) return rc;
   CUADMM_HIP_TRY(hipStreamSynchronize(st));
-  return plan.fetch(blk_vals, ranks, 1.0, W_host);
+  return plan.fetch(fl, blk_vals, ranks, 1.0, W_host);
 }
 
 // the host side of that kernel: loff_out (mat_num + 1, may be null) <- the offsets of V_k / W_k for rmax; tasks_out (may be null) <- up to
@@ -661,10 +666,8 @@ int cuadmm_op_lrg_multiplier(int m, const double* ax, const double* b, const dou
   if ((rc = staged_d2h(ytilde_out, yt.p, sizeof(double) * (size_t)m)) || (rc = staged_d2h(r_out, r.p, sizeof(double) * (size_t)m)) ||
       (rc = staged_d2h(h.data(), part.p, sizeof(double) * h.size())))
     return rc;
-  double yr = 0, rn2 = 0;
-  for (int j = 0; j < kBrSlots; ++j) { yr += h[j]; rn2 += h[kBrSlots + j]; }
-  out2[0] = yr * (bscale * Cscale);
-  out2[1] = rn2;
+  out2[0] = slot_sum(h.data()) * (bscale * Cscale);
+  out2[1] = slot_sum(h.data() + kBrSlots);
   return CUADMM_OK;
 }
 
@@ -677,29 +680,22 @@ int cuadmm_op_block_outer3(const double* L_host, const double* D_host, const int
     set_error("op_block_outer3: invalid argument");
     return CUADMM_ERR_INVALID;
   }
-  for (int k = 0; k < mat_num; ++k) {
-    const int n = blk_vals[k];
-    if (n == 0 || n > kMaxBlockSize) { set_error("op_block_outer3: block %d has size %d", k, n); return CUADMM_ERR_INVALID; }
-    if (n > 0 && (ranks[k] < 0 || ranks[k] > std::min(n, rmax) || (ranks[k] > 0 && (!L_host || !D_host)))) {
-      set_error("op_block_outer3: block %d of size %d has rank %d%s", k, n, ranks[k], L_host && D_host ? "" : " and L or D is null");
-      return CUADMM_ERR_INVALID;
-    }
-  }
-  std::vector<LoTask> probe;             // the planner's own refusals (split_from) before any device work
-  std::vector<long long> probe_off;
-  int rc = lo_build_tasks(mat_num, blk_vals, rmax, split_from ? split_from : kLoSplitFrom, &probe, &probe_off), ndev = 0;
+  int rc = op_check_ranks("op_block_outer3", blk_vals, mat_num, ranks, rmax, L_host && D_host, " and L or D is null"), ndev = 0;
   if (rc) return rc;
+  std::vector<LoTask> probe;             // the planner's own refusals (split_from) before any device work
+  if ((rc = lo_build_tasks(mat_num, blk_vals, rmax, split_from ? split_from : kLoSplitFrom, &probe, nullptr))) return rc;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_error("no HIP device available; this engine has no CPU fallback"); return CUADMM_ERR_NO_DEVICE; }
   hipStream_t st = (hipStream_t)stream;  // the current device is the vectors': it is not changed
   BlockTasksDev t;
+  FactorLayoutDev fl;
   LoPlan plan;
   DevBuf<double> Dbuf;
-  double bytes = 0;
-  if ((rc = t.build(blk_vals, mat_num, nullptr)) || (rc = plan.prepare(blk_vals, mat_num, rmax, split_from ? split_from : kLoSplitFrom)) ||
-      (rc = plan.stage(L_host && D_host ? L_host : nullptr, ranks, &bytes)) || (rc = Dbuf.alloc((size_t)plan.loff.back() + 1)))
+  const bool both = L_host && D_host;
+  if ((rc = t.build(blk_vals, mat_num, nullptr)) || (rc = fl.prepare(blk_vals, mat_num, rmax)) ||
+      (rc = plan.prepare(fl, blk_vals, split_from ? split_from : kLoSplitFrom)) || (rc = Dbuf.alloc(fl.count() + 1)) ||
+      (rc = fl.stage(plan.Lbuf, both ? L_host : nullptr)) || (rc = fl.stage(Dbuf, both ? D_host : nullptr)) || (rc = fl.stage_ranks(ranks)))
     return rc;
-  if (L_host && D_host && plan.loff.back() > 0 && (rc = Dbuf.upload(D_host, (size_t)plan.loff.back()))) return rc;
-  if ((rc = launch_block_outer3((int)plan.tasks.size(), plan.tasks_d.p, plan.Lbuf.p, Dbuf.p, plan.loff_d.p, plan.ranks_d.p, t.off.p, t.blk.p, x0_dev_inout,
+  if ((rc = launch_block_outer3((int)plan.tasks.size(), plan.tasks_d.p, plan.Lbuf.p, Dbuf.p, fl.loff_d.p, fl.ranks_d.p, t.off.p, t.blk.p, x0_dev_inout,
                                 x1_dev_inout, x2_dev_inout, st)))
     return rc;
   CUADMM_HIP_TRY(hipStreamSynchronize(st));
@@ -733,11 +729,19 @@ int cuadmm_op_lrl_sums(int m, const double* ax0, const double* ax1, const double
       (rc = staged_d2h(q_out, dev[8], sizeof(double) * (size_t)m)) || (rc = staged_d2h(h.data(), part.p, sizeof(double) * h.size())))
     return rc;
   for (int j = 0; j < kLlParts; ++j) {
-    double sum = 0;
-    for (int i = 0; i < kBrSlots; ++i) sum += h[(size_t)j * kBrSlots + i];
+    const double sum = slot_sum(h.data() + (size_t)j * kBrSlots);
     out9[j] = j < 3 ? sum * (bscale * Cscale) : sum;
   }
   return CUADMM_OK;
+}
+
+// cuadmm_set_lowrank's, cuadmm_block_multiply's, cuadmm_lowrank_grad's and cuadmm_lowrank_line's check of the caller's factors
+// (csrc/factor_layout.h: check_factors) under the name `who`, with the buffers named as that call names them: "V" for block_multiply, else
+// "L", and "D" beside it for lowrank_line (D is not looked at for the others).  Host only.
+int cuadmm_op_check_factors(const char* who, const int* blk_vals, int mat_num, const int* ranks, int rmax, const double* L, const double* D) {
+  if (!who || !blk_vals || mat_num < 1) { set_error("op_check_factors: invalid argument"); return CUADMM_ERR_INVALID; }
+  const bool two = !std::strcmp(who, "lowrank_line");
+  return check_factors(who, mat_num, blk_vals, ranks, rmax, std::strcmp(who, "block_multiply") ? "L" : "V", L, two ? "D" : nullptr, two ? D : nullptr, nullptr, nullptr);
 }
 
 int cuadmm_dev_malloc(void** ptr, size_t bytes) { CUADMM_HIP_TRY(hipMalloc(ptr, bytes ? bytes : 8)); return CUADMM_OK; }

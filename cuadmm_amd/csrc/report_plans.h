@@ -1,11 +1,13 @@
 // What the reports on a point own beside the iteration's state, and what the op hooks build on their own: the auxiliary projector, the
-// per-block task lists, the plans of cuadmm_lambda_min, cuadmm_lowrank, cuadmm_set_lowrank, cuadmm_block_multiply, cuadmm_lowrank_grad
-// and cuadmm_lowrank_line.  Nothing here is read by the iteration.
+// per-block task lists, the plan of cuadmm_lambda_min, and for the low-rank calls (cuadmm_lowrank, cuadmm_set_lowrank,
+// cuadmm_block_multiply, cuadmm_lowrank_grad, cuadmm_lowrank_line) the one factor layout on the device, each kernel's task list and
+// buffers, and the host helpers the calls share.  Nothing here is read by the iteration.
 #pragma once
 #include <algorithm>
 #include <cmath>
 
 #include "dev_buf.h"
+#include "factor_layout.h"
 #include "psd_plan.h"
 #include "block_reduce.h"
 #include "lambda_min.h"
@@ -107,10 +109,12 @@ struct LmPlan {
   }
 };
 
+static_assert(kFactorMaxBlock == kMaxBlockSize, "factor_layout.h refuses what the plans refuse");
+
 // Rank and low-rank factor per block (cuadmm_lowrank, cuadmm_op_block_lowrank; lowrank.h, DESIGN.md "Low-rank factors"): the size
-// classes' block lists, the offsets of the blocks' factors and pivots for the rmax of the last call, the factor, pivot and result
-// buffers (they grow with rmax and are kept), a pair of events.  The offsets and sizes per block are the task lists' (btasks).  Nothing
-// here is read by the iteration.
+// classes' block lists, the offsets of the blocks' factors (factor_layout.h) and pivots for the rmax of the last call, the factor, pivot
+// and result buffers (they grow with rmax and are kept), a pair of events.  The kernel writes the factors, so they are its own and not the
+// callers' (FactorLayoutDev).  The offsets and sizes per block are the task lists' (btasks).  Nothing here is read by the iteration.
 struct LrPlan {
   LrClass cls[kLrClasses];
   DevBuf<int> list[kLrClasses], piv;
@@ -133,8 +137,7 @@ struct LrPlan {
     }
     rmax_now = 0;                           // (until the offsets on the device are this rmax's)
     if ((rc = loff_d.upload(loff.data(), loff.size())) || (rc = poff_d.upload(poff.data(), poff.size()))) return rc;
-    if (Lbuf.n < (size_t)loff.back() + 1 && (rc = Lbuf.alloc((size_t)loff.back() + 1))) return rc;      // (+ 1: never empty)
-    if (piv.n < (size_t)poff.back() + 1 && (rc = piv.alloc((size_t)poff.back() + 1))) return rc;
+    if ((rc = Lbuf.grow((size_t)loff.back() + 1)) || (rc = piv.grow((size_t)poff.back() + 1))) return rc;      // (+ 1: never empty)
     nb = nblk;
     rmax_now = rmax;
     return first ? out.alloc(kLrOut * (size_t)nblk) : CUADMM_OK;      // last: marks the set as complete
@@ -149,7 +152,7 @@ struct LrPlan {
     return CUADMM_OK;
   }
   // The results behind a drained stream, on the host and in the units `unit` times the vector's: per_block (kLrOut nb, not null); L_out
-  // (may be null): loff.back() doubles; piv_out (may be null): as many ints, block k's min(n_k, rmax) pivots at loff[k], -1 elsewhere.
+  // (may be null): loff.back() doubles; piv_out (may be null): as many ints, block k's pivots at loff[k], -1 elsewhere.
   int fetch(double unit, double* per_block, double* L_out, int* piv_out) {
     int rc;
     if (nb > 0 && (rc = staged_d2h(per_block, out.p, sizeof(double) * kLrOut * (size_t)nb))) return rc;
@@ -176,115 +179,120 @@ struct LrPlan {
   }
 };
 
-// Start from low-rank factors (cuadmm_set_lowrank, cuadmm_op_block_outer; lowrank_apply.h, DESIGN.md "Starting from low-rank factors"):
-// the wavefront task list (it depends on the block sizes alone), the offsets of the blocks' factors for the rmax of the last call, the
-// device copy of the factor buffer and of the ranks (they grow with rmax and are kept), a pair of events.  The offsets and sizes per
-// block are the task lists' (btasks).  Nothing here is read by the iteration.
-struct LoPlan {
-  std::vector<LoTask> tasks;
+// The layout of the callers' factors on the device (factor_layout.h), one per solver for cuadmm_set_lowrank, cuadmm_block_multiply,
+// cuadmm_lowrank_grad and cuadmm_lowrank_line, and one per call of an op hook: the offsets of the rmax they were last asked for, here
+// and on the device, and the device copy of the ranks.  Every call prepares it for its own rmax first, so whatever it launches reads
+// offsets and ranks of one rmax; the buffers that hold factors are the users' and grow to count() + 1 (never empty).
+struct FactorLayoutDev {
   std::vector<long long> loff;              // of rmax_now, nb + 1 entries
-  DevBuf<LoTask> tasks_d;
   DevBuf<long long> loff_d;
   DevBuf<int> ranks_d;
-  DevBuf<double> Lbuf;
   int nb = 0, rmax_now = 0;
-  DevEvent ev[2];
-  int prepare(const int* blk_h, int nblk, int rmax, int split_from = kLoSplitFrom) {
+  int prepare(const int* blk_h, int nblk, int rmax) {
     if (ranks_d.p && rmax == rmax_now) return CUADMM_OK;
-    int rc = lo_build_tasks(nblk, blk_h, rmax, split_from, &tasks, &loff);
-    if (rc) return rc;
-    const bool first = !ranks_d.p;
-    if (first) {
-      if ((rc = tasks_d.from(tasks, 1)) || (rc = loff_d.alloc((size_t)nblk + 1))) return rc;      // (+ 1: never empty)
-      for (auto& e : ev) if ((rc = e.create())) return rc;
-    }
+    int rc = factor_offsets("factor_layout", nblk, blk_h, rmax, &loff);
+    if (rc) { rmax_now = 0; return rc; }
+    if (!ranks_d.p && (rc = loff_d.alloc((size_t)nblk + 1))) return rc;
     rmax_now = 0;                           // (until the offsets on the device are this rmax's)
     if ((rc = loff_d.upload(loff.data(), loff.size()))) return rc;
-    if (Lbuf.n < (size_t)loff.back() + 1 && (rc = Lbuf.alloc((size_t)loff.back() + 1))) return rc;
     nb = nblk;
     rmax_now = rmax;
-    return first ? ranks_d.alloc((size_t)nblk + 1) : CUADMM_OK;      // last: marks the set as complete
+    return ranks_d.p ? CUADMM_OK : ranks_d.alloc((size_t)nblk + 1);      // last: marks the set as complete
   }
-  // the factor buffer (whole, one copy; null: nothing, every rank is 0) and the ranks to the device; *bytes: those of the factor
-  int stage(const double* L_host, const int* ranks, double* bytes) {
+  size_t count() const { return (size_t)loff.back(); }
+  int stage_ranks(const int* ranks) { return ranks_d.upload(ranks, (size_t)nb); }
+  // a factor buffer whole, in one copy (null: nothing, every rank is 0)
+  int stage(DevBuf<double>& buf, const double* host) const { return host ? buf.upload(host, count()) : CUADMM_OK; }
+  double bytes() const { return 8.0 * (double)loff_d.n + 4.0 * (double)ranks_d.n; }
+};
+
+// dst <- the factors src in the units a vector of unit ux lies in: fl(src[e] * root), root = fl(1 / sqrt(ux)), in the columns that are read
+// and + 0.0 in the others.  cuadmm_lowrank_grad's L and cuadmm_lowrank_line's L and D go through here: the same L gives the same bits.
+inline void scale_factors(const FactorLayoutDev& fl, const int* blk_h, const int* ranks, const double* src, double ux, std::vector<double>& dst) {
+  const double root = 1 / std::sqrt(ux);
+  dst.assign(fl.count(), 0.0);
+  for (int k = 0; k < fl.nb; ++k)
+    for (size_t e = (size_t)fl.loff[k], end = e + (blk_h[k] > 0 ? (size_t)blk_h[k] * (size_t)ranks[k] : 0); e < end; ++e) dst[e] = src[e] * root;
+}
+// out[perm[i]] <- h[i]: an m-vector from the factor's order to the caller's (out may be null)
+inline void unpermute(const std::vector<int>& perm, int m, const double* h, double* out) {
+  for (int i = 0; out && i < m; ++i) out[perm[i]] = h[i];
+}
+// a kernel's kBrSlots slot partials added in slot order from 0.0
+inline double slot_sum(const double* part) {
+  double s = 0;
+  for (int j = 0; j < kBrSlots; ++j) s = s + part[j];
+  return s;
+}
+
+// Start from low-rank factors (cuadmm_set_lowrank, cuadmm_op_block_outer; lowrank_apply.h, DESIGN.md "Starting from low-rank factors"):
+// the wavefront task list, built once (it depends on the block sizes alone), a device factor buffer that grows with the layout and is
+// kept, a pair of events.  The offsets and sizes per block are the task lists' (btasks).  Nothing here is read by the iteration.
+struct LoPlan {
+  std::vector<LoTask> tasks;
+  DevBuf<LoTask> tasks_d;
+  DevBuf<double> Lbuf;
+  DevEvent ev[2];
+  int prepare(const FactorLayoutDev& fl, const int* blk_h, int split_from = kLoSplitFrom) {
     int rc;
-    const size_t count = L_host ? (size_t)loff.back() : 0;
-    if (count > 0 && (rc = Lbuf.upload(L_host, count))) return rc;
-    *bytes = 8.0 * (double)count;
-    return ranks_d.upload(ranks, (size_t)nb);
+    if (!ev[1]) {
+      if ((rc = lo_build_tasks(fl.nb, blk_h, fl.rmax_now, split_from, &tasks, nullptr)) || (rc = tasks_d.from(tasks, 1))) return rc;      // (+ 1: never empty)
+      for (auto& e : ev) if ((rc = e.create())) return rc;
+    }
+    return Lbuf.grow(fl.count() + 1);
   }
-  // v (device) <- svec(L_k L_k') on every PSD block, one launch
-  int run(const long long* off_d, const int* blk_d, double* v, hipStream_t st) {
-    return launch_block_outer((int)tasks.size(), tasks_d.p, Lbuf.p, loff_d.p, ranks_d.p, off_d, blk_d, v, st);
+  // v (device) <- svec(L_k L_k') on every PSD block from the device factors L, one launch
+  int run(const FactorLayoutDev& fl, const double* L, const long long* off_d, const int* blk_d, double* v, hipStream_t st) {
+    return launch_block_outer((int)tasks.size(), tasks_d.p, L, fl.loff_d.p, fl.ranks_d.p, off_d, blk_d, v, st);
   }
+  double bytes() const { return 8.0 * (double)Lbuf.n + (double)sizeof(LoTask) * (double)tasks_d.n; }
 };
 
 // Blocks times factors (cuadmm_block_multiply, cuadmm_op_block_mult; block_mult.h, DESIGN.md "Blocks times factors"): the wavefront
-// task list (it depends on the block sizes alone), the offsets of the blocks' V_k / W_k for the rmax of the last call, the device V, W and
-// ranks (they grow with rmax and are kept), the y of which = 2, a pair of events.  V travels whole in one staged copy and W comes back
-// whole, padding columns included; both copies lie outside the timed interval.  The offsets and
-// sizes per block are the task lists' (btasks).  Nothing here is read by the iteration.
+// task list, built once (it depends on the block sizes alone), the device V and W (they grow with the layout and are kept), the y of
+// which = 2, a pair of events.  V travels whole in one staged copy and W comes back whole, padding columns included; both copies lie
+// outside the timed interval.  The offsets and sizes per block are the task lists' (btasks).  Nothing here is read by the iteration.
 struct BmPlan {
   std::vector<BmTask> tasks;
-  std::vector<long long> loff;              // of rmax_now, nb + 1 entries
   DevBuf<BmTask> tasks_d;
-  DevBuf<long long> loff_d;
-  DevBuf<int> ranks_d;
   DevBuf<double> Vbuf, Wbuf, ybuf;
-  int nb = 0, rmax_now = 0;
   DevEvent ev[2];
   long long calls = 0;
-  int prepare(const int* blk_h, int nblk, int rmax) {
-    if (ranks_d.p && rmax == rmax_now) return CUADMM_OK;
-    int rc = bm_build_tasks(nblk, blk_h, rmax, &tasks, &loff);
-    if (rc) return rc;
-    const bool first = !ranks_d.p;
-    if (first) {
-      if ((rc = tasks_d.from(tasks, 1)) || (rc = loff_d.alloc((size_t)nblk + 1))) return rc;      // (+ 1: never empty)
+  int prepare(const FactorLayoutDev& fl, const int* blk_h) {
+    int rc;
+    if (!ev[1]) {
+      if ((rc = bm_build_tasks(fl.nb, blk_h, fl.rmax_now, &tasks, nullptr)) || (rc = tasks_d.from(tasks, 1))) return rc;      // (+ 1: never empty)
       for (auto& e : ev) if ((rc = e.create())) return rc;
     }
-    rmax_now = 0;                           // (until the offsets on the device are this rmax's)
-    if ((rc = loff_d.upload(loff.data(), loff.size()))) return rc;
-    const size_t need = (size_t)loff.back() + 1;
-    if (Vbuf.n < need && (rc = Vbuf.alloc(need))) return rc;
-    if (Wbuf.n < need && (rc = Wbuf.alloc(need))) return rc;
-    nb = nblk;
-    rmax_now = rmax;
-    return first ? ranks_d.alloc((size_t)nblk + 1) : CUADMM_OK;      // last: marks the set as complete
-  }
-  // V (whole, one copy; null: nothing, every rank is 0) and the ranks to the device
-  int stage(const double* V_host, const int* ranks) {
-    int rc;
-    const size_t count = V_host ? (size_t)loff.back() : 0;
-    if (count > 0 && (rc = Vbuf.upload(V_host, count))) return rc;
-    return ranks_d.upload(ranks, (size_t)nb);
+    if ((rc = Vbuf.grow(fl.count() + 1))) return rc;
+    return Wbuf.grow(fl.count() + 1);
   }
   // Wbuf (device) <- sign * M_k V_k on every PSD block of v, one launch
-  int run(const double* v, double sign, const long long* off_d, const int* blk_d, hipStream_t st) {
-    return launch_block_mult((int)tasks.size(), tasks_d.p, v, sign, Vbuf.p, Wbuf.p, loff_d.p, ranks_d.p, off_d, blk_d, st);
+  int run(const FactorLayoutDev& fl, const double* v, double sign, const long long* off_d, const int* blk_d, hipStream_t st) {
+    return launch_block_mult((int)tasks.size(), tasks_d.p, v, sign, Vbuf.p, Wbuf.p, fl.loff_d.p, fl.ranks_d.p, off_d, blk_d, st);
   }
-  // W_out (loff.back() doubles, host) behind a drained stream: the kernel's entries times `unit`, + 0.0 in the columns >= ranks[k]
-  int fetch(const int* blk_h, const int* ranks, double unit, double* W_out) {
+  // W_out (fl.count() doubles, host) behind a drained stream: the kernel's entries times `unit`, + 0.0 in the columns >= ranks[k]
+  int fetch(const FactorLayoutDev& fl, const int* blk_h, const int* ranks, double unit, double* W_out) {
     int rc;
-    const size_t count = (size_t)loff.back();
-    if (count > 0 && (rc = staged_d2h(W_out, Wbuf.p, sizeof(double) * count))) return rc;
-    for (int k = 0; k < nb; ++k) {
+    if (fl.count() > 0 && (rc = staged_d2h(W_out, Wbuf.p, sizeof(double) * fl.count()))) return rc;
+    for (int k = 0; k < fl.nb; ++k) {
       if (blk_h[k] <= 0) continue;
-      double* const w = W_out + loff[k];
+      double* const w = W_out + fl.loff[k];
       const size_t used = (size_t)blk_h[k] * (size_t)ranks[k];
       for (size_t e = 0; unit != 1.0 && e < used; ++e) w[e] *= unit;
-      std::fill(w + used, W_out + loff[k + 1], 0.0);
+      std::fill(w + used, W_out + fl.loff[k + 1], 0.0);
     }
     return CUADMM_OK;
   }
-  double bytes() const { return 8.0 * (double)(loff_d.n + Vbuf.n + Wbuf.n + ybuf.n + tasks_d.n) + 4.0 * (double)ranks_d.n; }
+  double bytes() const { return 8.0 * (double)(Vbuf.n + Wbuf.n + ybuf.n + tasks_d.n); }
 };
 
 // Value and gradient at factors (cuadmm_lowrank_grad; lowrank_grad.h, DESIGN.md "Value and gradient at factors"): the svec vector x is
 // assembled in (a device copy of X with svec(L_k L_k') over its PSD blocks), the m-vectors of the multiplier pass (y, A x, ytilde, r; the
 // column norms where the engine keeps none on the device), the slot partials, the per-block sums and a pair of events.  The factors are
-// the block product's V (BmPlan) and the outer product reads them there (LoPlan's task list) where x is in the caller's units; the
-// products go to BmPlan's W and A'ytilde - C to the auxiliary projector's input vector.  Nothing here is read by the iteration.
+// the block product's V (BmPlan) and the outer product (LoPlan's task list) reads them there where x is in the caller's units, else from
+// LoPlan's buffer; both launches read the solver's one FactorLayoutDev.  The products go to BmPlan's W and A'ytilde - C to the auxiliary
+// projector's input vector.  Nothing here is read by the iteration.
 struct LgPlan {
   DevBuf<double> xv, ybuf, ax, ytilde, r, normA, part, sums, cpart;
   std::vector<double> h_stage, h_back, h_G;      // host scratch kept between calls: the scaled factors, what comes back, G where the caller wants none
@@ -304,10 +312,10 @@ struct LgPlan {
 
 // The quartic along a line in factor space (cuadmm_lowrank_line; lowrank_line.h, DESIGN.md "Line search along factor steps"): the three
 // svec vectors x0 (a device copy of X with svec(L_k L_k') over its PSD blocks), x1 and x2 (zeroed once, here: the kernel writes their PSD
-// slots only, and always all of them, so the unconstrained slices stay zero), the device copy of D (it grows with rmax; L travels in
-// LoPlan's buffer, whose offsets, ranks and task list the launch reads), the m-vectors of the streaming pass (y, the three A x, r0, p, q;
-// the column norms where the engine keeps none on the device), the slot partials, the per-block sums and a pair of events.  Nothing here is
-// read by the iteration.
+// slots only, and always all of them, so the unconstrained slices stay zero), the device copy of D (it grows with the layout; L travels
+// in LoPlan's buffer, whose task list the launch walks with the solver's FactorLayoutDev), the m-vectors of the streaming pass (y, the
+// three A x, r0, p, q; the column norms where the engine keeps none on the device), the slot partials, the per-block sums and a pair of
+// events.  Nothing here is read by the iteration.
 struct LlPlan {
   DevBuf<double> x0, x1, x2, Dbuf, ybuf, ax0, ax1, ax2, r0, p, q, normA, part, sums, cpart;
   std::vector<double> h_L, h_D, h_back;          // host scratch kept between calls: the scaled factors, what comes back

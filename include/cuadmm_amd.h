@@ -798,6 +798,11 @@ int cuadmm_op_block_outer3(const double* L_host, const double* D_host, const int
  * synchronised. */
 int cuadmm_op_lrl_sums(int m, const double* ax0, const double* ax1, const double* ax2, const double* b, const double* normA, const double* y, double bscale,
                        double Cscale, double* r_out, double* p_out, double* q_out, double out9[9]);
+/* The check of a caller's factors that cuadmm_set_lowrank, cuadmm_block_multiply, cuadmm_lowrank_grad and cuadmm_lowrank_line share
+ * (csrc/factor_layout.h), alone: who is one of "set_lowrank", "block_multiply", "lowrank_grad", "lowrank_line" and words the message as
+ * that call does; L is its factor buffer (V for block_multiply), D the second one of lowrank_line (not looked at for the others).
+ * Returns what that call would return for these factors: 0, or CUADMM_ERR_INVALID with the message set.  Host only (no device needed). */
+int cuadmm_op_check_factors(const char* who, const int* blk_vals, int mat_num, const int* ranks, int rmax, const double* L, const double* D);
 int cuadmm_op_spmv_rows(int rows, int ncols, const int* row_ptrs, const int* col_ids, const double* vals, const double* X, const double* S, const double* C,
                         int want_x, int want_s, const int* rowmap, int out_len, double* outX, double* outS, int* info4);
 int cuadmm_op_rp_stats(int m, const double* ax, const double* b, const double* normA, const double* y, double bscale, const double* sums2, double* out4);

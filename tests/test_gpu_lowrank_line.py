@@ -498,7 +498,75 @@ def test_lowrank_descent():
     assert same_bits(s.X, X0)
 
 
-# ---- 4. the front ends ----------------------------------------------------------------------------------------------------
+# ---- 4. calls of different rmax on one solver -----------------------------------------------------------------------------
+# 3: inside one tile; 20: two tiles and a rank above 16; -2: a free block that shifts every later offset; 33: above kLoWaveMax (the outer
+# product's workgroup path, three panels of the block product).  (name, rmax, ranks, which): every ranks has a block at rank 0 and one at
+# min(n, rmax).
+BLK_I, M_I = [3, 20, -2, 33], 5
+MIX = (("block_multiply", 4, (3, 0, 0, 4), 2), ("lowrank_grad", 20, (0, 20, 0, 7), 0), ("lowrank_line", 1, (1, 0, 0, 1), 0), ("set_lowrank", 33, (0, 17, 0, 33), 0),
+       ("lowrank_grad", 4, (3, 4, 0, 0), 0), ("block_multiply", 33, (3, 0, 0, 33), 0), ("lowrank_line", 20, (0, 20, 0, 13), 0), ("lowrank", 4, None, 0))
+
+
+def mix_call(s, fx, step):
+    """every output of call `step` of MIX on s but the milliseconds and the bytes held, as a list of arrays"""
+    name, rmax, ranks, which = MIX[step]
+    lib = cuadmm_amd.load()
+    rng = np.random.default_rng(900 + step)
+    nb, size = len(BLK_I), max(lowrank_size(BLK_I, rmax), 1)
+    y = rng.standard_normal(fx.m)
+    o = np.full(8, np.nan)
+    if name == "lowrank":
+        pb, L, piv = np.full(6 * nb, np.nan), np.full(size, np.nan), np.full(size, -7, np.int32)
+        assert lib.cuadmm_lowrank(s._h, which, 1e-8, rmax, P(o), P(pb), P(L), P(piv)) == 0, lib.cuadmm_last_error()
+        return [o[:6], pb, L, piv.astype(np.float64)]
+    Fs = [[rng.standard_normal((max(n, 0), r if n > 0 else 0)) for n, r in zip(BLK_I, ranks)] for _ in range(2)]
+    (Lv, rk), (Dv, _) = pack(BLK_I, Fs[0], rmax), pack(BLK_I, Fs[1], rmax)      # NaN in every column that must not be read
+    if name == "set_lowrank":
+        o4 = np.full(4, np.nan)
+        assert lib.cuadmm_set_lowrank(s._h, which, P(Lv), P(rk), rmax, 0.0, P(o4)) == 0, lib.cuadmm_last_error()
+        assert o4[3] == 8 * lowrank_size(BLK_I, rmax)
+        return [o4[[0, 1, 3]], s.X]
+    if name == "block_multiply":
+        W, pb = np.full(size, np.nan), np.full(4 * nb, np.nan)
+        assert lib.cuadmm_block_multiply(s._h, which, P(Lv), P(rk), rmax, P(W), P(o), P(pb)) == 0, lib.cuadmm_last_error()
+        return [o[:6], W, pb]
+    if name == "lowrank_grad":
+        G, r, Sh, pb = np.full(size, np.nan), np.full(fx.m, np.nan), np.full(fx.L, np.nan), np.full(4 * nb, np.nan)
+        assert lib.cuadmm_lowrank_grad(s._h, P(Lv), P(rk), rmax, P(y), 0.7, P(G), P(r), P(Sh), P(o), P(pb)) == 0, lib.cuadmm_last_error()
+        return [o[:6], G, r, Sh, pb]
+    rc, c, r, p, q, o, pb = raw(s, Lv, Dv, rk, rmax, y, 0.7, 2.0, m=fx.m, nb=nb)
+    assert rc == 0, lib.cuadmm_last_error()
+    return [o[:6], c, r, p, q, pb]
+
+
+@pytest.mark.parametrize("iters", [0, 10])
+def test_calls_of_different_rmax_on_one_solver(iters):
+    """The eight calls of MIX in turn on one solver, each with an rmax of its own: every output equals, bit for bit, that of the same call
+    made alone on a fresh solver -- behind nothing for the calls before set_lowrank, behind that set_lowrank alone for the calls after
+    it.  iters = 10: behind a solve, where X lies scaled and the factors are staged times fl(1 / sqrt(bscale)) (until set_lowrank puts
+    the solver back into the caller's units)."""
+    fx = make_opt_fixture(BLK_I, M_I, 3)
+    X0 = np.random.default_rng(91).standard_normal(fx.L)
+    SET = [c[0] for c in MIX].index("set_lowrank")
+
+    def fresh():
+        s = solver(fx, X0)
+        if iters:
+            s.solve(iters, 0.0)
+        return s
+
+    one = fresh()
+    got = [mix_call(one, fx, step) for step in range(len(MIX))]
+    assert all(np.isfinite(a).all() for step in (1, 2, 4, 6) for a in got[step])
+    for step in range(len(MIX)):
+        alone = fresh()
+        if step > SET:
+            mix_call(alone, fx, SET)
+        want = mix_call(alone, fx, step)
+        assert len(want) == len(got[step]) and all(same_bits(a, b) for a, b in zip(got[step], want)), (step, MIX[step][:2])
+
+
+# ---- 5. the front ends ----------------------------------------------------------------------------------------------------
 BLK_C, M_C = [3, 12, -2, 20], 10
 
 
