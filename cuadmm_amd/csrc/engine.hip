@@ -981,564 +981,6 @@ int cuadmm_init(cuadmm_solver* s, int eig_stream_num_per_gpu, int cpu_eig_thread
   return CUADMM_OK;
 }
 
-// ------------------------------------------------------------------------------------------
-// SDPSolver::solve
-// ------------------------------------------------------------------------------------------
-int cuadmm_solve(cuadmm_solver* s, int max_iter, double stop_tol, int sig_update_threshold, int sig_update_stage_1,
-                 int sig_update_stage_2, int switch_admm, double sigscale, int if_first) {
-  if (!s || !s->initialised) { set_error("solve: solver not initialised"); return CUADMM_ERR_INVALID; }
-  if (s->factor_bad) { set_error("solve: the last cuadmm_update_A could not factor the new A A^T; the solver needs a successful cuadmm_update_A first"); return CUADMM_ERR_FACTOR; }
-  if (sig_update_stage_1 <= 0 || sig_update_stage_2 <= 0) { set_error("solve: sig_update stages must be positive"); return CUADMM_ERR_INVALID; }
-  if (s->group && !s->in_group_call)      // the leader of an in-process group (duo_group.hip): every rank solves, on its own host thread
-    return group_forward(s, [&](cuadmm_solver* q) {
-      return cuadmm_solve(q, max_iter, stop_tol, sig_update_threshold, sig_update_stage_1, sig_update_stage_2, switch_admm, sigscale, if_first);
-    });
-  int rc = check_device(s->device);
-  if (rc) return rc;
-  s->y_early = false;                       // (a solve that ended in an error may have left it set)
-  // the dense tail of the replicated y-solve: split by rows over the ranks of a sharded engine (tail_solve.h)
-  if (s->tail.k > 0) {
-    const bool shard = s->world > 1 && !s->local_mode && s->sw.tail_shard != 0;
-    s->tail.shard_rank = shard ? s->rank : 0;
-    s->tail.shard_world = shard ? s->world : 1;
-    s->tail.reduce_user = s;
-    s->tail.reduce_fn = [](void* user, double* buf, size_t count, hipStream_t) -> int { return static_cast<cuadmm_solver*>(user)->comm_allreduce(buf, count); };
-  }
-  const int m = s->m;
-  const long long L = s->L;
-  const bool verbose = s->verbose && s->rank == 0;
-  bool breakyes = false;
-  std::string final_msg;
-  s->info_iter_num = 0;
-
-  if (verbose) {
-    printf("\n -------------------------------------------------------------------------------");
-    printf("\n                                    cuADMM");
-    printf("\n -------------------------------------------------------------------------------");
-    printf("\n norm of C = %2.1e, norm of b = %2.1e\n", s->norm_Corg, s->norm_borg);
-  }
-
-  if (if_first && s->pending_unscale && (rc = s->materialise())) return rc;   // the reference's X, y, S are unscaled after a solve
-  if (!if_first && s->pending_unscale) {
-    // the previous solve left X, y, S scaled and [A X | A (S - C)], Rp as its last iteration formed them: nothing to redo
-    s->pending_unscale = false;
-  } else if (!if_first) {   // solver.cu:385-409: X,y,S currently hold UNSCALED values
-    if ((rc = s->sync_y_host())) return rc;
-    for (int i = 0; i < m; ++i) s->y_p[i] = (s->y_p[i] * s->normA_p[i]) * (1 / s->Cscale);
-    if (s->dev_solve && (rc = s->upload_y(true))) return rc;
-    if ((rc = launch_scale(s->X.p, L, 1 / s->bscale, s->st))) return rc;
-    if ((rc = launch_scale(s->S.p, L, 1 / s->Cscale, s->st))) return rc;
-    if ((rc = s->launch_spmv(true, true))) return rc;
-    if ((rc = s->fetch_out(0, 2 * (size_t)m + 2))) return rc;
-    s->refresh_Rp();
-  }
-
-  if (verbose) {
-    std::cout << std::endl << "  it. | p infeas d infeas | primal obj.   dual obj. rel. gap |  time |   sigma | " << std::endl;
-    std::cout << " -------------------------------------------------------------------------------" << std::endl;
-  }
-
-  if ((rc = s->batch_agree())) return rc;
-  if (s->accel_on() && (rc = s->accel_begin_solve())) return rc;
-  s->solve_status = 0;
-  if (s->infeas_on() && (rc = s->infeas_begin_solve())) return rc;
-  s->lb_reset();
-  s->lb.ms = 0;
-  if (s->gap_on() && (rc = s->lb_prepare())) return rc;
-  const bool lpt_enabled = s->sw.lpt != 0;
-  long long& lpt_ev = s->lpt_next;             // counts iterations over all solve calls of this solver
-  if (!lpt_enabled) lpt_ev = 0;
-  // iteration i may change sigma in its step 5 (by reference: the switch to ADMM halves sig_update_stage_2 mid-solve)
-  const auto sig_may_change_at = [&](int i) {
-    return (i <= sig_update_threshold && i % sig_update_stage_1 == 1) || (i > sig_update_threshold && i % sig_update_stage_2 == 1);
-  };
-  for (int iter = 1; iter <= max_iter + 1; ++iter) {
-    // ---- Step 0 (solver.cu:419-467)
-    if (std::max(s->maxfeas, s->relgap) < stop_tol) { breakyes = true; final_msg = "Solver ended: converged."; }
-    if (iter > max_iter) { breakyes = true; final_msg = "Solver ended: maximum iteration reached"; }
-    if (s->solve_status == 5) {           // the certified gap behind the previous iteration (lb_step)
-      breakyes = true;
-      char msg[160];
-      snprintf(msg, sizeof msg, "Solver ended: certified gap %.3e (lower bound %.10e at iteration %d)", s->lb.last_g, s->lb.last_lb, s->solve_status_iter);
-      final_msg = msg;
-    } else if (s->solve_status >= 3) {    // a certificate behind the previous iteration (infeas_step)
-      breakyes = true;
-      char msg[128];
-      snprintf(msg, sizeof msg, "Solver ended: %s infeasible (certificate at iteration %d)", s->solve_status == 3 ? "primal" : "dual", s->solve_status_iter);
-      final_msg = msg;
-    } else if (breakyes) {
-      s->solve_status = iter > max_iter ? 2 : 1;
-      s->solve_status_iter = iter - 1;
-    }
-    const double seconds = wall_s() - s->t_init0;
-    if (verbose && (breakyes || (iter <= 200 && iter % 50 == 1) || (iter > 200 && iter % 100 == 1))) {
-      printf(" %4d | %3.2e %3.2e | %- 5.4e %- 5.4e %3.2e | %5.1f | %2.1e |", iter - 1, s->errRp, s->errRd, s->pobj,
-             s->dobj, s->relgap, seconds, s->sig);
-      std::cout << std::endl;
-    }
-    if (breakyes) {
-      if (verbose) {
-        printf("\n -------------------------------------------------------------------------------\n\n");
-        std::cout << final_msg << std::endl;
-        printf("\n primal infeasibility = %2.1e \n dual   infeasibility = %2.1e \n relative gap         = %2.1e", s->errRp,
-               s->errRd, s->relgap);
-        printf("\n primal objective = %- 9.8e \n dual   objective = %- 9.8e", s->pobj, s->dobj);
-        printf("\n\n time per iteration = %2.4fs \n total time         = %2.1fs", seconds / iter, seconds);
-        printf("\n -------------------------------------------------------------------------------\n\n");
-      }
-      s->total_time = wall_s() - s->t_init0;
-    }
-
-    // the device is ahead of the host schedule by the unconsumed iterations of a batch: back to the accepted state
-    if (breakyes && s->bt.len > 0 && (rc = s->batch_rollback(s->bt.pos))) return rc;
-
-    // ---- Step 1 (solver.cu:478-500): y = (AA^T)^-1 (Rp/sig - A(S-C)); with closed blocks the fused projection of this
-    // iteration solves it (not on the last pass through the loop, which stops before the projection)
-    if (s->y_early) s->y_early = false;       // enqueued at the end of the previous iteration (fetch_out, solve_next)
-    else if (s->solve_status == 5) {}         // the bound was formed at the y the solve returns: no further y-solve behind the verdict
-    else if (s->bt.len == 0 && (rc = s->host_solve(s->fuse && !breakyes))) return rc;
-
-    if (breakyes) {   // solver.cu:567-576
-      if (iter > switch_admm && s->have_best && s->solve_status < 3) {   // (a certificate describes the last iterate: no restore)
-        CUADMM_HIP_TRY(hipMemcpyAsync(s->X.p, s->X_best.p, sizeof(double) * (size_t)L, hipMemcpyDeviceToDevice, s->st));
-        CUADMM_HIP_TRY(hipMemcpyAsync(s->S.p, s->S_best.p, sizeof(double) * (size_t)L, hipMemcpyDeviceToDevice, s->st));
-        CUADMM_HIP_TRY(hipStreamSynchronize(s->st));
-        if (s->dev_solve) CUADMM_HIP_TRY(hipMemcpy(s->y_d.p, s->y_best_d.p, sizeof(double) * (size_t)m, hipMemcpyDeviceToDevice));
-        else std::copy(s->y_best_p.begin(), s->y_best_p.end(), s->y_p.begin());   // in place: y_p's storage is page-locked
-        if (verbose) printf("best max KKT residual after switch  = %2.1e \n", s->best_KKT);
-      }
-      break;
-    }
-
-    // ---- Step 2 (solver.cu:514-656).  The host-side decisions of this iteration (tau, snapshot) depend only on the previous
-    // iteration's scalars, so they are taken first: the fused projection needs to know which post step follows it.
-    double tau = (iter < switch_admm) ? 1.95 : 1.618;                    // solver.cu:747-754
-    if (s->errRd < stop_tol) tau = std::max(1.618, tau / 1.1);
-
-    // does this iteration snapshot the iterate between the S update and the X update?
-    bool snapshot = false;
-    if (iter == switch_admm) {                                           // solver.cu:681-690
-      if (verbose) std::cout << " switching to normal ADMM!" << std::endl;
-      sig_update_stage_2 = sig_update_stage_2 / 2;
-      if (sig_update_stage_2 < 1) sig_update_stage_2 = 1;
-      sigscale = sigscale * 1.23;
-      s->sgs_KKT = std::max(s->maxfeas, s->relgap);
-      s->best_KKT = s->sgs_KKT;
-      snapshot = true;
-    } else if (iter > switch_admm && s->have_best && !s->aa.pending && s->best_KKT > std::max(s->maxfeas, s->relgap)) {
-      // (not in an iteration that started from a candidate of the acceleration: X, y, S there are not the iterate the scalars describe)
-      s->best_KKT = std::max(s->maxfeas, s->relgap);                     // solver.cu:732-741
-      snapshot = true;
-    }
-
-    const int post_mode_after_proj = (iter < switch_admm || snapshot) ? 1 : 0;
-    // ---- several iterations in one launch (SignFuse::iters): ADMM phase without best-iterate bookkeeping, every block closed.
-    // A batch ends at the next iteration that may change sigma; tau changes only through the errRd < stop_tol rule, checked
-    // below on every consumed iteration.
-    if (s->bt.len > 0 && tau != s->bt.tau) {
-      // this iteration was run with the wrong step length: keep the consumed ones, continue one launch at a time
-      if ((rc = s->batch_rollback(s->bt.pos))) return rc;
-    }
-    if (s->bt.len == 0 && iter > switch_admm && !s->have_best && !snapshot && s->can_batch()) {
-      if ((rc = s->batch_alloc())) return rc;
-      int K = std::min(std::min(s->bt.max_iters, s->bt.cap), max_iter - iter + 1);
-      for (int j = 0; j < K; ++j) {          // the batch may END on a sigma-update iteration, not contain one
-        if (sig_may_change_at(iter + j)) { K = j + 1; break; }
-      }
-      if (K >= 2) {
-        // a batch can only be invalidated by the stopping test or the errRd < stop_tol rule for tau: no checkpoint without a tolerance
-        s->bt.have_ck = stop_tol > 0.0;
-        if (s->bt.have_ck && (rc = s->batch_copy(true))) return rc;
-        s->bt.tau = tau; s->bt.sig = s->sig;
-        // longest block first without a stall: the step counts are fetched behind one batch; the next one is launched in the new
-        // order (the copy of the sorted descriptors is queued on the stream ahead of the launch; the host sort takes ~0.1 ms)
-        const bool lpt_sorted_now = lpt_ev > 0 && s->steps_d.p && s->lpt_steps_ready;
-        if (lpt_sorted_now) {
-          if ((rc = s->plan.reorder_by_steps_async(s->steps_pin.p, s->st))) return rc;
-          s->lpt_steps_ready = false;
-          lpt_ev *= 8;
-        }
-        if ((rc = s->launch_fused_step(0, tau, K))) return rc;
-        if (lpt_ev > 0 && s->steps_d.p && !lpt_sorted_now) {
-          if (s->lpt_iters + K >= lpt_ev) {
-            if (!s->steps_pin.p && (rc = s->steps_pin.alloc(s->steps_d.n))) return rc;
-            CUADMM_HIP_TRY(hipMemcpyAsync(s->steps_pin.p, s->steps_d.p, sizeof(int) * s->steps_d.n, hipMemcpyDeviceToHost, s->st));
-            s->lpt_steps_ready = true;     // valid once the stream has been synchronised (below)
-          }
-        }
-        CUADMM_HIP_TRY(hipStreamSynchronize(s->st));
-        s->prof_collect();
-        s->bt.len = K; s->bt.pos = 0;
-      }
-    }
-    const bool from_batch = s->bt.len > 0;
-    // the next iteration's y-solve may follow this iteration's last kernel at once (fetch_out, solve_next): the whole solve is on the
-    // device and belongs to the engine (not to a closed block's kernel), sigma does not change in this iteration's step 5, nothing of a
-    // batch is pending, and the per-class event timers (profile = 1) are off -- they are collected at the wait, before that solve ends
-    const bool sig_may_change = sig_may_change_at(iter);
-    const bool solve_next_ok = s->sw.solve_next != 0 && !s->accel_on() && !s->infeas_on() && !s->gap_on() && s->dev_solve && !from_batch && !sig_may_change && !(s->fuse && s->closed.active) && s->profile != 1;
-    if (from_batch) {
-      // consumed below (Step 5) from bt.h
-    } else if ((rc = s->upload_y())) return rc;
-    if (from_batch) {
-    } else if (s->fuse) {
-      if ((rc = s->launch_fused_step(post_mode_after_proj, tau))) return rc;
-    } else {
-      if ((rc = s->launch_aty(true))) return rc;
-      s->plan.rank_active = s->eig_rank > 0 && (iter >= s->eig_rank_begin_iter || s->maxfeas < s->eig_rank_maxfeas);   // duo_solver.cu:844
-      if ((rc = s->launch_project())) return rc;
-      const char* const debug_eig_dir = s->sw.debug_eig ? getenv("CUADMM_DEBUG_EIG") : nullptr;
-      if (debug_eig_dir) {   // developer aid (option debug_eig + CUADMM_DEBUG_EIG=<dir>): dump the projection input when a block hits the QL cap
-        int f = s->plan.fail_count(s->st);
-        if (f != s->eig_fail_total) {
-          fprintf(stderr, "[cuadmm debug] iter %d: QL cap hits %d -> %d\n", iter, s->eig_fail_total, f);
-          std::vector<double> h((size_t)L);
-          if (staged_d2h(h.data(), s->Xb.p, sizeof(double) * (size_t)L, s->st) == CUADMM_OK) {
-            char fn[256];
-            snprintf(fn, sizeof fn, "%s/xb_fail_iter%d.bin", debug_eig_dir, iter);
-            if (FILE* fp = fopen(fn, "wb")) { fwrite(h.data(), sizeof(double), (size_t)L, fp); fclose(fp); }
-          }
-          s->eig_fail_total = f;
-        }
-      }
-    }
-
-    if (from_batch) {
-    } else if (iter < switch_admm) {
-      // sGS half step: S^{k+1}, second solve with it, Rd1 from the new y (solver.cu:693-729)
-      if (!s->fuse && (rc = s->launch_post_mode(1, tau))) return rc;     // fused: done with the projection
-      if ((rc = s->launch_spmv(false, true, s->fuse))) return rc;
-      if ((rc = s->fetch_out((size_t)m + 2, (size_t)m))) return rc;
-      if ((rc = s->host_solve())) return rc;
-      if ((rc = s->upload_y())) return rc;
-      if (s->At_long.nlong == 0 && s->sw.aty_post2) {   // one pass, Rd1 not stored (vec_kernels.hip)
-        s->prof_begin(K_POST);
-        rc = launch_aty_post2(L, s->At_rp.p, s->At_ci.p, s->At_v.p, s->y_d.p, s->C.p, s->S.p, s->X.p, tau * s->sig, s->partials.p,
-                              s->out_w + (size_t)m, s->st);
-        s->prof_end(K_POST, 40.0 * (double)L);
-        if (rc) return rc;
-      } else {
-        if ((rc = s->launch_aty(false))) return rc;
-        if ((rc = s->launch_post_mode(2, tau))) return rc;
-      }
-      if ((rc = s->launch_spmv(true, false))) return rc;
-      if ((rc = s->fetch_out(0, (size_t)m + 2, solve_next_ok))) return rc;   // [A*X | sums]; A*(S-C) unchanged since the half step
-    } else {
-      if (snapshot) {
-        if (!s->X_best.p && L > 0) { if ((rc = s->X_best.alloc(L)) || (rc = s->S_best.alloc(L))) return rc; }
-        if (!s->fuse && (rc = s->launch_post_mode(1, tau))) return rc;
-        s->prof_begin(K_COPY);
-        CUADMM_HIP_TRY(hipMemcpyAsync(s->X_best.p, s->X.p, sizeof(double) * (size_t)L, hipMemcpyDeviceToDevice, s->st));
-        CUADMM_HIP_TRY(hipMemcpyAsync(s->S_best.p, s->S.p, sizeof(double) * (size_t)L, hipMemcpyDeviceToDevice, s->st));
-        s->prof_end(K_COPY, 32.0 * (double)L);
-        if (s->dev_solve) {
-          if (!s->y_best_d.p && (rc = s->y_best_d.alloc(std::max(m, 1)))) return rc;
-          CUADMM_HIP_TRY(hipMemcpyAsync(s->y_best_d.p, s->y_d.p, sizeof(double) * (size_t)m, hipMemcpyDeviceToDevice, s->st));
-        } else {
-          s->y_best_p = s->y_p;
-        }
-        s->have_best = true;
-        if ((rc = s->launch_post_mode(2, tau))) return rc;
-      } else if (!s->fuse) {
-        if ((rc = s->launch_post_mode(0, tau))) return rc;
-      }
-      if ((rc = s->launch_spmv(true, true, s->fuse && !snapshot))) return rc;
-      if ((rc = s->fetch_out(0, 2 * (size_t)m + 2, solve_next_ok))) return rc;
-    }
-
-    // ---- Step 5 (solver.cu:764-799)
-    const double sig_of_iter = s->sig;
-    {
-      double t0 = wall_s();
-      double nr = 0, bty = 0;
-      const double* ax = s->h_out.p;
-      double part[2 * kHostChunks] = {0};
-      if (!s->dev_solve) host_ranges(m, [&](int c, int lo, int hi) {
-        double a = 0, b = 0;
-        for (int i = lo; i < hi; ++i) {
-          const double rp = -ax[i] + s->b_p[i];
-          s->Rp_p[i] = rp;
-          const double ro = s->normA_p[i] * rp * s->bscale;
-          a += ro * ro;
-          b += s->b_p[i] * s->y_p[i];
-        }
-        part[2 * c] = a; part[2 * c + 1] = b;
-      });
-      for (int c = 0; c < kHostChunks; ++c) { nr += part[2 * c]; bty += part[2 * c + 1]; }
-      {
-        double v[4] = {nr, bty, s->h_out.p[(size_t)m], s->h_out.p[(size_t)m + 1]};
-        if (from_batch) {
-          for (int q = 0; q < 4; ++q) v[q] = s->bt.h.p[4 * (size_t)s->bt.pos + q];
-          if (++s->bt.pos == s->bt.len) s->bt.len = s->bt.pos = 0;
-        } else if (s->dev_scalars || s->dev_solve) { for (int q = 0; q < 4; ++q) v[q] = s->h_scal.p[q]; }   // formed (and summed over ranks) on the device
-        else if ((rc = s->allreduce_scalars(v, 4))) return rc;
-        nr = v[0]; bty = v[1]; s->h_out.p[(size_t)m] = v[2]; s->h_out.p[(size_t)m + 1] = v[3];
-        // a lost row exchange of the four-workgroups-per-row tail kernel leaves NaN in y and with it in these sums: stop NOW (not at
-        // max_iter), report once, and leave the handle on the two-GEMV path (TailSolve::take_failure)
-        if (s->tail.d_fail && !(std::fabs(nr) <= 1.7976931348623157e308 && std::fabs(bty) <= 1.7976931348623157e308)) {
-          const int tf = s->tail.take_failure(s->st);
-          if (tf != 0) {
-            set_error("solve: the dense tail of the A*A^T solve lost %d row exchanges at iteration %d (workgroups of a row not co-resident for seconds): "
-                      "y is not valid; the handle now uses the two-pass tail kernels", tf, iter);
-            return CUADMM_ERR_FACTOR;
-          }
-        }
-      }
-      s->set_residual_scalars(nr, bty);
-      s->feasratio = s->ratioconst * s->errRp / s->errRd;
-      if (s->feasratio < 1) s->prim_win += 1; else s->dual_win += 1;
-      if (sig_may_change) {
-        if (s->prim_win > 1.2 * s->dual_win) { s->prim_win = 0; s->sig = std::min(s->sigmax, s->sig * sigscale); }
-        else if (s->dual_win > 1.2 * s->prim_win) { s->dual_win = 0; s->sig = std::max(s->sigmin, s->sig / sigscale); }
-      }
-      s->prof_host(K_HOST, wall_s() - t0);
-    }
-    s->info[CUADMM_INFO_POBJ].push_back(s->pobj); s->info[CUADMM_INFO_DOBJ].push_back(s->dobj);
-    s->info[CUADMM_INFO_ERRRP].push_back(s->errRp); s->info[CUADMM_INFO_ERRRD].push_back(s->errRd);
-    s->info[CUADMM_INFO_RELGAP].push_back(s->relgap); s->info[CUADMM_INFO_SIG].push_back(s->sig);
-    s->info[CUADMM_INFO_BSCALE].push_back(s->bscale); s->info[CUADMM_INFO_CSCALE].push_back(s->Cscale);
-    s->info_iter_num++;
-    // longest block first (PsdPlan::reorder_by_steps): at iterations 3, 24, 192, ... of this solve the stream is idle here
-    if (s->fuse && lpt_ev > 0) ++s->lpt_iters;
-    if (s->fuse && lpt_ev > 0 && s->lpt_iters >= lpt_ev && s->bt.len == 0 && s->steps_d.p && !s->can_batch()) {
-      s->steps_h.resize(s->steps_d.n);
-      if ((rc = staged_d2h(s->steps_h.data(), s->steps_d.p, sizeof(int) * s->steps_d.n, s->st))) return rc;
-      if ((rc = s->plan.reorder_by_steps(s->steps_h.data(), s->st))) return rc;
-      lpt_ev *= 8;
-    }
-    // ---- acceleration: behind the iteration, on every path (the scalars above are those of the plain iterate f_k)
-    if (s->accel_on()) {
-      if ((rc = s->accel_step(iter, max_iter, stop_tol, switch_admm, tau, s->sig != sig_of_iter, sig_may_change_at(iter + 1)))) return rc;
-    }
-    // ---- infeasibility check: on the state at the end of the iteration, after the sigma update
-    if (s->infeas_on() && iter % s->inf.period == 0 && (rc = s->infeas_step(iter, stop_tol))) return rc;
-    // ---- certified-gap check: the lower bound at this iteration's y against this iteration's pobj
-    if (s->gap_on() && iter % s->lb.period == 0 && (rc = s->lb_step(iter, stop_tol))) return rc;
-  }
-
-  // unscale (solver.cu:814-816) -- deferred until somebody reads or replaces X, y, S (materialise): a following
-  // solve(if_first = false) continues from the scaled state.  With owned constraints over several ranks the y gather is a
-  // collective, so there it happens here, where every rank is.
-  s->pending_unscale = true;
-  if (s->lazy_unscale == 0 || (s->local_mode && s->comm_world > 1)) { if ((rc = s->materialise())) return rc; }
-  if (s->tail.k > 0) {
-    const int tf = s->tail.take_failure(s->st);
-    if (tf != 0) { set_error("solve: the dense tail of the A*A^T solve lost %d row exchanges (workgroups of a row not co-resident for seconds): y is not valid", tf); return CUADMM_ERR_FACTOR; }
-  }
-  s->eig_fail_total = s->plan.fail_count(s->st);
-  if (s->eig_fail_total > 0) {
-    set_error("solve: %d block projections hit the QL sweep cap", s->eig_fail_total);
-    return CUADMM_ERR_EIG;
-  }
-  return CUADMM_OK;
-}
-
-// per-solve bookkeeping as init leaves it, in front of the residual stage (profile counters, plans, the blocks' launch order stay)
-int cuadmm_solver::reset_solve_state(double t_begin) {
-  for (auto& a : info) a.clear();
-  info_iter_num = 0;
-  t_init0 = t_begin; total_time = 0;
-  best_KKT = 0; sgs_KKT = 0; have_best = false; eig_fail_total = 0;
-  prim_win = 0; dual_win = 0; feasratio = 0; ratioconst = 1e0; sigmax = 1e3; sigmin = 1e-3;
-  y_early = false; stats_fused = false;
-  bt.len = bt.pos = 0; bt.have_ck = false;
-  closed.iters_done = 0; closed.out_dirty = true;
-  infeas_reset();
-  lb_reset();
-  plan.n_project = 0;
-  if (hint_d.p) CUADMM_HIP_TRY(hipMemsetAsync(hint_d.p, 0, sizeof(int) * hint_d.n, st));     // the sign schedule's warm start
-  if (closed.cl_out.p) CUADMM_HIP_TRY(hipMemsetAsync(closed.cl_out.p, 0, sizeof(double) * closed.cl_out.n, st));
-  if (!dev_solve) std::fill(Rp_p.begin(), Rp_p.end(), 0.0);
-  y_full.clear();
-  return CUADMM_OK;
-}
-
-// y_d -> y_p after cuadmm_update_bC left the rescaled y on the device only
-int cuadmm_solver::sync_y_host() {
-  if (!y_host_stale) return CUADMM_OK;
-  y_host_stale = false;
-  if (m <= 0) return CUADMM_OK;
-  int rc;
-  if ((rc = check_device(device))) return rc;
-  CUADMM_HIP_TRY(hipMemcpyAsync(h_y.p, y_d.p, sizeof(double) * (size_t)m, hipMemcpyDeviceToHost, st));
-  CUADMM_HIP_TRY(hipStreamSynchronize(st));
-  std::memcpy(y_p.data(), h_y.p, sizeof(double) * (size_t)m);
-  return CUADMM_OK;
-}
-
-int cuadmm_solver::materialise() {
-  if (!pending_unscale) return sync_y_host();
-  pending_unscale = false;
-  y_host_stale = false;                 // y_d is copied down below
-  int rc;
-  if ((rc = check_device(device))) return rc;
-  if ((rc = launch_scale(X.p, L, bscale, st))) return rc;
-  if ((rc = launch_scale(S.p, L, Cscale, st))) return rc;
-  if (dev_solve && m > 0) {
-    if (y_registered) CUADMM_HIP_TRY(hipMemcpyAsync(y_p.data(), y_d.p, sizeof(double) * (size_t)m, hipMemcpyDeviceToHost, st));
-    else {   // never a runtime copy into pageable memory (staging.hip)
-      CUADMM_HIP_TRY(hipMemcpyAsync(h_y.p, y_d.p, sizeof(double) * (size_t)m, hipMemcpyDeviceToHost, st));
-      CUADMM_HIP_TRY(hipStreamSynchronize(st));
-      std::memcpy(y_p.data(), h_y.p, sizeof(double) * (size_t)m);
-    }
-  }
-  CUADMM_HIP_TRY(hipStreamSynchronize(st));
-  for (int i = 0; i < m; ++i) y_p[i] = y_p[i] / normA_p[i] * Cscale;
-  if (local_mode) {   // y is replicated for the caller: gather the owned pieces once per solve
-    y_full.assign((size_t)m_full, 0.0);
-    for (int i = 0; i < m; ++i) y_full[cons_local[perm[i]]] = y_p[i];
-    if (comm_world > 1 && m_full > 0) {
-      if (!yfull_d.p && (rc = yfull_d.alloc((size_t)m_full))) return rc;
-      if ((rc = staged_h2d(yfull_d.p, y_full.data(), sizeof(double) * (size_t)m_full, st))) return rc;
-      if ((rc = comm_allreduce(yfull_d.p, (size_t)m_full))) return rc;
-      if ((rc = staged_d2h(y_full.data(), yfull_d.p, sizeof(double) * (size_t)m_full, st))) return rc;
-    }
-  }
-  return CUADMM_OK;
-}
-
-// ------------------------------------------------------------------------------------------
-// Acceleration (option "accel"): DESIGN.md, "Acceleration"
-// ------------------------------------------------------------------------------------------
-// start of every solve: buffers on first use, empty memory, u_0 = the state the first iteration starts from
-int cuadmm_solver::accel_begin_solve() {
-  int rc;
-  if (!aa.fbuf.p) {
-    aa.hs = (L + 1) & ~1LL;
-    const size_t n2 = 2 * (size_t)aa.hs;
-    if ((rc = aa.ring_dF.alloc(n2 * aa.mem)) || (rc = aa.ring_dG.alloc(n2 * aa.mem)) || (rc = aa.state[0].alloc(n2)) || (rc = aa.gbuf.alloc(n2)) ||
-        (rc = aa.state[1].alloc(n2)) || (rc = aa.partials.alloc(kAccelPartials)) || (rc = aa.dots.alloc(kAccelDots)) || (rc = aa.h_dots.alloc(kAccelDots)) ||
-        (rc = aa.fb_y.alloc(std::max(m, 1))) || (rc = aa.fb_out.alloc(2 * (size_t)m + 2)))
-      return rc;
-    aa.fbuf.p = aa.state[0].p; aa.ubuf.p = aa.state[1].p;
-    // the pad element of an odd L is never read, but a column is copied whole nowhere either: zero once, for tidy dumps
-    CUADMM_HIP_TRY(hipMemsetAsync(aa.ubuf.p, 0, sizeof(double) * n2, st));
-    CUADMM_HIP_TRY(hipMemsetAsync(aa.fbuf.p, 0, sizeof(double) * n2, st));
-    CUADMM_HIP_TRY(hipMemsetAsync(aa.gbuf.p, 0, sizeof(double) * n2, st));
-    if (profile) for (auto& e : aa.ev) if ((rc = e.create())) return rc;
-  }
-  accel_clear();
-  CUADMM_HIP_TRY(hipMemcpyAsync(aa.fbuf.p, X.p, sizeof(double) * (size_t)L, hipMemcpyDeviceToDevice, st));
-  CUADMM_HIP_TRY(hipMemcpyAsync(aa.fbuf.p + aa.hs, S.p, sizeof(double) * (size_t)L, hipMemcpyDeviceToDevice, st));
-  return CUADMM_OK;
-}
-
-// End of iteration `iter` (its scalars are recorded, sigma may have changed in its step 5).  X, S hold f_k = F(u_k).
-int cuadmm_solver::accel_step(int iter, int max_iter, double stop_tol, int switch_admm, double tau, bool sig_changed, bool next_sig_may_change) {
-  int rc;
-  const size_t n2 = 2 * (size_t)aa.hs;
-  const bool timed = profile != 0 && aa.ev[0];
-  auto elapsed = [&](int a) { if (timed) aa.ms += event_ms(aa.ev[a], aa.ev[a + 1]); };   // after a synchronisation behind ev[a + 1]
-  // the map changed under this iteration's feet (sigma in step 5): nothing held describes the new map.  (No candidate is ever
-  // pending here: none is taken in front of an iteration that may change sigma.)
-  if (sig_changed) {
-    accel_clear();
-    aa.restarts++;
-    CUADMM_HIP_TRY(hipMemcpyAsync(aa.fbuf.p, X.p, sizeof(double) * (size_t)L, hipMemcpyDeviceToDevice, st));
-    CUADMM_HIP_TRY(hipMemcpyAsync(aa.fbuf.p + aa.hs, S.p, sizeof(double) * (size_t)L, hipMemcpyDeviceToDevice, st));
-    return CUADMM_OK;
-  }
-  // g_k, the new columns, f_k.  Behind a candidate u_k is ubuf and f_k goes there too, so that fbuf still holds the fallback.
-  const bool was_pending = aa.pending;
-  const bool have_col = aa.have_prev;
-  const int slot = aa.head;
-  double* const u = was_pending ? aa.ubuf.p : aa.fbuf.p;
-  if (timed) CUADMM_HIP_TRY(hipEventRecord(aa.ev[0], st));
-  if ((rc = launch_aa_push(L, aa.hs, u, X.p, S.p, sig, aa.fbuf.p, aa.gbuf.p, have_col ? 1 : 0, aa.gbuf.p, u, aa.ring_dF.p + (size_t)slot * n2,
-                           aa.ring_dG.p + (size_t)slot * n2, aa.partials.p, aa.dots.p + 2 * kAccelMaxMem, st)))
-    return rc;
-  int cols_new = aa.cols;
-  if (have_col) {
-    cols_new = std::min(aa.cols + 1, aa.mem);
-    if ((rc = launch_aa_gram(L, aa.hs, (long long)n2, cols_new, slot, aa.ring_dG.p, aa.gbuf.p, aa.partials.p, aa.dots.p, st))) return rc;
-  }
-  if (timed) CUADMM_HIP_TRY(hipEventRecord(aa.ev[1], st));
-  CUADMM_HIP_TRY(hipMemcpyAsync(aa.h_dots.p, aa.dots.p, sizeof(double) * kAccelDots, hipMemcpyDeviceToHost, st));
-  CUADMM_HIP_TRY(hipStreamSynchronize(st));
-  elapsed(0);
-  const double gnorm2 = aa.h_dots.p[2 * kAccelMaxMem];
-
-  if (was_pending) {
-    aa.pending = false;
-    const bool reject = !(aa.safeguard > 0) || !(std::sqrt(gnorm2) <= aa.safeguard * std::sqrt(aa.gnorm2_prev));
-    if (reject) {
-      // back to f_k, bit for bit: X, S, y, the fetched vectors, the scalars of the stopping test.  The wasted iteration stays recorded.
-      CUADMM_HIP_TRY(hipMemcpyAsync(X.p, aa.fbuf.p, sizeof(double) * (size_t)L, hipMemcpyDeviceToDevice, st));
-      CUADMM_HIP_TRY(hipMemcpyAsync(S.p, aa.fbuf.p + aa.hs, sizeof(double) * (size_t)L, hipMemcpyDeviceToDevice, st));
-      if (dev_solve) CUADMM_HIP_TRY(hipMemcpyAsync(y_d.p, aa.fb_y.p, sizeof(double) * (size_t)m, hipMemcpyDeviceToDevice, st));
-      else { std::copy(aa.h_fb_y.begin(), aa.h_fb_y.end(), y_p.begin()); std::copy(aa.h_fb_Rp.begin(), aa.h_fb_Rp.end(), Rp_p.begin()); }
-      if (!out_mapped) CUADMM_HIP_TRY(hipMemcpyAsync(out_d.p, aa.fb_out.p, sizeof(double) * (2 * (size_t)m + 2), hipMemcpyDeviceToDevice, st));
-      if (hint_d.p) CUADMM_HIP_TRY(hipMemcpyAsync(hint_d.p, aa.fb_hint.p, sizeof(int) * hint_d.n, hipMemcpyDeviceToDevice, st));
-      plan.n_project = aa.fb_nproj; closed.iters_done = aa.fb_iters_done;
-      CUADMM_HIP_TRY(hipStreamSynchronize(st));
-      std::copy(aa.h_fb_out.begin(), aa.h_fb_out.end(), h_out.p);
-      closed.out_dirty = true;
-      errRp = aa.sc[0]; errRd = aa.sc[1]; maxfeas = aa.sc[2]; pobj = aa.sc[3]; dobj = aa.sc[4]; relgap = aa.sc[5]; feasratio = aa.sc[6];
-      prim_win = aa.sc_win[0]; dual_win = aa.sc_win[1];
-      accel_clear();
-      aa.rejected++;
-      return CUADMM_OK;
-    }
-    aa.accepted++;
-    std::swap(aa.fbuf.p, aa.ubuf.p);      // f_k was written over the candidate
-  }
-  if (have_col) {
-    // the Gram matrix by ring slot: row and column `slot` are the new column's
-    for (int j = 0; j < cols_new; ++j) aa.G[slot][j] = aa.G[j][slot] = aa.h_dots.p[j];
-    aa.cols = cols_new;
-    aa.head = (slot + 1) % aa.mem;
-  }
-  aa.have_prev = true;
-
-  // what the next iteration will be
-  const int nx = iter + 1;
-  double tau_next = (nx < switch_admm) ? 1.95 : 1.618;
-  if (errRd < stop_tol) tau_next = std::max(1.618, tau_next / 1.1);
-  if (tau_next != tau || nx == switch_admm) {     // another map from the next iteration on
-    accel_clear();
-    aa.restarts++;
-    return CUADMM_OK;
-  }
-  // no candidate in front of the pass that stops (the result is a plain iterate), nor in front of a possible sigma update
-  if (nx > max_iter || std::max(maxfeas, relgap) < stop_tol || next_sig_may_change || aa.cols < 2) return CUADMM_OK;
-
-  double gram[kAccelMaxMem * kAccelMaxMem], rhs[kAccelMaxMem], gamma[kAccelMaxMem];
-  for (int i = 0; i < aa.cols; ++i) {
-    rhs[i] = aa.h_dots.p[cols_new + i];
-    for (int j = 0; j < aa.cols; ++j) gram[i * aa.cols + j] = aa.G[i][j];
-  }
-  if (accel_solve_ls(gram, rhs, aa.cols, aa.reg, gamma) != CUADMM_OK) {     // degenerate columns: start the memory afresh
-    accel_clear();
-    aa.restarts++;
-    return CUADMM_OK;
-  }
-  // the fallback beside fbuf: y, the fetched vectors, the host scalars
-  if (dev_solve) CUADMM_HIP_TRY(hipMemcpyAsync(aa.fb_y.p, y_d.p, sizeof(double) * (size_t)m, hipMemcpyDeviceToDevice, st));
-  else { aa.h_fb_y = y_p; aa.h_fb_Rp = Rp_p; }
-  if (!out_mapped) CUADMM_HIP_TRY(hipMemcpyAsync(aa.fb_out.p, out_d.p, sizeof(double) * (2 * (size_t)m + 2), hipMemcpyDeviceToDevice, st));
-  if (hint_d.p) {
-    if (!aa.fb_hint.p && (rc = aa.fb_hint.alloc(hint_d.n))) return rc;
-    CUADMM_HIP_TRY(hipMemcpyAsync(aa.fb_hint.p, hint_d.p, sizeof(int) * hint_d.n, hipMemcpyDeviceToDevice, st));
-  }
-  aa.fb_nproj = plan.n_project; aa.fb_iters_done = closed.iters_done;
-  aa.h_fb_out.assign(h_out.p, h_out.p + 2 * (size_t)m + 2);
-  aa.sc[0] = errRp; aa.sc[1] = errRd; aa.sc[2] = maxfeas; aa.sc[3] = pobj; aa.sc[4] = dobj; aa.sc[5] = relgap; aa.sc[6] = feasratio;
-  aa.sc_win[0] = prim_win; aa.sc_win[1] = dual_win;
-  aa.gnorm2_prev = gnorm2;
-
-  if (timed) CUADMM_HIP_TRY(hipEventRecord(aa.ev[2], st));
-  if ((rc = launch_aa_combine(L, aa.hs, (long long)n2, aa.cols, aa.ring_dF.p, gamma, sig, X.p, S.p, aa.ubuf.p, st))) return rc;
-  if (timed) CUADMM_HIP_TRY(hipEventRecord(aa.ev[3], st));
-  // X and S were overwritten: [A X | sums | A (S - C)] and Rp again, as a continued solve forms them
-  if ((rc = launch_spmv(true, true))) return rc;
-  if ((rc = fetch_out(0, 2 * (size_t)m + 2))) return rc;
-  refresh_Rp();
-  elapsed(2);
-  aa.pending = true;
-  aa.taken++;
-  return CUADMM_OK;
-}
-
 // SDPDuoSolver front (duo_solver.h:236-276): exactly two block sizes, then the generic engine.
 int cuadmm_duo_init(cuadmm_solver* s, int if_gpu_eig_mom, int device_num_requested, int eig_stream_num_per_gpu,
                     int cpu_eig_thread_num, int vec_len, int con_num, const int* At_cp, const int* At_ri, const double* At_vx,
@@ -1608,10 +1050,6 @@ int cuadmm_duo_init(cuadmm_solver* s, int if_gpu_eig_mom, int device_num_request
                        b_nnz, C_idx, C_vals, C_nnz, blk, mat_num, X0, y0, S0, sig);
   s->verbose = verbose;
   return rc;
-}
-int cuadmm_duo_solve(cuadmm_solver* s, int max_iter, double stop_tol, int sig_update_threshold, int sig_update_stage_1,
-                     int sig_update_stage_2, int switch_admm, double sigscale, int if_first) {
-  return cuadmm_solve(s, max_iter, stop_tol, sig_update_threshold, sig_update_stage_1, sig_update_stage_2, switch_admm, sigscale, if_first);
 }
 
 int cuadmm_get_dims(const cuadmm_solver* s, int* vec_len, int* con_num, int* mat_num) {

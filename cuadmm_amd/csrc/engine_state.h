@@ -91,6 +91,8 @@ struct cuadmm_solver {
   // all-reduced on the stream and copied down with the result vector: one stream synchronisation per iteration, no
   // H2D -> collective -> D2H -> sync round trip of their own
   bool dev_scalars = false;
+  // where a reduction leaves scalars for the host: the pinned buffer itself through its device mapping when no collective follows
+  double* scalars_dst(double* mapped, double* dev) const { return (!dev_scalars && mapped) ? mapped : dev; }
   // Device-side y-solve (forest_solve_kernel) when the elimination forest of the factor is many small trees (block-diagonal
   // A A^T: C2, C4, ros_2000 ...): y, A X, A(S-C), b stay in HBM, the host fetches only the four scalars of the stopping test.
   bool dev_solve = false;
@@ -297,6 +299,8 @@ struct cuadmm_solver {
   void accel_clear() { aa.cols = 0; aa.head = 0; aa.have_prev = false; aa.pending = false; }
   int accel_begin_solve();
   int accel_step(int iter, int max_iter, double stop_tol, int switch_admm, double tau, bool sig_changed, bool next_sig_may_change);
+  int accel_reject();                                   // accel_step's two arms behind a candidate's verdict: back to the fallback f_k,
+  int accel_candidate(int cols_new, double gnorm2);     // or the next candidate from the columns held
 
   // Infeasibility detection behind the iteration (option "infeas_check" = period p; infeas.h, DESIGN.md "Infeasibility certificates").
   // Every p iterations the differences of y and X against the snapshot taken p iterations earlier are tested for the two certificates.
@@ -433,303 +437,28 @@ struct cuadmm_solver {
     if (world <= 1 && !force_comm) return CUADMM_OK;
     return comm_allreduce(buf, count);
   }
-  // all-reduce over the communicator (the sharding world, or comm_world in owned-constraints mode)
-  int comm_allreduce(double* buf, size_t count) {
-    prof_begin(K_COMM);
-    int rc = 0;
-    if (allreduce) {
-      rc = allreduce(allreduce_user, buf, count, (void*)st);
-    } else if (rccl_comm) {
-      rc = g_rccl.AllReduce(buf, buf, count, /*ncclFloat64*/ 8, /*ncclSum*/ 0, rccl_comm, st);
-    } else {
-      set_error("world=%d but no all-reduce hook installed (cuadmm_set_allreduce / cuadmm_use_rccl)", local_mode ? comm_world : world);
-      return CUADMM_ERR_COMM;
-    }
-    prof_end(K_COMM, (double)count * 8);
-    if (rc) { set_error("all-reduce hook failed with code %d", rc); return CUADMM_ERR_COMM; }
-    return CUADMM_OK;
-  }
-
-  // owned-constraints mode: v[0..n) <- sum over ranks (host values through a small device buffer; blocks)
-  int allreduce_scalars(double* v, int n) {
-    if (!local_mode || comm_world <= 1) return CUADMM_OK;
-    // through the page-locked h_scal: the runtime must never register stack or caller memory (staging.hip)
-    for (int q = 0; q < n; ++q) h_scal.p[q] = v[q];
-    CUADMM_HIP_TRY(hipMemcpyAsync(scal_d.p, h_scal.p, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, st));
-    int rc = comm_allreduce(scal_d.p, (size_t)n);
-    if (rc) return rc;
-    CUADMM_HIP_TRY(hipMemcpyAsync(h_scal.p, scal_d.p, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, st));
-    CUADMM_HIP_TRY(hipStreamSynchronize(st));
-    for (int q = 0; q < n; ++q) v[q] = h_scal.p[q];
-    return CUADMM_OK;
-  }
-
-  // in_fused_step: the projection launch that follows solves for y itself (closed blocks)
-  int host_solve(bool in_fused_step = false) {  // y_p = (P(AA^T+eps I)P^T)^-1 rhs_p
-    double t0 = wall_s();
-    const double isig = 1 / sig;
-    if (in_fused_step && closed.active) return CUADMM_OK;
-    if (dev_solve) {   // everything it needs is in HBM (out_d: [A X | sums | A(S-C)]); y_d is the result
-      prof_begin(K_TAIL);
-      int rc = lead.ready ? lead.solve(out_d.p, out_d.p + (size_t)m + 2, b_d.p, isig, y_d.p, tail, st) : launch_forest_solve(forest_trees, f_tree_ptr.p, f_tree_cols.p, f_Lp.p, f_Li.p, f_Lx.p, f_D.p, out_d.p, out_d.p + (size_t)m + 2,
-                                   b_d.p, isig, y_d.p, st);
-      prof_end(K_TAIL, tail.k > 0 ? tail.shard_bytes : 0.0);     // bytes of inv(L22) this rank read (1 / world of 4 K^2 when the tail is sharded)
-      return rc;
-    }
-    // the right-hand side is formed in y_p from the pinned result buffer (A(S-C) lives at h_out[m+2..) since the last
-    // fetch) and solved in place: no copies of m-vectors on the critical path between two GPU phases
-    const double* asmc = h_out.p + (size_t)m + 2;
-    host_ranges(m, [&](int, int lo, int hi) {
-      for (int i = lo; i < hi; ++i) y_p[i] = -asmc[i] + isig * Rp_p[i];   // solver.cu:478-482
-    });
-    int rc;
-    if (tail.k == 0) {
-      rc = cuadmm_aat_solve_permuted(fac, y_p.data(), y_p.data());     // solver.cu:494
-    } else {   // sparse leading columns here, dense trailing triangle on the GPU
-      // hybrid (lead_solve.h): L21 lives on the device with the tail, the host sweeps L11 only
-      rc = lead.hybrid ? cuadmm_aat_solve_leading_forward11(fac, tail.k, y_p.data()) : cuadmm_aat_solve_leading_forward(fac, tail.k, y_p.data());
-      double t1 = wall_s();
-      if (!rc) rc = lead.hybrid ? lead.apply_l21(y_p.data(), y_registered, tail, st) : tail.solve(y_p.data() + (m - tail.k), st);
-      double t2 = wall_s();
-      prof_host(K_TAIL, t2 - t1);
-      t0 += t2 - t1;
-      if (!rc) rc = lead.hybrid ? cuadmm_aat_solve_leading_backward11(fac, tail.k, y_p.data(), lead.h_w) : cuadmm_aat_solve_leading_backward(fac, tail.k, y_p.data());
-    }
-    prof_host(K_HOST, wall_s() - t0);
-    return rc;
-  }
-
-  int upload_y(bool force = false) {
-    if (dev_solve && !force) return CUADMM_OK;     // y is produced on the device
-    prof_begin(K_COPY);
-    // y_p is registered (page-locked) at init: the copy engine reads it directly; it is not written again before the
-    // next fetch_out has synchronised the stream
-    const double* src = y_p.data();
-    if (!y_registered) { std::memcpy(h_y.p, y_p.data(), sizeof(double) * (size_t)m); src = h_y.p; }
-    CUADMM_HIP_TRY(hipMemcpyAsync(y_d.p, src, sizeof(double) * (size_t)m, hipMemcpyHostToDevice, st));
-    prof_end(K_COPY, (double)m * 8);
-    return CUADMM_OK;
-  }
-
-  // D2H of out_d[first, first+count) after the optional all-reduce; blocks until it has landed.
-  // solve_next (round 5): the y-solve of the NEXT iteration is enqueued behind this iteration's last kernel BEFORE the host waits --
-  // and the host then waits for an event recorded in front of it, not for the stream.  The reference solves for y at the top of every
-  // pass through the loop, the breaking one included (solver.cu:478-500 precede the break), so that solve is never speculative; its only
-  // host input is sigma, which the caller knows will not change in this iteration's step 5.  The GPU runs the solve (0.2 - 0.4 ms on the
-  // moment relaxations) while the host goes through the stopping test and enqueues the rest of the next iteration: the idle gap at
-  // the iteration boundary (kernel trace: the largest one of a latency-bound iteration) is gone.
+  int comm_allreduce(double* buf, size_t count);      // all-reduce over the communicator (the sharding world, or comm_world in owned-constraints mode)
+  int allreduce_scalars(double* v, int n);            // owned-constraints mode: v[0..n) <- sum over ranks (host values through a small device buffer; blocks)
+  // y_p = (P(AA^T+eps I)P^T)^-1 rhs_p; in_fused_step: the projection launch that follows solves for y itself (closed blocks)
+  int host_solve(bool in_fused_step = false);
+  int upload_y(bool force = false);                   // y_p -> y_d (nothing to do with the y-solve on the device, unless forced)
+  // D2H of out_d[first, first+count) after the optional all-reduce; blocks until it has landed.  solve_next: engine_iter.hip
   bool y_early = false;           // y_d already holds the y-solve of the coming iteration
   DevEvent ev_early;
-  int fetch_out(size_t first, size_t count, bool solve_next = false) {
-    if (!out_mapped) {
-      int rc = do_allreduce(out_d.p + first, count);
-      if (rc) return rc;
-      if ((dev_scalars || dev_solve) && first == 0) {     // [||Rp||^2, b.y, sum Rd^2, <C,X>] (of this rank -> sum over ranks), on the stream
-        // without a collective in between the final stage writes the four scalars straight into the pinned host buffer
-        // through its device mapping: the fetch is then a stream synchronisation without a copy command
-        double* dst = (!dev_scalars && h_scal_dev) ? h_scal_dev : scal_d.p;
-        if (stats_fused) stats_fused = false;               // formed by launch_reduce_quads in this iteration's fused step
-        else if ((rc = launch_rp_stats(m, out_d.p, b_d.p, normA_d.p, y_d.p, bscale, out_d.p + (size_t)m, scal_d.p + 8, dst, st))) return rc;
-        if (dev_scalars) {
-          if ((rc = comm_allreduce(scal_d.p, 4))) return rc;
-        }
-        if (dst == scal_d.p) CUADMM_HIP_TRY(hipMemcpyAsync(h_scal.p, scal_d.p, sizeof(double) * 4, hipMemcpyDeviceToHost, st));
-      }
-      if (dev_solve) {
-        if (first != 0) return CUADMM_OK;                 // sGS half step: A(S-C) is consumed on the device, nothing to wait for
-      } else {
-        CUADMM_HIP_TRY(hipMemcpyAsync(h_out.p + first, out_d.p + first, sizeof(double) * count, hipMemcpyDeviceToHost, st));
-      }
-    }
-    // (measured and rejected, round 5: a one-thread kernel storing a sequence number into a mapped pinned word with the host spinning on
-    // it instead of this call -- c5 2 494 -> 2 476, c1 1 290 -> 1 274 iters/s: the runtime's wait already spins, the extra launch costs)
-    if (solve_next && dev_solve && !out_mapped && st != nullptr) {
-      // system-scope release: the host reads the pinned h_scal / h_out behind this wait (the stream synchronisation it replaces was one)
-      if (!ev_early) { int rc = ev_early.create(hipEventDisableTiming | hipEventReleaseToSystem); if (rc) return rc; }
-      CUADMM_HIP_TRY(hipEventRecord(ev_early, st));
-      { int rc = host_solve(); if (rc) { (void)hipStreamSynchronize(st); return rc; } }     // nothing of this iteration stays in flight behind an error
-      y_early = true;
-      CUADMM_HIP_TRY(hipEventSynchronize(ev_early));
-    } else {
-      CUADMM_HIP_TRY(hipStreamSynchronize(st));
-    }
-    prof_collect();
-    return CUADMM_OK;
-  }
-
-  int launch_aty(bool write_xb) {
-    prof_begin(K_ATY);
-    int rc = launch_aty_xb(write_xb, L, At_rp.p, At_ci.p, At_v.p, y_d.p, C.p, X.p, sig, Rd1.p, Xb.p, st, &At_long);
-    prof_end(K_ATY, (write_xb ? 32.0 : 16.0) * (double)L + 4.0 * (double)L);
-    return rc;
-  }
+  int fetch_out(size_t first, size_t count, bool solve_next = false);
+  int launch_aty(bool write_xb);
   // after_fused: the local rows were written by the fused projection kernels of this step -- only the other rows are left
-  int launch_spmv(bool doX, bool doS, bool after_fused = false) {
-    if (!(after_fused && lrows.active && lrows.nrest == 0)) closed.out_dirty = true;
-    if (after_fused && lrows.active) {
-      if (lrows.nrest == 0) return CUADMM_OK;
-      prof_begin(K_SPMV);
-      int rc = launch_spmv_rows(lrows.nrest, lrows.rest_avg, lrows.rest_rp.p, lrows.rest_ci.p, lrows.rest_v.p, X.p, S.p, C.p, doX ? out_w : nullptr,
-                                doS ? out_w + m + 2 : nullptr, st, nullptr, lrows.rest_map.p);
-      prof_end(K_SPMV, 12.0 * (double)lrows.rest_v.n + 8.0 * lrows.nrest * ((doX ? 1 : 0) + (doS ? 1 : 0)));
-      return rc;
-    }
-    prof_begin(K_SPMV);
-    int rc = launch_spmv_rows(m, A_avg_nnz, A_rp.p, A_ci.p, A_v.p, X.p, S.p, C.p, doX ? out_w : nullptr,
-                              doS ? out_w + m + 2 : nullptr, st, &A_long);
-    prof_end(K_SPMV, 12.0 * (double)A_v.n + 8.0 * m * ((doX ? 1 : 0) + (doS ? 1 : 0)));
-    return rc;
-  }
-  int launch_project() {
-    prof_begin(K_PSD);
-    int rc = plan.project(Xb.p, Xproj.p, st);
-    prof_end(K_PSD, 16.0 * (double)L);
-    return rc;
-  }
-  // Step 2 of a fused iteration: Rd1 / Xb on the rest of the svec, then the projection whose fused blocks also do the
-  // post step `mode` (0: S, X, sums; 1: S only) on their own ranges, then the post step on the rest (+ the sums).
-  int launch_fused_step(int mode, double tau, int iters = 1) {
-    int rc;
-    prof_begin(K_ATY);
-    rc = launch_aty_xb_idx(plan.n_rest, plan.d_rest, At_rp.p, At_ci.p, At_v.p, y_d.p, C.p, X.p, sig, Rd1.p, Xb.p, st);
-    prof_end(K_ATY, 36.0 * (double)plan.n_rest);
-    if (rc) return rc;
-    SignFuse fz{};                                     // every optional part (local rows, closed blocks) off
-    fz.rp = At_rp.p; fz.ci = At_ci.p; fz.av = At_v.p; fz.y = y_d.p; fz.C = C.p;
-    fz.X = X.p; fz.Rd1 = Rd1.p; fz.S = S.p; fz.partials = partials.p;
-    fz.sig = sig; fz.inv_sig = 1 / sig; fz.tau_sig = tau * sig; fz.mode = mode;
-    if (lrows.active) {
-      fz.lc = lrows.desc.p; fz.lc_row = lrows.row.p; fz.lc_nzptr = lrows.nzptr.p; fz.lc_e = lrows.e.p; fz.lc_v = lrows.v.p;
-      fz.outX = mode == 0 ? out_w : nullptr;
-      fz.outS = out_w + m + 2;
-    }
-    if (closed.active) {
-      fz.rec = closed.rec.p; fz.cl_out = closed.cl_out.p; fz.y_out = y_d.p;
-      fz.iter0 = (int)(closed.iters_done & 0x3fffffff);
-      closed.iters_done += iters > 1 ? iters : 1;
-      fz.partials2 = closed.partials2.p;
-      fz.isig = 1 / sig; fz.bscale = bscale;
-      if (closed.out_dirty) {
-        if ((rc = launch_closed_gather_out(closed.rec.p, plan.fused_blocks(), out_d.p, out_d.p + (size_t)m + 2, closed.cl_out.p, st))) return rc;
-        closed.out_dirty = false;
-      }
-    }
-    if (iters > 1) {   // batch: every block is closed and fused (can_batch), nothing runs beside the projection launches
-      fz.iters = iters; fz.pstride = bt.pstride; fz.partials = bt.p1.p; fz.partials2 = bt.p2.p;
-      prof_begin(K_PSD);
-      rc = plan.project(Xb.p, Xproj.p, st, &fz);
-      prof_end(K_PSD, 68.0 * (double)L * iters);
-      if (rc) return rc;
-      prof_begin(K_POST);
-      double* dst = (!dev_scalars && bt.h_dev) ? bt.h_dev : bt.scal_d.p;
-      rc = launch_reduce_quads_batch(bt.p1.p, bt.p2.p, plan.fused_blocks(), bt.pstride, iters, dst, st);
-      prof_end(K_POST, 0.0);
-      if (rc) return rc;
-      if (dev_scalars && (rc = comm_allreduce(bt.scal_d.p, 4 * (size_t)iters))) return rc;
-      if (dst == bt.scal_d.p) CUADMM_HIP_TRY(hipMemcpyAsync(bt.h.p, bt.scal_d.p, sizeof(double) * 4 * (size_t)iters, hipMemcpyDeviceToHost, st));
-      bt.launches++; bt.iters += iters;
-      return CUADMM_OK;
-    }
-    prof_begin(K_PSD);
-    rc = plan.project(Xb.p, Xproj.p, st, &fz);
-    prof_end(K_PSD, 68.0 * (double)(L - plan.n_rest) + 16.0 * (double)plan.n_rest);
-    if (rc) return rc;
-    prof_begin(K_POST);
-    stats_fused = closed.active && mode == 0;
-    int nparts = 0;
-    rc = launch_post_rest(mode, plan.n_rest, plan.d_rest, plan.fused_blocks(), Xproj.p, Rd1.p, C.p, X.p, S.p, 1 / sig, tau * sig, partials.p,
-                          out_w + (size_t)m, st, stats_fused ? &nparts : nullptr);
-    if (!rc && stats_fused) {   // all four scalars of the stopping test in one launch (rp_stats is not needed this iteration)
-      double* dst = (!dev_scalars && h_scal_dev) ? h_scal_dev : scal_d.p;
-      if (!quad_seg.p && reduce_quads_segments(nparts, plan.fused_blocks()) > 1 && (rc = quad_seg.alloc(4 * (size_t)reduce_quads_segments(nparts, plan.fused_blocks()) + 4))) return rc;
-      rc = launch_reduce_quads(partials.p, nparts, closed.partials2.p, plan.fused_blocks(), dst, out_w + (size_t)m, quad_seg.p, st);
-    }
-    prof_end(K_POST, (mode == 0 ? 48.0 : 32.0) * (double)plan.n_rest);
-    return rc;
-  }
+  int launch_spmv(bool doX, bool doS, bool after_fused = false);
+  int launch_project();
+  int launch_fused_step(int mode, double tau, int iters = 1);      // Step 2 of a fused iteration; iters > 1: a batch
+  int launch_post_mode(int mode, double tau);
   // --- several iterations per launch ---------------------------------------------------------------------------------
-  bool can_batch() const {
-    return can_batch_local() && bt.peers_agree && aa.mem == 0 && inf.period == 0 && lb.period == 0;
-  }
-  bool can_batch_local() const {
-    return bt.max_iters >= 2 && fuse && closed.active && dev_solve && !lead.ready && plan.n_rest == 0 && eig_rank == 0 && !out_mapped &&
-           plan.fused_blocks() > 0 && (bt.allow_mixed || plan.one_dominant_geometry());
-  }
-  // Ranks must take the batching decision TOGETHER: it decides which collective a rank issues (shards of a heterogeneous problem
-  // can differ: no dominant geometry on one, a block with more than 8 rows on another, no blocks at all on a third).  One small
-  // all-reduce at the start of every solve (options may have changed since the last one).
-  int batch_agree() {
-    bt.peers_agree = true;
-    const int cw = local_mode ? comm_world : world;
-    if (cw <= 1 && !force_comm) return CUADMM_OK;
-    if (!allreduce && !rccl_comm) return CUADMM_OK;      // no transport yet: the first collective of the solve reports it
-    h_scal.p[0] = can_batch_local() ? 1.0 : 0.0;
-    h_scal.p[1] = 1.0;
-    CUADMM_HIP_TRY(hipMemcpyAsync(scal_d.p, h_scal.p, sizeof(double) * 2, hipMemcpyHostToDevice, st));
-    int rc = comm_allreduce(scal_d.p, 2);
-    if (rc) return rc;
-    CUADMM_HIP_TRY(hipMemcpyAsync(h_scal.p, scal_d.p, sizeof(double) * 2, hipMemcpyDeviceToHost, st));
-    CUADMM_HIP_TRY(hipStreamSynchronize(st));
-    bt.peers_agree = h_scal.p[0] >= h_scal.p[1] - 0.5;    // every rank said yes
-    return CUADMM_OK;
-  }
-  int batch_alloc() {
-    // sized for the CURRENT option value: "batch" may be raised between solves, and a launch of K iterations writes K partial
-    // arrays and 4 K scalars
-    if (bt.p1.p && bt.cap >= bt.max_iters) return CUADMM_OK;
-    bt.pstride = 2 * (long long)plan.fused_blocks() + 2;
-    bt.cap = 0; bt.h_dev = nullptr;
-    int rc;
-    if ((rc = bt.p1.alloc((size_t)bt.pstride * bt.max_iters)) || (rc = bt.p2.alloc((size_t)bt.pstride * bt.max_iters)) ||
-        (rc = bt.scal_d.alloc(4 * (size_t)bt.max_iters)) || (rc = bt.h.alloc(4 * (size_t)bt.max_iters)))
-      return rc;
-    if (!bt.ck_X.p && ((rc = bt.ck_X.alloc(L)) || (rc = bt.ck_S.alloc(L)) || (rc = bt.ck_y.alloc(std::max(m, 1))) || (rc = bt.ck_out.alloc(2 * (size_t)m + 2))))
-      return rc;
-    bt.cap = bt.max_iters;
-    void* dp = nullptr;
-    if (sw.mapped_out && hipHostGetDevicePointer(&dp, bt.h.p, 0) == hipSuccess && dp) bt.h_dev = static_cast<double*>(dp);
-    else { hipError_t e = hipGetLastError(); (void)e; }
-    return CUADMM_OK;
-  }
-  int batch_copy(bool save) {   // checkpoint of everything an iteration reads and writes: X, S, y, [A X | sums | A (S - C)]
-    prof_begin(K_COPY);
-    struct { double* live; double* ck; size_t n; } v[4] = {{X.p, bt.ck_X.p, (size_t)L}, {S.p, bt.ck_S.p, (size_t)L}, {y_d.p, bt.ck_y.p, (size_t)m},
-                                                           {out_d.p, bt.ck_out.p, 2 * (size_t)m + 2}};
-    CopyJobs jobs{};                       // ONE launch for the whole checkpoint (five copies of ~0.03 ms each were 1.3 % of a batch of 44)
-    for (auto& q : v) {
-      jobs.dst[jobs.count] = save ? q.ck : q.live; jobs.src[jobs.count] = save ? q.live : q.ck; jobs.nbytes[jobs.count] = (long long)(q.n * sizeof(double));
-      ++jobs.count;
-    }
-    if (hint_d.p) {   // the schedule hints are part of the state an iteration reads and writes
-      if (!bt.ck_hint.p) { int rc = bt.ck_hint.alloc(hint_d.n); if (rc) return rc; }
-      jobs.dst[jobs.count] = save ? bt.ck_hint.p : hint_d.p; jobs.src[jobs.count] = save ? hint_d.p : bt.ck_hint.p; jobs.nbytes[jobs.count] = (long long)(sizeof(int) * hint_d.n);
-      ++jobs.count;
-    }
-    { int rc = launch_copy_multi(jobs, st); if (rc) return rc; }
-    if (save) bt.ck_iters_done = closed.iters_done; else closed.iters_done = bt.ck_iters_done;
-    prof_end(K_COPY, 16.0 * (2.0 * (double)L + 3.0 * m + 2));
-    return CUADMM_OK;
-  }
-  // the device ran bt.len iterations, the host schedule accepts only the first `keep` of them: back to the checkpoint and
-  // forward again by `keep` iterations (bit-identical: same kernels, same inputs)
-  int batch_rollback(int keep) {
-    if (!bt.have_ck) { set_error("internal: batch invalidated without a checkpoint"); return CUADMM_ERR_INVALID; }
-    int rc = batch_copy(false);
-    if (rc) return rc;
-    closed.out_dirty = true;
-    const double sig_now = sig;
-    sig = bt.sig;
-    if (keep == 1) rc = launch_fused_step(0, bt.tau);
-    else if (keep > 1) rc = launch_fused_step(0, bt.tau, keep);
-    sig = sig_now;
-    if (rc) return rc;
-    CUADMM_HIP_TRY(hipStreamSynchronize(st));
-    prof_collect();
-    stats_fused = false;
-    bt.len = bt.pos = 0;
-    bt.rollbacks++;
-    return CUADMM_OK;
-  }
+  bool can_batch() const;
+  bool can_batch_local() const;
+  int batch_agree();            // the ranks take the batching decision together, once per solve
+  int batch_alloc();
+  int batch_copy(bool save);    // checkpoint of everything an iteration reads and writes: X, S, y, [A X | sums | A (S - C)]
+  int batch_rollback(int keep); // back to the checkpoint and forward again by the `keep` iterations the host schedule accepted
   // X, S, y back in the caller's units (solver.cu:814-816); a no-op unless a solve left them scaled
   int materialise();
   int sync_y_host();
@@ -753,13 +482,6 @@ struct cuadmm_solver {
     pobj = h_out.p[(size_t)m + 1] * objscale;
     dobj = bty * objscale;
     relgap = std::fabs(pobj - dobj) / (1 + std::fabs(pobj) + std::fabs(dobj));
-  }
-
-  int launch_post_mode(int mode, double tau) {
-    prof_begin(K_POST);
-    int rc = launch_post(mode, L, Xproj.p, Rd1.p, C.p, X.p, S.p, 1 / sig, tau * sig, partials.p, out_w + (size_t)m, st);
-    prof_end(K_POST, (mode == 0 ? 48.0 : (mode == 1 ? 32.0 : 40.0)) * (double)L);
-    return rc;
   }
 };
 

@@ -3,7 +3,7 @@
 
 namespace cuadmm {
 
-// The svec-length vector work of one ADMM iteration, FUSED around the projection of a block (engine_state.h: launch_fused_step, PsdPlan::project):
+// The svec-length vector work of one ADMM iteration, FUSED around the projection of a block (engine_iter.hip: launch_fused_step, PsdPlan::project):
 //   prologue  Rd1 = A^T y - C,  Xb = X + sigma Rd1            (aty_xb_kernel; src/solver.cu:514-527) -- Xb never reaches HBM
 //   epilogue  S = (P(Xb) - X) / sigma - Rd1  [mode 1 stops here]
 //             Rd = Rd1 + S,  X += tau sigma Rd,  sum Rd^2,  <C, X>   (post_kernel<0>; solver.cu:652-656,746-758,774-776)

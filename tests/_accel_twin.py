@@ -1,4 +1,4 @@
-"""numpy twin of the accelerated iteration (option "accel": DESIGN.md, "Acceleration"; csrc/engine.hip, accel_step).
+"""numpy twin of the accelerated iteration (option "accel": DESIGN.md, "Acceleration"; csrc/engine_iter.hip, accel_step).
 
 Built on oracle.cuadmm_oracle.OracleSolver: its init, its scaling, _linsys and project.  ``accel_solve`` is OracleSolver.solve
 statement for statement with the acceleration attached behind step 5; with accel = 0 it reproduces that method bit for bit
@@ -150,7 +150,7 @@ def accel_solve(o, max_iter, stop_tol, sig_update_threshold=500, sig_update_stag
         if stage_hook is not None:
             stage_hook(it, "end", X=o.X, y=o.y, S=o.S)
 
-        # ---- acceleration, behind the iteration (engine.hip: accel_step)
+        # ---- acceleration, behind the iteration (engine_iter.hip: accel_step)
         if accel > 0:
             nx = it + 1
             next_sig_may_change = ((nx <= sig_update_threshold and nx % sig_update_stage_1 == 1) or

@@ -1,4 +1,4 @@
-"""Option "accel": safeguarded Anderson acceleration behind the iteration ("Acceleration"; csrc/accel.hip, csrc/engine.hip).
+"""Option "accel": safeguarded Anderson acceleration behind the iteration ("Acceleration"; csrc/accel.hip, csrc/engine_iter.hip).
 
 Op level: the three kernels against numpy in longdouble.  Engine level: accel = 0 changes nothing; trajectories against the numpy
 twin (tests/_accel_twin.py, recorded in tests/golden/accel_twin_traj.json by tests/golden/make_accel_traj.py); the safeguard drill;
