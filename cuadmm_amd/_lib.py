@@ -33,6 +33,9 @@ PROTOTYPES = {
     "cuadmm_create": (C.c_int, [C.POINTER(C.c_void_p)]),
     "cuadmm_destroy": (None, [C.c_void_p]),
     "cuadmm_set_option": (C.c_int, [C.c_void_p, C.c_char_p, C.c_double]),
+    "cuadmm_get_option": (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_double)]),
+    "cuadmm_option_count": (C.c_int, []),
+    "cuadmm_option_info": (C.c_int, [C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.POINTER(C.c_double), C.POINTER(C.c_uint)]),
     "cuadmm_set_allreduce": (C.c_int, [C.c_void_p, ALLREDUCE_FN, C.c_void_p]),
     "cuadmm_rccl_unique_id": (C.c_int, [C.c_char_p]),
     "cuadmm_use_rccl": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int, C.c_int]),

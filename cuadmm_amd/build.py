@@ -93,5 +93,17 @@ def build_host_sanitized():
     return out
 
 
+def build_option_selftest():
+    """ASan + UBSan build of tests/option_table_selftest.cpp, a program of its own over the host-only option tables, with the sanitizers'
+    runtimes linked statically (it needs no preload and runs beside whatever the environment preloads) -> cuadmm_amd/lib/option_table_selftest."""
+    os.makedirs(LIBDIR, exist_ok=True)
+    out = os.path.join(LIBDIR, "option_table_selftest")
+    deps = [os.path.join(HERE, "..", "tests", "option_table_selftest.cpp")] + [os.path.join(CSRC, h) for h in ("option_table.h", "psd_options.h")]
+    if not _newer(out, deps):
+        _run(["g++", "-O0", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-omit-frame-pointer", "-fno-sanitize-recover=undefined",
+              "-static-libasan", "-static-libubsan", "-I" + INCLUDE, "-I" + CSRC, deps[0], "-o", out])
+    return out
+
+
 if __name__ == "__main__":
     print(build(force="--force" in sys.argv, verbose=True))

@@ -9,7 +9,7 @@
 
 namespace cuadmm {
 
-constexpr int kAccelMaxMem = 16;      // most columns of the rings (option "accel")
+constexpr int kAccelMaxMem = 16;      // most columns of the rings (option "accel": its row in option_table.h spells this bound, kOptAccelMaxMem and the refusal text)
 constexpr int kAccelSlots = 1024;     // workgroups of the reductions = partial sums per dot product (fixed: the sums do not depend on the device)
 constexpr int kAccelThreads = 256;
 

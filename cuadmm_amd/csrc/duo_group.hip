@@ -295,10 +295,8 @@ int duo_group_create(cuadmm_solver* parent, int world, int parent_device, bool s
     cuadmm_solver* c = nullptr;
     if ((rc = cuadmm_create(&c))) break;
     g->child[(size_t)r] = c;
-    for (const auto& kv : option_log) {
-      if (kv.first == "device" || kv.first == "rank" || kv.first == "world" || kv.first == "verbose") continue;
+    for (const auto& kv : option_log)      // (the log holds no per-rank option: option_table.h, kGroupPerRank)
       if ((rc = cuadmm_set_option(c, kv.first.c_str(), kv.second))) break;
-    }
     if (rc) break;
     const int dev = g->ranks[(size_t)r].device;
     if ((rc = cuadmm_set_option(c, "device", dev)) || (rc = cuadmm_set_option(c, "verbose", 0)) || (rc = cuadmm_set_option(c, "rank", r)) ||

@@ -737,91 +737,54 @@ void cuadmm_destroy(cuadmm_solver* s) {
   delete s;
 }
 
+static_assert(kOptAccelMaxMem == kAccelMaxMem, "option_table.h: the bound of accel");
+// lookup -> check -> normalise -> store -> log -> forward: what a key takes and where it goes are the rows of the two tables (option_table.h,
+// psd_options.h); a refused value leaves the solver and its log as they were
 int cuadmm_set_option(cuadmm_solver* s, const char* key, double value) {
   if (!s || !key) { set_error("set_option: null"); return CUADMM_ERR_INVALID; }
-  std::string k(key);
-  s->option_log.emplace_back(k, value);
-  if (k == "device") s->device = (int)value;
-  else if (k == "verbose") s->verbose = (int)value;
-  else if (k == "rank") s->rank = (int)value;
-  else if (k == "world") s->world = (int)value;
-  else if (k == "profile") s->profile = (int)value;
-  else if (k == "force_comm") s->force_comm = (int)value;   // call the collective hook even when world == 1 (testing)
-  else if (k == "eig_rank") s->eig_rank = (int)value;
-  else if (k == "eig_rank_begin_iter") s->eig_rank_begin_iter = (int)value;
-  else if (k == "eig_rank_maxfeas") s->eig_rank_maxfeas = value;
-  else if (k == "psd_steps") s->psd_steps = (int)value;       // record the sign kernels' step count per block (cuadmm_get_psd_steps)
-  else if (k == "batch") s->bt.max_iters = std::max(0, std::min(256, (int)value));   // iterations per launch, closed blocks (0 / 1: off)
-  else if (k == "fuse") s->sw.fuse = (int)value;
-  else if (k == "fuse_rows") s->sw.fuse_rows = (int)value;
-  else if (k == "fuse_solve") s->sw.fuse_solve = (int)value;
-  else if (k == "host_solve") s->sw.host_solve = (int)value;
-  else if (k == "host_scalars") s->sw.host_scalars = (int)value;
-  else if (k == "tail_k") s->sw.tail_k = (int)value;
-  else if (k == "local_constraints") s->sw.local_constraints = (int)value;
-  else if (k == "mapped_out") s->sw.mapped_out = (int)value;
-  else if (k == "lpt") s->sw.lpt = (int)value;
-  else if (k == "aty_post2") s->sw.aty_post2 = (int)value;
-  else if (k == "lead_stream") s->sw.lead_stream = (int)value;
-  else if (k == "lead_debug") s->sw.lead_debug = (int)value;
-  else if (k == "lead_tops") s->sw.lead_tops = (int)value;
-  else if (k == "lead_small_kb") s->sw.lead_small_kb = (int)value;
-  else if (k == "l21_device") s->sw.l21_device = (int)value;
-  else if (k == "tail_one_pass") s->sw.tail_one_pass = (int)value;
-  else if (k == "tail_shard") s->sw.tail_shard = (int)value;
-  else if (k == "tail_refine") s->sw.tail_refine = (int)value;
-  else if (k == "tail_pivot") s->sw.tail_pivot = (int)value;
-  else if (k == "tail_max_k") s->sw.tail_max_k = (int)value;
-  else if (k == "solve_next") s->sw.solve_next = (int)value;
-  else if (k == "debug_eig") s->sw.debug_eig = (int)value;
-  else if (s->plan.opt.set(k, value)) {}                      // "psd_*": the projection planner's switches (psd_options.h)
-  else if (k == "batch_mixed") s->bt.allow_mixed = value != 0;
-  else if (k == "lazy_unscale") s->lazy_unscale = (int)value;            // 0: unscale X, y, S at the end of every solve
-  else if (k == "psd_hint") s->opt_hint = (int)value;                    // schedule warm start (before init)
-  else if (k == "duo_cpu_eig_on_gpu") s->duo_cpu_eig_on_gpu = (int)value;
-  else if (k == "duo_share_device") s->duo_share_device = (int)value;   // duo_init(device_num_requested = N) from one process: all N engines on this solver's device
-  else if (k == "tiny_sign") s->opt_tiny_sign = (int)value;              // n <= 8 on the sign kernel (before init)
-  else if (k == "duo_exchange") s->duo_exchange = (int)value;           // in-process group: -1 choose, 0 host-staged, 1 device-side exchange
-  else if (k == "accel") {                                              // memory of the Anderson acceleration (0: off), before init
-    if (!(value >= 0 && value <= kAccelMaxMem && value == std::floor(value))) {
-      s->option_log.pop_back(); set_error("set_option: accel must be an integer from 0 (off) to %d", kAccelMaxMem); return CUADMM_ERR_INVALID;
-    }
-    s->aa.mem = (int)value;
+  const OptionSpec<cuadmm_solver>* eng = engine_option_table<cuadmm_solver>().find(key);
+  const OptionSpec<PsdOptions>* psd = eng ? nullptr : psd_option_table().find(key);
+  const OptionRow* row = eng ? static_cast<const OptionRow*>(eng) : psd;
+  if (!row) { set_error("set_option: unknown key '%s'", key); return CUADMM_ERR_INVALID; }
+  double v = 0;
+  switch (option_check(*row, value, &v)) {
+    case kOptInvalid: set_error("%s", row->refusal); return CUADMM_ERR_INVALID;
+    case kOptNotFinite: set_error("set_option: %s takes a finite value", key); return CUADMM_ERR_INVALID;
+    case kOptOutOfRange: set_error("set_option: %s is out of range", key); return CUADMM_ERR_INVALID;
+    case kOptOk: break;
   }
-  else if (k == "accel_safeguard") s->aa.safeguard = value;             // a candidate is rejected when ||g|| grows by more than this factor (<= 0: always)
-  else if (k == "accel_reg") s->aa.reg = value;                         // relative Tikhonov term of the least-squares solve
-  else if (k == "infeas_check") {                                       // period of the infeasibility check (0: off), before init
-    if (!(value == 0 || (value >= 2 && value <= 1e6 && value == std::floor(value)))) {
-      s->option_log.pop_back(); set_error("set_option: infeas_check must be 0 (off) or an integer period from 2 to 1000000"); return CUADMM_ERR_INVALID;
-    }
-    if (s->initialised) { s->option_log.pop_back(); set_error("set_option: infeas_check is set before init"); return CUADMM_ERR_INVALID; }
-    s->inf.period = (int)value;
-  }
-  else if (k == "infeas_tol") {
-    if (!(value >= 0)) { s->option_log.pop_back(); set_error("set_option: infeas_tol must not be negative"); return CUADMM_ERR_INVALID; }
-    s->inf.tol = value;
-  }
-  else if (k == "gap_check") {                                          // period of the certified-gap check (0: off), before init
-    if (!(value == 0 || (value >= 2 && value <= 1e6 && value == std::floor(value)))) {
-      s->option_log.pop_back(); set_error("set_option: gap_check must be 0 (off) or an integer period from 2 to 1000000"); return CUADMM_ERR_INVALID;
-    }
-    if (s->initialised) { s->option_log.pop_back(); set_error("set_option: gap_check is set before init"); return CUADMM_ERR_INVALID; }
-    s->lb.period = (int)value;
-  }
-  else if (k == "gap_tol") {
-    if (!(value >= 0)) { s->option_log.pop_back(); set_error("set_option: gap_tol must not be negative"); return CUADMM_ERR_INVALID; }
-    s->lb.tol = value;
-  }
-  else if (k == "update_A_inject_fail") s->upa.inject_fail = (int)value;   // test hook
-  else if (k == "duo_inject_fail") { s->duo_inject = (long long)value; if (s->group) duo_group_inject(s->group, s->duo_inject); }   // test hook
-  else { s->option_log.pop_back(); set_error("set_option: unknown key '%s'", key); return CUADMM_ERR_INVALID; }
+  if (row->when == kBeforeInit && s->initialised) { set_error("set_option: %s is set before init", key); return CUADMM_ERR_INVALID; }
+  if (eng) eng->field(*s, &v);
+  else psd->field(s->plan.opt, &v);
+  if (row->group == kGroupInject && s->group) duo_group_inject(s->group, s->duo_inject);
+  if (row->group != kGroupPerRank) s->option_log.emplace_back(key, value);      // the log is what a group replays on its new ranks
   // a group handle: every rank follows -- AFTER the key has been validated on the leader; a child that refuses leaves the option
   // out of the log (it is not replayed on later children) and the error with the caller
-  if (s->group && !s->in_group_call && k != "device" && k != "rank" && k != "world" && k != "verbose" && k != "duo_inject_fail")
+  if (s->group && !s->in_group_call && row->group == kGroupShared)
     for (int r = 1; r < duo_group_world(s->group); ++r) {
       int rc = cuadmm_set_option(duo_group_rank(s->group, r), key, value);
       if (rc) { s->option_log.pop_back(); return rc; }
     }
+  return CUADMM_OK;
+}
+
+// read-only views of the two tables, the engine's rows first (host only; nothing in the engine calls them)
+int cuadmm_option_count(void) { return engine_option_table<cuadmm_solver>().n + psd_option_table().n; }
+int cuadmm_option_info(int i, const char** key, const char** env, double* def, unsigned* flags) {
+  const int ne = engine_option_table<cuadmm_solver>().n;
+  if (i < 0 || i >= cuadmm_option_count()) { set_error("option_info: no option %d", i); return CUADMM_ERR_INVALID; }
+  const OptionRow& o = i < ne ? static_cast<const OptionRow&>(engine_option_table<cuadmm_solver>().rows[i]) : psd_option_table().rows[i - ne];
+  if (key) *key = o.key;
+  if (env) *env = o.env;
+  if (def) *def = o.def;
+  if (flags) *flags = o.flags() | (i < ne ? 0u : 256u);
+  return CUADMM_OK;
+}
+int cuadmm_get_option(cuadmm_solver* s, const char* key, double* value) {
+  if (!s || !key || !value) { set_error("get_option: null"); return CUADMM_ERR_INVALID; }
+  if (const OptionSpec<cuadmm_solver>* o = engine_option_table<cuadmm_solver>().find(key)) *value = option_get(*o, *s);
+  else if (const OptionSpec<PsdOptions>* p = psd_option_table().find(key)) *value = option_get(*p, s->plan.opt);
+  else { set_error("get_option: unknown key '%s'", key); return CUADMM_ERR_INVALID; }
   return CUADMM_OK;
 }
 
@@ -999,18 +962,13 @@ int cuadmm_duo_init(cuadmm_solver* s, int if_gpu_eig_mom, int device_num_request
   // check_gpus.cu:29-43).  Here a GPU is a rank of the block-sharded engine: with rank / world already set by the caller (one
   // process per GPU) the request must agree with them; from a single process (world = 1) the handle becomes rank 0 of a GROUP of
   // N engines on N host threads with an in-process all-reduce (duo_group.hip).
-  if (device_num_requested > 1 && s->aa.mem > 0) {
-    set_error("duo_init: option accel works on one engine (device_num_requested = %d): its Gram matrix is not all-reduced", device_num_requested);
-    return CUADMM_ERR_INVALID;
-  }
-  if (device_num_requested > 1 && s->inf.period > 0) {
-    set_error("duo_init: option infeas_check works on one engine (device_num_requested = %d): its sums are not all-reduced", device_num_requested);
-    return CUADMM_ERR_INVALID;
-  }
-  if (device_num_requested > 1 && s->lb.period > 0) {
-    set_error("duo_init: option gap_check works on one engine (device_num_requested = %d): its sums are not all-reduced", device_num_requested);
-    return CUADMM_ERR_INVALID;
-  }
+  const struct { bool on; const char* option; const char* why; } single_engine[] = {
+      {s->aa.mem > 0, "accel", "Gram matrix is"}, {s->inf.period > 0, "infeas_check", "sums are"}, {s->lb.period > 0, "gap_check", "sums are"}};
+  for (const auto& f : single_engine)
+    if (device_num_requested > 1 && f.on) {
+      set_error("duo_init: option %s works on one engine (device_num_requested = %d): its %s not all-reduced", f.option, device_num_requested, f.why);
+      return CUADMM_ERR_INVALID;
+    }
   if (device_num_requested > 1 && s->world == 1 && !s->in_group_call) {
     if (s->group) { set_error("duo_init: this handle already leads a group of %d engines", duo_group_world(s->group)); return CUADMM_ERR_INVALID; }
     if (s->initialised) { set_error("duo_init: already initialised"); return CUADMM_ERR_INVALID; }

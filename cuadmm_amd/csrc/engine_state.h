@@ -10,6 +10,7 @@
 #include <dlfcn.h>
 
 #include "dev_buf.h"
+#include "option_table.h"
 #include "report_plans.h"
 #include "tail_solve.h"
 #include "lead_solve.h"
@@ -129,7 +130,7 @@ struct cuadmm_solver {
   // (pinned, written by the reduction through its device mapping when no collective is needed), ck_*: the checkpoint a batch
   // starts from (restored when the stopping test or the tau rule fires inside it).
   // SDPDuoSolver's N-devices-from-one-process mode (duo_group.hip): this handle is rank 0 of a group; `in_group_call` marks the
-  // calls the group makes on its own ranks.  option_log: every cuadmm_set_option so far (replayed on the group's children).
+  // calls the group makes on its own ranks.  option_log: every accepted cuadmm_set_option so far but the per-rank keys (replayed on the group's children).
   void* group = nullptr;
   bool in_group_call = false;
   int duo_share_device = 0;
@@ -186,7 +187,8 @@ struct cuadmm_solver {
   } upa;
   bool factor_bad = false;
   // Behavioural switches (cuadmm_set_option, before init).  The environment variables of round 1 / 2 only give the DEFAULTS, read
-  // once per solver in its constructor: two solvers in a process can choose differently, and tests reach every variant.
+  // once per solver in its constructor: two solvers in a process can choose differently, and tests reach every variant.  The keys of
+  // these and of every other option of the handle, their variables and their checks: engine_option_table (option_table.h).
   struct Switches {
     int fuse = 1;                 // "fuse": the vector work of 9 <= n <= 64 blocks inside their projection kernels
     int fuse_rows = 1;            // "fuse_rows": constraint rows local to one fused block evaluated there
@@ -213,13 +215,7 @@ struct cuadmm_solver {
     int debug_eig = 0;            // developer aid
   } sw;
   cuadmm_solver() {
-    auto env = [](const char* n, int d) { const char* e = getenv(n); return e ? atoi(e) : d; };
-    sw.fuse = env("CUADMM_FUSE", 1); sw.fuse_rows = env("CUADMM_FUSE_ROWS", 1); sw.fuse_solve = env("CUADMM_FUSE_SOLVE", -1);
-    sw.host_solve = env("CUADMM_HOST_SOLVE", 0); sw.tail_k = env("CUADMM_TAIL_K", -1);
-    sw.local_constraints = env("CUADMM_NO_LOCAL_CONSTRAINTS", 0) ? 0 : 1;
-    sw.mapped_out = env("CUADMM_NO_MAPPED_OUT", 0) ? 0 : 1;
-    sw.host_scalars = env("CUADMM_HOST_SCALARS", 0);
-    opt_hint = env("CUADMM_PSD_HINT", 1);
+    options_from_env(engine_option_table<cuadmm_solver>(), *this);
     plan.opt = PsdOptions::from_env();
   }
   int opt_tiny_sign = 1;       // option "tiny_sign": 0 never, 1 closed candidates, 2 always

@@ -232,12 +232,20 @@ int cuadmm_op_psd_project_ex(const double* Xb, double* Xproj, const int* blk_hos
   return CUADMM_OK;
 }
 
+// one pair of a test hook's options; a known key with a value no key takes (not finite, beyond an int) is not called unknown
+static int psd_option_from_pair(const char* who, const char* key, double value, PsdOptions& opt) {
+  OptCheck why = kOptOk;
+  if (key && opt.set(key, value, &why)) return CUADMM_OK;
+  if (!key || why == kOptOk) set_error("%s: unknown option %s", who, key ? key : "(null)");
+  else set_error(why == kOptNotFinite ? "%s: option %s takes a finite value" : "%s: option %s is out of range", who, key);
+  return CUADMM_ERR_INVALID;
+}
 // the default options (NOT the environment's) changed by opt_keys[n_opts] = opt_vals[n_opts]
 static int psd_options_from_pairs(const char* who, const char* const* opt_keys, const double* opt_vals, int n_opts, PsdOptions& opt) {
   if (n_opts < 0 || (n_opts > 0 && (!opt_keys || !opt_vals))) { set_error("%s: bad arguments", who); return CUADMM_ERR_INVALID; }
   opt = PsdOptions();
   for (int i = 0; i < n_opts; ++i)
-    if (!opt_keys[i] || !opt.set(opt_keys[i], opt_vals[i])) { set_error("%s: unknown option %s", who, opt_keys[i] ? opt_keys[i] : "(null)"); return CUADMM_ERR_INVALID; }
+    if (int rc = psd_option_from_pair(who, opt_keys[i], opt_vals[i], opt)) return rc;
   return CUADMM_OK;
 }
 
@@ -316,7 +324,7 @@ int cuadmm_psd_plan_ranges(const int* blk_host, int mat_num, int eig_rank, int t
   PsdPlan plan;
   plan.opt = PsdOptions();
   for (int i = 0; i < n_opts; ++i)
-    if (!plan.opt.set(opt_keys[i], opt_vals[i])) { set_error("psd_plan_ranges: unknown option %s", opt_keys[i]); return CUADMM_ERR_INVALID; }
+    if (int rc = psd_option_from_pair("psd_plan_ranges", opt_keys[i], opt_vals[i], plan.opt)) return rc;
   plan.eig_rank = eig_rank;
   plan.tiny_sign = tiny_sign != 0;
   int rc = plan.build_host(blk_host, mat_num);

@@ -1,6 +1,7 @@
 // Switches of the projection planner and its kernels.  ONE INSTANCE PER PLAN (PsdPlan::opt): two solvers in a process can
 // choose differently, and every variant is reachable by a test through cuadmm_set_option (keys "psd_*").  Nothing here is
-// cached process-wide; from_env() gives the defaults and reads the developer-aid variables.
+// cached process-wide; from_env() gives the defaults and reads the developer-aid variables.  The keys, their environment variables and
+// their clamps are the rows of psd_option_table() below.
 // PsdPlan::build() resolves every option that selects a kernel or an instantiation into the plan's launch table (psd_plan.h) and
 // into SignPsd::opt: set on a built plan, such an option is kept for the plans built afterwards and changes nothing in this one.
 // Only psd_overlap and psd_debug are read at every projection.
@@ -8,6 +9,8 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+
+#include "option_table.h"
 
 namespace cuadmm {
 
@@ -36,51 +39,50 @@ struct PsdOptions {
 
   // the defaults: each option's environment variable (round 1 / 2 names) is consulted ONCE here, per plan -- never cached -- and
   // goes through set() like a value from cuadmm_set_option
-  static PsdOptions from_env() {
-    PsdOptions o;
-    static const struct { const char* env; const char* key; } tab[] = {
-        {"CUADMM_PSD_DEBUG", "psd_debug"},           {"CUADMM_PSD_WAVE4_MIN", "psd_wave4_min"}, {"CUADMM_PSD_SIGN_MIN", "psd_sign_min"},
-        {"CUADMM_PSD_W32_OCC", "psd_w32_occ"},       {"CUADMM_PSD_CU_OCC", "psd_cu_occ"},       {"CUADMM_PSD_OVERLAP", "psd_overlap"},
-        {"CUADMM_PSD_N16", "psd_n16"},               {"CUADMM_PSD_N32", "psd_n32"},             {"CUADMM_PSD_MID", "psd_mid"},
-        {"CUADMM_PSD_LG_CLUSTER", "psd_lg_cluster"}, {"CUADMM_PSD_LDS_TRIPLE", "psd_lds_triple"}, {"CUADMM_PSD_LG_MERGE", "psd_lg_merge"},
-        {"CUADMM_PSD_LG_FUSE", "psd_lg_fuse"},       {"CUADMM_PSD_LG_CLUSTER_WGS", "psd_lg_cluster_wgs"}};
-    for (const auto& t : tab)
-      if (const char* e = getenv(t.env)) {
-        // historical spellings: N16 / N32 = "eig" (register eigensolver), MID = "eig" | "lds"
-        int v;
-        if (!strcmp(e, "eig")) v = strcmp(t.key, "psd_mid") ? 0 : 1;
-        else if (!strcmp(e, "lds")) v = 2;
-        else v = atoi(e);
-        o.set(t.key, v);
-      }
-    return o;
-  }
-  // returns false when the key is not one of this struct's
-  bool set(const std::string& k, double value) {
-    const int v = (int)value;
-    if (k == "psd_n16") n16_sign = v;
-    else if (k == "psd_n32") n32_sign = v;
-    else if (k == "psd_mid") mid = v;
-    else if (k == "psd_wave4_min") wave4_min = v;
-    else if (k == "psd_w32_occ") w32_occ = v == 3 ? 3 : 4;
-    else if (k == "psd_cu_occ") cu_occ = v == 3 ? 3 : 4;
-    else if (k == "psd_lds_triple") lds_triple = v;
-    else if (k == "psd_sign_min") sign_min = v < 65 ? 65 : v;
-    else if (k == "psd_overlap") overlap = v;
-    else if (k == "psd_lg_tile") lg_tile = v;
-    else if (k == "psd_lg_pad32") lg_pad32 = v;
-    else if (k == "psd_lg_decide") lg_decide = v;
-    else if (k == "psd_lg_cluster") lg_cluster = v;
-    else if (k == "psd_lg_merge") lg_merge = v;
-    else if (k == "psd_lg_fuse") lg_fuse = v;
-    else if (k == "psd_lg_cluster_wgs") lg_cluster_wgs = v < 8 ? 8 : (v > 960 ? 960 : v);
-    else if (k == "psd_sign_maxsteps") sign_maxsteps = v;
-    else if (k == "psd_sign_sync") sign_sync = v;
-    else if (k == "psd_sign_ws_mb") sign_ws_mb = v < 1 ? 1 : v;
-    else if (k == "psd_debug") debug = v < 0 ? 0 : v;
-    else return false;
-    return true;
-  }
+  static PsdOptions from_env();
+  // false when the key is not one of this struct's or the value is refused; *why (optional): kOptOk for an unknown key, else the refusal
+  bool set(const std::string& k, double value, OptCheck* why = nullptr);
 };
+
+// The table of the keys (option_table.h: adding an option is adding its row and its field), in the order INTEGRATION.md section 6 lists them.
+inline OptionTable<PsdOptions> psd_option_table() {
+  using O = OptionSpec<PsdOptions>;
+#define F(member) CUADMM_OPT_FIELD(PsdOptions, member)
+  static const O rows[] = {
+      O("psd_n16", F(n16_sign), kOptInt, 1, "9 <= n <= 16 on the one-wavefront sign kernel (0: register eigensolver)").from_env("CUADMM_PSD_N16", kEnvEig0).read(kAtPlanBuild),
+      O("psd_n32", F(n32_sign), kOptInt, 1, "17 <= n <= 32 likewise").from_env("CUADMM_PSD_N32", kEnvEig0).read(kAtPlanBuild),
+      O("psd_mid", F(mid), kOptInt, 0, "33 <= n <= 64: 0 by count, 1 register eigensolver, 2 one workgroup per block").from_env("CUADMM_PSD_MID", kEnvEig1).read(kAtPlanBuild),
+      O("psd_wave4_min", F(wave4_min), kOptInt, 1024, "blocks of a 33 <= n <= 64 class from which one wavefront per block wins").from_env("CUADMM_PSD_WAVE4_MIN").read(kAtPlanBuild),
+      O("psd_sign_min", F(sign_min), kOptInt, 65, "blocks from this size on take the batched-GEMM matrix-sign path").from_env("CUADMM_PSD_SIGN_MIN").at_least(65).read(kAtPlanBuild),
+      O("psd_lds_triple", F(lds_triple), kOptInt, 1, "one-workgroup kernels of 33 <= n <= 64 with a third LDS matrix (classes of <= 256 blocks)").from_env("CUADMM_PSD_LDS_TRIPLE").read(kAtPlanBuild),
+      O("psd_w32_occ", F(w32_occ), kOptInt, 4, "wavefronts per SIMD of the n <= 32 one-wavefront kernels (3 | 4)").from_env("CUADMM_PSD_W32_OCC").normalised(kNorm3or4).read(kAtPlanBuild),
+      O("psd_cu_occ", F(cu_occ), kOptInt, 4, "the same for the launches that run several iterations").from_env("CUADMM_PSD_CU_OCC").normalised(kNorm3or4).read(kAtPlanBuild),
+      O("psd_overlap", F(overlap), kOptInt, 1, "size classes on their own streams").from_env("CUADMM_PSD_OVERLAP").read(kLive),
+      O("psd_lg_tile", F(lg_tile), kOptInt, 0, "sign path: 0 = tile by size, 32 | 64 forces it").read(kAtPlanBuild),
+      O("psd_lg_pad32", F(lg_pad32), kOptInt, 1, "sign path: groups on 32 x 32 tiles pad to a multiple of 32").read(kAtPlanBuild),
+      O("psd_lg_decide", F(lg_decide), kOptInt, 0, "sign path: 0 by tile count, 1 decisions inside the product kernels, 2 a separate kernel").read(kAtPlanBuild),
+      O("psd_lg_cluster", F(lg_cluster), kOptInt, 1, "sign path: a handful of mid-size blocks run their whole iteration in one launch").from_env("CUADMM_PSD_LG_CLUSTER").read(kAtPlanBuild),
+      O("psd_lg_merge", F(lg_merge), kOptInt, 1, "sign path: one-launch groups of different padded sizes share one launch").from_env("CUADMM_PSD_LG_MERGE").read(kAtPlanBuild),
+      O("psd_sign_sync", F(sign_sync), kOptInt, 1, "sign path: poll \"members not finished\" between chunks of steps").read(kAtPlanBuild),
+      O("psd_sign_maxsteps", F(sign_maxsteps), kOptInt, 0, "sign path: cap of the schedule (0: SignSched::kCap)").read(kAtPlanBuild),
+      O("psd_sign_ws_mb", F(sign_ws_mb), kOptInt, 8192, "sign path: workspace bound of a group").at_least(1).read(kAtPlanBuild),
+      O("psd_lg_cluster_wgs", F(lg_cluster_wgs), kOptInt, 224, "sign path: the largest grid the one-launch kernel takes").from_env("CUADMM_PSD_LG_CLUSTER_WGS").clamp(8, 960).read(kAtPlanBuild),
+      O("psd_lg_fuse", F(lg_fuse), kOptInt, 1, "sign path: the one-launch kernel does its own prologue and epilogue").from_env("CUADMM_PSD_LG_FUSE").read(kAtPlanBuild),
+      O("psd_debug", F(debug), kOptInt, 0, "developer aid: phase ticks of the kernels on stderr; serialises the classes").from_env("CUADMM_PSD_DEBUG").at_least(0).read(kLive),
+  };
+#undef F
+  return {rows, (int)(sizeof(rows) / sizeof(rows[0]))};
+}
+inline PsdOptions PsdOptions::from_env() {
+  PsdOptions o;
+  options_from_env(psd_option_table(), o);
+  return o;
+}
+inline bool PsdOptions::set(const std::string& k, double value, OptCheck* why) {
+  const OptionSpec<PsdOptions>* o = psd_option_table().find(k.c_str());
+  const OptCheck c = o ? option_store(*o, *this, value) : kOptOk;
+  if (why) *why = c;
+  return o && c == kOptOk;
+}
 
 }  // namespace cuadmm

@@ -46,33 +46,25 @@ typedef struct cuadmm_solver cuadmm_solver;
 int cuadmm_create(cuadmm_solver** out);
 void cuadmm_destroy(cuadmm_solver* s);
 
-/* Engine options; call before cuadmm_init.  Unknown keys -> CUADMM_ERR_INVALID.
+/* Engine options; call before cuadmm_init.  Unknown keys -> CUADMM_ERR_INVALID; so are a value that is not finite and, for a key that takes an
+ * integer (every key but eig_rank_maxfeas, batch_mixed, accel_safeguard, accel_reg, infeas_tol, gap_tol), a value beyond the range of int.
+ * Integer keys truncate toward zero.  The keys below are in the order of the option tables (csrc/option_table.h, csrc/psd_options.h: the one
+ * place where keys, defaults, environment variables and checks are written down; cuadmm_option_info lists them).
  *   "device"        HIP device ordinal (default 0; the reference hard-wires GPU0, utils.h:4)
  *   "verbose"       1 = print the reference's census + iteration table to stdout (default 1)
  *   "rank","world"  shard blocks by index over `world` engines (default 0,1); see
  *                   cuadmm_set_allreduce
- *   "profile"       1 = time every kernel class with HIP events on the engine stream;
+ *   "profile"       default 0; 1 = time every kernel class with HIP events on the engine stream;
  *                   2 = time only the dominant kernel (psd_project)
- *   "force_comm"    1 = call the collective hook even when world == 1 (transport tests on one GPU)
- *   "eig_rank"      r > 0: rank-limited projection (only the r largest eigenvalues of every PSD block survive; reference
+ *   "force_comm"    default 0; 1 = call the collective hook even when world == 1 (transport tests on one GPU)
+ *   "eig_rank"      default 0; r > 0: rank-limited projection (only the r largest eigenvalues of every PSD block survive; reference
  *                   dense_scalar.cu:51-57 + get_eig_rank_mask.cu, dormant there); active from iteration
  *                   "eig_rank_begin_iter" (default 0) on, or once maxfeas < "eig_rank_maxfeas" (default 0 = never);
  *                   set before cuadmm_init (every block then takes the eigensolver kernels)
- *   "psd_steps"     1 = record how many Newton-Schulz steps the adaptive matrix-sign projection took per block
+ *   "psd_steps"     default 0; 1 = record how many Newton-Schulz steps the adaptive matrix-sign projection took per block
  *                   (cuadmm_get_psd_steps); set before cuadmm_init
- *   "tail_shard"    world > 1, coupled constraints: 1 (default) = each rank applies 1 / world of the rows of the dense GPU tail of the
- *                   replicated y-solve and the K partial results are all-reduced; 0 = every rank applies the whole tail
- *   "tail_pivot"    1 (default) = the dense LDL^T of the y-solve's GPU tail pivots on the diagonal (P S P^T = L D L^T, |L_ij| <= 1): its explicit inverse stays
- *                   accurate where the Schur complement is nearly singular; 0 = the unpivoted elimination order (rounds 2 - 5)
- *   "tail_refine"   1 = one more accuracy device of the dense GPU tail of the y-solve: one refinement step of each triangular solve against the factor itself
- *                   (u <- u + W (z - L u), x <- x + W^T (v - L^T x)) on top of the explicit inverse W = inv(L22), whose accuracy is u cond(L22) -- a
- *                   nearly singular Schur complement (large moment relaxations) otherwise leaves 1e-8 ... 1e-7 in the primal objective against an exact
- *                   LDL^T solve (the reference's contract, include/cuadmm/cholesky_cpu.h:146-155).  Costs 6x the tail's bytes per solve and two more
- *                   K x K matrices; default 0.  cuadmm_get_tail_info [4] reports the measured accuracy of the explicit inverse.
- *   "psd_lg_fuse"   1 (default) = a handful of blocks of 65 <= n <= 512 run their whole projection -- svec -> dense, norm, every step of the matrix-sign
- *                   iteration, final product, svec store -- in ONE launch; 0 = prologue and epilogue as launches of their own (bit-identical)
  *   "duo_share_device", "duo_exchange"   the in-process group of cuadmm_duo_init(device_num_requested = N): all engines on the
- *                   caller's device; all-reduce through device memory (1), host staging (0), chosen by peer accessibility (-1, default)
+ *                   caller's device (1; default 0); all-reduce through device memory (1), host staging (0), chosen by peer accessibility (-1, default)
  *   "accel"         memory m of the safeguarded Anderson acceleration of the iteration ("Acceleration"): 0 (default) = off,
  *                   1 .. 16 = keep the last m differences of the fixed-point map (X, sigma S) -> (X+, sigma S+) and extrapolate behind every
  *                   iteration; anything else is CUADMM_ERR_INVALID.  Costs (2 m + 3) 2 L doubles of device memory (two rings of m columns,
@@ -97,9 +89,29 @@ void cuadmm_destroy(cuadmm_solver* s);
  *                   group, eig_rank > 0, accel > 0 or infeas_check > 0.  Without a verdict the run is the run with the option off, bit for
  *                   bit.  Set before cuadmm_init.
  *   "gap_tol"       default 0 = the solve's stop_tol: the tolerance of the certified-gap verdict
- *   (every other switch: INTEGRATION.md section 6)
+ *   "tail_shard"    world > 1, coupled constraints: 1 (default) = each rank applies 1 / world of the rows of the dense GPU tail of the
+ *                   replicated y-solve and the K partial results are all-reduced; 0 = every rank applies the whole tail
+ *   "tail_pivot"    1 (default) = the dense LDL^T of the y-solve's GPU tail pivots on the diagonal (P S P^T = L D L^T, |L_ij| <= 1): its explicit inverse stays
+ *                   accurate where the Schur complement is nearly singular; 0 = the unpivoted elimination order (rounds 2 - 5)
+ *   "tail_refine"   1 = one more accuracy device of the dense GPU tail of the y-solve: one refinement step of each triangular solve against the factor itself
+ *                   (u <- u + W (z - L u), x <- x + W^T (v - L^T x)) on top of the explicit inverse W = inv(L22), whose accuracy is u cond(L22) -- a
+ *                   nearly singular Schur complement (large moment relaxations) otherwise leaves 1e-8 ... 1e-7 in the primal objective against an exact
+ *                   LDL^T solve (the reference's contract, include/cuadmm/cholesky_cpu.h:146-155).  Costs 6x the tail's bytes per solve and two more
+ *                   K x K matrices; default 0.  cuadmm_get_tail_info [4] reports the measured accuracy of the explicit inverse.
+ *   "psd_lg_fuse"   1 (default) = a handful of blocks of 65 <= n <= 512 run their whole projection -- svec -> dense, norm, every step of the matrix-sign
+ *                   iteration, final product, svec store -- in ONE launch; 0 = prologue and epilogue as launches of their own (bit-identical)
+ *   (every other switch: INTEGRATION.md section 6, which lists every key with its default)
  */
 int cuadmm_set_option(cuadmm_solver* s, const char* key, double value);
+/* Read-only views of the option tables, host only (no device is touched).  cuadmm_option_count: the number of keys.  cuadmm_option_info: row i
+ * in table order, the engine's keys first, then the psd_* keys; any output pointer may be null.  *env: the environment variable that gives the
+ * default, or null.  *def: the built-in default.  *flags: bits 0-1 kind (0 int, 1 long long, 2 real); bits 2-3 when the value is read (0 before
+ * cuadmm_init only: refused afterwards, 1 by cuadmm_init, 2 when a projection plan is built, 3 while solving); bits 4-5 in-process group (0 shared
+ * by all ranks, 1 per rank, 2 the leader's test hook); bit 6 the variable is negated (VAR != 0 means 0); bit 7 the variable also takes the
+ * spellings eig / lds; bit 8 a psd_* key.  cuadmm_get_option: the value the solver holds for key, as a double. */
+int cuadmm_option_count(void);
+int cuadmm_option_info(int i, const char** key, const char** env, double* default_value, unsigned* flags);
+int cuadmm_get_option(cuadmm_solver* s, const char* key, double* value);
 
 /* Collective hook for block-sharded multi-GPU runs.  `fn` must sum
  * `count` doubles at device pointer `buf` over all ranks, in place, ordered on `hip_stream`

@@ -229,6 +229,13 @@ def test_refusals():
     s.init_problem(p)
     with pytest.raises(RuntimeError, match="infeas_check"):
         s.set_option("infeas_check", 25)                            # the period is set before init
+    lib, got = cuadmm_amd.load(), C.c_double()
+    for key in (b"infeas_check", b"gap_check"):                     # the two keys refused on an initialised solver, in their words
+        assert lib.cuadmm_set_option(s._h, key, C.c_double(25)) == -1 and lib.cuadmm_last_error() == b"set_option: %s is set before init" % key
+        assert lib.cuadmm_set_option(s._h, key, C.c_double(1)) == -1                              # (the range is checked first, as it was)
+        assert lib.cuadmm_last_error() == b"set_option: %s must be 0 (off) or an integer period from 2 to 1000000" % key
+        assert lib.cuadmm_get_option(s._h, key, C.byref(got)) == 0 and got.value == (50 if key == b"infeas_check" else 0)
+    assert lib.cuadmm_set_option(s._h, b"infeas_tol", C.c_double(1e-6)) == 0                      # (its default) every other key stays settable
     s.solve(CAP, STOP, 500, 50, 100, SGS, 1.05)
     assert s.status()["status"] == 1
     with pytest.raises(RuntimeError, match="certificate"):
