@@ -124,6 +124,11 @@ PROTOTYPES = {
     "cuadmm_op_lrg_multiplier": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
     "cuadmm_lowrank_line": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "cuadmm_quartic_min": (C.c_int, [C.c_void_p, C.c_double, C.c_void_p]),
+    "cuadmm_lowrank_refine": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_double, C.c_int, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cuadmm_cg_update": (C.c_int, [C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, C.c_void_p]),
+    "cuadmm_op_lrr_dots": (C.c_int, [C.c_longlong, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cuadmm_op_lrr_direction": (C.c_int, [C.c_longlong, C.c_void_p, C.c_double, C.c_double, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cuadmm_op_lrr_step": (C.c_int, [C.c_longlong, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
     "cuadmm_op_block_outer3": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "cuadmm_op_lrl_sums": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "cuadmm_op_check_factors": (C.c_int, [C.c_char_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),

@@ -20,8 +20,8 @@ INCLUDE = os.path.join(HERE, "..", "include")
 LIB = os.path.join(LIBDIR, "libcuadmm_amd.so")
 EXE = os.path.join(LIBDIR, "cuadmm_exe")
 
-HIP_SOURCES = ["psd_kernels.hip", "psd_large.hip", "tail_solve.hip", "eig_large.hip", "lead_solve.hip", "vec_kernels.hip", "accel.hip", "infeas.hip", "lower_bound.hip", "evaluate.hip", "lambda_min.hip", "lowrank.hip", "lowrank_apply.hip", "block_mult.hip", "lowrank_grad.hip", "lowrank_line.hip", "staging.hip", "engine.hip", "engine_iter.hip", "engine_reports.hip", "engine_update.hip", "op_hooks.hip", "duo_group.hip"]
-CPP_SOURCES = ["io.cpp", "blocks.cpp", "aat_ldlt.cpp", "mex_entry.cpp", "quartic_min.cpp"]
+HIP_SOURCES = ["psd_kernels.hip", "psd_large.hip", "tail_solve.hip", "eig_large.hip", "lead_solve.hip", "vec_kernels.hip", "accel.hip", "infeas.hip", "lower_bound.hip", "evaluate.hip", "lambda_min.hip", "lowrank.hip", "lowrank_apply.hip", "block_mult.hip", "lowrank_grad.hip", "lowrank_line.hip", "lowrank_refine.hip", "staging.hip", "engine.hip", "engine_iter.hip", "engine_reports.hip", "engine_update.hip", "op_hooks.hip", "duo_group.hip"]
+CPP_SOURCES = ["io.cpp", "blocks.cpp", "aat_ldlt.cpp", "mex_entry.cpp", "quartic_min.cpp", "cg_update.cpp"]
 HEADERS = None   # every header under csrc/ plus the public C header (computed in build())
 ARCH = "gfx950"
 

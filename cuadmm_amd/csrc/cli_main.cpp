@@ -36,6 +36,10 @@
 //   --lowrank-line=LDIR/,DDIR/[,SIGMA[,TMAX]]: behind every solve, the quartic t -> f(L + t D) of that value along the direction read from
 //   DDIR/ (factor files as LDIR/'s, the same ranks), y from LDIR/y.txt when present, and its minimiser on [0, TMAX] (default: inf, which
 //   needs SIGMA > 0) (cuadmm_lowrank_line); one line with c0 .. c4, t* and f(t*), and "lowrank_line" in the sidecar
+//   --lowrank-refine=DIR/[,SIGMA[,STEPS[,TMAX]]]: behind every solve, STEPS (10) steps of conjugate gradients on that value over the factors
+//   read from DIR/ (as --lowrank-out writes them) with y from DIR/y.txt when present, SIGMA (1) >= 0, TMAX (inf) > 0
+//   (cuadmm_lowrank_refine); one line per step and "lowrank_refine" in the sidecar
+//   --lowrank-refine-out=DIR2/ (with --lowrank-refine): the refined factors, DIR2/L_X_<k>.txt as --start-lowrank reads them
 //   --block-mult-out=DIR2/ (with --block-mult): DIR2/W_<k>.txt per PSD block k, n_k r_k numbers column by column with 17 significant
 //   digits (of the last --block-mult where there are several)
 //   --json=<file>: a sidecar with the run's figures (iterations, residuals, iters/s, per-phase milliseconds, the projection's
@@ -245,6 +249,37 @@ static void write_lowrank_line(FILE* f, const LowRankLineCall& c) {
           "\"qnorm\": %.17g, \"critical\": %.0f, \"ms\": %.17g, \"bytes\": %.0f}", c.rmax, c.have_y ? "true" : "false", c.coef[0], c.coef[1], c.coef[2], c.coef[3],
           c.coef[4], o[0], o[1], o[2], o[3], o[4], o[5], o[6], o[7]);
 }
+// --lowrank-refine: the factors, y (when DIR/y.txt exists), sigma, steps, t_max and the results of cuadmm_lowrank_refine
+struct LowRankRefineCall {
+  bool on = false, have_y = false;
+  int rmax = 1, steps = 10;
+  double sigma = 1, t_max = INFINITY;
+  std::string dir;
+  std::vector<int> ranks;
+  std::vector<double> L, y, trace;
+  double o[8] = {0};
+  int rows() const { return (int)o[0] + (o[1] != 0 ? 1 : 0); }
+};
+// a double as JSON: null where it is not finite
+static void write_num(FILE* f, double x) { if (std::isfinite(x)) fprintf(f, "%.17g", x); else fprintf(f, "null"); }
+// "lowrank_refine": {...} with the eight numbers of cuadmm_lowrank_refine and the trace's rows (t_max: null for inf)
+static void write_lowrank_refine(FILE* f, const LowRankRefineCall& c) {
+  fprintf(f, " \"lowrank_refine\": {\"sigma\": %.17g, \"max_steps\": %d, \"t_max\": ", c.sigma, c.steps);
+  write_num(f, c.t_max);
+  fprintf(f, ", \"rmax\": %d, \"y\": %s, \"steps\": %.0f, \"reason\": %.0f, \"f0\": ", c.rmax, c.have_y ? "true" : "false", c.o[0], c.o[1]);
+  write_num(f, c.o[2]);
+  fprintf(f, ", \"f\": ");
+  write_num(f, c.o[3]);
+  fprintf(f, ", \"gnorm\": ");
+  write_num(f, c.o[4]);
+  fprintf(f, ", \"ms\": %.17g, \"bytes\": %.0f, \"trace\": [", c.o[5], c.o[6]);
+  for (int k = 0; k < c.rows(); ++k) {
+    fprintf(f, "%s[", k ? ", " : "");
+    for (int j = 0; j < 14; ++j) { if (j) fprintf(f, ", "); write_num(f, c.trace[16 * (size_t)k + j]); }
+    fprintf(f, "]");
+  }
+  fprintf(f, "]}");
+}
 // <dir/>name.txt, one number per line (cuadmm_write_dense_txt); a missing file: zeros
 static bool read_point_vec(const std::string& fn, std::vector<double>& out, size_t n, const char* who = "--kkt-point") {
   out.assign(n, 0.0);
@@ -264,7 +299,7 @@ static bool write_sidecar(const std::string& path, const std::string& prefix, cu
                           const double* kkt = nullptr, const std::vector<double>& kkt_blocks = std::vector<double>(), int lm_steps = 0,
                           const double (*lm)[8] = nullptr, const LowRankReport* lr = nullptr, const LowRankStart* start = nullptr,
                           const std::vector<BlockMultCall>* bmc = nullptr, const LowRankGradCall* lgc = nullptr,
-                          const LowRankLineCall* llc = nullptr) {
+                          const LowRankLineCall* llc = nullptr, const LowRankRefineCall* lrc = nullptr) {
   FILE* f = fopen(path.c_str(), "w");
   if (!f) return false;
   const int iters = cuadmm_get_info_iter_num(solver);
@@ -309,6 +344,7 @@ static bool write_sidecar(const std::string& path, const std::string& prefix, cu
   if (bmc) { write_block_mult(f, *bmc); fprintf(f, ",\n"); }
   if (lgc) { write_lowrank_grad(f, *lgc); fprintf(f, ",\n"); }
   if (llc) { write_lowrank_line(f, *llc); fprintf(f, ",\n"); }
+  if (lrc) { write_lowrank_refine(f, *lrc); fprintf(f, ",\n"); }
   double acc[8] = {0};
   cuadmm_get_accel_info(solver, acc);
   if (acc[0] > 0)
@@ -354,6 +390,8 @@ int main(int argc, char* argv[]) {
   std::string json_path, bounds_arg, kkt_point, lr_out, start_dir, bm_out, lg_out;
   LowRankGradCall lgc;                 // --lowrank-grad
   LowRankLineCall llc;                 // --lowrank-line
+  LowRankRefineCall lrc;               // --lowrank-refine
+  std::string lrc_out;                 // --lowrank-refine-out
   std::vector<BlockMultCall> bmc;      // --block-mult, in the order given
   std::vector<std::string> then_dirs;
   std::vector<char> then_is_A;
@@ -430,6 +468,21 @@ int main(int argc, char* argv[]) {
       llc.on = true;
       continue;
     }
+    if (strncmp(argv[i], "--lowrank-refine-out=", 21) == 0) { lrc_out = argv[i] + 21; continue; }
+    if (strncmp(argv[i], "--lowrank-refine=", 17) == 0) {
+      std::vector<std::string> part(1);
+      for (const char* a = argv[i] + 17; *a; ++a)
+        if (*a == ',') part.emplace_back(); else part.back() += *a;
+      bool ok = part.size() <= 4 && !part[0].empty();
+      char* end = nullptr;
+      if (ok && part.size() >= 2) { lrc.sigma = strtod(part[1].c_str(), &end); ok = !part[1].empty() && *end == 0 && lrc.sigma >= 0 && std::isfinite(lrc.sigma); }
+      if (ok && part.size() >= 3) { const long q = strtol(part[2].c_str(), &end, 10); ok = !part[2].empty() && *end == 0 && q >= 1 && q <= 1000000; lrc.steps = (int)q; }
+      if (ok && part.size() == 4) { lrc.t_max = strtod(part[3].c_str(), &end); ok = !part[3].empty() && *end == 0 && lrc.t_max > 0; }
+      if (!ok) { std::cerr << "--lowrank-refine=DIR/[,SIGMA[,STEPS[,TMAX]]]: SIGMA >= 0, STEPS >= 1, TMAX > 0" << std::endl; return 1; }
+      lrc.dir = part[0];
+      lrc.on = true;
+      continue;
+    }
     std::cerr << "unknown option " << argv[i] << std::endl;
     return 1;
   }
@@ -437,6 +490,7 @@ int main(int argc, char* argv[]) {
   if (!lr_out.empty() && !lr_on) { std::cerr << "--lowrank-out needs --lowrank=TOL[,RMAX]" << std::endl; return 1; }
   if (!bm_out.empty() && bmc.empty()) { std::cerr << "--block-mult-out needs --block-mult=X|S|dual,DIR/" << std::endl; return 1; }
   if (!lg_out.empty() && !lgc.on) { std::cerr << "--lowrank-grad-out needs --lowrank-grad=DIR/[,SIGMA]" << std::endl; return 1; }
+  if (!lrc_out.empty() && !lrc.on) { std::cerr << "--lowrank-refine-out needs --lowrank-refine=DIR/[,SIGMA[,STEPS[,TMAX]]]" << std::endl; return 1; }
   for (size_t k = 0; k < then_dirs.size(); ++k) {   // before any work: a stage that cannot be read must not cost the stages before it
     const std::string& d = then_dirs[k];
     DIR* dp = d.empty() ? nullptr : opendir(d.c_str());
@@ -494,6 +548,19 @@ int main(int argc, char* argv[]) {
     if (ok && llc.have_y) ok = read_point_vec(llc.ldir + "y.txt", llc.y, (size_t)v.con_num, "--lowrank-line");
     if (!ok) { cuadmm_problem_free(prob); return 1; }
     llc.rmax = sl.rmax[wl]; llc.ranks = sl.ranks[wl]; llc.L = sl.L[wl]; llc.D = sd.L[wd];   // (equal ranks: equal rmax, one layout)
+  }
+
+  if (lrc.on) {            // --lowrank-refine: read and checked before any device work
+    LowRankStart st;
+    bool ok = read_lowrank_start(lrc.dir, v, st, 0) && (st.have[0] || read_lowrank_start(lrc.dir, v, st, 1));
+    const int w = st.have[0] ? 0 : 1;
+    if (ok && !st.have[w]) { std::cerr << "--lowrank-refine: no factor file L_X_<k>.txt or L_S_<k>.txt in '" << lrc.dir << "'" << std::endl; ok = false; }
+    FILE* yf = ok ? fopen((lrc.dir + "y.txt").c_str(), "r") : nullptr;
+    if (yf) { fclose(yf); lrc.have_y = true; }
+    if (ok && lrc.have_y) ok = read_point_vec(lrc.dir + "y.txt", lrc.y, (size_t)v.con_num, "--lowrank-refine");
+    if (!ok) { cuadmm_problem_free(prob); return 1; }
+    lrc.rmax = st.rmax[w]; lrc.ranks = st.ranks[w]; lrc.L = st.L[w];
+    lrc.trace.assign(16 * (size_t)lrc.steps, 0.0);
   }
 
   cuadmm_solver* solver = nullptr;
@@ -670,6 +737,37 @@ int main(int argc, char* argv[]) {
            c.coef[1], c.coef[2], c.coef[3], c.coef[4], c.o[0], c.o[1], c.o[6]);
     return true;
   };
+  // --lowrank-refine: conjugate gradients over the factors at the point a solve returns, taken before anything reads the iterate; every
+  // solve refines the factors that were read
+  auto lrr_report = [&]() {
+    if (!lrc.on) return false;
+    LowRankRefineCall& c = lrc;
+    std::vector<double> Lo(c.L.size(), 0.0);
+    if (cuadmm_lowrank_refine(solver, c.L.data(), c.ranks.data(), c.rmax, c.have_y ? c.y.data() : nullptr, c.sigma, c.steps, c.t_max, 0.0, Lo.data(), c.trace.data(),
+                              c.o, nullptr) != CUADMM_OK) {
+      std::cerr << cuadmm_last_error() << std::endl;
+      return false;
+    }
+    for (int k = 0; k < c.rows(); ++k) {
+      const double* q = c.trace.data() + 16 * (size_t)k;
+      printf(" lowrank_refine step %d: f = %.10e, ||G||_F = %.10e, beta = %.3e%s, t = %.10e, f(t) = %.10e, %.3f ms\n", k, q[6], std::sqrt(q[0]), q[3],
+             q[5] != 0 ? " (restart)" : "", q[11], q[12], q[13]);
+    }
+    printf(" lowrank_refine(sigma = %g, t_max = %g): %.0f steps, reason %.0f, f %.10e -> %.10e, %.3f ms\n", c.sigma, c.t_max, c.o[0], c.o[1], c.o[2], c.o[3], c.o[5]);
+    if (lrc_out.empty()) return true;
+    size_t at = 0;
+    for (int k = 0; k < v.mat_num; ++k) {
+      const long long n = v.blk_vals[k];
+      if (n <= 0) continue;
+      const std::string fn = lrc_out + "L_X_" + std::to_string(k) + ".txt";
+      FILE* f = fopen(fn.c_str(), "w");
+      if (!f) { std::cerr << "cannot write " << fn << std::endl; return false; }
+      for (long long e = 0; e < n * c.ranks[k]; ++e) fprintf(f, "%.17g\n", Lo[at + (size_t)e]);
+      fclose(f);
+      at += (size_t)(n * std::min<long long>(n, c.rmax));
+    }
+    return true;
+  };
   // --start-lowrank: the point replaces init's zeros, and the solve takes the iterate as it stands (if_first = 0)
   const bool started = start.have[0] || start.have[1] || start.have_y;
   for (int w = 0; w < 2 && rc == CUADMM_OK; ++w) {
@@ -692,6 +790,7 @@ int main(int argc, char* argv[]) {
   bool have_bm = bm_report();
   bool have_lg = lg_report();
   bool have_ll = ll_report();
+  bool have_lrr = lrr_report();
 
   if (accel != 0) {
     double acc[8] = {0};
@@ -700,7 +799,7 @@ int main(int argc, char* argv[]) {
   }
   std::vector<double> X((size_t)v.vec_len);
   if (cuadmm_get_X(solver, X.data()) == CUADMM_OK) cuadmm_write_dense_txt((prefix + "X_opt.txt").c_str(), X.data(), v.vec_len);
-  if (!json_path.empty() && !write_sidecar(json_path, prefix, solver, v, !bounds_arg.empty(), have_kkt ? kk : nullptr, kkb, lm_steps, have_lm ? lm : nullptr, have_lr ? &lr : nullptr, started ? &start : nullptr, have_bm ? &bmc : nullptr, have_lg ? &lgc : nullptr, have_ll ? &llc : nullptr)) std::cerr << "cannot write " << json_path << std::endl;
+  if (!json_path.empty() && !write_sidecar(json_path, prefix, solver, v, !bounds_arg.empty(), have_kkt ? kk : nullptr, kkb, lm_steps, have_lm ? lm : nullptr, have_lr ? &lr : nullptr, started ? &start : nullptr, have_bm ? &bmc : nullptr, have_lg ? &lgc : nullptr, have_ll ? &llc : nullptr, have_lrr ? &lrc : nullptr)) std::cerr << "cannot write " << json_path << std::endl;
   for (size_t k = 0; k < then_dirs.size() && rc == CUADMM_OK; ++k) {
     const std::string& d = then_dirs[k];
     std::vector<int> bi, ci;
@@ -730,9 +829,10 @@ int main(int argc, char* argv[]) {
     have_bm = bm_report();
     have_lg = lg_report();
     have_ll = ll_report();
+    have_lrr = lrr_report();
     if (cuadmm_get_X(solver, X.data()) == CUADMM_OK) cuadmm_write_dense_txt((d + "X_opt.txt").c_str(), X.data(), v.vec_len);
     const std::string side = json_path + "." + std::to_string(k + 1);
-    if (!json_path.empty() && !write_sidecar(side, d, solver, v, !bounds_arg.empty(), have_kkt ? kk : nullptr, kkb, lm_steps, have_lm ? lm : nullptr, have_lr ? &lr : nullptr, nullptr, have_bm ? &bmc : nullptr, have_lg ? &lgc : nullptr, have_ll ? &llc : nullptr)) std::cerr << "cannot write " << side << std::endl;
+    if (!json_path.empty() && !write_sidecar(side, d, solver, v, !bounds_arg.empty(), have_kkt ? kk : nullptr, kkb, lm_steps, have_lm ? lm : nullptr, have_lr ? &lr : nullptr, nullptr, have_bm ? &bmc : nullptr, have_lg ? &lgc : nullptr, have_ll ? &llc : nullptr, have_lrr ? &lrc : nullptr)) std::cerr << "cannot write " << side << std::endl;
   }
   cuadmm_destroy(solver);
   cuadmm_problem_free(prob);

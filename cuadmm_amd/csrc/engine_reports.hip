@@ -1,8 +1,8 @@
 // What the engine reports beside the iteration: the infeasibility check and the certified lower bound behind the iteration's steps, and
 // the reports on a point (cuadmm_lower_bound, cuadmm_evaluate, cuadmm_lambda_min, cuadmm_lowrank, cuadmm_block_multiply,
-// cuadmm_lowrank_grad, cuadmm_lowrank_line) with their C entry points.  Host code only: the kernels are those of infeas.hip,
-// lower_bound.hip, evaluate.hip, lambda_min.hip, lowrank.hip, lowrank_apply.hip, block_mult.hip, lowrank_grad.hip, lowrank_line.hip and the
-// iteration's own.
+// cuadmm_lowrank_grad, cuadmm_lowrank_line, cuadmm_lowrank_refine) with their C entry points.  Host code only: the kernels are those of
+// infeas.hip, lower_bound.hip, evaluate.hip, lambda_min.hip, lowrank.hip, lowrank_apply.hip, block_mult.hip, lowrank_grad.hip,
+// lowrank_line.hip, lowrank_refine.hip and the iteration's own.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -528,6 +528,23 @@ int cuadmm_solver::lg_prepare(int rmax) {
   return aux.ensure(*this);
 }
 
+// The launches of lg_run's chain at the scaled y in lg.ybuf, on device buffers: Lx the factors in the units X lies in (the outer product
+// reads them), bm.Vbuf those in the caller's units (the block product reads them).  The per-block terms only where f is wanted from them.
+int cuadmm_solver::lg_enqueue(const double* Lx, double sigma, bool block_terms) {
+  int rc;
+  const double* const normA_dev = normA_d.p ? normA_d.p : lg.normA.p;
+  CUADMM_HIP_TRY(hipMemcpyAsync(lg.xv.p, X.p, sizeof(double) * (size_t)L, hipMemcpyDeviceToDevice, st));
+  if ((rc = lo.run(fl, Lx, btasks.off.p, btasks.blk.p, lg.xv.p, st))) return rc;
+  if (m > 0 && (rc = launch_spmv_rows(m, A_avg_nnz, A_rp.p, A_ci.p, A_v.p, lg.xv.p, S.p, C.p, lg.ax.p, nullptr, st, &A_long))) return rc;
+  if ((rc = launch_lrg_multiplier(m, lg.ax.p, aux.b_dev(*this), normA_dev, lg.ybuf.p, pending_unscale ? 1.0 : 1 / bscale, bscale, 1 / Cscale, sigma, lg.ytilde.p,
+                                  lg.r.p, lg.part.p, st)))
+    return rc;
+  if ((rc = launch_aty_xb(false, L, At_rp.p, At_ci.p, At_v.p, lg.ytilde.p, C.p, X.p, 1.0, aux.in.p, nullptr, st, &At_long))) return rc;
+  if ((rc = bm.run(fl, aux.in.p, -1.0, btasks.off.p, btasks.blk.p, st))) return rc;
+  if (block_terms && (rc = launch_lrg_block_terms(C.p, lg.xv.p, aux.in.p, btasks.view(), lg.cpart.p, lg.sums.p, st))) return rc;
+  return CUADMM_OK;
+}
+
 // The chain at the scaled y in lg.ybuf.  x is assembled in lg.xv in the units X lies in (X = ux xv: ux = bscale behind a solve, else 1): a
 // device copy of X, then svec(L_k L_k') over its PSD blocks from the factors in those units -- the caller's own, as the block product's V
 // holds them, where ux = 1, else a second staged copy through scale_factors.  Then A x, the multiplier pass, M = A'ytilde - C into the
@@ -538,7 +555,6 @@ int cuadmm_solver::lg_run(const double* Lf, const int* ranks, double sigma, doub
   int rc;
   const int nb = (int)blk_local.size();
   const double ux = pending_unscale ? bscale : 1.0;
-  const double* const normA_dev = normA_d.p ? normA_d.p : lg.normA.p;
   if ((rc = fl.stage(bm.Vbuf, Lf)) || (rc = fl.stage_ranks(ranks))) return rc;
   const double* Lx = bm.Vbuf.p;
   if (ux != 1.0 && Lf) {
@@ -547,15 +563,7 @@ int cuadmm_solver::lg_run(const double* Lf, const int* ranks, double sigma, doub
     Lx = lo.Lbuf.p;
   }
   CUADMM_HIP_TRY(hipEventRecord(lg.ev[0], st));
-  CUADMM_HIP_TRY(hipMemcpyAsync(lg.xv.p, X.p, sizeof(double) * (size_t)L, hipMemcpyDeviceToDevice, st));
-  if ((rc = lo.run(fl, Lx, btasks.off.p, btasks.blk.p, lg.xv.p, st))) return rc;
-  if (m > 0 && (rc = launch_spmv_rows(m, A_avg_nnz, A_rp.p, A_ci.p, A_v.p, lg.xv.p, S.p, C.p, lg.ax.p, nullptr, st, &A_long))) return rc;
-  if ((rc = launch_lrg_multiplier(m, lg.ax.p, aux.b_dev(*this), normA_dev, lg.ybuf.p, pending_unscale ? 1.0 : 1 / bscale, bscale, 1 / Cscale, sigma, lg.ytilde.p,
-                                  lg.r.p, lg.part.p, st)))
-    return rc;
-  if ((rc = launch_aty_xb(false, L, At_rp.p, At_ci.p, At_v.p, lg.ytilde.p, C.p, X.p, 1.0, aux.in.p, nullptr, st, &At_long))) return rc;
-  if ((rc = bm.run(fl, aux.in.p, -1.0, btasks.off.p, btasks.blk.p, st))) return rc;
-  if ((rc = launch_lrg_block_terms(C.p, lg.xv.p, aux.in.p, btasks.view(), lg.cpart.p, lg.sums.p, st))) return rc;
+  if ((rc = lg_enqueue(Lx, sigma, true))) return rc;
   CUADMM_HIP_TRY(hipEventRecord(lg.ev[1], st));
   CUADMM_HIP_TRY(hipStreamSynchronize(st));
   const float ms = event_ms(lg.ev[0], lg.ev[1]);
@@ -619,26 +627,11 @@ int cuadmm_solver::ll_prepare(int rmax) {
   return aux.ensure(*this);
 }
 
-// The chain at the scaled y in ll.ybuf.  L and D are staged in the units X lies in (X = ux x: ux = bscale behind a solve, else 1), through
-// scale_factors where ux != 1 as lg_run stages L, so that x0 and with it r0 carry lg_run's bits.  Then the device copy of X into
-// ll.x0, the three outer products, three A x, the streaming pass and the per-block terms; the coefficients on the host in the order
-// lowrank_line.h states.  Reads X, A, b, C; writes only the plans' own buffers.  Every output of the caller is written behind the last
-// refusal.
-int cuadmm_solver::ll_run(const double* Lf, const double* Df, const int* ranks, double sigma, double t_max, double coef5[5], double* r_out, double* p_out,
-                          double* q_out, double o[8], double* per_block) {
-#pragma clang fp contract(off)
+// The launches of ll_run's chain at the scaled y in ll.ybuf, on the factors in lo.Lbuf and the direction in ll.Dbuf, both in the units X
+// lies in.
+int cuadmm_solver::ll_enqueue() {
   int rc;
-  const int nb = (int)blk_local.size();
-  const double ux = pending_unscale ? bscale : 1.0;
   const double* const normA_dev = normA_d.p ? normA_d.p : ll.normA.p;
-  const double *Ls = Lf, *Ds = Df;
-  if (ux != 1.0 && Lf) {
-    scale_factors(fl, blk_local.data(), ranks, Lf, ux, ll.h_L);
-    scale_factors(fl, blk_local.data(), ranks, Df, ux, ll.h_D);
-    Ls = ll.h_L.data(); Ds = ll.h_D.data();
-  }
-  if ((rc = fl.stage(lo.Lbuf, Ls)) || (rc = fl.stage(ll.Dbuf, Ds)) || (rc = fl.stage_ranks(ranks))) return rc;
-  CUADMM_HIP_TRY(hipEventRecord(ll.ev[0], st));
   CUADMM_HIP_TRY(hipMemcpyAsync(ll.x0.p, X.p, sizeof(double) * (size_t)L, hipMemcpyDeviceToDevice, st));
   if ((rc = launch_block_outer3((int)lo.tasks.size(), lo.tasks_d.p, lo.Lbuf.p, ll.Dbuf.p, fl.loff_d.p, fl.ranks_d.p, btasks.off.p, btasks.blk.p, ll.x0.p, ll.x1.p,
                                 ll.x2.p, st)))
@@ -652,32 +645,70 @@ int cuadmm_solver::ll_run(const double* Lf, const double* Df, const int* ranks, 
   if ((rc = launch_lrl_sums(m, ll.ax0.p, ll.ax1.p, ll.ax2.p, aux.b_dev(*this), normA_dev, ll.ybuf.p, pending_unscale ? 1.0 : 1 / bscale, bscale, ll.r0.p, ll.p.p, ll.q.p,
                             ll.part.p, st)))
     return rc;
-  if ((rc = launch_lrl_block_terms(C.p, ll.x0.p, ll.x1.p, ll.x2.p, btasks.view(), ll.cpart.p, ll.sums.p, st))) return rc;
-  CUADMM_HIP_TRY(hipEventRecord(ll.ev[1], st));
-  CUADMM_HIP_TRY(hipStreamSynchronize(st));
-  const float ms = event_ms(ll.ev[0], ll.ev[1]);
-  // --- back to the host and to the caller's units (the host scratch is the plan's and is kept)
+  return launch_lrl_block_terms(C.p, ll.x0.p, ll.x1.p, ll.x2.p, btasks.view(), ll.cpart.p, ll.sums.p, st);
+}
+
+// Behind ll_enqueue: the slot partials and the per-block sums to the plan's host scratch (ll.h_back: three m-vectors for the caller of
+// ll_run, then the partials, then the sums; *sums points at the last), sm <- the nine slot sums, c <- the coefficients in the order
+// lowrank_line.h states.
+int cuadmm_solver::ll_coef(double sigma, double ux, double c[5], double sm[kLlParts], const double** sums_out) {
+#pragma clang fp contract(off)
+  int rc;
+  const int nb = (int)blk_local.size();
   const size_t mm = (size_t)std::max(m, 1);
   std::vector<double>& h = ll.h_back;
   h.resize(3 * mm + kLlParts * (size_t)kBrSlots + kLlSums * (size_t)std::max(nb, 1));
-  double *const rh = h.data(), *const ph = rh + mm, *const qh = ph + mm, *const part = qh + mm, *const sums = part + kLlParts * (size_t)kBrSlots;
-  if (m > 0 && r_out && (rc = staged_d2h(rh, ll.r0.p, sizeof(double) * (size_t)m, st))) return rc;
-  if (m > 0 && p_out && (rc = staged_d2h(ph, ll.p.p, sizeof(double) * (size_t)m, st))) return rc;
-  if (m > 0 && q_out && (rc = staged_d2h(qh, ll.q.p, sizeof(double) * (size_t)m, st))) return rc;
+  double *const part = h.data() + 3 * mm, *const sums = part + kLlParts * (size_t)kBrSlots;
   if ((rc = staged_d2h(part, ll.part.p, sizeof(double) * kLlParts * (size_t)kBrSlots, st))) return rc;
   if (nb > 0 && (rc = staged_d2h(sums, ll.sums.p, sizeof(double) * kLlSums * (size_t)nb, st))) return rc;
-  double sm[kLlParts], cx[kLlSums] = {0, 0, 0};
+  double cx[kLlSums] = {0, 0, 0};
   for (int j = 0; j < kLlParts; ++j) sm[j] = slot_sum(part + (size_t)j * kBrSlots);
   const double cxu = Cscale * ux;
   for (int k = 0; k < nb; ++k)
     for (int j = 0; j < kLlSums; ++j) cx[j] = cx[j] + sums[kLlSums * (size_t)k + j] * cxu;
   const double yr0 = sm[0] * objscale, yr1 = sm[1] * objscale, yr2 = sm[2] * objscale, hs = 0.5 * sigma;
-  double c[5];
   c[0] = (cx[0] - yr0) + hs * sm[3];
   c[1] = (cx[1] - yr1) + sigma * sm[4];
   c[2] = (cx[2] - yr2) + hs * (sm[5] + 2.0 * sm[6]);
   c[3] = sigma * sm[7];
   c[4] = hs * sm[8];
+  *sums_out = sums;
+  return CUADMM_OK;
+}
+
+// The chain at the scaled y in ll.ybuf.  L and D are staged in the units X lies in (X = ux x: ux = bscale behind a solve, else 1), through
+// scale_factors where ux != 1 as lg_run stages L, so that x0 and with it r0 carry lg_run's bits.  Then the device copy of X into
+// ll.x0, the three outer products, three A x, the streaming pass and the per-block terms; the coefficients on the host in the order
+// lowrank_line.h states.  Reads X, A, b, C; writes only the plans' own buffers.  Every output of the caller is written behind the last
+// refusal.
+int cuadmm_solver::ll_run(const double* Lf, const double* Df, const int* ranks, double sigma, double t_max, double coef5[5], double* r_out, double* p_out,
+                          double* q_out, double o[8], double* per_block) {
+#pragma clang fp contract(off)
+  int rc;
+  const int nb = (int)blk_local.size();
+  const double ux = pending_unscale ? bscale : 1.0;
+  const double *Ls = Lf, *Ds = Df;
+  if (ux != 1.0 && Lf) {
+    scale_factors(fl, blk_local.data(), ranks, Lf, ux, ll.h_L);
+    scale_factors(fl, blk_local.data(), ranks, Df, ux, ll.h_D);
+    Ls = ll.h_L.data(); Ds = ll.h_D.data();
+  }
+  if ((rc = fl.stage(lo.Lbuf, Ls)) || (rc = fl.stage(ll.Dbuf, Ds)) || (rc = fl.stage_ranks(ranks))) return rc;
+  CUADMM_HIP_TRY(hipEventRecord(ll.ev[0], st));
+  if ((rc = ll_enqueue())) return rc;
+  CUADMM_HIP_TRY(hipEventRecord(ll.ev[1], st));
+  CUADMM_HIP_TRY(hipStreamSynchronize(st));
+  const float ms = event_ms(ll.ev[0], ll.ev[1]);
+  // --- back to the host and to the caller's units (the host scratch is the plan's and is kept)
+  double sm[kLlParts], c[5];
+  const double* sums = nullptr;
+  if ((rc = ll_coef(sigma, ux, c, sm, &sums))) return rc;
+  const size_t mm = (size_t)std::max(m, 1);
+  double *const rh = ll.h_back.data(), *const ph = rh + mm, *const qh = ph + mm;
+  if (m > 0 && r_out && (rc = staged_d2h(rh, ll.r0.p, sizeof(double) * (size_t)m, st))) return rc;
+  if (m > 0 && p_out && (rc = staged_d2h(ph, ll.p.p, sizeof(double) * (size_t)m, st))) return rc;
+  if (m > 0 && q_out && (rc = staged_d2h(qh, ll.q.p, sizeof(double) * (size_t)m, st))) return rc;
+  const double cxu = Cscale * ux;
   double q4[4] = {0.0, c[0], 0.0, 0.0};
   if (t_max > 0.0) {
     for (int j = 0; j < 5; ++j)
@@ -697,6 +728,109 @@ int cuadmm_solver::ll_run(const double* Lf, const double* Df, const int* ranks, 
   o[0] = q4[0]; o[1] = q4[1]; o[2] = q4[2]; o[3] = std::sqrt(sm[5]); o[4] = std::sqrt(sm[8]); o[5] = q4[3];
   o[6] = ms;
   o[7] = ll.bytes() + lo.bytes() + fl.bytes() + btasks.bytes() + aux.bytes();
+  return CUADMM_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// Conjugate gradients over the factors (cuadmm_lowrank_refine): DESIGN.md, "Refinement over factors"
+// ------------------------------------------------------------------------------------------
+// what cuadmm_lowrank_grad and cuadmm_lowrank_line prepare for this rmax, and the loop's own buffers on the same layout
+int cuadmm_solver::rf_prepare(int rmax) {
+  int rc;
+  if ((rc = lg_prepare(rmax)) || (rc = ll_prepare(rmax))) return rc;
+  return rf.prepare(fl);
+}
+
+// `steps` steps of Polak-Ribiere+ conjugate gradients at the scaled y in lg.ybuf and ll.ybuf (the same bits).  Resident between the steps:
+// L in the caller's units in bm.Vbuf (the block product reads it) and in the units X lies in in lo.Lbuf (both outer products read it), the
+// direction in the caller's units in rf.D and scaled in ll.Dbuf, the block product's W in bm.Wbuf (G = 2 (Cscale W) wherever it is read)
+// and the previous G in rf.Gold.  A step enqueues lg_run's chain without the per-block terms, the three sums, the direction, ll_run's
+// chain and the update of L, and synchronises twice: for the three sums and for the quartic's partials.  The host packs the caller's L
+// into a clean buffer first (+ 0.0 in the columns that are not read) and zeroes W, D and G_old once: the block product never writes
+// the columns >= r_k, so the flat kernels see zeros there throughout.  Every output of the caller is written at the end.
+// Reads X, y, A, A', b, C; writes only the plans' own buffers and the auxiliary projector's input vector.
+int cuadmm_solver::rf_run(const double* Lf, const int* ranks, double sigma, int steps, double t_max, double gtol, double* L_out, double* trace, double o[8],
+                          double* r_out) {
+#pragma clang fp contract(off)
+  int rc;
+  const int nb = (int)blk_local.size();
+  const size_t count = fl.count();
+  const long long cnt = (long long)count;
+  const double ux = pending_unscale ? bscale : 1.0, root = 1 / std::sqrt(ux);
+  std::vector<double>& hL = rf.h_L;
+  hL.assign(count + 1, 0.0);
+  for (int k = 0; k < nb; ++k)
+    for (size_t e = (size_t)fl.loff[k], end = e + (blk_local[k] > 0 ? (size_t)blk_local[k] * (size_t)ranks[k] : 0); e < end; ++e) hL[e] = Lf[e];
+  scale_factors(fl, blk_local.data(), ranks, hL.data(), ux, lg.h_stage);
+  if ((rc = fl.stage(bm.Vbuf, hL.data())) || (rc = fl.stage(lo.Lbuf, lg.h_stage.data())) || (rc = fl.stage_ranks(ranks))) return rc;
+  if (count > 0) {
+    CUADMM_HIP_TRY(hipMemsetAsync(bm.Wbuf.p, 0, sizeof(double) * count, st));
+    CUADMM_HIP_TRY(hipMemsetAsync(rf.D.p, 0, sizeof(double) * count, st));
+    CUADMM_HIP_TRY(hipMemsetAsync(rf.Gold.p, 0, sizeof(double) * count, st));
+  }
+  std::vector<double> tr((size_t)kRfTrace * (size_t)steps, 0.0);
+  std::vector<double>& hp = rf.h_part;
+  hp.resize(kRfParts * (size_t)kBrSlots);
+  double gg_prev = 0, first_c0 = NAN, last_f = NAN, last_gn = NAN;
+  int taken = 0, reason = 0, rows = 0;
+  hipEvent_t prev0 = nullptr, prev1 = nullptr;
+  CUADMM_HIP_TRY(hipEventRecord(rf.ev[0], st));
+  for (int k = 0; k < steps; ++k) {
+    double* const row = tr.data() + (size_t)kRfTrace * (size_t)k;
+    hipEvent_t e0 = rf.ev[2 + 2 * (k & 1)], e1 = rf.ev[3 + 2 * (k & 1)];
+    rows = k + 1;
+    CUADMM_HIP_TRY(hipEventRecord(e0, st));
+    // --- the gradient at L_k and the three sums
+    if ((rc = lg_enqueue(lo.Lbuf.p, sigma, false))) return rc;
+    if ((rc = launch_lrr_dots(cnt, bm.Wbuf.p, Cscale, rf.Gold.p, rf.D.p, rf.part.p, st))) return rc;
+    if ((rc = staged_d2h(hp.data(), rf.part.p, sizeof(double) * hp.size(), st))) return rc;      // (drains the stream: the step before is over)
+    if (prev0) tr[(size_t)kRfTrace * (size_t)(k - 1) + 13] = event_ms(prev0, prev1);
+    prev0 = e0; prev1 = e1;
+    const double gg = slot_sum(hp.data()), go = slot_sum(hp.data() + kBrSlots), gd = slot_sum(hp.data() + 2 * (size_t)kBrSlots);
+    row[0] = gg; row[1] = go; row[2] = gd;
+    last_gn = std::sqrt(gg);
+    double u3[3];
+    if (!std::isfinite(gg) || !std::isfinite(go) || !std::isfinite(gd) || cuadmm_cg_update(gg, go, gd, gg_prev, k == 0, u3)) { reason = 3; CUADMM_HIP_TRY(hipEventRecord(e1, st)); break; }
+    row[3] = u3[0]; row[4] = u3[1]; row[5] = u3[2];
+    if (gtol > 0.0 && last_gn <= gtol) { reason = 2; CUADMM_HIP_TRY(hipEventRecord(e1, st)); break; }
+    // --- the direction and the quartic along it
+    if ((rc = launch_lrr_direction(cnt, bm.Wbuf.p, Cscale, u3[0], u3[2] != 0.0, root, rf.D.p, ll.Dbuf.p, rf.Gold.p, st))) return rc;
+    if ((rc = ll_enqueue())) return rc;
+    double c[5], sm[kLlParts], q4[4];
+    const double* sums = nullptr;
+    if ((rc = ll_coef(sigma, ux, c, sm, &sums))) return rc;
+    for (int j = 0; j < 5; ++j) row[6 + j] = c[j];
+    if (k == 0) first_c0 = c[0];
+    bool finite = true;
+    for (int j = 0; j < 5; ++j) finite = finite && std::isfinite(c[j]);
+    if (!finite) { reason = 3; CUADMM_HIP_TRY(hipEventRecord(e1, st)); break; }
+    if (cuadmm_quartic_min(c, t_max, q4)) { reason = 4; CUADMM_HIP_TRY(hipEventRecord(e1, st)); break; }
+    row[11] = q4[0]; row[12] = q4[1];
+    last_f = q4[1];
+    if (q4[0] == 0.0) { reason = 1; CUADMM_HIP_TRY(hipEventRecord(e1, st)); break; }
+    // --- the step
+    if ((rc = launch_lrr_step(cnt, q4[0], root, rf.D.p, bm.Vbuf.p, lo.Lbuf.p, st))) return rc;
+    CUADMM_HIP_TRY(hipEventRecord(e1, st));
+    gg_prev = gg;
+    taken++;
+  }
+  CUADMM_HIP_TRY(hipEventRecord(rf.ev[1], st));
+  CUADMM_HIP_TRY(hipStreamSynchronize(st));
+  if (prev0) tr[(size_t)kRfTrace * (size_t)(rows - 1) + 13] = event_ms(prev0, prev1);
+  const float ms = event_ms(rf.ev[0], rf.ev[1]);
+  rf.calls++;
+  // --- back to the host: L in the caller's units (its columns >= r_k have stayed + 0.0), r of the last gradient chain (the bits of the
+  // line search's r0 at the same factors)
+  if (count > 0 && (rc = staged_d2h(hL.data(), bm.Vbuf.p, sizeof(double) * count, st))) return rc;
+  std::vector<double> rh((size_t)std::max(m, 1));
+  if (m > 0 && r_out && (rc = staged_d2h(rh.data(), lg.r.p, sizeof(double) * (size_t)m, st))) return rc;
+  // --- nothing fails from here on
+  std::copy(hL.begin(), hL.begin() + count, L_out);
+  std::copy(tr.begin(), tr.begin() + (size_t)kRfTrace * (size_t)rows, trace);
+  unpermute(perm, m, rh.data(), r_out);
+  o[0] = (double)taken; o[1] = (double)reason; o[2] = first_c0; o[3] = last_f; o[4] = last_gn; o[5] = ms;
+  o[6] = rf.bytes() + lg.bytes() + ll.bytes() + bm.bytes() + lo.bytes() + fl.bytes() + btasks.bytes() + aux.bytes();
+  o[7] = 0;
   return CUADMM_OK;
 }
 
@@ -868,6 +1002,23 @@ int cuadmm_lowrank_line(cuadmm_solver* s, const double* Lf, const double* Df, co
   if (!Lf || !Df) Lf = Df = nullptr;     // every rank is 0: neither is read
   if ((rc = s->ll_prepare(rmax)) || (rc = s->stage_scaled_y(s->ll.ybuf.p, y))) return rc;
   return s->ll_run(Lf, Df, ranks, sigma, t_max, coef5, r_out, p_out, q_out, o, per_block);
+}
+int cuadmm_lowrank_refine(cuadmm_solver* s, const double* Lf, const int* ranks, int rmax, const double* y, double sigma, int steps, double t_max, double gtol,
+                          double* L_out, double* trace, double o[8], double* r_out) {
+  int rc = report_guard(s, o, "lowrank_refine", "results", true);
+  if (rc) return rc;
+  if (!L_out || !trace) { set_error("lowrank_refine: L_out or trace is null"); return CUADMM_ERR_INVALID; }
+  if (!(sigma >= 0.0) || !std::isfinite(sigma)) { set_error("lowrank_refine: sigma = %g, allowed is a finite sigma >= 0", sigma); return CUADMM_ERR_INVALID; }
+  if (steps < 1) { set_error("lowrank_refine: steps = %d, allowed is steps >= 1", steps); return CUADMM_ERR_INVALID; }
+  if (!(t_max > 0.0)) { set_error("lowrank_refine: t_max = %g, allowed is t_max > 0 (+inf included)", t_max); return CUADMM_ERR_INVALID; }
+  if (!(gtol >= 0.0) || !std::isfinite(gtol)) { set_error("lowrank_refine: gtol = %g, allowed is a finite gtol >= 0", gtol); return CUADMM_ERR_INVALID; }
+  if (rmax < 1 || rmax > kMaxBlockSize) { set_error("lowrank_refine: rmax = %d, allowed are 1 to %d", rmax, kMaxBlockSize); return CUADMM_ERR_INVALID; }
+  if (!ranks) { set_error("lowrank_refine: ranks is null"); return CUADMM_ERR_INVALID; }
+  if ((rc = check_factors("lowrank_refine", (int)s->blk_local.size(), s->blk_local.data(), ranks, rmax, "L", Lf, nullptr, nullptr, nullptr, nullptr))) return rc;
+  for (int i = 0; y && i < s->m; ++i)
+    if (!std::isfinite(y[i])) { set_error("lowrank_refine: y[%d] is not finite", i); return CUADMM_ERR_INVALID; }
+  if ((rc = s->rf_prepare(rmax)) || (rc = s->stage_scaled_y(s->lg.ybuf.p, y)) || (rc = s->stage_scaled_y(s->ll.ybuf.p, y))) return rc;
+  return s->rf_run(Lf, ranks, sigma, steps, t_max, gtol, L_out, trace, o, r_out);
 }
 int cuadmm_get_evaluate_info(const cuadmm_solver* s, double o[4]) {
   if (!s || !o) { set_error("get_evaluate_info: null"); return CUADMM_ERR_INVALID; }

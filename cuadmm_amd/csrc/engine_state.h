@@ -375,7 +375,7 @@ struct cuadmm_solver {
   int lr_prepare(int rmax);
   int lr_run(int which, double tol, double out8[8], double* per_block, double* L_out, int* piv_out);
 
-  FactorLayoutDev fl;          // (report_plans.h): the callers' factor layout of the four calls below, prepared by each for its rmax
+  FactorLayoutDev fl;          // (report_plans.h): the callers' factor layout of the five calls below, prepared by each for its rmax
   LoPlan lo;                   // (report_plans.h): cuadmm_set_lowrank
 
   BmPlan bm;                   // (report_plans.h): cuadmm_block_multiply
@@ -390,6 +390,13 @@ struct cuadmm_solver {
   int ll_prepare(int rmax);
   int ll_run(const double* Lf, const double* Df, const int* ranks, double sigma, double t_max, double coef5[5], double* r_out, double* p_out, double* q_out,
              double out8[8], double* per_block);
+  int lg_enqueue(const double* Lx, double sigma, bool block_terms);      // the chains of lg_run / ll_run on resident buffers, nothing fetched
+  int ll_enqueue();
+  int ll_coef(double sigma, double ux, double c[5], double sm[kLlParts], const double** sums);
+
+  RfPlan rf;                   // (report_plans.h): cuadmm_lowrank_refine
+  int rf_prepare(int rmax);
+  int rf_run(const double* Lf, const int* ranks, double sigma, int steps, double t_max, double gtol, double* L_out, double* trace, double out8[8], double* r_out);
 
   // profiling
   DevEvent ev0[K_NUM][2], ev1[K_NUM][2];

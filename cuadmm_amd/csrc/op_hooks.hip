@@ -743,7 +743,76 @@ int cuadmm_op_lrl_sums(int m, const double* ax0, const double* ax1, const double
   return CUADMM_OK;
 }
 
-// cuadmm_set_lowrank's, cuadmm_block_multiply's, cuadmm_lowrank_grad's and cuadmm_lowrank_line's check of the caller's factors
+// The three streaming kernels of cuadmm_lowrank_refine on host arrays (csrc/lowrank_refine.h).  Each device vector starts in the 16-byte
+// phase of its host array, so that a caller's view chooses the element-to-thread map.  An array a kernel writes has n + 1 doubles: entry n
+// is a guard that travels to the device and back and must come back with its bits.  The default stream, synchronised.
+static int lrr_stage(int nv, const double* const* src, const long long* len, DevBuf<double>* buf, double** dev) {
+  int rc;
+  for (int v = 0; v < nv; ++v) {
+    if ((rc = buf[v].alloc((size_t)len[v] + 2))) return rc;
+    dev[v] = buf[v].p + ((reinterpret_cast<uintptr_t>(src[v]) >> 3) & 1);
+    if ((rc = staged_h2d(dev[v], src[v], sizeof(double) * (size_t)len[v]))) return rc;
+  }
+  return CUADMM_OK;
+}
+static int lrr_device() {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_error("no HIP device available; this engine has no CPU fallback"); return CUADMM_ERR_NO_DEVICE; }
+  return CUADMM_OK;
+}
+// out3 <- gg, go, gd of G = 2 (unit W): the kernel's slot partials added in slot order
+int cuadmm_op_lrr_dots(long long n, const double* W, double unit, const double* G_old, const double* D_old, double out3[3]) {
+  if (n < 1 || !W || !G_old || !D_old || !out3) { set_error("op_lrr_dots: invalid argument"); return CUADMM_ERR_INVALID; }
+  int rc = lrr_device();
+  if (rc) return rc;
+  DevBuf<double> buf[3], part;
+  double* dev[3];
+  const double* const src[3] = {W, G_old, D_old};
+  const long long len[3] = {n, n, n};
+  if ((rc = lrr_stage(3, src, len, buf, dev)) || (rc = part.alloc(kRfParts * (size_t)kBrSlots))) return rc;
+  if ((rc = launch_lrr_dots(n, dev[0], unit, dev[1], dev[2], part.p, nullptr))) return rc;
+  CUADMM_HIP_TRY(hipStreamSynchronize(nullptr));
+  std::vector<double> h(kRfParts * (size_t)kBrSlots);
+  if ((rc = staged_d2h(h.data(), part.p, sizeof(double) * h.size()))) return rc;
+  for (int j = 0; j < kRfParts; ++j) out3[j] = slot_sum(h.data() + (size_t)j * kBrSlots);
+  return CUADMM_OK;
+}
+// D_inout, Ds_out, Gold_out: n + 1 doubles each (the guard last); W: n
+int cuadmm_op_lrr_direction(long long n, const double* W, double unit, double beta, int restart, double root, double* D_inout, double* Ds_out, double* Gold_out) {
+  if (n < 1 || !W || !D_inout || !Ds_out || !Gold_out) { set_error("op_lrr_direction: invalid argument"); return CUADMM_ERR_INVALID; }
+  int rc = lrr_device();
+  if (rc) return rc;
+  DevBuf<double> buf[4];
+  double* dev[4];
+  double* const dst[4] = {nullptr, D_inout, Ds_out, Gold_out};
+  const double* const src[4] = {W, D_inout, Ds_out, Gold_out};
+  const long long len[4] = {n, n + 1, n + 1, n + 1};
+  if ((rc = lrr_stage(4, src, len, buf, dev))) return rc;
+  if ((rc = launch_lrr_direction(n, dev[0], unit, beta, restart, root, dev[1], dev[2], dev[3], nullptr))) return rc;
+  CUADMM_HIP_TRY(hipStreamSynchronize(nullptr));
+  for (int v = 1; v < 4; ++v)
+    if ((rc = staged_d2h(dst[v], dev[v], sizeof(double) * (size_t)len[v]))) return rc;
+  return CUADMM_OK;
+}
+// L_inout, Ls_out: n + 1 doubles each (the guard last); D: n
+int cuadmm_op_lrr_step(long long n, double t, double root, const double* D, double* L_inout, double* Ls_out) {
+  if (n < 1 || !D || !L_inout || !Ls_out) { set_error("op_lrr_step: invalid argument"); return CUADMM_ERR_INVALID; }
+  int rc = lrr_device();
+  if (rc) return rc;
+  DevBuf<double> buf[3];
+  double* dev[3];
+  double* const dst[3] = {nullptr, L_inout, Ls_out};
+  const double* const src[3] = {D, L_inout, Ls_out};
+  const long long len[3] = {n, n + 1, n + 1};
+  if ((rc = lrr_stage(3, src, len, buf, dev))) return rc;
+  if ((rc = launch_lrr_step(n, t, root, dev[0], dev[1], dev[2], nullptr))) return rc;
+  CUADMM_HIP_TRY(hipStreamSynchronize(nullptr));
+  for (int v = 1; v < 3; ++v)
+    if ((rc = staged_d2h(dst[v], dev[v], sizeof(double) * (size_t)len[v]))) return rc;
+  return CUADMM_OK;
+}
+
+// cuadmm_set_lowrank's, cuadmm_block_multiply's, cuadmm_lowrank_grad's, cuadmm_lowrank_line's and cuadmm_lowrank_refine's check of the caller's factors
 // (csrc/factor_layout.h: check_factors) under the name `who`, with the buffers named as that call names them: "V" for block_multiply, else
 // "L", and "D" beside it for lowrank_line (D is not looked at for the others).  Host only.
 int cuadmm_op_check_factors(const char* who, const int* blk_vals, int mat_num, const int* ranks, int rmax, const double* L, const double* D) {

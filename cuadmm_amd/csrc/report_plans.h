@@ -1,6 +1,6 @@
 // What the reports on a point own beside the iteration's state, and what the op hooks build on their own: the auxiliary projector, the
 // per-block task lists, the plan of cuadmm_lambda_min, and for the low-rank calls (cuadmm_lowrank, cuadmm_set_lowrank,
-// cuadmm_block_multiply, cuadmm_lowrank_grad, cuadmm_lowrank_line) the one factor layout on the device, each kernel's task list and
+// cuadmm_block_multiply, cuadmm_lowrank_grad, cuadmm_lowrank_line, cuadmm_lowrank_refine) the one factor layout on the device, each kernel's task list and
 // buffers, and the host helpers the calls share.  Nothing here is read by the iteration.
 #pragma once
 #include <algorithm>
@@ -16,6 +16,7 @@
 #include "block_mult.h"
 #include "lowrank_grad.h"
 #include "lowrank_line.h"
+#include "lowrank_refine.h"
 
 struct cuadmm_solver;
 
@@ -336,6 +337,27 @@ struct LlPlan {
   double bytes() const {
     return 8.0 * (double)(x0.n + x1.n + x2.n + Dbuf.n + ybuf.n + ax0.n + ax1.n + ax2.n + r0.n + p.n + q.n + normA.n + part.n + sums.n + cpart.n);
   }
+};
+
+// Conjugate gradients over the factors (cuadmm_lowrank_refine; lowrank_refine.h, DESIGN.md "Refinement over factors"): the two factor-sized
+// device buffers the loop adds -- the direction in the caller's units and the previous gradient; L lives in BmPlan's V (caller's units) and
+// LoPlan's buffer (the units X lies in), the scaled direction in LlPlan's D, the gradient in BmPlan's W -- the slot partials of the three
+// sums, the host scratch kept between calls and the events: one pair around the loop and two pairs the steps take in turn, so that a
+// step's interval is read behind the next step's first synchronisation.  Nothing here is read by the iteration.
+struct RfPlan {
+  DevBuf<double> D, Gold, part;
+  std::vector<double> h_L, h_part;
+  DevEvent ev[6];
+  long long calls = 0;
+  int prepare(const FactorLayoutDev& fl) {
+    int rc;
+    if (!part.p) {
+      for (auto& e : ev) if ((rc = e.create())) return rc;
+    }
+    if ((rc = D.grow(fl.count() + 1)) || (rc = Gold.grow(fl.count() + 1))) return rc;
+    return part.p ? CUADMM_OK : part.alloc(kRfParts * (size_t)kBrSlots);      // last: marks the set as complete
+  }
+  double bytes() const { return 8.0 * (double)(D.n + Gold.n + part.n); }
 };
 
 }  // namespace cuadmm

@@ -108,6 +108,39 @@ def quartic_min(c, t_max):
     return {"t": float(o[0]), "f": float(o[1]), "decrease": float(o[2]), "critical": int(o[3])}
 
 
+def cg_update(gg, go, gd, gg_prev, first):
+    """The scalar step of lowrank_refine between a gradient and a direction (cuadmm_cg_update; no device is needed): from gg = <G, G>,
+    go = <G, G_old>, gd = <G, D_old> and the gg of the step before, a dict with "beta" = max(0, (gg - go) / gg_prev) (0 where first or
+    gg_prev == 0, and on a restart), "slope" = beta gd - gg and "restart" (first, or a slope that is not negative).  CuadmmError on an
+    input that is not finite."""
+    o = np.zeros(3)
+    check(_lib.load().cuadmm_cg_update(float(gg), float(go), float(gd), float(gg_prev), int(bool(first)), _p(o)))
+    return {"beta": float(o[0]), "slope": float(o[1]), "restart": bool(o[2])}
+
+
+def lowrank_refine_args(blk_vals, con_num, L, y, sigma, steps, t_max, gtol):
+    """(L buffer, ranks, rmax, y or None, sigma, steps, t_max, gtol) as cuadmm_lowrank_refine takes them; ValueError where
+    lowrank_grad_args raises one, on steps < 1, a t_max that is not positive, a gtol that is negative or not finite"""
+    sigma, t_max, gtol, steps = float(sigma), float(t_max), float(gtol), int(steps)
+    if not (sigma >= 0.0 and np.isfinite(sigma)):
+        raise ValueError("lowrank_refine: sigma = %r, allowed is a finite sigma >= 0" % sigma)
+    if steps < 1:
+        raise ValueError("lowrank_refine: steps = %d, allowed is steps >= 1" % steps)
+    if not t_max > 0.0:
+        raise ValueError("lowrank_refine: t_max = %r, allowed is t_max > 0" % t_max)
+    if not (gtol >= 0.0 and np.isfinite(gtol)):
+        raise ValueError("lowrank_refine: gtol = %r, allowed is a finite gtol >= 0" % gtol)
+    Lv, ranks, rmax = pack_lowrank(blk_vals, L, "lowrank_refine")
+    if y is not None:
+        y = _f64(y).ravel()
+        if y.size != int(con_num):
+            raise ValueError("lowrank_refine: y has %d entries, the problem %d" % (y.size, int(con_num)))
+    return Lv, ranks, rmax, y, sigma, steps, t_max, gtol
+
+
+REFINE_TRACE = ("gg", "go", "gd", "beta", "slope", "restart", "c0", "c1", "c2", "c3", "c4", "t", "f", "ms")
+
+
 class Problem:
     """TXT problem directory (blk.txt, con_num.txt, At.txt, b.txt, C.txt), src/problem.cu:11-83."""
 
@@ -430,6 +463,28 @@ class SDPSolver:
             Ls = [a + ln["t"] * d for a, d in zip(Ls, D)]
             G_old = G
         return {"L": Ls, "trace": trace}
+
+    def lowrank_refine(self, L, y=None, sigma=1.0, steps=10, t_max=float("inf"), gtol=0.0):
+        """`steps` steps of Polak-Ribiere+ nonlinear conjugate gradients on lowrank_grad's f over the factors, with lowrank_line's exact
+        line search, in one call: the factors, the direction and the gradients stay on the device and the host reads a few scalars per
+        step (cuadmm_lowrank_refine; the recurrence of lowrank_descent without its per-step round trips).  L: a list of (n_k, r_k) arrays
+        as lowrank()["L"] returns; y, sigma as in lowrank_grad, fixed for the call; gtol: stop where ||G||_F <= gtol (0: never).
+        Returns "L": the refined factors, shaped like L; "trace": one dict per step begun with "gg", "go", "gd", "beta", "slope",
+        "restart", "c0" .. "c4" ("c0" is f at the step's factors), "t", "f" = f(t), "ms"; "steps": steps taken; "reason": 0 all steps done,
+        1 a step of t = 0, 2 gtol reached, 3 a sum or coefficient that is not finite, 4 a quartic that is not bounded below with t_max =
+        inf (the last row of the trace is then the step that was not taken); "f0", "f", "gnorm", "ms", "bytes"; "r" = A x - b at the
+        factors of the last step begun.  X is not changed (set_lowrank takes "L"); no multiplier update, no rank adaptation, no
+        preconditioning.  The solver is left as it was: behind a solve the pending scaled state stays pending."""
+        Lv, ranks, rmax, yv, sigma, steps, t_max, gtol = lowrank_refine_args(self.blk_vals, self.con_num, L, y, sigma, steps, t_max, gtol)
+        Lo, tr, o, r = np.zeros(Lv.size), np.zeros(16 * steps), np.zeros(8), np.zeros(max(self.con_num, 1))
+        check(self._lib.cuadmm_lowrank_refine(self._h, _p(Lv), _p(ranks), rmax, _p(yv), sigma, steps, t_max, gtol, _p(Lo), _p(tr), _p(o), _p(r)))
+        taken, reason = int(o[0]), int(o[1])
+        rows = tr.reshape(steps, 16)[:taken + (1 if reason else 0)]
+        trace = [dict(zip(REFINE_TRACE, (float(v) for v in row[:14]))) for row in rows]
+        for t in trace:
+            t["restart"] = bool(t["restart"])
+        return {"L": unpack_lowrank(self.blk_vals, ranks, rmax, Lo), "trace": trace, "steps": taken, "reason": reason, "f0": float(o[2]), "f": float(o[3]),
+                "gnorm": float(o[4]), "ms": float(o[5]), "bytes": float(o[6]), "r": r[:self.con_num]}
 
     def set_allreduce(self, fn):
         """fn(dev_ptr:int, count:int, hip_stream:int) -> None : in-place sum over ranks on that stream."""

@@ -281,6 +281,44 @@ int cuadmm_lowrank_line(cuadmm_solver* s, const double* L, const double* D, cons
  * CUADMM_ERR_INVALID: c or out4 NULL, a coefficient that is not finite, t_max negative or NaN, t_max = +inf on a quartic that is not
  * bounded below by the rule above. */
 int cuadmm_quartic_min(const double c[5], double t_max, double out4[4]);
+/* `steps` iterations of Polak-Ribiere+ nonlinear conjugate gradients on cuadmm_lowrank_grad's f over the factors of the PSD blocks, with
+ * the exact line search of cuadmm_lowrank_line, and the factors, the direction and the gradients resident on the device throughout
+ * ("Refinement over factors"; csrc/lowrank_refine.h).  L, ranks, rmax, y, sigma as in cuadmm_lowrank_grad: columns >= r_k of L
+ * are never read (they may hold NaN).  y and sigma are fixed for the whole call.  All scalars are fp64, every operation rounded once.
+ * Step k = 0, 1, ... with e over the cuadmm_lowrank_size(rmax) entries:
+ *   1. G = the gradient at L_k, bit for bit cuadmm_lowrank_grad's G_out (that chain without its per-block terms);
+ *   2. gg = sum G^2, go = sum G G_old, gd = sum G D_old (one kernel; 256 slot partials each, added in slot order; G_old = D_old = 0 at k = 0);
+ *   3. [beta, slope, restart] = cuadmm_cg_update(gg, go, gd, gg of the step before, k == 0);  D[e] = fl(fl(beta D_old[e]) - G[e]), on a
+ *      restart - G[e];  G_old = G;
+ *   4. c0 .. c4 bit for bit cuadmm_lowrank_line(L_k, D_k)'s coef5 (that chain) and [t, f(t)] = cuadmm_quartic_min(c, t_max, .);
+ *   5. L_{k+1}[e] = fl(L_k[e] + fl(t D_k[e])).
+ * Behind a solve, where X lies scaled, the copies of L and D in X's units are fl(. root), root = fl(1 / sqrt(bscale)), formed on the
+ * device as cuadmm_lowrank_grad and cuadmm_lowrank_line form them on the host.  No atomics: the same bits on every run.  The host waits
+ * for the device twice per step (the three sums; the quartic's partials); nothing else crosses.
+ * The loop ends with reason 0: `steps` steps done; 1: t == 0, the step is not taken; 2: gtol > 0 and sqrt(gg) <= gtol, tested before the
+ * line search (gtol in the caller's units, 0: never); 3: a sum or a coefficient is not finite; 4: cuadmm_quartic_min refuses (t_max =
+ * +inf on a quartic that is not bounded below: sigma = 0, or A (D D') = 0).  Every reason returns CUADMM_OK with the factors behind the
+ * last step taken.
+ * L_out: cuadmm_lowrank_size(rmax) doubles, + 0.0 in the columns >= r_k; it may alias L.
+ * trace: 16 doubles per step, room for `steps` rows; row k = [gg, go, gd, beta, slope, restart, c0, c1, c2, c3, c4, t, f(t), device
+ * milliseconds of the step (HIP events), 0, 0].  f at L_k is c0.  A step that ends the loop early leaves a last row with what it had
+ * formed and 0 elsewhere; the rows behind it are not written.
+ * out8: [0] steps taken, [1] reason, [2] c0 of the first step (NaN where none was formed), [3] the last f(t) (NaN where none),
+ * [4] the last sqrt(gg), [5] device milliseconds of the whole loop, [6] bytes of device memory the call holds, [7] 0.
+ * r_out (con_num doubles, the caller's order; may be NULL): r = A x - b at the factors of the last step begun (cuadmm_lowrank_line's r_out
+ * there, bit for bit); r(t) = r + t p + t^2 q is not formed.
+ * Nothing the iteration reads is written and the deferred unscaling is not triggered: a following cuadmm_solve(..., if_first = 0)
+ * continues bit for bit.  X is not changed: the caller passes L_out to cuadmm_set_lowrank.  Not in the call: updates of y or an outer
+ * augmented-Lagrangian loop, rank adaptation, preconditioning.
+ * CUADMM_ERR_INVALID, the solver and every output as they were: the list of cuadmm_lowrank_grad; L_out, trace or out8 NULL; steps < 1;
+ * t_max <= 0 or NaN; gtol negative or not finite.  CUADMM_ERR_FACTOR behind a failed cuadmm_update_A. */
+int cuadmm_lowrank_refine(cuadmm_solver* s, const double* L, const int* ranks, int rmax, const double* y, double sigma, int steps, double t_max, double gtol,
+                          double* L_out, double* trace, double out8[8], double* r_out);
+/* The scalar step of cuadmm_lowrank_refine between a gradient and a direction.  Host only: no device, no solver handle.  Plain doubles:
+ *   beta = max(0, (gg - go) / gg_prev), 0 where first != 0 or gg_prev == 0;   slope = beta gd - gg;   restart = first != 0 or not slope < 0.
+ * out3: [0] beta (0 on a restart), [1] slope as formed above, [2] restart (1 or 0).
+ * CUADMM_ERR_INVALID: out3 NULL, or one of gg, go, gd, gg_prev not finite. */
+int cuadmm_cg_update(double gg, double go, double gd, double gg_prev, int first, double out3[3]);
 /* Replace X (which = 0) or S (1) between two solves by per-block factors: every PSD block k becomes L_k L_k' with r_k = ranks[k] columns
  * ("Starting from low-rank factors"; csrc/lowrank_apply.h).  L is laid out as cuadmm_lowrank's L_out for this rmax: block k at the
  * prefix sum of n_j min(n_j, rmax) over the PSD blocks before it, column by column, n_k doubles per column; unconstrained blocks occupy
@@ -810,8 +848,19 @@ int cuadmm_op_block_outer3(const double* L_host, const double* D_host, const int
  * synchronised. */
 int cuadmm_op_lrl_sums(int m, const double* ax0, const double* ax1, const double* ax2, const double* b, const double* normA, const double* y, double bscale,
                        double Cscale, double* r_out, double* p_out, double* q_out, double out9[9]);
-/* The check of a caller's factors that cuadmm_set_lowrank, cuadmm_block_multiply, cuadmm_lowrank_grad and cuadmm_lowrank_line share
- * (csrc/factor_layout.h), alone: who is one of "set_lowrank", "block_multiply", "lowrank_grad", "lowrank_line" and words the message as
+/* The three streaming kernels of cuadmm_lowrank_refine alone (csrc/lowrank_refine.hip) on host arrays of n >= 1 doubles; G[e] =
+ * 2.0 * (W[e] * unit) throughout, every operation rounded once.  A device vector starts in the 16-byte phase its host array has: arrays
+ * that are all 16-byte aligned take the two-entry map, any other the one-entry map.  An array that is written has n + 1 doubles: entry n
+ * travels to the device and back and comes back with its bits.  The default stream, synchronised.
+ * lrr_dots: out3 = [sum G^2, sum G G_old, sum G D_old], each from 256 slot partials added in slot order.
+ * lrr_direction: D[e] = fl(fl(beta D[e]) - G[e]), or - G[e] where restart != 0 (D is then not read); Ds[e] = fl(D[e] root); G_old[e] = G[e].
+ * lrr_step: L[e] = fl(L[e] + fl(t D[e])); Ls[e] = fl(L[e] root). */
+int cuadmm_op_lrr_dots(long long n, const double* W, double unit, const double* G_old, const double* D_old, double out3[3]);
+int cuadmm_op_lrr_direction(long long n, const double* W, double unit, double beta, int restart, double root, double* D_inout, double* Ds_out, double* Gold_out);
+int cuadmm_op_lrr_step(long long n, double t, double root, const double* D, double* L_inout, double* Ls_out);
+/* The check of a caller's factors that cuadmm_set_lowrank, cuadmm_block_multiply, cuadmm_lowrank_grad, cuadmm_lowrank_line and
+ * cuadmm_lowrank_refine share (csrc/factor_layout.h), alone: who is one of "set_lowrank", "block_multiply", "lowrank_grad", "lowrank_line",
+ * "lowrank_refine" and words the message as
  * that call does; L is its factor buffer (V for block_multiply), D the second one of lowrank_line (not looked at for the others).
  * Returns what that call would return for these factors: 0, or CUADMM_ERR_INVALID with the message set.  Host only (no device needed). */
 int cuadmm_op_check_factors(const char* who, const int* blk_vals, int mat_num, const int* ranks, int rmax, const double* L, const double* D);

@@ -276,6 +276,34 @@ class SDPSolver {
     return g;
   }
 
+  // cuadmm_lowrank_refine: `steps` steps of Polak-Ribiere+ conjugate gradients on lowrank_grad's f with lowrank_line's line search, the
+  // factors resident on the device; L, ranks, rmax, y, sigma as lowrank_grad's; trace: 16 doubles per step begun ([gg, go, gd, beta,
+  // slope, restart, c0 .. c4, t, f(t), ms, 0, 0]); reason: 0 all steps, 1 t = 0, 2 gtol, 3 not finite, 4 unbounded quartic; not in the
+  // reference
+  struct LowRankRefine {
+    std::vector<double> L, trace, r;
+    int steps, reason;
+    double f0, f, gnorm, ms, bytes;
+  };
+  LowRankRefine lowrank_refine(const double* L, const int* ranks, int rmax, const double* y = nullptr, double sigma = 1.0, int steps = 10,
+                               double t_max = std::numeric_limits<double>::infinity(), double gtol = 0.0) {
+    double o[8] = {0};
+    int vl = 0, cn = 0, mn = 0;
+    long long count = 0;
+    check(cuadmm_get_dims(h_, &vl, &cn, &mn));
+    check(cuadmm_lowrank_size(h_, rmax, &count));
+    LowRankRefine g;
+    g.L.assign((size_t)count + 1, 0.0);
+    g.trace.assign(16 * (size_t)(steps > 0 ? steps : 0) + 1, 0.0);
+    g.r.assign((size_t)cn + 1, 0.0);
+    check(cuadmm_lowrank_refine(h_, L, ranks, rmax, y, sigma, steps, t_max, gtol, g.L.data(), g.trace.data(), o, g.r.data()));
+    g.steps = (int)o[0]; g.reason = (int)o[1]; g.f0 = o[2]; g.f = o[3]; g.gnorm = o[4]; g.ms = o[5]; g.bytes = o[6];
+    g.L.resize((size_t)count);
+    g.trace.resize(16 * (size_t)(g.steps + (g.reason ? 1 : 0)));
+    g.r.resize((size_t)cn);
+    return g;
+  }
+
   // cuadmm_update_bC: new b and / or C on the factored solver (nnz < 0: unchanged); not in the reference
   void update_bC(const int* cpu_b_indices, const double* cpu_b_vals, int b_nnz, const int* cpu_C_indices, const double* cpu_C_vals,
                  int C_nnz, bool keep_iterate = true, double sig = 0.0) {
